@@ -9,14 +9,21 @@ child process -- before anything touches the GPU -- and relays the child's JSON 
 A step = one pass of the fused render+verify path over the rank's shard of the hypothesis table
 (BASELINE.json configs[2]: 4096 hypotheses over 64 synthetic 1024x512 panoramas, rasteriser + ResNet-50 fp16,
 per GPU -> weak scaling).  Inputs are resident in HBM when the timed region starts.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the steps and prints that line; its `roofline` / `roofline_verifier` fields come from
+the HIP events of the timed steps and profiles/traffic.json, no run of their own.
+`--dump-outputs DIR` writes what the last timed step computed -- the logits of the whole hypothesis table, float32, in table
+order -- to DIR/logits.npy (same arguments, same seeded inputs: two builds compare output for output).
 
-At N = 1 the same JSON line also carries, all measured OUTSIDE the timed region:
+With `--full` at N = 1 the same JSON line also carries, all measured OUTSIDE the timed region (each can be left out with its
+`--no-*` option):
   * `roofline.hbm_copy_gbs_measured` -- a 4 GB device copy on this box (SURVEY 8d: "confirm with a copy microbenchmark on the box");
   * `roofline_verifier.gemm_*` -- a plain fp16 GEMM (fp32 accumulation, random data, torch.matmul = hipBLASLt: a MEASUREMENT REFERENCE,
     never product) at the three 3 x 3 shapes of the forward + one square shape, each with board power and shader clock: what the matrix
     pipes of THIS box sustain at its power cap, beside what conv8_kernel gets;
+  * `roofline.densify_without_tile_phase_ms` -- the densify stage without its tile phase, like-for-like with rounds 1-5;
   * `config5` -- BASELINE.json configs[4] (2048 x 1024 panoramas, floor + ceiling, ResNet-152 12-channel), 3 timed steps at the launch
-    size the pipeline picks (pipeline.pick_launch).
+    size the pipeline picks (pipeline.pick_launch);
+  * `cpu_baseline` -- BASELINE.json configs[0] on the host's cores.
 BASELINE.json configs[4] alone (same JSON schema, `config.workload` names it):
     python bench.py --pano-hw 1024x2048 --surfaces floor,ceiling --layers 152 --panos 16
 `--chunk N` fixes the hypotheses per launch (default: chosen by the pipeline from the free HBM -- the whole shard when it fits).
@@ -395,13 +402,16 @@ def main() -> None:
                     "fits half of the free HBM -- the whole shard here (launches of 4096 run 10 %% faster per unit than launches of 1024)")
     ap.add_argument("--no-overlap", action="store_true", help="same as --streams 1")
     ap.add_argument("--streams", type=int, default=1, help="1: one HIP stream (default: with whole-shard launches the overlapped schedules gain\n"
-                    "1 % -- the kernels then share the CUs and each runs longer -- and blur the per-kernel times the rooflines are computed from);\n"
+                    "1 %% -- the kernels then share the CUs and each runs longer -- and blur the per-kernel times the rooflines are computed from);\n"
                     "2: rasteriser | verifier; 3: scatter | densify | verifier, the rasteriser of pass k + 1 under the verifier of pass k")
     ap.add_argument("--layers", type=int, default=50)
     ap.add_argument("--pano-hw", default="512x1024", help="panorama HxW: 512x1024 (configs 1-4) | 1024x2048 (config 5)")
     ap.add_argument("--surfaces", default="floor", help="floor | ceiling | floor,ceiling (config 5: 12-channel early fusion)")
     ap.add_argument("--force-dist", action="store_true", help="initialise RCCL and run the logits all-gather even with one rank")
     ap.add_argument("--scene", default="box", help="synthetic scene: box (SURVEY 8d) | cluttered (occluding boxes + door opening) | noisy (cluttered + network-like depth errors)")
+    ap.add_argument("--full", action="store_true", help="also measure, outside the timed region, what the headline figure does not need (N = 1): board power\n"
+                    "and clock, densify without its tile phase, HBM copy and GEMM roofs, BASELINE config 5, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the logits of the last timed step (float32, table order) to DIR/logits.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-power-probe", action="store_true", help="skip the 3 s loop of verifier forwards during which board power and shader clock are read from sysfs")
     ap.add_argument("--no-calibration", action="store_true", help="skip the GEMM and copy microbenchmarks (measured roofs of this box)")
@@ -476,6 +486,10 @@ def main() -> None:
     dt = float(tmax.item())
     pipe.check("bench.py")            # no star walk failed, no activation left the fp16 range
     assert allg.shape[0] == n_total and bool(torch.isfinite(allg).all())
+    if rank == 0 and args.dump_outputs:
+        dump = Path(args.dump_outputs)
+        dump.mkdir(parents=True, exist_ok=True)
+        np.save(dump / "logits.npy", allg.float().cpu().numpy())   # what a caller of the path receives: every hypothesis's logits
 
     if rank == 0:
         value = n_total * args.steps / dt
@@ -536,14 +550,15 @@ def main() -> None:
                                   "bound_hbm_ms": None if ver_alg is None else round(ver_alg * full_n / (HBM_ACHIEVABLE_GBS * 1e9) * 1e3, 3),
                                   "traffic": None if ver_traffic is None else int(ver_traffic * full_n), "traffic_source": ver_src},
         }
-        if world == 1 and not args.no_power_probe:
+        extras = world == 1 and args.full   # the measurements below take runs of their own: only a --full line carries them
+        if extras and not args.no_power_probe:
             # the verifier forward in a sustained loop (outside the timed region) while a thread reads the GPU's hwmon files: power and the clock it leaves
             probe = power_probe(lambda: pipe.engine.forward_nhwc(pipe.tile_bufs[0][:full_n], out=logits[:full_n]), device_index=local_rank)
             if probe is not None:
                 out["roofline_verifier"].update({"power_w": probe["power_w"], "power_cap_w": probe["power_cap_w"], "sclk_mhz": probe["sclk_mhz"], "power_samples": probe["samples"],
                                                  "peak_at_sclk": round(MFMA_PEAK_TFLOPS * probe["sclk_mhz"] / 2400.0, 1),
                                                  "frac_at_sclk": round(tflops / (MFMA_PEAK_TFLOPS * probe["sclk_mhz"] / 2400.0), 5)})
-        if world == 1 and not args.no_calibration:
+        if extras and not args.no_calibration:
             # the densify stage WITHOUT its tile phase (salve_bev_densify instead of salve_bev_densify_tiles), outside the timed region: since round 6 the
             # verifier tiles are written by the densify kernel's last phase, so `densify_ms` above carries work SURVEY 8d's bytes do not count --
             # this is the stage as rounds 1-5 timed it, for a like-for-like `frac`
@@ -564,12 +579,12 @@ def main() -> None:
             except Exception as ex:
                 out["roofline"]["densify_without_tile_phase_ms"] = None
                 out["roofline"]["densify_without_tile_phase_error"] = str(ex)[:200]
-        if world == 1 and not (args.no_calibration and args.no_config5):
+        if extras and not (args.no_calibration and args.no_config5):
             # everything below needs the memory, not the pipeline: release the main workload's buffers
             del pipe, prepared, logits, allg, table
             torch.cuda.empty_cache()
         # (the extras below run OUTSIDE the timed region; none of them may cost the line its main measurement: a failure is reported in its field)
-        if world == 1 and not args.no_calibration:
+        if extras and not args.no_calibration:
             try:
                 gbs, what = copy_probe(dev)
                 out["roofline"].update({"hbm_copy_gbs_measured": gbs, "hbm_copy_kernel": what,
@@ -589,13 +604,13 @@ def main() -> None:
             except Exception as ex:
                 out["roofline_verifier"]["gemm_tflops_measured"] = None
                 out["roofline_verifier"]["gemm_error"] = str(ex)[:200]
-        if world == 1 and not args.no_config5 and not config5 and args.scene == "box":
+        if extras and not args.no_config5 and not config5 and args.scene == "box":
             try:
                 out["config5"] = config5_line(dev)
             except Exception as ex:
                 out["config5"] = {"value": None, "error": str(ex)[:300]}
             torch.cuda.empty_cache()
-        if world == 1 and not args.no_cpu_baseline:
+        if extras and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline()
             except Exception as ex:

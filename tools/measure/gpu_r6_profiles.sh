@@ -10,8 +10,8 @@ rm -rf "$OUT"; mkdir -p "$OUT"
 cd "$GRAFT_REPO_ROOT"
 step() { local secs=$1 log=$2; shift 2; echo "== $*" | tee -a "$OUT/steps.log"; timeout -k 10 "$secs" "$@" > "$OUT/$log" 2>&1; local rc=$?; echo "   rc=$rc" | tee -a "$OUT/steps.log"; if [ $rc -eq 124 ] || [ $rc -eq 137 ]; then echo TIMEOUT | tee -a "$OUT/steps.log"; exit 1; fi; return 0; }
 C5="--pano-hw 1024x2048 --surfaces floor,ceiling --layers 152 --panos 16"
-LEAN="--no-cpu-baseline --no-calibration --no-config5"
-step 500 bench.log python bench.py --steps 20 --warmup 5
+LEAN="--full --no-cpu-baseline --no-calibration --no-config5"
+step 500 bench.log python bench.py --steps 20 --warmup 5 --full
 step 300 bench_cluttered.log python bench.py --steps 10 --warmup 3 --scene cluttered $LEAN
 step 300 bench_noisy.log python bench.py --steps 10 --warmup 3 --scene noisy $LEAN
 step 400 bench_c5.log python bench.py $C5 --steps 5 --warmup 2 $LEAN
