@@ -34,13 +34,14 @@ typedef enum {
     SALVE_ERR_WORKSPACE = -4
 } salve_status_t;
 
-#define SALVE_HIP_ABI_VERSION 6  /* 3: device status word (densify, resnet_forward), in-window counts from salve_bev_scatter;
+#define SALVE_HIP_ABI_VERSION 7  /* 3: device status word (densify, resnet_forward), in-window counts from salve_bev_scatter;
                                      4: salve_bev_tile_pairs; 5: panorama index (salve_bev_pano_index_*), the scatter stage writes the
                                      sparse image into out_bev (no key image in memory, salve_bev_workspace_init is gone), salve_resnet_create
                                      takes its kernel selection as `flags` -- the library reads no environment variable;
                                      6: SALVE_RESNET_CHAIN_STORE_ALL / _NO_TRANSPOSED_TILES / _NO_NEXT_FUSE, out_flags bit 4 (renders densified in the
                                      given order), salve_bev_densify_tiles, a launch of >= 1025 renders keeps its dispatch order in the workspace's key image; unknown
-                                     `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them) */
+                                     `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
+                                     7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -333,6 +334,32 @@ size_t salve_resnet_workspace_bytes(void* handle, int32_t batch);
  * status: device int32 status word or NULL (SALVE_STATUS_FP16_RANGE). */
 int salve_resnet_forward(void* handle, const void* input, int32_t batch, float* logits, void* workspace,
                          size_t workspace_bytes, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Verifier in fp32 (ABI 7): the reference's own precision, opt-in.
+ * The reference evaluates the verifier in float32 with no AMP anywhere (salve/train_utils.py:18-41) through
+ * salve/models/early_fusion.py:41-83.  The fp16 engine above stores weights and activations in fp16, which costs an
+ * error relative to the logit and a range of 65504.  This second handle family runs the SAME op
+ * program (salve_resnet_op_t rows, ktab, in2_buf projection shortcuts) with an fp32 weight blob, fp32 NHWC activations
+ * and the exact fp32-input MFMA (v_mfma_f32_32x32x2_f32): one rounding per fp32 operation, no fp16 anywhere, NaN
+ * propagated by ReLU / max-pool as torch does, no status bit for large magnitudes.  The fp16 engine and its flags are
+ * unchanged.
+ *   create:   ops / ktab exactly as for salve_resnet_create; CONV w_off is an element offset into weights_f32 (float
+ *             [*], same packing order as the fp16 blob); in_channels = the REAL input channel count (6, 12, 18), whose
+ *             padded form (a multiple of 8) must equal the Cin of the convolution that reads SALVE_NET_INPUT.
+ *             flags must be 0 (anything else is refused).  NULL on failure (salve_last_error()).
+ *   forward:  input = device float NCHW [batch, in_channels, H, W] -- the reference's torch.cat([x1..xn], 1) as it is;
+ *             the engine's first launch pads and transposes it to NHWC inside the workspace.  logits: device float
+ *             [batch, n_classes].  status: accepted for symmetry with salve_resnet_forward, never written.
+ *   workspace_bytes counts the padded input copy and the activation buffers.
+ * ------------------------------------------------------------------------------------------------ */
+void* salve_resnet_f32_create(int32_t num_layers, int32_t in_channels, const salve_resnet_op_t* ops, int32_t n_ops,
+                              const float* weights_f32, size_t weights_bytes, const float* params_f32, size_t params_bytes,
+                              const int32_t* ktab, size_t ktab_entries, int32_t flags);
+void salve_resnet_f32_destroy(void* handle);
+size_t salve_resnet_f32_workspace_bytes(void* handle, int32_t batch);
+int salve_resnet_f32_forward(void* handle, const float* input, int32_t batch, float* logits, void* workspace,
+                             size_t workspace_bytes, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,7 +17,7 @@ import os
 LIB_PATH = Path(os.environ.get("SALVE_HIP_LIB") or (Path(__file__).resolve().parent / "libsalve_hip.so"))
 
 SALVE_OK = 0
-EXPECTED_ABI = 6          # include/salve_hip.h: SALVE_HIP_ABI_VERSION
+EXPECTED_ABI = 7          # include/salve_hip.h: SALVE_HIP_ABI_VERSION
 TILE_F32_NCHW = 0
 TILE_F16_NHWC = 1
 TILE_U8X4 = 2
@@ -47,6 +47,10 @@ EXPORTED_SYMBOLS = (
     "salve_resnet_workspace_bytes",
     "salve_resnet_forward",
     "salve_resnet_num_layers",
+    "salve_resnet_f32_create",
+    "salve_resnet_f32_destroy",
+    "salve_resnet_f32_workspace_bytes",
+    "salve_resnet_f32_forward",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -145,6 +149,14 @@ def load() -> ctypes.CDLL:
     lib.salve_resnet_forward.restype = ctypes.c_int
     lib.salve_resnet_num_layers.argtypes = [vp]
     lib.salve_resnet_num_layers.restype = ctypes.c_int
+    lib.salve_resnet_f32_create.argtypes = [i32, i32, vp, i32, vp, sz, vp, sz, vp, sz, i32]
+    lib.salve_resnet_f32_create.restype = vp
+    lib.salve_resnet_f32_destroy.argtypes = [vp]
+    lib.salve_resnet_f32_destroy.restype = None
+    lib.salve_resnet_f32_workspace_bytes.argtypes = [vp, i32]
+    lib.salve_resnet_f32_workspace_bytes.restype = sz
+    lib.salve_resnet_f32_forward.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp]
+    lib.salve_resnet_f32_forward.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

@@ -1,4 +1,5 @@
 """python -m salve_amd.check_checkpoint <train_ckpt.pth> [--layers 152] [--modalities ceiling_rgb_texture,floor_rgb_texture] [--tiles DIR] [-n 64]
+                                   [--precision fp16|fp32]
 
 What fp16 storage costs THIS checkpoint: loads a reference-format checkpoint (`{"state_dict": ...}`, optional `module.` prefix --
 scripts/train.py:97-107, loaded strictly as salve/train_utils.py:229-242 does), runs N tile sets through the HIP engine (fp16
@@ -16,6 +17,11 @@ Tiles: `--tiles DIR` reads rendered BEV tiles (JPEG / PNG, the files scripts/ren
 order into sets of 2 / 4 / 6 images and put through the val / test transform (train_utils.get_val_test_transform).  Without it the
 tile sets are rendered here: seeded synthetic panoramas and random hypotheses through the fused pipeline -- mostly black images
 with textured regions, the input the verifier actually sees.
+
+--precision fp32 checks the fp32 engine instead (EarlyFusionCEResnet.set_precision("fp32"): fp32 weights, activations and tiles, the
+reference's own precision): the tiles stay fp32 (no fp16 cast of the files' tiles; rendered tile sets come from the fp32 pipeline), the
+float32 evaluation sees the same fp32 tiles, and the contract is north_star's ABSOLUTE one:
+    |logit error| <= 1e-3   and   equal arg-max,   at any logit magnitude.
 
 This module is a CHECK beside the product path, never part of it: the float32 evaluation below exists only to be compared with.
 """
@@ -60,8 +66,9 @@ def float32_forward(model, xs: Sequence[torch.Tensor]) -> torch.Tensor:
     return F.linear(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1), model.fc.weight, model.fc.bias)
 
 
-def compare(got: torch.Tensor, ref: torch.Tensor) -> dict:
-    """Statistics of HIP logits `got` against float32 logits `ref` ([N, classes], CPU)."""
+def compare(got: torch.Tensor, ref: torch.Tensor, absolute: bool = False) -> dict:
+    """Statistics of HIP logits `got` against float32 logits `ref` ([N, classes], CPU).  absolute (the fp32 engine's contract):
+    `contract_holds` asks for |logit error| <= 1e-3 absolute and equal arg-max."""
     got, ref = got.float().cpu(), ref.float().cpu()
     err = (got - ref).abs().max(1).values
     mag = ref.abs().max(1).values
@@ -73,10 +80,20 @@ def compare(got: torch.Tensor, ref: torch.Tensor) -> dict:
             "rel_err_p99": q(rel, 0.99), "rel_err_max": float(rel.max()), "prob_err_max": float(perr.max()),
             "argmax_equal": int((got.argmax(1) == ref.argmax(1)).sum()),
             "abs_1e3_holds": bool(float(err.max()) <= 1e-3),
-            "contract_holds": bool(float(rel.max()) <= 1e-3 and float(perr.max()) <= 1e-3 and bool((got.argmax(1) == ref.argmax(1)).all()))}
+            "absolute_contract": bool(absolute),
+            "contract_holds": bool((float(err.max()) <= 1e-3 if absolute else (float(rel.max()) <= 1e-3 and float(perr.max()) <= 1e-3))
+                                   and bool((got.argmax(1) == ref.argmax(1)).all()))}
 
 
 def report(st: dict, what: str) -> str:
+    if st.get("absolute_contract"):
+        return (f"{what}: {st['n']} tile sets\n"
+                f"  |logit| (largest per sample): min {st['logit_abs_min']:.2f}  median {st['logit_abs_median']:.2f}  max {st['logit_abs_max']:.2f}\n"
+                f"  logit error, absolute:        median {st['err_median']:.2e}  p99 {st['err_p99']:.2e}  max {st['err_max']:.2e}   (contract: <= 1e-3)\n"
+                f"  error / max(1, |logit|):      p99 {st['rel_err_p99']:.2e}  max {st['rel_err_max']:.2e}\n"
+                f"  softmax probabilities:        max error {st['prob_err_max']:.2e}\n"
+                f"  arg-max equal:                {st['argmax_equal']} / {st['n']}\n"
+                f"  contract (fp32 engine: absolute 1e-3) {'MET' if st['contract_holds'] else 'NOT MET'}")
     return (f"{what}: {st['n']} tile sets\n"
             f"  |logit| (largest per sample): min {st['logit_abs_min']:.2f}  median {st['logit_abs_median']:.2f}  max {st['logit_abs_max']:.2f}\n"
             f"  logit error, absolute:        median {st['err_median']:.2e}  p99 {st['err_p99']:.2e}  max {st['err_max']:.2e}"
@@ -108,12 +125,32 @@ def _tiles_from_dir(tile_dir: str, n_images: int, n_sets: int, device) -> torch.
     return torch.cat(sets)
 
 
-def _rendered_tiles(model, n_sets: int, device) -> torch.Tensor:
-    """fp16 NHWC tile sets rendered by the fused pipeline from seeded synthetic panoramas (cluttered scene) and random hypotheses."""
+def _tiles_from_dir_f32(tile_dir: str, n_images: int, n_sets: int, device) -> torch.Tensor:
+    """fp32 NCHW tile sets [N, 3 n_images, 224, 224] from image files (as _tiles_from_dir, without the fp16 cast)."""
+    import glob
+    import os
+
+    from salve_amd.utils.image_io import read_rgb
+    from salve_amd.transforms import ValTestTransform
+
+    files = sorted(f for ext in ("jpg", "jpeg", "png") for f in glob.glob(os.path.join(tile_dir, "**", f"*.{ext}"), recursive=True))
+    if len(files) < n_images:
+        raise SystemExit(f"check_checkpoint: {tile_dir} holds {len(files)} image(s); one tile set needs {n_images}")
+    tf = ValTestTransform((234, 234), (224, 224))
+    sets = []
+    for lo in range(0, min(len(files) // n_images, n_sets) * n_images, n_images):
+        xs = tf(*[read_rgb(f) for f in files[lo:lo + n_images]])
+        sets.append(torch.cat([x[None].float() for x in xs[:n_images]], 1).to(device))
+    return torch.cat(sets)
+
+
+def _rendered_tiles(model, n_sets: int, device, precision: str = "fp16") -> torch.Tensor:
+    """Tile sets rendered by the fused pipeline from seeded synthetic panoramas (cluttered scene) and random hypotheses: fp16 NHWC, or
+    with precision="fp32" fp32 NCHW (the fp32 pipeline's tiles)."""
     from salve_amd import synthetic
     from salve_amd.pipeline import RenderVerifyPipeline
 
-    pipe = RenderVerifyPipeline(model, device, chunk=None, overlap=False, streams=1, n_hypotheses=n_sets)
+    pipe = RenderVerifyPipeline(model, device, chunk=None, overlap=False, streams=1, n_hypotheses=n_sets, precision=precision)
     P = 8
     panos = [synthetic.make_pano(i, scene="cluttered") for i in range(P)]
     pipe.load_panos(np.stack([p[0] for p in panos]), np.stack([p[1] for p in panos]))
@@ -142,6 +179,31 @@ def run(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 0) -
     return compare(got, ref)
 
 
+def run_f32(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 0) -> dict:
+    """The fp32 engine against the float32 evaluation on the same fp32 NCHW tiles [N, 3 n, 224, 224] on `device`; absolute contract."""
+    import copy
+
+    n_img = model.num_images
+    prev = model.precision
+    with torch.no_grad():
+        model.set_precision("fp32")
+        try:
+            xs = [tiles[:, 3 * k:3 * k + 3].contiguous() for k in range(n_img)]
+            got = model(*(xs + [None] * (6 - n_img))).cpu()
+        finally:
+            model.set_precision(prev)
+        model.check(device, "check_checkpoint: HIP fp32 forward")
+        if threads:
+            torch.set_num_threads(threads)
+        cpu_model = model
+        if next(model.parameters()).device.type != "cpu":
+            cpu_model = copy.deepcopy(model).cpu()
+            cpu_model._compiled = None
+        x = tiles.cpu()
+        ref = torch.cat([float32_forward(cpu_model, [x[lo:lo + batch, 3 * k:3 * k + 3] for k in range(n_img)]) for lo in range(0, x.shape[0], batch)])
+    return compare(got, ref, absolute=True)
+
+
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m salve_amd.check_checkpoint", description=__doc__.split("\n\n")[1])
     ap.add_argument("checkpoint", help="train_ckpt.pth: a dict with 'state_dict' (scripts/train.py:97-107)")
@@ -150,6 +212,8 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("--tiles", default=None, help="directory of rendered BEV tiles; default: render synthetic tile sets here")
     ap.add_argument("-n", type=int, default=64, help="tile sets to run")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--precision", choices=("fp16", "fp32"), default="fp16",
+                    help="verifier engine to check: fp16 (the default engine; relative contract) or fp32 (the reference's precision; absolute 1e-3)")
     args = ap.parse_args(argv)
 
     from salve_amd.models.early_fusion import EarlyFusionCEResnet
@@ -162,9 +226,13 @@ def main(argv: List[str] = None) -> int:
     dev = torch.device(args.device)
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise SystemExit("check_checkpoint: needs the HIP device (the engine under test has no CPU path)")
-    tiles = _tiles_from_dir(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev)
-    st = run(model, tiles, dev)
-    print(report(st, f"{args.checkpoint} (ResNet-{args.layers}, {model.num_images} images per set, "
+    if args.precision == "fp32":
+        tiles = _tiles_from_dir_f32(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev, "fp32")
+        st = run_f32(model, tiles, dev)
+    else:
+        tiles = _tiles_from_dir(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev)
+        st = run(model, tiles, dev)
+    print(report(st, f"{args.checkpoint} (ResNet-{args.layers}, {model.num_images} images per set, {'fp32 engine, ' if args.precision == 'fp32' else ''}"
                      f"{'tiles from ' + args.tiles if args.tiles else 'tile sets rendered from synthetic panoramas'})"))
     return 0 if st["contract_holds"] else 1
 

@@ -6,6 +6,10 @@ names (`conv1.weight`, `fc.{weight,bias}`, `resnet.*`) so the reference's checkp
 (eval-mode semantics, what scripts/test.py runs under torch.no_grad) and executes the network in
 salve_amd/csrc/resnet.hip.  There is no CPU or eager fallback: without the HIP library, or on a CPU tensor,
 `forward` raises.
+
+Precision: "fp16" (default; fp16 weights and activations, fp32 accumulation -- DESIGN.md section 2) or, after
+`model.set_precision("fp32")`, the reference's own float32 evaluation (salve/train_utils.py:18-41 uses no AMP) on the fp32
+engine of salve_amd/csrc/resnet_f32.hip: the input is passed as the fp32 tensor it is, with no fp16 rounding.
 """
 
 from __future__ import annotations
@@ -16,7 +20,7 @@ import torch
 from torch import Tensor, nn
 
 import salve_amd.models.resnet_factory as resnet_factory
-from salve_amd.models.hip_resnet import HipResNet, nchw_to_input
+from salve_amd.models.hip_resnet import PRECISIONS, HipResNet, HipResNetF32, nchw_to_input
 
 _TWO = [{"layout"}, {"ceiling_rgb_texture"}, {"floor_rgb_texture"}]
 _FOUR = {"ceiling_rgb_texture", "floor_rgb_texture"}
@@ -47,27 +51,43 @@ class EarlyFusionCEResnet(nn.Module):
         self.num_images = num_input_images(self.modalities)
         self.conv1 = nn.Conv2d(3 * self.num_images, self.inplanes, kernel_size=7, stride=2, padding=3, bias=False)
         self.fc = nn.Linear(resnet_factory.get_resnet_feature_dim(num_layers), num_classes)
+        self.precision = "fp16"
         self._compiled: Optional[HipResNet] = None
         self._compiled_key = None
+
+    def set_precision(self, precision: str) -> "EarlyFusionCEResnet":
+        """"fp16" (default) or "fp32" (the reference's precision: fp32 weights, activations and arithmetic).  Returns self."""
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        self.precision = precision
+        return self
 
     # ------------------------------------------------------------------ HIP engine
     def _state_key(self, device: torch.device):
         return (str(device), tuple((k, v._version, v.data_ptr()) for k, v in self.state_dict().items()))
 
-    def compiled(self, device: torch.device, flags: int = 0) -> HipResNet:
-        """Fold + pack the current weights for `device` (cached until a parameter changes).  flags: the library's kernel
-        selection (_lib.RESNET_*; 0 = the product's -- development tools and the bit-identity tests pass others)."""
-        key = (self._state_key(device), int(flags))
+    def compiled(self, device: torch.device, flags: int = 0, precision: Optional[str] = None):
+        """Fold + pack the current weights for `device` (cached per weights, flags and precision): a HipResNet (fp16) or a
+        HipResNetF32 (fp32).  precision: None = the model's (`set_precision`); the pipeline passes its own.  flags: the fp16
+        library's kernel selection (_lib.RESNET_*; 0 = the product's -- development tools and the bit-identity tests pass
+        others); the fp32 engine accepts 0 only."""
+        precision = self.precision if precision is None else precision
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+        key = (self._state_key(device), int(flags), precision)
         if self._compiled is None or self._compiled_key != key:
-            self._compiled = HipResNet(self.state_dict(), self.num_layers, device, flags=flags)
+            self._compiled = None   # (the old handle's device memory goes before the new one is allocated)
+            engine = HipResNetF32 if precision == "fp32" else HipResNet
+            self._compiled = engine(self.state_dict(), self.num_layers, device, flags=flags)
             self._compiled_key = key
         return self._compiled
 
     def forward(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor], x4: Optional[Tensor], x5: Optional[Tensor],
                 x6: Optional[Tensor]) -> torch.Tensor:
         """Early fusion = concatenation along channels (early_fusion.py:55-65), then the ResNet.
-        Inputs must be finite: the HIP kernels' ReLUs turn a NaN activation into 0 instead of propagating it to the logits
-        as torch does (salve_amd/csrc/resnet.hip: track4).  Magnitudes beyond fp16 are reported through `check()`."""
+        fp16 (default): inputs must be finite -- the HIP kernels' ReLUs turn a NaN activation into 0 instead of propagating it
+        to the logits as torch does (salve_amd/csrc/resnet.hip: track4) -- and magnitudes beyond fp16 are reported through
+        `check()`.  fp32 (`set_precision("fp32")`): torch.cat(xs, 1) goes to the fp32 engine unrounded; NaN propagates."""
         n = num_input_images(self.modalities)  # raises RuntimeError on unsupported sets, like the reference
         xs = [x1, x2, x3, x4, x5, x6][:n]
         if any(x is None for x in xs):
@@ -77,6 +97,8 @@ class EarlyFusionCEResnet(nn.Module):
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("the HIP verifier is inference-only: call model.eval() / use torch.no_grad()")
         eng = self.compiled(x1.device)
+        if self.precision == "fp32":
+            return eng.forward_nchw(torch.cat(xs, dim=1))
         return eng.forward_nhwc(nchw_to_input(xs, eng.in_channels))
 
     def check(self, device=None, what: str = "EarlyFusionCEResnet.forward") -> None:
@@ -88,5 +110,8 @@ class EarlyFusionCEResnet(nn.Module):
         status.check(device if device is not None else torch.device("cuda", torch.cuda.current_device()), what)
 
     def forward_nhwc(self, x: Tensor) -> Tensor:
-        """Fused-pipeline entry: fp16 [B,224,224,Cpad] tiles written by the rasteriser -> fp32 logits."""
+        """Fused-pipeline entry: fp16 [B,224,224,Cpad] tiles written by the rasteriser -> fp32 logits (fp16 precision only)."""
+        if self.precision == "fp32":
+            raise RuntimeError("EarlyFusionCEResnet.forward_nhwc takes fp16 NHWC tiles: it is the fp16 engine's entry and the model is "
+                               "set to fp32 -- call forward(x1..x6) with the fp32 NCHW tensors, or set_precision(\"fp16\")")
         return self.compiled(x.device).forward_nhwc(x)

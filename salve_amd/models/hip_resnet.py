@@ -1,7 +1,8 @@
 """Host side of the HIP verifier: fold BatchNorm, pack weights, emit the op program, run it.
 
 No arithmetic of the forward pass happens here -- this module only prepares the immutable weight blobs
-(once per checkpoint) and owns the workspace; the network runs in salve_amd/csrc/resnet.hip.
+(once per checkpoint) and owns the workspace; the network runs in salve_amd/csrc/resnet.hip (fp16 storage, the product's
+default) or salve_amd/csrc/resnet_f32.hip (fp32 throughout, the reference's precision: `precision="fp32"`).
 """
 
 from __future__ import annotations
@@ -38,8 +39,20 @@ def fold_bn(w: torch.Tensor, bn: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor,
     return w.float() * scale[:, None, None, None], bn["bias"].float() - bn["running_mean"].float() * scale
 
 
+PRECISIONS = ("fp16", "fp32")
+
+
+def _check_precision(precision: str) -> str:
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return precision
+
+
 class _Builder:
-    def __init__(self) -> None:
+    """precision "fp16" (default): `weights` holds the fp16 BITS (int16 arrays); "fp32": the same layout as float32."""
+
+    def __init__(self, precision: str = "fp16") -> None:
+        self.precision = _check_precision(precision)
         self.ops: List[tuple] = []
         self.weights: List[np.ndarray] = []
         self.params: List[np.ndarray] = []
@@ -47,6 +60,11 @@ class _Builder:
         self.w_elems = 0
         self.p_elems = 0
         self.k_elems = 0
+
+    def _pack(self, w: torch.Tensor) -> np.ndarray:
+        if self.precision == "fp32":
+            return w.float().numpy().copy()
+        return w.to(torch.float16).view(torch.int16).numpy().copy()
 
     def conv(self, w: torch.Tensor, b: torch.Tensor, in_buf: int, out_buf: int, res_buf: int, Hi: int, Wi: int,
              stride: int, pad: int, relu: bool, kw_pad: int = 0) -> Tuple[int, int]:
@@ -70,7 +88,7 @@ class _Builder:
             c8 = q % (Cinp // 8)
             kw = (q // (Cinp // 8)) % KWp
             kh = q // ((Cinp // 8) * KWp)
-        bits = wp.reshape(Cout, K).to(torch.float16).view(torch.int16).numpy().copy()
+        bits = self._pack(wp.reshape(Cout, K))
         tab = ((kh & 0xFF) | ((kw & 0xFF) << 8) | ((c8 * 8) << 16)).astype(np.int32)
         Ho = (Hi + 2 * pad - KH) // stride + 1
         Wo = (Wi + 2 * pad - KW) // stride + 1
@@ -94,7 +112,7 @@ class _Builder:
         assert w.shape[2:] == (1, 1) and w2.shape[2:] == (1, 1) and Cin % 64 == 0 and Cin2 % 64 == 0 and Cout % 64 == 0
         assert (Hi2 - 1) // stride2 + 1 == Hi and (Wi2 - 1) // stride2 + 1 == Wi
         wcat = torch.cat([w.reshape(Cout, Cin), w2.reshape(Cout, Cin2)], dim=1).float()
-        bits = wcat.to(torch.float16).view(torch.int16).numpy().copy()
+        bits = self._pack(wcat)
         tab = np.zeros((Cin + Cin2) // 8, dtype=np.int32)  # not read by the point-wise kernel
         self.ops.append((OP_CONV, in_buf, out_buf, NO_BUF, Hi, Wi, Cin, Hi, Wi, Cout, 1, 1, 1, 0, 1, 0,
                          self.w_elems, self.p_elems, self.k_elems, in2_buf, Cin2, stride2, Hi2, Wi2, 0))
@@ -125,12 +143,13 @@ def _bn(sd: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
     return {k: sd[f"{prefix}.{k}"] for k in ("weight", "bias", "running_mean", "running_var")}
 
 
-def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: Tuple[int, int] = (224, 224)):
+def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: Tuple[int, int] = (224, 224), precision: str = "fp16"):
     """state_dict with the reference's keys (conv1.weight, fc.*, resnet.*; an optional `module.` prefix from
-    DataParallel is stripped) -> (ops array, fp16 weight bits, fp32 params, ktab, padded input channels)."""
+    DataParallel is stripped) -> (ops array, fp16 weight bits, fp32 params, ktab, padded input channels).
+    precision="fp32": the same program and ktab with the weights as float32 (the fp32 engine's blob) instead of fp16 bits."""
     sd = {(k[len("module."):] if k.startswith("module.") else k): v.detach().cpu() for k, v in state_dict.items()}
     kind, blocks = RESNET_SPECS[num_layers]
-    b = _Builder()
+    b = _Builder(_check_precision(precision))
     H, W = in_hw
     w1, bias1 = fold_bn(sd["conv1.weight"], _bn(sd, "resnet.bn1"))
     cin_p = pad_channels(w1.shape[1])
@@ -169,6 +188,14 @@ def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: T
     feat = sd["fc.weight"].shape[1]
     b.fc(sd["fc.weight"], sd["fc.bias"], x, H, W, feat)
     ops = np.array(b.ops, dtype=OP_DTYPE)
+    if precision == "fp32":
+        # the fp32 engine propagates NaN as torch does, but a non-finite weight is a diverged checkpoint either way: refused as in
+        # fp16.  Magnitudes beyond 65504 are fp32's to hold.
+        weights = np.concatenate(b.weights).astype(np.float32)
+        for arr, what in ((weights, "convolution weights (after folding BatchNorm)"), (np.concatenate(b.params), "biases / fc parameters")):
+            if not np.isfinite(arr).all():
+                raise ValueError(f"checkpoint has non-finite {what}")
+        return ops, weights, np.concatenate(b.params).astype(np.float32), np.concatenate(b.ktab).astype(np.int32), cin_p
     # the kernels' ReLUs and range tracking swallow NaNs (resnet.hip: track4): a non-finite weight -- a diverged checkpoint --
     # would come out as finite, wrong logits; refuse it here, where torch would have propagated it to the output
     for arr, what in ((np.concatenate(b.weights).astype(np.int16).view(np.float16), "convolution weights (after folding BatchNorm)"),
@@ -227,6 +254,70 @@ class HipResNet:
                 ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
             )
         _lib.check(st, "salve_resnet_forward")
+        return out
+
+
+class HipResNetF32:
+    """The fp32 verifier on one GPU (salve_resnet_f32_*, salve_amd/csrc/resnet_f32.hip): the reference's precision -- fp32
+    weights, activations and MFMA arithmetic, NaN propagated, no fp16 range.  Same op program as HipResNet; immutable device
+    weights inside a library handle + a workspace this object owns."""
+
+    def __init__(self, state_dict: Dict[str, torch.Tensor], num_layers: int, device: torch.device, flags: int = 0) -> None:
+        """flags: must be 0 (the library refuses anything else; the argument exists so that callers see the refusal)."""
+        self.lib = _lib.load()
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.SalveHipError("HipResNetF32 needs a HIP device ('cuda:N'); there is no CPU path")
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
+        ops, weights, params, ktab, cin_p = build_program(state_dict, num_layers, precision="fp32")
+        self.in_channels = int(sd["conv1.weight"].shape[1])   # the real count (6, 12, 18): the input is the reference's NCHW tensor
+        self.padded_channels = cin_p
+        self.num_classes = int(ops[-1]["Cout"])
+        self.n_ops = len(ops)
+        self.in_hw = (int(ops[0]["Hi"]), int(ops[0]["Wi"]))
+        with torch.cuda.device(self.device):
+            h = self.lib.salve_resnet_f32_create(
+                num_layers, self.in_channels, ops.ctypes.data_as(ctypes.c_void_p), len(ops),
+                weights.ctypes.data_as(ctypes.c_void_p), weights.nbytes, params.ctypes.data_as(ctypes.c_void_p), params.nbytes,
+                ktab.ctypes.data_as(ctypes.c_void_p), ktab.size, int(flags),
+            )
+        if not h:
+            _lib.check(-1, "salve_resnet_f32_create")
+        self.handle = ctypes.c_void_p(h)
+        self._ws = None
+
+    def __del__(self) -> None:
+        try:
+            if getattr(self, "handle", None):
+                self.lib.salve_resnet_f32_destroy(self.handle)
+                self.handle = None
+        except Exception:
+            pass
+
+    def workspace_bytes(self, batch: int) -> int:
+        return int(self.lib.salve_resnet_f32_workspace_bytes(self.handle, int(batch)))
+
+    def forward_nchw(self, x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+        """x: fp32 [B, in_channels, 224, 224] on the device (torch.cat([x1..xn], 1), unrounded) -> fp32 logits [B, num_classes]."""
+        if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != self.in_channels or tuple(x.shape[2:]) != self.in_hw:
+            raise ValueError(f"HipResNetF32.forward_nchw takes fp32 [B, {self.in_channels}, {self.in_hw[0]}, {self.in_hw[1]}], "
+                             f"got {x.dtype} {tuple(x.shape)}")
+        if x.device != self.device:
+            raise ValueError(f"input on {x.device}, engine on {self.device}")
+        x = x.contiguous()
+        B = int(x.shape[0])
+        need = self.workspace_bytes(B)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if out is None:
+            out = torch.empty((B, self.num_classes), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            st = self.lib.salve_resnet_f32_forward(
+                self.handle, ctypes.c_void_p(x.data_ptr()), B, ctypes.c_void_p(out.data_ptr()),
+                ctypes.c_void_p(self._ws.data_ptr()), self._ws.numel(), status.ptr(self.device),
+                ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream),
+            )
+        _lib.check(st, "salve_resnet_f32_forward")
         return out
 
 

@@ -93,21 +93,30 @@ class RenderVerifyPipeline:
     LAUNCH_HBM_FRACTION = 0.5   # of the HBM that is free when the pipeline is created: BEV + tile + rasteriser + activation workspaces of one launch
 
     def __init__(self, model, device: torch.device, pano_hw: Tuple[int, int] = (512, 1024), chunk: Optional[int] = None,
-                 overlap: bool = True, streams: int = 3, n_hypotheses: Optional[int] = None, fuse_tiles: bool = True) -> None:
+                 overlap: bool = True, streams: int = 3, n_hypotheses: Optional[int] = None, fuse_tiles: bool = True,
+                 precision: str = "fp16") -> None:
         """chunk: hypotheses per render / verify launch.  None (default): chosen by `pick_launch` from the HBM that is free now --
         the whole shard of `n_hypotheses` rows in one launch if its workspaces fit LAUNCH_HBM_FRACTION of it (a shard of 4096
-        hypotheses needs 57 GB with one surface / ResNet-50, 80 GB with two / ResNet-152, of 288), else the fewest equal launches."""
+        hypotheses needs 57 GB with one surface / ResNet-50, 80 GB with two / ResNet-152, of 288), else the fewest equal launches.
+        precision: "fp16" (default: fp16 NHWC tiles, the fp16 verifier engine) or "fp32" -- the reference's precision: fp32 NCHW tiles
+        [chunk, 3 n, 224, 224] (salve_bev_tiles, SALVE_TILE_F32_NCHW: the same LUT values, not rounded to fp16) into the fp32 engine.
+        fp32 renders its tiles with launches of their own (fuse_tiles is forced off) and does not support the layout modality."""
         self.device = torch.device(device)
+        if precision not in ("fp16", "fp32"):
+            raise ValueError(f"precision must be 'fp16' or 'fp32', got {precision!r}")
+        self.precision = precision
         # the status word is one per device: a bit an earlier, unchecked caller left behind must be reported as ITS failure,
         # not raised later by this pipeline's check() under the wrong name
         status.check(self.device, "a launch issued before this RenderVerifyPipeline was created")
         self.model = model
         # fuse_tiles (default): the densify kernel writes every render's verifier tile itself (salve_bev_densify_tiles); False: densify, then
         # salve_bev_tile_pairs in a launch of its own (the form of rounds 2-5; same bits: tests/test_gpu_rasteriser.py)
-        self.fuse_tiles = bool(fuse_tiles)
+        self.fuse_tiles = bool(fuse_tiles) and precision == "fp16"
         self.surfaces = surfaces_for(model.modalities)
         self.has_layout = "layout" in set(model.modalities)
-        self.engine = model.compiled(self.device)
+        if precision == "fp32" and self.has_layout:
+            raise ValueError('RenderVerifyPipeline(precision="fp32") does not support the "layout" modality (its tiles are fp16 only)')
+        self.engine = model.compiled(self.device, precision=precision)
         self.ras = BevRasteriser(self.device, pano_hw=pano_hw)
         S = len(self.surfaces)
         Hb, Wb = self.ras.bev_hw
@@ -123,9 +132,13 @@ class RenderVerifyPipeline:
         # kernel.  (Requires the library to be built without SLP-packed fp32: DESIGN.md section 8.)
         self.nbuf = nbuf
         self.bevs = [torch.empty((chunk * S, Hb, Wb), dtype=torch.int32, device=self.device) for _ in range(self.nbuf)]
-        # tiles: fp16 NHWC, pad channels (never written) stay zero
-        self.tile_bufs = [torch.zeros((chunk, self.ras.crop, self.ras.crop, self.engine.in_channels), dtype=torch.float16,
-                                      device=self.device) for _ in range(self.nbuf)]
+        # tiles: fp16 NHWC, pad channels (never written) stay zero; fp32: NCHW with the real channel count, every channel written
+        if precision == "fp32":
+            self.tile_bufs = [torch.zeros((chunk, self.engine.in_channels, self.ras.crop, self.ras.crop), dtype=torch.float32,
+                                          device=self.device) for _ in range(self.nbuf)]
+        else:
+            self.tile_bufs = [torch.zeros((chunk, self.ras.crop, self.ras.crop, self.engine.in_channels), dtype=torch.float16,
+                                          device=self.device) for _ in range(self.nbuf)]
         self.bev, self.tiles = self.bevs[0], self.tile_bufs[0]
         # layout modality: the posed layout images of a chunk (salve_layout_rasterise), one per hypothesis
         self.layout_bevs = [torch.empty((chunk, Hb, Wb), dtype=torch.int32, device=self.device) for _ in range(self.nbuf)] if self.has_layout else None
@@ -152,8 +165,12 @@ class RenderVerifyPipeline:
         Hb, Wb = self.ras.bev_hw
         lib = self.ras.lib
         ws_render = lib.salve_bev_workspace_bytes(ctypes.byref(self.ras.cfg), 2) - lib.salve_bev_workspace_bytes(ctypes.byref(self.ras.cfg), 1)
-        act = lib.salve_resnet_workspace_bytes(self.engine.handle, 2) - lib.salve_resnet_workspace_bytes(self.engine.handle, 1)
-        tile = self.ras.crop * self.ras.crop * self.engine.in_channels * 2
+        if self.precision == "fp32":
+            act = self.engine.workspace_bytes(2) - self.engine.workspace_bytes(1)
+            tile = self.ras.crop * self.ras.crop * self.engine.in_channels * 4
+        else:
+            act = lib.salve_resnet_workspace_bytes(self.engine.handle, 2) - lib.salve_resnet_workspace_bytes(self.engine.handle, 1)
+            tile = self.ras.crop * self.ras.crop * self.engine.in_channels * 2
         bev = (S + (1 if self.has_layout else 0)) * Hb * Wb * 4
         return int(nbuf * (bev + tile) + ws_slots * S * ws_render + act)
 
@@ -252,6 +269,8 @@ class RenderVerifyPipeline:
             "jobs2": self.ras.upload_tile_jobs(st(jobs2_bev), st(jobs2_slot), st(jobs2_chan), pretiled=True),
             "rjobs_a": self.ras.upload_tile_jobs(np.zeros(N * S, dtype=np.int64), rj_slot, rj_chan_a),
             "rjobs_b": self.ras.upload_tile_jobs(rj_ident, rj_slot, rj_chan_b, pretiled=True),
+            # fp32 tiles: the identity renders' tiles straight from self.ref_bev (salve_bev_tiles has no pretiled input)
+            "jobs2_bev": self.ras.upload_tile_jobs(st(jobs2_bev), st(jobs2_slot), st(jobs2_chan)) if self.precision == "fp32" else None,
             "in_window": torch.zeros(N * S, dtype=torch.int32, device=self.device),  # posed renders IN RENDER ORDER, filled by score()
             "ready": torch.cuda.Event(),   # the tables are on the device: launches on other streams wait for it
         }
@@ -316,7 +335,15 @@ class RenderVerifyPipeline:
                     self.ras.densify(n * S, bev)
             if e1 is not None:
                 e1.record()
-            if not self.fuse_tiles:
+            if self.precision == "fp32":
+                with tracing.range("salve.tiles"):
+                    # fp32 NCHW tiles of the posed renders (this chunk's images) and of the identity renders (ref_bev), in the channel
+                    # and pair order of the fp16 job tables; a call takes at most 65535 jobs
+                    for jobs, src in ((prepared["jobs1"], bev), (prepared["jobs2_bev"], self.ref_bev)):
+                        for k in range(0, n * S, 65535):
+                            m = min(65535, n * S - k)
+                            self.ras.tiles(src, jobs[(lo * S + k) * jb:], m, tiles, _lib.TILE_F32_NCHW, self.engine.in_channels)
+            elif not self.fuse_tiles:
                 with tracing.range("salve.tiles"):
                     # (jobs1[k] / jobs2[k] are the two halves of one surface's six channels of one sample: prepare())
                     self.ras.tile_pairs(bev, prepared["jobs1"][lo * S * jb:], self.ref_tiles, prepared["jobs2"][lo * S * jb:], n * S, tiles,
@@ -334,7 +361,10 @@ class RenderVerifyPipeline:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         with tracing.range("salve.verify"):
-            self.engine.forward_nhwc(self.tile_bufs[buf][:n], out=out)
+            if self.precision == "fp32":
+                self.engine.forward_nchw(self.tile_bufs[buf][:n], out=out)
+            else:
+                self.engine.forward_nhwc(self.tile_bufs[buf][:n], out=out)
         if vtimers is not None:
             e1.record()
             vtimers.append((e0, e1, n))
