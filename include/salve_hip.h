@@ -41,7 +41,8 @@ typedef enum {
                                      6: SALVE_RESNET_CHAIN_STORE_ALL / _NO_TRANSPOSED_TILES / _NO_NEXT_FUSE, out_flags bit 4 (renders densified in the
                                      given order), salve_bev_densify_tiles, a launch of >= 1025 renders keeps its dispatch order in the workspace's key image; unknown
                                      `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
-                                     7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged) */
+                                     7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
+                                        additive within 7: salve_conv_f32_* (training convolutions) and salve_bev_tiles_aug */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -240,6 +241,24 @@ int salve_bev_tiles(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const sal
                     const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
                     void* out, int32_t out_format, int32_t out_c, void* stream);
 
+/* The reference's TRAIN transform (salve/train_utils.py:63-124): Resize -> Crop at a given offset -> RandomHorizontalFlip ->
+ * RandomVerticalFlip -> ToTensor -> Normalize, fp32 NCHW only; the draws are the caller's (one per job).  Same 11-bit taps and LUT
+ * as salve_bev_tiles: with crop_y = crop_x = (resize - crop) / 2 and flags = 0 the output is bit-identical to salve_bev_tiles'
+ * SALVE_TILE_F32_NCHW output.
+ *   aug   device salve_tile_aug_t [n_jobs]: crop offsets inside the resized image, 0 <= crop_y, crop_x <= resize - crop (the
+ *         kernel clamps them into that range: it never reads outside the taps), flags SALVE_TILE_HFLIP | SALVE_TILE_VFLIP
+ *   out   float [slots, out_c, crop, crop] */
+typedef struct {
+    int32_t crop_y, crop_x; /* top-left corner of the crop inside the resize x resize image */
+    int32_t flags;          /* SALVE_TILE_HFLIP (mirror columns) | SALVE_TILE_VFLIP (mirror rows) */
+    int32_t reserved;
+} salve_tile_aug_t;
+#define SALVE_TILE_HFLIP 1
+#define SALVE_TILE_VFLIP 2
+int salve_bev_tiles_aug(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs, const salve_tile_aug_t* aug,
+                        int32_t n_jobs, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                        float* out, int32_t out_c, void* stream);
+
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,
  * both go to sample jobs_a[k].slot ( == jobs_b[k].slot), channels jobs_a[k].chan .. + 2 and jobs_b[k].chan .. + 2, which
@@ -360,6 +379,39 @@ void salve_resnet_f32_destroy(void* handle);
 size_t salve_resnet_f32_workspace_bytes(void* handle, int32_t batch);
 int salve_resnet_f32_forward(void* handle, const float* input, int32_t batch, float* logits, void* workspace,
                              size_t workspace_bytes, int32_t* status, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training convolutions in fp32 (additive within ABI 7): forward, backward-data and backward-weight of ONE convolution, the
+ * hot path of a training step of the verifier (the reference trains in fp32: scripts/train.py and the configs under salve/configs).
+ * Everything around them -- BatchNorm with batch statistics, ReLU, residual adds, pooling, the fc layer, the loss and Adam --
+ * is the caller's (torch autograd: salve_amd/models/trainable.py).
+ *   Layouts: activations NHWC fp32 [batch, H, W, C] (torch's channels_last memory), weights [Cout][KH][KW][Cin] fp32.  Every
+ *            pointer is a device pointer, 16-byte aligned.  Cin counts the caller's zero-padded channels: the stem's 6 / 12 / 18
+ *            input channels are passed as 8 / 16 / 24.
+ *   Shapes:  1 x 1 (pad 0) and 3 x 3 (pad 1) with stride 1 or 2, Cin and Cout 64..2048 in steps of 64; the 7 x 7 / 2 / pad 3 stem
+ *            with Cin 8, 16 or 24 and Cout 64..2048 in steps of 64.  Ho, Wo must be the convolution's output size.  Anything
+ *            else: SALVE_ERR_BAD_ARG.  The stem's backward-data is SALVE_ERR_UNSUPPORTED: the network input needs no gradient.
+ *   Workspace: salve_conv_f32_workspace_bytes(d, pass) bytes of device memory (0 = the descriptor or pass is refused); it holds
+ *            nothing from one call to the next.
+ *   Results: forward / backward-data are one fp32 fma chain per output; backward-weight splits the batch * Ho * Wo pixels over
+ *            workgroups into fp32 partial sums that are added in a fixed order -- no atomics, the same inputs give bit-identical
+ *            dW.  All three overwrite their output (no accumulation into it).
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t batch, Hi, Wi, Cin, Ho, Wo, Cout, KH, KW, stride, pad;
+} salve_conv_desc_t;
+#define SALVE_CONV_FWD 0
+#define SALVE_CONV_DGRAD 1
+#define SALVE_CONV_WGRAD 2
+size_t salve_conv_f32_workspace_bytes(const salve_conv_desc_t* d, int32_t pass);
+/* y [batch, Ho, Wo, Cout] = conv(x [batch, Hi, Wi, Cin], w): no bias, no activation. */
+int salve_conv_f32_forward(const salve_conv_desc_t* d, const float* x, const float* w, float* y, void* ws, size_t ws_bytes, void* stream);
+/* dx [batch, Hi, Wi, Cin] = d(sum dy . y) / dx for dy [batch, Ho, Wo, Cout]. */
+int salve_conv_f32_backward_data(const salve_conv_desc_t* d, const float* dy, const float* w, float* dx, void* ws, size_t ws_bytes,
+                                 void* stream);
+/* dw [Cout][KH][KW][Cin] = sum over pixels of dy (x) the input patch. */
+int salve_conv_f32_backward_weight(const salve_conv_desc_t* d, const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes,
+                                   void* stream);
 
 #ifdef __cplusplus
 }

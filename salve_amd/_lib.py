@@ -51,6 +51,11 @@ EXPORTED_SYMBOLS = (
     "salve_resnet_f32_destroy",
     "salve_resnet_f32_workspace_bytes",
     "salve_resnet_f32_forward",
+    "salve_bev_tiles_aug",
+    "salve_conv_f32_workspace_bytes",
+    "salve_conv_f32_forward",
+    "salve_conv_f32_backward_data",
+    "salve_conv_f32_backward_weight",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -84,7 +89,19 @@ HYP_DTYPE = np.dtype(
 )
 TILE_JOB_DTYPE = np.dtype([("bev_offset", "<i8"), ("slot", "<i4"), ("chan", "<i4")])
 LAYOUT_DTYPE = np.dtype([("n_poly", "<i4"), ("poly_off", "<i4"), ("n_seg", "<i4"), ("seg_off", "<i4")])
-assert HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16
+TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
+TILE_HFLIP, TILE_VFLIP = 1, 2
+assert HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
+
+# salve_conv_f32_* passes (include/salve_hip.h: SALVE_CONV_*)
+CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
+SALVE_ERR_BAD_ARG, SALVE_ERR_UNSUPPORTED = -1, -2
+
+
+class ConvDesc(ctypes.Structure):
+    """salve_conv_desc_t"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("batch", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad")]
 
 _lib = None
 
@@ -157,6 +174,13 @@ def load() -> ctypes.CDLL:
     lib.salve_resnet_f32_workspace_bytes.restype = sz
     lib.salve_resnet_f32_forward.argtypes = [vp, vp, i32, vp, vp, sz, vp, vp]
     lib.salve_resnet_f32_forward.restype = ctypes.c_int
+    lib.salve_bev_tiles_aug.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]
+    lib.salve_bev_tiles_aug.restype = ctypes.c_int
+    lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
+    lib.salve_conv_f32_workspace_bytes.restype = sz
+    for name in ("salve_conv_f32_forward", "salve_conv_f32_backward_data", "salve_conv_f32_backward_weight"):
+        getattr(lib, name).argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, sz, vp]
+        getattr(lib, name).restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

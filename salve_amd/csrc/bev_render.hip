@@ -913,6 +913,29 @@ __global__ __launch_bounds__(256) void bev_tile_kernel(const uint32_t* __restric
     }
 }
 
+// salve_bev_tiles_aug: the train transform's tile -- bev_tile_kernel's F32_NCHW arithmetic (tile_pixel: the same taps, the same LUT) at
+// the job's crop offset, with the output pixel (i, j) taken from the crop's (crop-1-i if VFLIP, crop-1-j if HFLIP): the flips come after
+// the crop, as in the reference's Compose.  Offsets are clamped into [0, resize - crop] so that no tap outside the tables is read.
+__global__ __launch_bounds__(256) void bev_tile_aug_kernel(const uint32_t* __restrict__ bev, int W, const salve_tile_job_t* __restrict__ jobs,
+                                                           const salve_tile_aug_t* __restrict__ aug, const int32_t* __restrict__ coef_y,
+                                                           const int32_t* __restrict__ coef_x, int resize, int crop, const float* __restrict__ lut,
+                                                           float* __restrict__ out, int out_c) {
+    const salve_tile_job_t job = jobs[blockIdx.y];
+    const salve_tile_aug_t a = aug[blockIdx.y];
+    const int idx = blockIdx.x * 256 + threadIdx.x;
+    if (idx >= crop * crop) return;
+    const int i = idx / crop, j = idx % crop;
+    const int oy = min(max(a.crop_y, 0), resize - crop), ox = min(max(a.crop_x, 0), resize - crop);
+    const int si = (a.flags & SALVE_TILE_VFLIP) ? crop - 1 - i : i, sj = (a.flags & SALVE_TILE_HFLIP) ? crop - 1 - j : j;
+    const int4 cy = reinterpret_cast<const int4*>(coef_y)[si + oy];
+    const int4 cx = reinterpret_cast<const int4*>(coef_x)[sj + ox];
+    float v[3];
+    tile_pixel(bev + job.bev_offset, W, cy, cx, lut, v);
+    float* o = out + ((size_t)job.slot * out_c + job.chan) * crop * crop + idx;
+#pragma unroll
+    for (int ch = 0; ch < 3; ch++) o[(size_t)ch * crop * crop] = v[ch];
+}
+
 // One tile pixel of image `img`: cv2 INTER_LINEAR on uint8 with 11-bit taps, then the normalisation LUT (bev_tile_kernel's arithmetic).
 // Both tiles of an early-fusion pair per thread, six channels (plus the sample's zero padding behind its last group) in
 // whole-pixel stores: see salve_bev_tile_pairs in salve_hip.h.
@@ -1442,6 +1465,23 @@ int salve_bev_tiles(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const sal
     dim3 g((crop * crop + 255) / 256, n_jobs);
     hipLaunchKernelGGL(bev_tile_kernel, g, dim3(256), 0, (hipStream_t)stream, bev, bev_w, jobs, coef_y, coef_x, resize, crop,
                        lut, out, out_format, out_c);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
+int salve_bev_tiles_aug(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs, const salve_tile_aug_t* aug,
+                        int32_t n_jobs, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                        float* out, int32_t out_c, void* stream) {
+    if (n_jobs == 0) return SALVE_OK;
+    if (!bev || !jobs || !aug || !coef_y || !coef_x || !lut || !out || n_jobs < 0 || bev_h <= 0 || bev_w <= 0) {
+        salve_fail("salve_bev_tiles_aug: null pointer or bad size");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (crop <= 0 || resize < crop || out_c < 3) { salve_fail("salve_bev_tiles_aug: need 0 < crop <= resize, out_c >= 3"); return SALVE_ERR_BAD_ARG; }
+    if (n_jobs > 65535) { salve_fail("at most 65535 tile jobs per call"); return SALVE_ERR_BAD_ARG; }
+    dim3 g((crop * crop + 255) / 256, n_jobs);
+    hipLaunchKernelGGL(bev_tile_aug_kernel, g, dim3(256), 0, (hipStream_t)stream, bev, bev_w, jobs, aug, coef_y, coef_x, resize, crop, lut, out,
+                       out_c);
     SALVE_HIP_CHECK(hipGetLastError());
     return SALVE_OK;
 }

@@ -1,0 +1,151 @@
+"""The early-fusion verifier as a TRAINABLE module: every convolution on the HIP fp32 entries, the rest in torch autograd.
+
+Training stands behind the reference's scripts/train.py (fp32, no AMP, every released config).  A training step's FLOPs are
+nearly all convolutions: their forward, backward-data and backward-weight run in salve_amd/csrc/conv_train_f32.hip
+(salve_conv_f32_*).  torch autograd is the plumbing for what remains -- BatchNorm (batch statistics in train mode, running
+statistics in eval mode), ReLU, residual adds, max-pool, average pool + fc and the loss.
+
+`TrainableEarlyFusionCEResnet` subclasses `EarlyFusionCEResnet`: the same parameters and buffers under the same names, so state
+dicts move between the two with strict=True, and a checkpoint trained here loads into the inference model (fp16 or fp32 engine).
+There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
+"""
+
+from __future__ import annotations
+
+import ctypes
+from typing import Optional
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor, nn
+
+from salve_amd import _lib
+from salve_amd.models.early_fusion import EarlyFusionCEResnet, num_input_images
+
+
+def _pad8(c: int) -> int:
+    return (c + 7) // 8 * 8
+
+
+def _nhwc(x: Tensor, cp: int) -> Tensor:
+    """[B, C, H, W] (any memory format) -> contiguous NHWC [B, H, W, cp], channels C..cp-1 zero."""
+    b, c, h, w = x.shape
+    if c == cp:
+        return x.permute(0, 2, 3, 1).contiguous()
+    out = torch.zeros((b, h, w, cp), dtype=x.dtype, device=x.device)
+    out[..., :c] = x.permute(0, 2, 3, 1)
+    return out
+
+
+def _pack_weight(w: Tensor, cp: int) -> Tensor:
+    """torch [Cout, Cin, KH, KW] -> the kernel layout [Cout, KH, KW, cp] (input channels zero-padded to cp)."""
+    return _nhwc(w, cp)
+
+
+def _run(fn: str, desc: "_lib.ConvDesc", pass_: int, a: Tensor, b: Tensor, out: Tensor) -> None:
+    lib = _lib.load()
+    nbytes = int(lib.salve_conv_f32_workspace_bytes(ctypes.byref(desc), pass_))
+    if nbytes == 0:
+        raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
+    stream = torch.cuda.current_stream(a.device).cuda_stream
+    st = getattr(lib, fn)(ctypes.byref(desc), ctypes.c_void_p(a.data_ptr()), ctypes.c_void_p(b.data_ptr()),
+                          ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream))
+    _lib.check(st, fn)
+
+
+class Conv2dF32Function(torch.autograd.Function):
+    """y = conv2d(x, weight, stride, padding) without bias, in fp32 on the HIP entries (forward / dgrad / wgrad).
+
+    x: fp32 CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: fp32 CUDA torch layout
+    [Cout, Cin, KH, KW].  Returns channels_last fp32 [B, Cout, Ho, Wo].  Input channels that are not a multiple of 8 (the stem's
+    6 / 12 / 18) are zero-padded here; the stem's dgrad is never needed (the network input takes no gradient) and raises if asked.
+    dgrad is skipped when x needs no gradient."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int) -> Tensor:
+        for name, t in (("x", x), ("weight", weight)):
+            if t.device.type != "cuda":
+                raise RuntimeError(f"Conv2dF32Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
+                                   "(no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"Conv2dF32Function: {name} must be float32 (training runs in the reference's fp32), got {t.dtype}")
+        b, cin, h, w = x.shape
+        cout, cin_w, kh, kw = weight.shape
+        if cin_w != cin:
+            raise RuntimeError(f"Conv2dF32Function: weight takes {cin_w} input channels, x has {cin}")
+        cp = _pad8(cin)
+        ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
+        desc = _lib.ConvDesc(b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
+        xn = _nhwc(x.detach(), cp)
+        wk = _pack_weight(weight.detach(), cp)
+        y = torch.empty((b, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        _run("salve_conv_f32_forward", desc, _lib.CONV_FWD, xn, wk, y)
+        ctx.save_for_backward(xn, wk)
+        ctx.desc = (b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
+        ctx.cin = cin
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        xn, wk = ctx.saved_tensors
+        desc = _lib.ConvDesc(*ctx.desc)
+        b, h, w, cp = ctx.desc[:4]
+        gyn = gy.float().permute(0, 2, 3, 1).contiguous()   # NHWC [B, Ho, Wo, Cout]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            if cp != ctx.cin:
+                raise RuntimeError("Conv2dF32Function: no input gradient for the stem (its input channels are zero-padded)")
+            dxn = torch.empty((b, h, w, cp), dtype=torch.float32, device=gy.device)
+            _run("salve_conv_f32_backward_data", desc, _lib.CONV_DGRAD, gyn, wk, dxn)
+            dx = dxn.permute(0, 3, 1, 2)   # channels_last view
+        if ctx.needs_input_grad[1]:
+            dwk = torch.empty_like(wk)
+            _run("salve_conv_f32_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
+            dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
+        return dx, dw, None, None
+
+
+def conv2d_f32(x: Tensor, conv: nn.Conv2d) -> Tensor:
+    assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
+    return Conv2dF32Function.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+
+
+def _basic(blk, x: Tensor) -> Tensor:
+    out = F.relu(blk.bn1(conv2d_f32(x, blk.conv1)))
+    out = blk.bn2(conv2d_f32(out, blk.conv2))
+    idt = x if blk.downsample is None else blk.downsample[1](conv2d_f32(x, blk.downsample[0]))
+    return F.relu(out + idt)
+
+
+def _bottleneck(blk, x: Tensor) -> Tensor:
+    out = F.relu(blk.bn1(conv2d_f32(x, blk.conv1)))
+    out = F.relu(blk.bn2(conv2d_f32(out, blk.conv2)))
+    out = blk.bn3(conv2d_f32(out, blk.conv3))
+    idt = x if blk.downsample is None else blk.downsample[1](conv2d_f32(x, blk.downsample[0]))
+    return F.relu(out + idt)
+
+
+class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
+    """EarlyFusionCEResnet whose forward is an autograd graph (salve/models/early_fusion.py:41-83 op for op): HIP fp32
+    convolutions, torch BatchNorm2d / ReLU / max-pool / average pool / Linear.  Train mode: batch statistics, running statistics
+    updated, gradients for every parameter.  Eval mode: running statistics -- the validation pass scripts/train.py:76-77 runs under
+    torch.no_grad().  The inference engines (`compiled`, `forward_nhwc`) stay available through the parent class."""
+
+    def forward(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor] = None, x4: Optional[Tensor] = None, x5: Optional[Tensor] = None,
+                x6: Optional[Tensor] = None) -> Tensor:
+        n = num_input_images(self.modalities)
+        xs = [x1, x2, x3, x4, x5, x6][:n]
+        if any(x is None for x in xs):
+            raise RuntimeError(f"{n} input images are required for modalities {self.modalities}")
+        if x1.device.type != "cuda":
+            raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
+        x = torch.cat(xs, dim=1)
+        r = self.resnet
+        x = r.maxpool(F.relu(r.bn1(conv2d_f32(x, self.conv1))))
+        block = _bottleneck if r.block_kind == "bottleneck" else _basic
+        for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
+            for blk in layer:
+                x = block(blk, x)
+        x = torch.flatten(r.avgpool(x), 1)
+        return self.fc(x)

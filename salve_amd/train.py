@@ -1,0 +1,48 @@
+"""Train the verifier (scripts/train.py's command line, one GPU):
+
+    python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
+                              [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR]
+
+Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
+model_save_dirpath / a time stamp, as the reference does).  See salve_amd/training.py.
+"""
+
+from __future__ import annotations
+
+import argparse
+import logging
+import time
+
+from salve_amd import training
+from salve_amd.training_config import load_training_config
+
+
+def main(argv=None) -> None:
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", required=True, help="a reference config (salve/configs/*.yaml layout)")
+    ap.add_argument("--epochs", type=int, default=None, help="override num_epochs")
+    ap.add_argument("--batch-size", type=int, default=None, help="override batch_size")
+    ap.add_argument("--data-root", default=None, help="override data_root")
+    ap.add_argument("--layout-data-root", default=None, help="override layout_data_root")
+    ap.add_argument("--seed", type=int, default=0, help="seeds random, numpy, torch and the shuffle order (the reference: 0)")
+    ap.add_argument("--init-ckpt", default=None, help="fine-tune: start from this checkpoint's state_dict (strict)")
+    ap.add_argument("--out", default=None, help="results directory (default: model_save_dirpath/<time stamp>)")
+    a = ap.parse_args(argv)
+    logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
+    args = load_training_config(a.config)
+    if a.epochs is not None:
+        args.num_epochs = a.epochs
+    if a.batch_size is not None:
+        args.batch_size = a.batch_size
+    if a.data_root is not None:
+        args.data_root = a.data_root
+    if a.layout_data_root is not None:
+        args.layout_data_root = a.layout_data_root
+    out = a.out or f"{args.model_save_dirpath}/{time.strftime('%Y_%m_%d_%H_%M_%S')}"
+    logging.info(str(args))
+    results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt)
+    logging.info(f"results in {out}: {results}")
+
+
+if __name__ == "__main__":
+    main()

@@ -1,0 +1,184 @@
+"""Training the verifier: the reference's training helpers and loop (salve/train_utils.py, scripts/train.py) on the HIP fp32
+training convolutions.
+
+Same names as the reference: get_model, get_optimizer, poly_learning_rate, cross_entropy_forward, get_train_transform,
+get_dataloader, run_epoch, plus `train` (scripts/train.py:41-119's main).  The model is
+salve_amd.models.trainable.TrainableEarlyFusionCEResnet (its checkpoints load into the inference EarlyFusionCEResnet with
+strict=True).  salve_amd.train_utils stays inference-only and keeps refusing the train split: training is reached through this
+module (and `python -m salve_amd.train`) only.
+
+Differences from the reference, all deliberate: one GPU (`dataparallel` is accepted and ignored, the state dict carries no
+`module.` prefix), num_workers = 0 (the transforms launch GPU kernels), photometric augmentation (False in every released config)
+and crop-with-padding are refused, the shuffle order comes from a seeded torch.Generator.
+"""
+
+from __future__ import annotations
+
+import json
+import logging
+import random
+import time
+from collections import defaultdict
+from pathlib import Path
+from typing import Dict, Optional, Tuple
+
+import numpy as np
+import torch
+from torch import Tensor, nn
+
+from salve_amd.evaluate import ClassAccuracyMeter
+from salve_amd.models.trainable import TrainableEarlyFusionCEResnet
+from salve_amd.training_config import TrainingConfig
+
+CRIT_ACC_STAT = "val_mAcc"   # scripts/train.py:85: the checkpoint-selection criterion
+
+
+def get_model(args: TrainingConfig) -> nn.Module:
+    """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("salve_amd.training needs the HIP device (no CPU fallback)")
+    return TrainableEarlyFusionCEResnet(args.num_layers, args.pretrained, args.num_ce_classes, args).cuda()
+
+
+def get_optimizer(args: TrainingConfig, model: nn.Module) -> torch.optim.Optimizer:
+    """Adam(lr=base_lr, weight_decay) -- the only algorithm the reference knows (salve/train_utils.py:173-180)."""
+    if args.optimizer_algo == "adam":
+        return torch.optim.Adam(model.parameters(), lr=args.base_lr, weight_decay=args.weight_decay)
+    raise RuntimeError("Unknown optimizer")
+
+
+def poly_learning_rate(base_lr: float, curr_iter: int, max_iter: int, power: float = 0.9) -> float:
+    """poly learning rate policy (salve/train_utils.py:57-60)."""
+    return base_lr * (1 - float(curr_iter) / max_iter) ** power
+
+
+def cross_entropy_forward(model: nn.Module, split: str, x1: Tensor, x2: Tensor, x3: Optional[Tensor], x4: Optional[Tensor],
+                          x5: Optional[Tensor], x6: Optional[Tensor], is_match: Tensor) -> Tuple[Tensor, Tensor]:
+    """(softmax probabilities, cross-entropy loss) as salve/train_utils.py:18-41: with gradients for split == "train", under
+    torch.no_grad() otherwise."""
+    if split == "train":
+        logits = model(x1, x2, x3, x4, x5, x6)
+    else:
+        with torch.no_grad():
+            logits = model(x1, x2, x3, x4, x5, x6)
+    probs = torch.nn.functional.softmax(logits.detach().clone(), dim=1)
+    loss = torch.nn.functional.cross_entropy(logits, is_match.squeeze())
+    return probs, loss
+
+
+def get_train_transform(args: TrainingConfig):
+    """Resize -> random Crop -> random horizontal flip -> random vertical flip -> ToTensor -> Normalize for 2 / 4 / 6 images
+    (salve/train_utils.py:63-124), on the GPU (transforms.TrainTransform)."""
+    from salve_amd.transforms import TrainTransform
+
+    if len(args.modalities) not in (1, 2, 3):
+        raise RuntimeError(f"Unsupported modalities. {str(args.modalities)}")
+    if args.apply_photometric_augmentation:
+        raise RuntimeError("apply_photometric_augmentation=True (PhotometricShift) is not implemented; every released config has False")
+    if args.train_h > args.resize_h or args.train_w > args.resize_w:
+        raise RuntimeError("crop larger than the resized image: the reference pads with the mean there, which is not implemented")
+    return TrainTransform((args.resize_h, args.resize_w), (args.train_h, args.train_w))
+
+
+def get_dataloader(args: TrainingConfig, split: str, seed: int = 0) -> torch.utils.data.DataLoader:
+    """salve/train_utils.py:183-203.  train: the train transform, shuffled (a torch.Generator seeded with `seed`), last partial
+    batch dropped; val / test: the centre-crop transform, in order, nothing dropped.  num_workers = 0."""
+    from salve_amd import train_utils
+    from salve_amd.dataset.zind_data import ZindData
+
+    if split == "train":
+        data = ZindData(split=split, transform=get_train_transform(args), args=args)
+        gen = torch.Generator()
+        gen.manual_seed(seed)
+        return torch.utils.data.DataLoader(data, batch_size=args.batch_size, shuffle=True, generator=gen, num_workers=0, drop_last=True)
+    data = ZindData(split=split, transform=train_utils.get_img_transform_list(args, split), args=args)
+    return torch.utils.data.DataLoader(data, batch_size=args.batch_size, shuffle=False, num_workers=0, drop_last=False)
+
+
+def _unpack(args: TrainingConfig, example):
+    m = set(args.modalities)
+    if len(m) == 1:
+        x1, x2, is_match, fp0, fp1 = example
+        return (x1, x2, None, None, None, None), is_match
+    if m == {"ceiling_rgb_texture", "floor_rgb_texture"}:
+        x1, x2, x3, x4, is_match, fp0, fp1 = example
+        return (x1, x2, x3, x4, None, None), is_match
+    x1, x2, x3, x4, x5, x6, is_match, fp0, fp1 = example
+    return (x1, x2, x3, x4, x5, x6), is_match
+
+
+def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
+    """One pass over a split (scripts/train.py:169-278): train mode + Adam steps + the poly schedule for "train", eval mode
+    otherwise.  Returns {"avg_loss", "mAcc"}; as in the reference, avg_loss counts training batches only (0 for val)."""
+    model.train() if split == "train" else model.eval()
+    loss_sum, loss_n = 0.0, 0
+    meter = ClassAccuracyMeter(args.num_ce_classes)
+    dev = next(model.parameters()).device
+    max_iter = args.num_epochs * len(data_loader)
+    t0 = time.time()
+    for it, example in enumerate(data_loader):
+        xs, is_match = _unpack(args, example)
+        xs = tuple(None if x is None else x.to(dev, non_blocking=True) for x in xs)
+        gt = is_match.to(dev, non_blocking=True)
+        probs, loss = cross_entropy_forward(model, split, *xs, gt)
+        meter.update(torch.argmax(probs, dim=1).cpu().numpy(), gt.squeeze().cpu().numpy())
+        current_iter = epoch * len(data_loader) + it + 1
+        if split == "train":
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            if args.lr_annealing_strategy == "poly":   # decayed after the step, as the reference does
+                lr = poly_learning_rate(args.base_lr, current_iter, max_iter, power=args.poly_lr_power)
+                for group in optimizer.param_groups:
+                    group["lr"] = lr
+            n = xs[0].shape[0]
+            loss_sum += float(loss.item()) * n
+            loss_n += n
+            if it % max(1, args.print_every) == 0:
+                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f} ({time.time() - t0:.1f} s)")
+    accs, mAcc = meter.get_metrics()
+    logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
+    return {"avg_loss": loss_sum / loss_n if loss_n else 0.0, "mAcc": float(mAcc)}
+
+
+def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None) -> Dict[str, list]:
+    """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
+    epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
+    results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
+    checkpoint's state dict (strict)."""
+    np.random.seed(seed)
+    random.seed(seed)
+    torch.manual_seed(seed)
+    train_loader = get_dataloader(args, "train", seed=seed)
+    val_loader = get_dataloader(args, "val")
+    if len(train_loader) == 0:
+        raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
+    model = get_model(args)
+    if init_ckpt:
+        from salve_amd import train_utils
+
+        train_utils.load_model_checkpoint(init_ckpt, model, args)
+    optimizer = get_optimizer(args, model)
+    out = Path(results_dir)
+    out.mkdir(parents=True, exist_ok=True)
+    results: Dict[str, list] = defaultdict(list)
+    for epoch in range(args.num_epochs):
+        logging.info(f"On epoch {epoch}")
+        for k, v in run_epoch(args, epoch, model, train_loader, optimizer, "train").items():
+            results[f"train_{k}"].append(v)
+        with torch.no_grad():
+            for k, v in run_epoch(args, epoch, model, val_loader, optimizer, "val").items():
+                results[f"val_{k}"].append(v)
+        crit = results[CRIT_ACC_STAT]
+        if epoch == 0 or crit[-1] > max(crit[:-1]):
+            torch.save({
+                "epoch": epoch,
+                "state_dict": model.state_dict(),
+                "optimizer": optimizer.state_dict(),
+                "max_epochs": args.num_epochs,
+                f"curr_{CRIT_ACC_STAT}": crit[-1],
+                f"best_so_far_{CRIT_ACC_STAT}": max(crit),
+            }, out / "train_ckpt.pth")
+        with open(out / f"results-{args.cfg_stem}.json", "w") as f:
+            json.dump(dict(results), f, indent=4)
+    return dict(results)

@@ -1,0 +1,113 @@
+"""Time one fp32 training step of the verifier (forward + backward + Adam) on the HIP training convolutions, split into HIP
+convolution time and the rest (torch: BatchNorm, ReLU, pooling, fc, loss, Adam), and the same step with torch's own F.conv2d
+beside it, in the same process and alternating (context only: the product never calls F.conv2d).
+
+    python tools/measure/bench_train.py [--configs 50:1,152:2] [--batches 64,256] [--steps 3] [--warmup 1] [--hw 224]
+
+Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train.py ...` on its own.
+"""
+
+from __future__ import annotations
+
+import argparse
+import sys
+import time
+from pathlib import Path
+from types import SimpleNamespace
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT))
+
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from salve_amd.models import trainable  # noqa: E402
+
+MODS = {1: ["floor_rgb_texture"], 2: ["ceiling_rgb_texture", "floor_rgb_texture"], 3: ["ceiling_rgb_texture", "floor_rgb_texture", "layout"]}
+_events = []
+_hip_run = trainable._run
+_hip_conv = trainable.conv2d_f32
+
+
+def _timed_run(fn, desc, pass_, a, b, out):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    _hip_run(fn, desc, pass_, a, b, out)
+    e.record()
+    _events.append((fn, s, e))
+
+
+def _torch_conv(x, conv):
+    return F.conv2d(x, conv.weight, stride=conv.stride, padding=conv.padding)
+
+
+def step(model, opt, xs, y):
+    opt.zero_grad(set_to_none=True)
+    loss = F.cross_entropy(model(*xs), y)
+    loss.backward()
+    opt.step()
+
+
+def timed(model, opt, xs, y, conv_impl, split: bool):
+    trainable.conv2d_f32 = conv_impl
+    trainable._run = _timed_run if split else _hip_run
+    _events.clear()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    step(model, opt, xs, y)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t0
+    conv = sum(s.elapsed_time(e) for _, s, e in _events) / 1e3 if split else 0.0
+    per = {}
+    for fn, s, e in _events:
+        per[fn] = per.get(fn, 0.0) + s.elapsed_time(e) / 1e3
+    return dt, conv, per
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="50:1,152:2", help="layers:modalities, comma separated")
+    ap.add_argument("--batches", default="64,256")
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--hw", type=int, default=224)
+    ap.add_argument("--no-torch", action="store_true", help="skip the F.conv2d comparison")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    print(f"# {torch.cuda.get_device_name(dev)}; fp32 training step = forward + backward + Adam, input {a.hw}x{a.hw}, "
+          f"median of {a.steps} after {a.warmup} warm-up; alternating HIP / torch-conv steps")
+    for cfg in a.configs.split(","):
+        layers, nm = (int(v) for v in cfg.split(":"))
+        for batch in (int(b) for b in a.batches.split(",")):
+            torch.manual_seed(0)
+            model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=MODS[nm])).to(dev).train()
+            model = model.to(memory_format=torch.channels_last)
+            opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+            xs = [torch.randn(batch, 3, a.hw, a.hw, device=dev) for _ in range(2 * nm)]
+            y = torch.randint(0, 2, (batch,), device=dev)
+            impls = [("hip", _hip_conv)] + ([] if a.no_torch else [("torch", _torch_conv)])
+            res = {k: [] for k, _ in impls}
+            split = []
+            for i in range(a.warmup + a.steps):
+                for name, impl in impls:
+                    dt, _, _ = timed(model, opt, xs, y, impl, False)
+                    if i >= a.warmup:
+                        res[name].append(dt)
+            for i in range(a.steps):   # separate steps with an event pair around every HIP convolution call
+                split.append(timed(model, opt, xs, y, _hip_conv, True))
+            trainable.conv2d_f32, trainable._run = _hip_conv, _hip_run
+            med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
+            sp = sorted(split, key=lambda t: t[0])[len(split) // 2]
+            line = (f"resnet{layers} {6 * nm}ch batch {batch}: step {med['hip'] * 1e3:.1f} ms ({batch / med['hip']:.0f} samples/s); "
+                    f"HIP convolutions {sp[1] * 1e3:.1f} ms of a {sp[0] * 1e3:.1f} ms event-split step "
+                    f"[fwd {sp[2].get('salve_conv_f32_forward', 0) * 1e3:.1f}, dgrad {sp[2].get('salve_conv_f32_backward_data', 0) * 1e3:.1f}, "
+                    f"wgrad {sp[2].get('salve_conv_f32_backward_weight', 0) * 1e3:.1f} ms], torch + host {(sp[0] - sp[1]) * 1e3:.1f} ms")
+            if "torch" in med:
+                line += f"; same step with F.conv2d: {med['torch'] * 1e3:.1f} ms ({batch / med['torch']:.0f} samples/s)"
+            print(line, flush=True)
+            del model, opt, xs
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
