@@ -413,6 +413,29 @@ int salve_conv_f32_backward_data(const salve_conv_desc_t* d, const float* dy, co
 int salve_conv_f32_backward_weight(const salve_conv_desc_t* d, const float* x, const float* dy, float* dw, void* ws, size_t ws_bytes,
                                    void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training convolutions in bf16 (additive within ABI 7): opt-in mixed-precision training.  The same three passes, descriptors,
+ * layouts, accepted shapes and refusals as salve_conv_f32_* above, word for word (SALVE_ERR_BAD_ARG for any other shape,
+ * SALVE_ERR_UNSUPPORTED for the stem's backward-data, 0 workspace bytes for a refused descriptor or pass).  bf16 values are passed
+ * as uint16_t bit patterns (the upper half of the fp32 bits).  The caller keeps fp32 master weights and hands over their bf16
+ * copy; the reference trains in fp32, so this is never the default (salve_amd/models/trainable.py: set_train_precision).
+ *   Arithmetic: bf16 operands on the bf16 matrix cores (v_mfma_f32_16x16x32_bf16), fp32 accumulation.  forward / backward-data
+ *            round each output ONCE to bf16 (round to nearest even, NaN stays NaN); backward-weight writes fp32 dW and never
+ *            accumulates in bf16: bf16 x bf16 products are exact in fp32, the pixels are split over workgroups into fp32 partial
+ *            sums that are added in a fixed order -- no atomics, the same inputs give bit-identical dW.
+ *   All three overwrite their output (no accumulation into it); the workspace holds nothing from one call to the next.
+ * ------------------------------------------------------------------------------------------------ */
+size_t salve_conv_bf16_workspace_bytes(const salve_conv_desc_t* d, int32_t pass);
+/* y [batch, Ho, Wo, Cout] bf16 = conv(x [batch, Hi, Wi, Cin] bf16, w [Cout][KH][KW][Cin] bf16): no bias, no activation. */
+int salve_conv_bf16_forward(const salve_conv_desc_t* d, const uint16_t* x, const uint16_t* w, uint16_t* y, void* ws, size_t ws_bytes,
+                            void* stream);
+/* dx [batch, Hi, Wi, Cin] bf16 = d(sum dy . y) / dx for dy [batch, Ho, Wo, Cout] bf16. */
+int salve_conv_bf16_backward_data(const salve_conv_desc_t* d, const uint16_t* dy, const uint16_t* w, uint16_t* dx, void* ws, size_t ws_bytes,
+                                  void* stream);
+/* dw [Cout][KH][KW][Cin] fp32 = sum over pixels of dy (x) the input patch (bf16 operands). */
+int salve_conv_bf16_backward_weight(const salve_conv_desc_t* d, const uint16_t* x, const uint16_t* dy, float* dw, void* ws, size_t ws_bytes,
+                                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -56,6 +56,10 @@ EXPORTED_SYMBOLS = (
     "salve_conv_f32_forward",
     "salve_conv_f32_backward_data",
     "salve_conv_f32_backward_weight",
+    "salve_conv_bf16_workspace_bytes",
+    "salve_conv_bf16_forward",
+    "salve_conv_bf16_backward_data",
+    "salve_conv_bf16_backward_weight",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -93,7 +97,7 @@ TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"
 TILE_HFLIP, TILE_VFLIP = 1, 2
 assert HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
 
-# salve_conv_f32_* passes (include/salve_hip.h: SALVE_CONV_*)
+# salve_conv_f32_* / salve_conv_bf16_* passes (include/salve_hip.h: SALVE_CONV_*)
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
 SALVE_ERR_BAD_ARG, SALVE_ERR_UNSUPPORTED = -1, -2
 
@@ -178,7 +182,10 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_tiles_aug.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
-    for name in ("salve_conv_f32_forward", "salve_conv_f32_backward_data", "salve_conv_f32_backward_weight"):
+    lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
+    lib.salve_conv_bf16_workspace_bytes.restype = sz
+    for name in ("salve_conv_f32_forward", "salve_conv_f32_backward_data", "salve_conv_f32_backward_weight", "salve_conv_bf16_forward",
+                 "salve_conv_bf16_backward_data", "salve_conv_bf16_backward_weight"):
         getattr(lib, name).argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, sz, vp]
         getattr(lib, name).restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override

@@ -5,6 +5,10 @@ nearly all convolutions: their forward, backward-data and backward-weight run in
 (salve_conv_f32_*).  torch autograd is the plumbing for what remains -- BatchNorm (batch statistics in train mode, running
 statistics in eval mode), ReLU, residual adds, max-pool, average pool + fc and the loss.
 
+Opt-in bf16 mixed precision (`set_train_precision("bf16")`): activations in bf16, every convolution on the HIP bf16 entries
+(salve_amd/csrc/conv_train_bf16.hip, salve_conv_bf16_*) through `Conv2dBF16Function`, fp32 master weights, fp32 weight
+gradients, BatchNorm in fp32 (upcast at its input), fp32 logits and loss.  bf16 needs no loss scaling.  fp32 stays the default.
+
 `TrainableEarlyFusionCEResnet` subclasses `EarlyFusionCEResnet`: the same parameters and buffers under the same names, so state
 dicts move between the two with strict=True, and a checkpoint trained here loads into the inference model (fp16 or fp32 engine).
 There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
@@ -44,7 +48,8 @@ def _pack_weight(w: Tensor, cp: int) -> Tensor:
 
 def _run(fn: str, desc: "_lib.ConvDesc", pass_: int, a: Tensor, b: Tensor, out: Tensor) -> None:
     lib = _lib.load()
-    nbytes = int(lib.salve_conv_f32_workspace_bytes(ctypes.byref(desc), pass_))
+    ws_query = lib.salve_conv_bf16_workspace_bytes if fn.startswith("salve_conv_bf16_") else lib.salve_conv_f32_workspace_bytes
+    nbytes = int(ws_query(ctypes.byref(desc), pass_))
     if nbytes == 0:
         raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
@@ -111,18 +116,93 @@ def conv2d_f32(x: Tensor, conv: nn.Conv2d) -> Tensor:
     return Conv2dF32Function.apply(x, conv.weight, conv.stride[0], conv.padding[0])
 
 
-def _basic(blk, x: Tensor) -> Tensor:
-    out = F.relu(blk.bn1(conv2d_f32(x, blk.conv1)))
-    out = blk.bn2(conv2d_f32(out, blk.conv2))
-    idt = x if blk.downsample is None else blk.downsample[1](conv2d_f32(x, blk.downsample[0]))
+class Conv2dBF16Function(torch.autograd.Function):
+    """y = conv2d(x, weight, stride, padding) without bias, bf16 operands on the HIP bf16 entries, fp32 accumulation.
+
+    x: bf16 CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: the fp32 master weight,
+    torch layout [Cout, Cin, KH, KW], packed and cast to bf16 once per forward (the bf16 copy is saved for the backward pass).
+    Returns channels_last bf16 [B, Cout, Ho, Wo].  Backward: bf16 dx, fp32 dW (never accumulated in bf16).  The stem's input
+    channels are zero-padded to a multiple of 8 as for Conv2dF32Function; its dgrad raises if asked."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int) -> Tensor:
+        for name, t, dt in (("x", x, torch.bfloat16), ("weight", weight, torch.float32)):
+            if t.device.type != "cuda":
+                raise RuntimeError(f"Conv2dBF16Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
+                                   "(no CPU fallback)")
+            if t.dtype != dt:
+                raise RuntimeError(f"Conv2dBF16Function: {name} must be {dt} (bf16 activations, fp32 master weights), got {t.dtype}")
+        b, cin, h, w = x.shape
+        cout, cin_w, kh, kw = weight.shape
+        if cin_w != cin:
+            raise RuntimeError(f"Conv2dBF16Function: weight takes {cin_w} input channels, x has {cin}")
+        cp = _pad8(cin)
+        ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
+        desc = _lib.ConvDesc(b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
+        xn = _nhwc(x.detach(), cp)
+        wk = _pack_weight(weight.detach().to(torch.bfloat16), cp)
+        y = torch.empty((b, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
+        _run("salve_conv_bf16_forward", desc, _lib.CONV_FWD, xn, wk, y)
+        ctx.save_for_backward(xn, wk)
+        ctx.desc = (b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
+        ctx.cin = cin
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        xn, wk = ctx.saved_tensors
+        desc = _lib.ConvDesc(*ctx.desc)
+        b, h, w, cp = ctx.desc[:4]
+        gyn = gy.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()   # NHWC [B, Ho, Wo, Cout]
+        dx = dw = None
+        if ctx.needs_input_grad[0]:
+            if cp != ctx.cin:
+                raise RuntimeError("Conv2dBF16Function: no input gradient for the stem (its input channels are zero-padded)")
+            dxn = torch.empty((b, h, w, cp), dtype=torch.bfloat16, device=gy.device)
+            _run("salve_conv_bf16_backward_data", desc, _lib.CONV_DGRAD, gyn, wk, dxn)
+            dx = dxn.permute(0, 3, 1, 2)   # channels_last view
+        if ctx.needs_input_grad[1]:
+            dwk = torch.empty(wk.shape, dtype=torch.float32, device=gy.device)
+            _run("salve_conv_bf16_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
+            dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
+        return dx, dw, None, None
+
+
+def conv2d_bf16(x: Tensor, conv: nn.Conv2d) -> Tensor:
+    assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
+    return Conv2dBF16Function.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+
+
+TRAIN_PRECISIONS = ("fp32", "bf16")
+
+
+def _conv(precision: str):
+    """The convolution of a training precision, looked up at call time (tools/measure/bench_train.py swaps these functions)."""
+    return conv2d_bf16 if precision == "bf16" else conv2d_f32
+
+
+def _bn(bn: nn.BatchNorm2d, x: Tensor) -> Tensor:
+    return bn(x)
+
+
+def _bn_bf16(bn: nn.BatchNorm2d, x: Tensor) -> Tensor:
+    """BatchNorm of a bf16 activation, upcast at its input: fp32 statistics, normalisation and parameters, the output rounded to
+    bf16 once.  (Why not torch's mixed-type BatchNorm: DESIGN.md section 4.8.)"""
+    return bn(x.float()).to(torch.bfloat16)
+
+
+def _basic(blk, x: Tensor, conv, bn) -> Tensor:
+    out = F.relu(bn(blk.bn1, conv(x, blk.conv1)))
+    out = bn(blk.bn2, conv(out, blk.conv2))
+    idt = x if blk.downsample is None else bn(blk.downsample[1], conv(x, blk.downsample[0]))
     return F.relu(out + idt)
 
 
-def _bottleneck(blk, x: Tensor) -> Tensor:
-    out = F.relu(blk.bn1(conv2d_f32(x, blk.conv1)))
-    out = F.relu(blk.bn2(conv2d_f32(out, blk.conv2)))
-    out = blk.bn3(conv2d_f32(out, blk.conv3))
-    idt = x if blk.downsample is None else blk.downsample[1](conv2d_f32(x, blk.downsample[0]))
+def _bottleneck(blk, x: Tensor, conv, bn) -> Tensor:
+    out = F.relu(bn(blk.bn1, conv(x, blk.conv1)))
+    out = F.relu(bn(blk.bn2, conv(out, blk.conv2)))
+    out = bn(blk.bn3, conv(out, blk.conv3))
+    idt = x if blk.downsample is None else bn(blk.downsample[1], conv(x, blk.downsample[0]))
     return F.relu(out + idt)
 
 
@@ -130,7 +210,25 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     """EarlyFusionCEResnet whose forward is an autograd graph (salve/models/early_fusion.py:41-83 op for op): HIP fp32
     convolutions, torch BatchNorm2d / ReLU / max-pool / average pool / Linear.  Train mode: batch statistics, running statistics
     updated, gradients for every parameter.  Eval mode: running statistics -- the validation pass scripts/train.py:76-77 runs under
-    torch.no_grad().  The inference engines (`compiled`, `forward_nhwc`) stay available through the parent class."""
+    torch.no_grad().  The inference engines (`compiled`, `forward_nhwc`) stay available through the parent class.
+
+    `set_train_precision("bf16")` opts into mixed precision: the concatenated input is cast to bf16 once before the stem, the
+    convolutions run on Conv2dBF16Function, BatchNorm upcasts its bf16 input to fp32 (fp32 weight, bias, running statistics and
+    arithmetic; the output is rounded to bf16), ReLU / max-pool / residual adds run in bf16, and the average pool output is cast to fp32 before `fc`.
+    Parameters and gradients stay fp32.  Train and eval mode alike.  Separate from the parent's inference `set_precision`."""
+
+    _train_precision = "fp32"
+
+    def set_train_precision(self, precision: str) -> "TrainableEarlyFusionCEResnet":
+        """"fp32" (the default, the reference's precision) or "bf16" (opt-in mixed precision).  Returns self."""
+        if precision not in TRAIN_PRECISIONS:
+            raise ValueError(f"training precision must be one of {TRAIN_PRECISIONS}, got {precision!r}")
+        self._train_precision = precision
+        return self
+
+    @property
+    def train_precision(self) -> str:
+        return self._train_precision
 
     def forward(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor] = None, x4: Optional[Tensor] = None, x5: Optional[Tensor] = None,
                 x6: Optional[Tensor] = None) -> Tensor:
@@ -141,11 +239,17 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
         if x1.device.type != "cuda":
             raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
         x = torch.cat(xs, dim=1)
+        bf16 = self._train_precision == "bf16"
+        if bf16:
+            x = x.to(torch.bfloat16)
+        conv, bn = _conv(self._train_precision), (_bn_bf16 if bf16 else _bn)
         r = self.resnet
-        x = r.maxpool(F.relu(r.bn1(conv2d_f32(x, self.conv1))))
+        x = r.maxpool(F.relu(bn(r.bn1, conv(x, self.conv1))))
         block = _bottleneck if r.block_kind == "bottleneck" else _basic
         for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
             for blk in layer:
-                x = block(blk, x)
+                x = block(blk, x, conv, bn)
         x = torch.flatten(r.avgpool(x), 1)
+        if bf16:
+            x = x.float()
         return self.fc(x)

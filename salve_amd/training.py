@@ -27,17 +27,25 @@ import torch
 from torch import Tensor, nn
 
 from salve_amd.evaluate import ClassAccuracyMeter
-from salve_amd.models.trainable import TrainableEarlyFusionCEResnet
+from salve_amd.models.trainable import TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
 from salve_amd.training_config import TrainingConfig
 
 CRIT_ACC_STAT = "val_mAcc"   # scripts/train.py:85: the checkpoint-selection criterion
 
 
-def get_model(args: TrainingConfig) -> nn.Module:
-    """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored."""
+def _check_precision(precision: str) -> None:
+    if precision not in TRAIN_PRECISIONS:
+        raise ValueError(f"training precision must be one of {TRAIN_PRECISIONS}, got {precision!r}")
+
+
+def get_model(args: TrainingConfig, precision: str = "fp32") -> nn.Module:
+    """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored.
+    precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision)."""
+    _check_precision(precision)
     if not torch.cuda.is_available():
         raise RuntimeError("salve_amd.training needs the HIP device (no CPU fallback)")
-    return TrainableEarlyFusionCEResnet(args.num_layers, args.pretrained, args.num_ce_classes, args).cuda()
+    model = TrainableEarlyFusionCEResnet(args.num_layers, args.pretrained, args.num_ce_classes, args)
+    return model.set_train_precision(precision).cuda()
 
 
 def get_optimizer(args: TrainingConfig, model: nn.Module) -> torch.optim.Optimizer:
@@ -141,11 +149,13 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
     return {"avg_loss": loss_sum / loss_n if loss_n else 0.0, "mAcc": float(mAcc)}
 
 
-def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None) -> Dict[str, list]:
+def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32") -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
-    checkpoint's state dict (strict)."""
+    checkpoint's state dict (strict).  precision: "fp32" (default) or "bf16" -- the checkpoint is fp32 either way (fp32 master
+    weights), with the same keys."""
+    _check_precision(precision)
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
@@ -153,7 +163,7 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     val_loader = get_dataloader(args, "val")
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
-    model = get_model(args)
+    model = get_model(args, precision)
     if init_ckpt:
         from salve_amd import train_utils
 

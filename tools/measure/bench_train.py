@@ -1,8 +1,11 @@
-"""Time one fp32 training step of the verifier (forward + backward + Adam) on the HIP training convolutions, split into HIP
+"""Time one training step of the verifier (forward + backward + Adam) on the HIP training convolutions, split into HIP
 convolution time and the rest (torch: BatchNorm, ReLU, pooling, fc, loss, Adam), and the same step with torch's own F.conv2d
-beside it, in the same process and alternating (context only: the product never calls F.conv2d).
+beside it, in the same process and alternating (context only: the product never calls F.conv2d).  --precision fp32,bf16 times
+the reference's fp32 step and the opt-in bf16 mixed-precision step (TrainableEarlyFusionCEResnet.set_train_precision) one after
+the other in the same process; the torch step of a precision runs F.conv2d in that precision.
 
     python tools/measure/bench_train.py [--configs 50:1,152:2] [--batches 64,256] [--steps 3] [--warmup 1] [--hw 224]
+                                        [--precision fp32,bf16]
 
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train.py ...` on its own.
 """
@@ -26,7 +29,8 @@ from salve_amd.models import trainable  # noqa: E402
 MODS = {1: ["floor_rgb_texture"], 2: ["ceiling_rgb_texture", "floor_rgb_texture"], 3: ["ceiling_rgb_texture", "floor_rgb_texture", "layout"]}
 _events = []
 _hip_run = trainable._run
-_hip_conv = trainable.conv2d_f32
+_hip_conv = {"fp32": trainable.conv2d_f32, "bf16": trainable.conv2d_bf16}
+_conv_attr = {"fp32": "conv2d_f32", "bf16": "conv2d_bf16"}
 
 
 def _timed_run(fn, desc, pass_, a, b, out):
@@ -38,7 +42,7 @@ def _timed_run(fn, desc, pass_, a, b, out):
 
 
 def _torch_conv(x, conv):
-    return F.conv2d(x, conv.weight, stride=conv.stride, padding=conv.padding)
+    return F.conv2d(x, conv.weight.to(x.dtype), stride=conv.stride, padding=conv.padding)
 
 
 def step(model, opt, xs, y):
@@ -48,8 +52,8 @@ def step(model, opt, xs, y):
     opt.step()
 
 
-def timed(model, opt, xs, y, conv_impl, split: bool):
-    trainable.conv2d_f32 = conv_impl
+def timed(model, opt, xs, y, conv_impl, split: bool, prec: str = "fp32"):
+    setattr(trainable, _conv_attr[prec], conv_impl)
     trainable._run = _timed_run if split else _hip_run
     _events.clear()
     torch.cuda.synchronize()
@@ -60,7 +64,8 @@ def timed(model, opt, xs, y, conv_impl, split: bool):
     conv = sum(s.elapsed_time(e) for _, s, e in _events) / 1e3 if split else 0.0
     per = {}
     for fn, s, e in _events:
-        per[fn] = per.get(fn, 0.0) + s.elapsed_time(e) / 1e3
+        pass_ = fn.split("_", 3)[3]   # salve_conv_{f32,bf16}_<pass>
+        per[pass_] = per.get(pass_, 0.0) + s.elapsed_time(e) / 1e3
     return dt, conv, per
 
 
@@ -72,38 +77,49 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--hw", type=int, default=224)
     ap.add_argument("--no-torch", action="store_true", help="skip the F.conv2d comparison")
+    ap.add_argument("--precision", default="fp32", help="training precisions, comma separated: fp32, bf16")
     a = ap.parse_args()
+    precs = a.precision.split(",")
+    if not precs or any(p not in trainable.TRAIN_PRECISIONS for p in precs):
+        ap.error(f"--precision takes a comma-separated list of {trainable.TRAIN_PRECISIONS}")
     dev = torch.device("cuda:0")
-    print(f"# {torch.cuda.get_device_name(dev)}; fp32 training step = forward + backward + Adam, input {a.hw}x{a.hw}, "
+    fp32_step = {}
+    print(f"# {torch.cuda.get_device_name(dev)}; {' / '.join(precs)} training step = forward + backward + Adam, input {a.hw}x{a.hw}, "
           f"median of {a.steps} after {a.warmup} warm-up; alternating HIP / torch-conv steps")
     for cfg in a.configs.split(","):
         layers, nm = (int(v) for v in cfg.split(":"))
-        for batch in (int(b) for b in a.batches.split(",")):
+        for batch, prec in ((int(b), p) for b in a.batches.split(",") for p in precs):
             torch.manual_seed(0)
             model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=MODS[nm])).to(dev).train()
+            model.set_train_precision(prec)
             model = model.to(memory_format=torch.channels_last)
             opt = torch.optim.Adam(model.parameters(), lr=1e-4)
             xs = [torch.randn(batch, 3, a.hw, a.hw, device=dev) for _ in range(2 * nm)]
             y = torch.randint(0, 2, (batch,), device=dev)
-            impls = [("hip", _hip_conv)] + ([] if a.no_torch else [("torch", _torch_conv)])
+            impls = [("hip", _hip_conv[prec])] + ([] if a.no_torch else [("torch", _torch_conv)])
             res = {k: [] for k, _ in impls}
             split = []
             for i in range(a.warmup + a.steps):
                 for name, impl in impls:
-                    dt, _, _ = timed(model, opt, xs, y, impl, False)
+                    dt, _, _ = timed(model, opt, xs, y, impl, False, prec)
                     if i >= a.warmup:
                         res[name].append(dt)
             for i in range(a.steps):   # separate steps with an event pair around every HIP convolution call
-                split.append(timed(model, opt, xs, y, _hip_conv, True))
-            trainable.conv2d_f32, trainable._run = _hip_conv, _hip_run
+                split.append(timed(model, opt, xs, y, _hip_conv[prec], True, prec))
+            setattr(trainable, _conv_attr[prec], _hip_conv[prec])
+            trainable._run = _hip_run
             med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
             sp = sorted(split, key=lambda t: t[0])[len(split) // 2]
-            line = (f"resnet{layers} {6 * nm}ch batch {batch}: step {med['hip'] * 1e3:.1f} ms ({batch / med['hip']:.0f} samples/s); "
+            tag = "" if prec == "fp32" else f" {prec}"
+            line = (f"resnet{layers} {6 * nm}ch batch {batch}{tag}: step {med['hip'] * 1e3:.1f} ms ({batch / med['hip']:.0f} samples/s); "
                     f"HIP convolutions {sp[1] * 1e3:.1f} ms of a {sp[0] * 1e3:.1f} ms event-split step "
-                    f"[fwd {sp[2].get('salve_conv_f32_forward', 0) * 1e3:.1f}, dgrad {sp[2].get('salve_conv_f32_backward_data', 0) * 1e3:.1f}, "
-                    f"wgrad {sp[2].get('salve_conv_f32_backward_weight', 0) * 1e3:.1f} ms], torch + host {(sp[0] - sp[1]) * 1e3:.1f} ms")
+                    f"[fwd {sp[2].get('forward', 0) * 1e3:.1f}, dgrad {sp[2].get('backward_data', 0) * 1e3:.1f}, "
+                    f"wgrad {sp[2].get('backward_weight', 0) * 1e3:.1f} ms], torch + host {(sp[0] - sp[1]) * 1e3:.1f} ms")
             if "torch" in med:
                 line += f"; same step with F.conv2d: {med['torch'] * 1e3:.1f} ms ({batch / med['torch']:.0f} samples/s)"
+            fp32_step[(layers, nm, batch, prec)] = med["hip"]
+            if prec != "fp32" and (layers, nm, batch, "fp32") in fp32_step:
+                line += f"; {med['hip'] / fp32_step[(layers, nm, batch, 'fp32')]:.2f} x the fp32 step's time"
             print(line, flush=True)
             del model, opt, xs
             torch.cuda.empty_cache()
