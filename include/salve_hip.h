@@ -436,6 +436,57 @@ int salve_conv_bf16_backward_data(const salve_conv_desc_t* d, const uint16_t* dy
 int salve_conv_bf16_backward_weight(const salve_conv_desc_t* d, const uint16_t* x, const uint16_t* dy, float* dw, void* ws, size_t ws_bytes,
                                     void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training BatchNorm with fused ReLU and residual add (additive within ABI 7): opt-in, fp32 and bf16.
+ * The reference normalises with torchvision's nn.BatchNorm2d inside its ResNet trunk (salve/models/early_fusion.py:69-76:
+ * resnet.bn1 + relu, then layer1..layer4, whose blocks end in bn + identity add + relu) and trains it with batch statistics
+ * (scripts/train.py).  These entries compute one BatchNorm2d in train mode -- or, with SALVE_BN_EVAL, on the running
+ * statistics -- together with the residual add and the ReLU that follow it, and the matching backward pass
+ * (salve_amd/models/trainable.py: BatchNormHipFunction; the default stays torch's BatchNorm).
+ *   Layout:  activations [rows, C], rows = batch * H * W, channel innermost (NHWC), fp32 or bf16 bit patterns (uint16_t, the upper
+ *            half of the fp32 bits); device pointers, 16-byte aligned.  gamma, beta, running_mean, running_var, save_mean,
+ *            save_invstd, dgamma, dbeta: device float [C], always fp32.
+ *   Shapes:  C a multiple of 8 from 8 to 4096, rows >= 2; flags a combination of SALVE_BN_*; eps >= 0, momentum in [0, 1].
+ *            Anything else, an unknown flag bit included: SALVE_ERR_BAD_ARG, and 0 workspace bytes.
+ *   forward, train:  per channel over the rows mean and biased variance, save_mean = mean, save_invstd = 1 / sqrt(var + eps);
+ *            running = (1 - momentum) * running + momentum * batch statistic with the UNBIASED variance (torch's definitions;
+ *            running_mean / running_var may be NULL: no update).  y = gamma * (x - mean) * invstd + beta, then + residual with
+ *            SALVE_BN_ADD, then max(0, .) with SALVE_BN_RELU; the bf16 entry rounds y once.  residual is read only with
+ *            SALVE_BN_ADD (else it may be NULL).
+ *   forward, eval (SALVE_BN_EVAL):  the same y from running_mean and 1 / sqrt(running_var + eps); nothing else is read or
+ *            written (save_mean / save_invstd may be NULL).
+ *   backward (train only; with SALVE_BN_EVAL: SALVE_ERR_UNSUPPORTED):  g = dy, or with SALVE_BN_RELU g = dy where the saved
+ *            forward output y > 0 and 0 elsewhere (y is read only then).  dbeta = sum g, dgamma = sum g * xhat with
+ *            xhat = (x - save_mean) * save_invstd, dx = gamma * save_invstd * (g - dbeta / rows - xhat * dgamma / rows), and with
+ *            SALVE_BN_ADD dres = g, the gradient of the residual branch (dres may be NULL otherwise).
+ *   Arithmetic: fp32 throughout, also for bf16 activations.  The statistics are Welford sums per thread combined with Chan's
+ *            formula in a fixed order (never E[x^2] - E[x]^2); dgamma / dbeta are fp32 partial sums per workgroup added in a
+ *            fixed order.  No atomics: the same inputs give bit-identical results.  Element offsets are 64-bit.
+ *   Workspace: salve_bn_workspace_bytes(d, pass) bytes of device memory (0 = the descriptor or pass is refused); it holds nothing
+ *            from one call to the next.  All outputs are overwritten.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    int32_t rows, C, flags;
+    float eps, momentum;
+} salve_bn_desc_t;
+#define SALVE_BN_RELU 1   /* max(0, .) after the normalisation (and after the residual add) */
+#define SALVE_BN_ADD 2    /* + residual before the ReLU */
+#define SALVE_BN_EVAL 4   /* normalise with the running statistics; forward only */
+#define SALVE_BN_FWD 0
+#define SALVE_BN_BWD 1
+size_t salve_bn_workspace_bytes(const salve_bn_desc_t* d, int32_t pass);
+int salve_bn_f32_forward(const salve_bn_desc_t* d, const float* x, const float* residual, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, float* y, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
+                         void* stream);
+int salve_bn_f32_backward(const salve_bn_desc_t* d, const float* dy, const float* x, const float* y, const float* gamma, const float* save_mean,
+                          const float* save_invstd, float* dx, float* dres, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream);
+int salve_bn_bf16_forward(const salve_bn_desc_t* d, const uint16_t* x, const uint16_t* residual, const float* gamma, const float* beta,
+                          float* running_mean, float* running_var, uint16_t* y, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes,
+                          void* stream);
+int salve_bn_bf16_backward(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* gamma,
+                           const float* save_mean, const float* save_invstd, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta, void* ws,
+                           size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -60,6 +60,11 @@ EXPORTED_SYMBOLS = (
     "salve_conv_bf16_forward",
     "salve_conv_bf16_backward_data",
     "salve_conv_bf16_backward_weight",
+    "salve_bn_workspace_bytes",
+    "salve_bn_f32_forward",
+    "salve_bn_f32_backward",
+    "salve_bn_bf16_forward",
+    "salve_bn_bf16_backward",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -106,6 +111,19 @@ class ConvDesc(ctypes.Structure):
     """salve_conv_desc_t"""
 
     _fields_ = [(n, ctypes.c_int32) for n in ("batch", "Hi", "Wi", "Cin", "Ho", "Wo", "Cout", "KH", "KW", "stride", "pad")]
+
+
+# salve_bn_* flags and passes (include/salve_hip.h: SALVE_BN_*)
+BN_RELU, BN_ADD, BN_EVAL = 1, 2, 4
+BN_FWD, BN_BWD = 0, 1
+
+
+class BnDesc(ctypes.Structure):
+    """salve_bn_desc_t"""
+
+    _fields_ = [("rows", ctypes.c_int32), ("C", ctypes.c_int32), ("flags", ctypes.c_int32), ("eps", ctypes.c_float),
+                ("momentum", ctypes.c_float)]
+
 
 _lib = None
 
@@ -187,6 +205,14 @@ def load() -> ctypes.CDLL:
     for name in ("salve_conv_f32_forward", "salve_conv_f32_backward_data", "salve_conv_f32_backward_weight", "salve_conv_bf16_forward",
                  "salve_conv_bf16_backward_data", "salve_conv_bf16_backward_weight"):
         getattr(lib, name).argtypes = [ctypes.POINTER(ConvDesc), vp, vp, vp, vp, sz, vp]
+        getattr(lib, name).restype = ctypes.c_int
+    lib.salve_bn_workspace_bytes.argtypes = [ctypes.POINTER(BnDesc), i32]
+    lib.salve_bn_workspace_bytes.restype = sz
+    for name in ("salve_bn_f32_forward", "salve_bn_bf16_forward"):   # d, x, residual, gamma, beta, running_mean, running_var, y, save_mean, save_invstd
+        getattr(lib, name).argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 9 + [vp, sz, vp]
+        getattr(lib, name).restype = ctypes.c_int
+    for name in ("salve_bn_f32_backward", "salve_bn_bf16_backward"):   # d, dy, x, y, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta
+        getattr(lib, name).argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 10 + [vp, sz, vp]
         getattr(lib, name).restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.

@@ -9,6 +9,10 @@ Opt-in bf16 mixed precision (`set_train_precision("bf16")`): activations in bf16
 (salve_amd/csrc/conv_train_bf16.hip, salve_conv_bf16_*) through `Conv2dBF16Function`, fp32 master weights, fp32 weight
 gradients, BatchNorm in fp32 (upcast at its input), fp32 logits and loss.  bf16 needs no loss scaling.  fp32 stays the default.
 
+Opt-in HIP BatchNorm (`set_train_norm("hip")`): every BatchNorm runs on salve_amd/csrc/norm_train.hip (salve_bn_*) through
+`BatchNormHipFunction`, with the ReLU and the residual add that follow it fused in, forward and backward, in either precision;
+in bf16 no cast remains around BatchNorm.  torch's BatchNorm stays the default.
+
 `TrainableEarlyFusionCEResnet` subclasses `EarlyFusionCEResnet`: the same parameters and buffers under the same names, so state
 dicts move between the two with strict=True, and a checkpoint trained here loads into the inference model (fp16 or fp32 engine).
 There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
@@ -174,6 +178,105 @@ def conv2d_bf16(x: Tensor, conv: nn.Conv2d) -> Tensor:
 
 
 TRAIN_PRECISIONS = ("fp32", "bf16")
+TRAIN_NORMS = ("torch", "hip")
+
+
+def _run_bn(fn: str, desc: "_lib.BnDesc", pass_: int, ptrs, device) -> None:
+    """One salve_bn_* call: `ptrs` are the entry's pointer arguments in order (tensors or None)."""
+    lib = _lib.load()
+    nbytes = int(lib.salve_bn_workspace_bytes(ctypes.byref(desc), pass_))
+    if nbytes == 0:
+        raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    args = [ctypes.c_void_p(None if t is None else t.data_ptr()) for t in ptrs]
+    st = getattr(lib, fn)(ctypes.byref(desc), *args, ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream))
+    _lib.check(st, fn)
+
+
+_BN_ENTRY = {torch.float32: "salve_bn_f32", torch.bfloat16: "salve_bn_bf16"}
+
+
+class BatchNormHipFunction(torch.autograd.Function):
+    """relu?(batch_norm(x) + residual?) on the HIP entries (salve_bn_*), forward and backward.
+
+    x: fp32 or bf16 CUDA [B, C, H, W] (channels_last memory is used as is; other layouts are copied); residual: None or a tensor
+    of x's shape and dtype; weight, bias, running_mean, running_var: the fp32 parameters and buffers of an nn.BatchNorm2d,
+    num_batches_tracked its counter (or None); relu: fuse max(0, .); training: batch statistics (running statistics updated in
+    place with `momentum`, or with the cumulative average 1 / num_batches_tracked when momentum is None, and the counter
+    incremented, as torch does) or, when False, the running statistics -- forward only, the eval form has no backward pass.
+    Returns channels_last [B, C, H, W] in x's dtype.  Backward: dx and the residual's gradient in x's dtype, fp32 dweight and
+    dbias; the ReLU mask is taken from the saved output."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: Tensor, running_mean: Optional[Tensor],
+                running_var: Optional[Tensor], num_batches_tracked: Optional[Tensor], relu: bool, eps: float, momentum: Optional[float],
+                training: bool) -> Tensor:
+        if x.dtype not in _BN_ENTRY:
+            raise RuntimeError(f"BatchNormHipFunction: x must be float32 or bfloat16, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError(f"BatchNormHipFunction: x is on {x.device}; the HIP BatchNorm runs on the HIP device only (no CPU fallback)")
+        if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape or residual.device != x.device):
+            raise RuntimeError(f"BatchNormHipFunction: residual must match x ({x.dtype}, {tuple(x.shape)}, {x.device}), got {residual.dtype}, "
+                               f"{tuple(residual.shape)}, {residual.device}")
+        for name, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if t is None:
+                if name in ("weight", "bias") or not training:
+                    raise RuntimeError(f"BatchNormHipFunction: {name} is required")
+                continue
+            if t.device != x.device:
+                raise RuntimeError(f"BatchNormHipFunction: {name} is on {t.device}, x on {x.device} (no CPU fallback)")
+            if t.dtype != torch.float32 or t.numel() != x.shape[1]:
+                raise RuntimeError(f"BatchNormHipFunction: {name} must be float32 [{x.shape[1]}], got {t.dtype} {tuple(t.shape)}")
+        b, c, h, w = x.shape
+        factor = 0.0
+        if training and running_mean is not None:
+            if num_batches_tracked is not None:
+                num_batches_tracked.add_(1)
+            factor = momentum if momentum is not None else 1.0 / float(num_batches_tracked)
+        flags = (_lib.BN_RELU if relu else 0) | (_lib.BN_ADD if residual is not None else 0) | (0 if training else _lib.BN_EVAL)
+        desc = (b * h * w, c, flags, eps, factor)
+        xn = _nhwc(x.detach(), c)
+        rn = None if residual is None else _nhwc(residual.detach(), c)
+        y = torch.empty((b, c, h, w), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        mean = invstd = None
+        if training:
+            mean = torch.empty(c, dtype=torch.float32, device=x.device)
+            invstd = torch.empty(c, dtype=torch.float32, device=x.device)
+        _run_bn(_BN_ENTRY[x.dtype] + "_forward", _lib.BnDesc(*desc), _lib.BN_FWD,
+                (xn, rn, weight, bias, running_mean, running_var, y.permute(0, 2, 3, 1), mean, invstd), x.device)
+        ctx.desc, ctx.relu, ctx.add, ctx.training = desc, relu, residual is not None, training
+        if training:
+            ctx.save_for_backward(xn, weight, mean, invstd, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        if not ctx.training:
+            raise RuntimeError("BatchNormHipFunction: the eval form has no backward pass")
+        xn, weight, mean, invstd, y = ctx.saved_tensors
+        b, h, w, c = xn.shape
+        gyn = gy.to(xn.dtype).permute(0, 2, 3, 1).contiguous()
+        dxn = torch.empty_like(xn)
+        dresn = torch.empty_like(xn) if ctx.add else None
+        dgamma = torch.empty(c, dtype=torch.float32, device=xn.device)
+        dbeta = torch.empty(c, dtype=torch.float32, device=xn.device)
+        yn = None if y is None else y.permute(0, 2, 3, 1)
+        _run_bn(_BN_ENTRY[xn.dtype] + "_backward", _lib.BnDesc(*ctx.desc), _lib.BN_BWD,
+                (gyn, xn, yn, weight, mean, invstd, dxn, dresn, dgamma, dbeta), xn.device)
+        dres = None if dresn is None else dresn.permute(0, 3, 1, 2)
+        return dxn.permute(0, 3, 1, 2), dres, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+def batch_norm_hip(bn: nn.BatchNorm2d, x: Tensor, residual: Optional[Tensor] = None, relu: bool = False) -> Tensor:
+    """relu?(bn(x) + residual?) on BatchNormHipFunction: batch statistics when the module is in train mode (or tracks none),
+    running statistics otherwise."""
+    training = bn.training or bn.running_mean is None
+    tracked = bn.training and bn.track_running_stats
+    return BatchNormHipFunction.apply(x, residual, bn.weight, bn.bias, bn.running_mean if (tracked or not training) else None,
+                                      bn.running_var if (tracked or not training) else None, bn.num_batches_tracked if tracked else None,
+                                      relu, bn.eps, bn.momentum, training)
 
 
 def _conv(precision: str):
@@ -206,6 +309,19 @@ def _bottleneck(blk, x: Tensor, conv, bn) -> Tensor:
     return F.relu(out + idt)
 
 
+def _basic_hip(blk, x: Tensor, conv) -> Tensor:
+    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True)
+    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]))
+    return batch_norm_hip(blk.bn2, conv(out, blk.conv2), residual=idt, relu=True)
+
+
+def _bottleneck_hip(blk, x: Tensor, conv) -> Tensor:
+    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True)
+    out = batch_norm_hip(blk.bn2, conv(out, blk.conv2), relu=True)
+    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]))
+    return batch_norm_hip(blk.bn3, conv(out, blk.conv3), residual=idt, relu=True)
+
+
 class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     """EarlyFusionCEResnet whose forward is an autograd graph (salve/models/early_fusion.py:41-83 op for op): HIP fp32
     convolutions, torch BatchNorm2d / ReLU / max-pool / average pool / Linear.  Train mode: batch statistics, running statistics
@@ -215,9 +331,15 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     `set_train_precision("bf16")` opts into mixed precision: the concatenated input is cast to bf16 once before the stem, the
     convolutions run on Conv2dBF16Function, BatchNorm upcasts its bf16 input to fp32 (fp32 weight, bias, running statistics and
     arithmetic; the output is rounded to bf16), ReLU / max-pool / residual adds run in bf16, and the average pool output is cast to fp32 before `fc`.
-    Parameters and gradients stay fp32.  Train and eval mode alike.  Separate from the parent's inference `set_precision`."""
+    Parameters and gradients stay fp32.  Train and eval mode alike.  Separate from the parent's inference `set_precision`.
+
+    `set_train_norm("hip")` opts into the HIP BatchNorm: one fused operation per BatchNorm (bn + relu after the stem, conv1 and
+    conv2, plain bn on the downsample branch, bn + add + relu at the end of a block), in fp32 and in bf16 (no casts around
+    BatchNorm then).  Train mode uses batch statistics; eval mode under torch.no_grad() (the validation pass) the eval form; eval
+    mode with gradients enabled runs the torch path, which has a backward pass.  The same parameters and buffers either way."""
 
     _train_precision = "fp32"
+    _train_norm = "torch"
 
     def set_train_precision(self, precision: str) -> "TrainableEarlyFusionCEResnet":
         """"fp32" (the default, the reference's precision) or "bf16" (opt-in mixed precision).  Returns self."""
@@ -229,6 +351,18 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     @property
     def train_precision(self) -> str:
         return self._train_precision
+
+    def set_train_norm(self, norm: str) -> "TrainableEarlyFusionCEResnet":
+        """"torch" (the default: nn.BatchNorm2d, F.relu and the add as separate operations) or "hip" (opt-in: BatchNormHipFunction).
+        Returns self."""
+        if norm not in TRAIN_NORMS:
+            raise ValueError(f"training norm must be one of {TRAIN_NORMS}, got {norm!r}")
+        self._train_norm = norm
+        return self
+
+    @property
+    def train_norm(self) -> str:
+        return self._train_norm
 
     def forward(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor] = None, x4: Optional[Tensor] = None, x5: Optional[Tensor] = None,
                 x6: Optional[Tensor] = None) -> Tensor:
@@ -244,11 +378,18 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
             x = x.to(torch.bfloat16)
         conv, bn = _conv(self._train_precision), (_bn_bf16 if bf16 else _bn)
         r = self.resnet
-        x = r.maxpool(F.relu(bn(r.bn1, conv(x, self.conv1))))
-        block = _bottleneck if r.block_kind == "bottleneck" else _basic
-        for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
-            for blk in layer:
-                x = block(blk, x, conv, bn)
+        if self._train_norm == "hip" and (self.training or not torch.is_grad_enabled()):
+            x = r.maxpool(batch_norm_hip(r.bn1, conv(x, self.conv1), relu=True))
+            block = _bottleneck_hip if r.block_kind == "bottleneck" else _basic_hip
+            for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
+                for blk in layer:
+                    x = block(blk, x, conv)
+        else:
+            x = r.maxpool(F.relu(bn(r.bn1, conv(x, self.conv1))))
+            block = _bottleneck if r.block_kind == "bottleneck" else _basic
+            for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
+                for blk in layer:
+                    x = block(blk, x, conv, bn)
         x = torch.flatten(r.avgpool(x), 1)
         if bf16:
             x = x.float()

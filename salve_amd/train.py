@@ -2,10 +2,12 @@
 
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
+                              [--norm {torch,hip}]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
-convolutions, fp32 master weights, gradients and checkpoint); the default fp32 is the reference's.  See salve_amd/training.py.
+convolutions, fp32 master weights, gradients and checkpoint); the default fp32 is the reference's.  --norm hip opts into the HIP
+BatchNorm with fused ReLU and residual add (same checkpoint); the default is torch's BatchNorm.  See salve_amd/training.py.
 """
 
 from __future__ import annotations
@@ -30,6 +32,8 @@ def main(argv=None) -> None:
     ap.add_argument("--out", default=None, help="results directory (default: model_save_dirpath/<time stamp>)")
     ap.add_argument("--precision", choices=("fp32", "bf16"), default="fp32",
                     help="fp32 (default, the reference's) or bf16 mixed precision (fp32 master weights and checkpoint)")
+    ap.add_argument("--norm", choices=("torch", "hip"), default="torch",
+                    help="torch (default: nn.BatchNorm2d) or hip (BatchNorm with fused ReLU and residual add on the HIP kernels)")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     args = load_training_config(a.config)
@@ -43,7 +47,7 @@ def main(argv=None) -> None:
         args.layout_data_root = a.layout_data_root
     out = a.out or f"{args.model_save_dirpath}/{time.strftime('%Y_%m_%d_%H_%M_%S')}"
     logging.info(str(args))
-    results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision)
+    results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm)
     logging.info(f"results in {out}: {results}")
 
 

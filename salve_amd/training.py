@@ -27,7 +27,7 @@ import torch
 from torch import Tensor, nn
 
 from salve_amd.evaluate import ClassAccuracyMeter
-from salve_amd.models.trainable import TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
+from salve_amd.models.trainable import TRAIN_NORMS, TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
 from salve_amd.training_config import TrainingConfig
 
 CRIT_ACC_STAT = "val_mAcc"   # scripts/train.py:85: the checkpoint-selection criterion
@@ -38,14 +38,21 @@ def _check_precision(precision: str) -> None:
         raise ValueError(f"training precision must be one of {TRAIN_PRECISIONS}, got {precision!r}")
 
 
-def get_model(args: TrainingConfig, precision: str = "fp32") -> nn.Module:
+def _check_norm(norm: str) -> None:
+    if norm not in TRAIN_NORMS:
+        raise ValueError(f"training norm must be one of {TRAIN_NORMS}, got {norm!r}")
+
+
+def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch") -> nn.Module:
     """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored.
-    precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision)."""
+    precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision).
+    norm: "torch" (nn.BatchNorm2d) or "hip" (opt-in fused HIP BatchNorm: TrainableEarlyFusionCEResnet.set_train_norm)."""
     _check_precision(precision)
+    _check_norm(norm)
     if not torch.cuda.is_available():
         raise RuntimeError("salve_amd.training needs the HIP device (no CPU fallback)")
     model = TrainableEarlyFusionCEResnet(args.num_layers, args.pretrained, args.num_ce_classes, args)
-    return model.set_train_precision(precision).cuda()
+    return model.set_train_precision(precision).set_train_norm(norm).cuda()
 
 
 def get_optimizer(args: TrainingConfig, model: nn.Module) -> torch.optim.Optimizer:
@@ -149,13 +156,16 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
     return {"avg_loss": loss_sum / loss_n if loss_n else 0.0, "mAcc": float(mAcc)}
 
 
-def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32") -> Dict[str, list]:
+def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
+          norm: str = "torch") -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
     checkpoint's state dict (strict).  precision: "fp32" (default) or "bf16" -- the checkpoint is fp32 either way (fp32 master
-    weights), with the same keys."""
+    weights), with the same keys.  norm: "torch" (default) or "hip", the fused HIP BatchNorm -- same parameters, buffers and
+    checkpoint."""
     _check_precision(precision)
+    _check_norm(norm)
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
@@ -163,7 +173,7 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     val_loader = get_dataloader(args, "val")
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
-    model = get_model(args, precision)
+    model = get_model(args, precision, norm)
     if init_ckpt:
         from salve_amd import train_utils
 

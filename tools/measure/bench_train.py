@@ -2,10 +2,12 @@
 convolution time and the rest (torch: BatchNorm, ReLU, pooling, fc, loss, Adam), and the same step with torch's own F.conv2d
 beside it, in the same process and alternating (context only: the product never calls F.conv2d).  --precision fp32,bf16 times
 the reference's fp32 step and the opt-in bf16 mixed-precision step (TrainableEarlyFusionCEResnet.set_train_precision) one after
-the other in the same process; the torch step of a precision runs F.conv2d in that precision.
+the other in the same process; the torch step of a precision runs F.conv2d in that precision.  --norm torch,hip times the step
+with torch's BatchNorm and with the opt-in fused HIP BatchNorm (TrainableEarlyFusionCEResnet.set_train_norm), alternating the two
+step by step inside the same process; the event split then also reports the time inside the salve_bn_* calls.
 
     python tools/measure/bench_train.py [--configs 50:1,152:2] [--batches 64,256] [--steps 3] [--warmup 1] [--hw 224]
-                                        [--precision fp32,bf16]
+                                        [--precision fp32,bf16] [--norm torch,hip]
 
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train.py ...` on its own.
 """
@@ -29,6 +31,7 @@ from salve_amd.models import trainable  # noqa: E402
 MODS = {1: ["floor_rgb_texture"], 2: ["ceiling_rgb_texture", "floor_rgb_texture"], 3: ["ceiling_rgb_texture", "floor_rgb_texture", "layout"]}
 _events = []
 _hip_run = trainable._run
+_hip_run_bn = trainable._run_bn
 _hip_conv = {"fp32": trainable.conv2d_f32, "bf16": trainable.conv2d_bf16}
 _conv_attr = {"fp32": "conv2d_f32", "bf16": "conv2d_bf16"}
 
@@ -37,6 +40,14 @@ def _timed_run(fn, desc, pass_, a, b, out):
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
     _hip_run(fn, desc, pass_, a, b, out)
+    e.record()
+    _events.append((fn, s, e))
+
+
+def _timed_run_bn(fn, desc, pass_, ptrs, device):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    _hip_run_bn(fn, desc, pass_, ptrs, device)
     e.record()
     _events.append((fn, s, e))
 
@@ -55,16 +66,17 @@ def step(model, opt, xs, y):
 def timed(model, opt, xs, y, conv_impl, split: bool, prec: str = "fp32"):
     setattr(trainable, _conv_attr[prec], conv_impl)
     trainable._run = _timed_run if split else _hip_run
+    trainable._run_bn = _timed_run_bn if split else _hip_run_bn
     _events.clear()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     step(model, opt, xs, y)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    conv = sum(s.elapsed_time(e) for _, s, e in _events) / 1e3 if split else 0.0
+    conv = sum(s.elapsed_time(e) for fn, s, e in _events if fn.startswith("salve_conv_")) / 1e3 if split else 0.0
     per = {}
     for fn, s, e in _events:
-        pass_ = fn.split("_", 3)[3]   # salve_conv_{f32,bf16}_<pass>
+        pass_ = fn.split("_", 3)[3] if fn.startswith("salve_conv_") else "bn"   # salve_conv_{f32,bf16}_<pass> | salve_bn_*
         per[pass_] = per.get(pass_, 0.0) + s.elapsed_time(e) / 1e3
     return dt, conv, per
 
@@ -78,10 +90,14 @@ def main() -> None:
     ap.add_argument("--hw", type=int, default=224)
     ap.add_argument("--no-torch", action="store_true", help="skip the F.conv2d comparison")
     ap.add_argument("--precision", default="fp32", help="training precisions, comma separated: fp32, bf16")
+    ap.add_argument("--norm", default="torch", help="BatchNorm implementations, comma separated: torch, hip (alternated step by step)")
     a = ap.parse_args()
     precs = a.precision.split(",")
     if not precs or any(p not in trainable.TRAIN_PRECISIONS for p in precs):
         ap.error(f"--precision takes a comma-separated list of {trainable.TRAIN_PRECISIONS}")
+    norms = a.norm.split(",")
+    if not norms or any(n not in trainable.TRAIN_NORMS for n in norms):
+        ap.error(f"--norm takes a comma-separated list of {trainable.TRAIN_NORMS}")
     dev = torch.device("cuda:0")
     fp32_step = {}
     print(f"# {torch.cuda.get_device_name(dev)}; {' / '.join(precs)} training step = forward + backward + Adam, input {a.hw}x{a.hw}, "
@@ -97,30 +113,44 @@ def main() -> None:
             xs = [torch.randn(batch, 3, a.hw, a.hw, device=dev) for _ in range(2 * nm)]
             y = torch.randint(0, 2, (batch,), device=dev)
             impls = [("hip", _hip_conv[prec])] + ([] if a.no_torch else [("torch", _torch_conv)])
-            res = {k: [] for k, _ in impls}
-            split = []
+            res = {(norm, k): [] for norm in norms for k, _ in impls}
+            split = {norm: [] for norm in norms}
             for i in range(a.warmup + a.steps):
-                for name, impl in impls:
-                    dt, _, _ = timed(model, opt, xs, y, impl, False, prec)
-                    if i >= a.warmup:
-                        res[name].append(dt)
-            for i in range(a.steps):   # separate steps with an event pair around every HIP convolution call
-                split.append(timed(model, opt, xs, y, _hip_conv[prec], True, prec))
+                for norm in norms:
+                    model.set_train_norm(norm)
+                    for name, impl in impls:
+                        dt, _, _ = timed(model, opt, xs, y, impl, False, prec)
+                        if i >= a.warmup:
+                            res[(norm, name)].append(dt)
+            for i in range(a.steps):   # separate steps with an event pair around every HIP convolution (and HIP BatchNorm) call
+                for norm in norms:
+                    model.set_train_norm(norm)
+                    split[norm].append(timed(model, opt, xs, y, _hip_conv[prec], True, prec))
             setattr(trainable, _conv_attr[prec], _hip_conv[prec])
             trainable._run = _hip_run
+            trainable._run_bn = _hip_run_bn
             med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-            sp = sorted(split, key=lambda t: t[0])[len(split) // 2]
-            tag = "" if prec == "fp32" else f" {prec}"
-            line = (f"resnet{layers} {6 * nm}ch batch {batch}{tag}: step {med['hip'] * 1e3:.1f} ms ({batch / med['hip']:.0f} samples/s); "
-                    f"HIP convolutions {sp[1] * 1e3:.1f} ms of a {sp[0] * 1e3:.1f} ms event-split step "
-                    f"[fwd {sp[2].get('forward', 0) * 1e3:.1f}, dgrad {sp[2].get('backward_data', 0) * 1e3:.1f}, "
-                    f"wgrad {sp[2].get('backward_weight', 0) * 1e3:.1f} ms], torch + host {(sp[0] - sp[1]) * 1e3:.1f} ms")
-            if "torch" in med:
-                line += f"; same step with F.conv2d: {med['torch'] * 1e3:.1f} ms ({batch / med['torch']:.0f} samples/s)"
-            fp32_step[(layers, nm, batch, prec)] = med["hip"]
-            if prec != "fp32" and (layers, nm, batch, "fp32") in fp32_step:
-                line += f"; {med['hip'] / fp32_step[(layers, nm, batch, 'fp32')]:.2f} x the fp32 step's time"
-            print(line, flush=True)
+            for norm in norms:
+                sp = sorted(split[norm], key=lambda t: t[0])[len(split[norm]) // 2]
+                step_s = med[(norm, "hip")]
+                tag = ("" if prec == "fp32" else f" {prec}") + ("" if norms == ["torch"] else f" norm {norm}")
+                bn = sp[2].get("bn", 0.0)
+                line = (f"resnet{layers} {6 * nm}ch batch {batch}{tag}: step {step_s * 1e3:.1f} ms ({batch / step_s:.0f} samples/s); "
+                        f"HIP convolutions {sp[1] * 1e3:.1f} ms of a {sp[0] * 1e3:.1f} ms event-split step "
+                        f"[fwd {sp[2].get('forward', 0) * 1e3:.1f}, dgrad {sp[2].get('backward_data', 0) * 1e3:.1f}, "
+                        f"wgrad {sp[2].get('backward_weight', 0) * 1e3:.1f} ms], ")
+                if norm == "hip":
+                    line += f"HIP BatchNorm {bn * 1e3:.1f} ms, "
+                line += f"torch + host {(sp[0] - sp[1] - bn) * 1e3:.1f} ms"
+                if (norm, "torch") in med:
+                    line += f"; same step with F.conv2d: {med[(norm, 'torch')] * 1e3:.1f} ms ({batch / med[(norm, 'torch')]:.0f} samples/s)"
+                fp32_step[(layers, nm, batch, prec, norm)] = step_s
+                if prec != "fp32" and (layers, nm, batch, "fp32", norm) in fp32_step:
+                    line += f"; {step_s / fp32_step[(layers, nm, batch, 'fp32', norm)]:.2f} x the fp32 step's time"
+                if norm != "torch" and (norm, "hip") in med and ("torch", "hip") in med:
+                    line += f"; {step_s / med[('torch', 'hip')]:.2f} x the torch-norm step's time"
+                print(line, flush=True)
+            model.set_train_norm("torch")
             del model, opt, xs
             torch.cuda.empty_cache()
 
