@@ -42,7 +42,7 @@ typedef enum {
                                      given order), salve_bev_densify_tiles, a launch of >= 1025 renders keeps its dispatch order in the workspace's key image; unknown
                                      `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
-                                        additive within 7: salve_conv_f32_* (training convolutions) and salve_bev_tiles_aug */
+                                        additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug and salve_bev_train_tiles */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -55,6 +55,8 @@ typedef enum {
 
 #define SALVE_STATUS_LAYOUT_THICKNESS 8 /* layout_rasterise: a segment of thickness >= 19 pixels (OpenCV draws its end caps as 20- / 72-gons,
                                           which are not implemented) -- that segment is not drawn */
+#define SALVE_STATUS_BAD_TILE_JOB 16 /* bev_train_tiles: a job names another sample, channels outside the sample, an image outside its array, or
+                                        a draw carries unknown flag bits -- that sample is not written */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -258,6 +260,34 @@ typedef struct {
 int salve_bev_tiles_aug(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs, const salve_tile_aug_t* aug,
                         int32_t n_jobs, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
                         float* out, int32_t out_c, void* stream);
+
+/* The TRAIN transform of a whole batch in ONE launch, in the layout and precision the trainable model's stem convolution reads:
+ * salve/train_utils.py:63-124 (Resize -> Crop(rand) -> RandomHorizontalFlip -> RandomVerticalFlip -> ToTensor -> Normalize, ONE set of
+ * draws per example shared by its 2 / 4 images) followed by the channel concatenation of salve/models/early_fusion.py:52-60, for
+ * images that are still in device memory as the rasteriser left them (no JPEG hop: salve/dataset/zind_data.py:306-315 reads them
+ * from disk).  Same 11-bit taps and LUT as salve_bev_tiles_aug: the fp32 values are bit-identical to its output, the bf16 values are
+ * those rounded once to nearest even.
+ *   bev_a / bev_b   two arrays of uint32 0x00BBGGRR images, n_bev_a / n_bev_b images of bev_h x bev_w (as for salve_bev_tile_pairs:
+ *                   the batch's posed renders; the identity renders, one per panorama and surface)
+ *   jobs_a / jobs_b device salve_tile_job_t [batch][per_sample], sample-major: the per_sample (1..3: one per surface) images of
+ *                   sample s from bev_a / bev_b.  .bev_offset = element offset of the image inside its array, .slot = s,
+ *                   .chan = first of its 3 channels, a multiple of 3 with chan + 3 <= out_c
+ *   aug             device salve_tile_aug_t [batch]: ONE draw per sample; offsets are clamped into [0, resize - crop] as by
+ *                   salve_bev_tiles_aug
+ *   out             SALVE_TILE_F32_NHWC: float [batch, crop, crop, out_c]; SALVE_TILE_BF16_NHWC: bf16 bit patterns (uint16_t) of the same
+ *                   shape; 16-byte aligned.  out_c: a multiple of 8 >= 6 * per_sample (8, 16 or 24).  EVERY channel is written:
+ *                   channels no job names (the padding behind the last image) are zero, so `out` needs no memset.
+ *   status          device int32 status word or NULL.  The job tables and draws are device memory, so the kernel checks them before
+ *                   it forms an address: a job with .slot != s, channels outside [0, out_c), an image outside its array, or a draw
+ *                   with unknown flag bits raises SALVE_STATUS_BAD_TILE_JOB and leaves sample s unwritten.
+ * SALVE_ERR_BAD_ARG on null pointers, crop <= 0, resize < crop, per_sample outside 1..3, an out_c that is not such a multiple of 8,
+ * an unknown format, a misaligned `out`, batch > 65535. */
+#define SALVE_TILE_F32_NHWC 3
+#define SALVE_TILE_BF16_NHWC 4
+int salve_bev_train_tiles(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                          const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
+                          int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                          void* out, int32_t out_format, int32_t out_c, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

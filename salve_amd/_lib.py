@@ -21,6 +21,8 @@ EXPECTED_ABI = 7          # include/salve_hip.h: SALVE_HIP_ABI_VERSION
 TILE_F32_NCHW = 0
 TILE_F16_NHWC = 1
 TILE_U8X4 = 2
+TILE_F32_NHWC = 3         # salve_bev_train_tiles only
+TILE_BF16_NHWC = 4
 
 # every symbol include/salve_hip.h declares (tests check the library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -65,6 +67,7 @@ EXPORTED_SYMBOLS = (
     "salve_bn_f32_backward",
     "salve_bn_bf16_forward",
     "salve_bn_bf16_backward",
+    "salve_bev_train_tiles",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -74,6 +77,7 @@ STATUS_WALK_FAILED = 1
 STATUS_FP16_RANGE = 2
 STATUS_BAD_HYPOTHESIS = 4
 STATUS_LAYOUT_THICKNESS = 8
+STATUS_BAD_TILE_JOB = 16
 
 
 class BevConfig(ctypes.Structure):
@@ -198,6 +202,8 @@ def load() -> ctypes.CDLL:
     lib.salve_resnet_f32_forward.restype = ctypes.c_int
     lib.salve_bev_tiles_aug.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, i32, i32, vp, vp, i32, vp]
     lib.salve_bev_tiles_aug.restype = ctypes.c_int
+    lib.salve_bev_train_tiles.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
+    lib.salve_bev_train_tiles.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -235,6 +241,9 @@ def check_status_word(word: int, what: str) -> None:
         raise SalveHipError(f"{what}: a render row names a panorama outside the uploaded batch (or an unknown surface); its image is empty")
     if word & STATUS_LAYOUT_THICKNESS:
         raise SalveHipError(f"{what}: a layout segment of 19 pixels or more was left out (its OpenCV end caps are not implemented)")
+    if word & STATUS_BAD_TILE_JOB:
+        raise SalveHipError(f"{what}: a train-tile job names another sample, channels or an image outside its arrays (or a draw has unknown "
+                            "flag bits); that sample was not written")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

@@ -992,6 +992,90 @@ __global__ __launch_bounds__(256) void bev_tile_pair_kernel(const uint32_t* __re
     }
 }
 
+// salve_bev_train_tiles: the TRAIN transform of a whole batch in the training model's input layout -- NHWC [batch, crop, crop, CP],
+// fp32 or bf16, the channels behind the last image written as zero.  The workgroups of sample `smp` read its 2 * per_sample images (posed
+// renders from bev_a, identity renders from bev_b) with tile_pixel -- bev_tile_aug_kernel's arithmetic at the sample's ONE draw -- and a
+// thread stores all CP channels of its pixel with 16-byte stores.  The job tables live in device memory, so their ranges are checked HERE,
+// before any address is formed: a job outside its sample, its channels or its image array raises SALVE_STATUS_BAD_TILE_JOB and the
+// sample is left unwritten.
+struct TrainTiles {
+    const uint32_t* bev_a;
+    const uint32_t* bev_b;
+    const salve_tile_job_t* jobs_a;   // [batch][per_sample]
+    const salve_tile_job_t* jobs_b;   // [batch][per_sample]
+    const salve_tile_aug_t* aug;      // [batch]
+    const int32_t* coef_y;
+    const int32_t* coef_x;
+    const float* lut;
+    void* out;
+    int32_t* status;
+    long long px_a, px_b;             // uint32 elements of bev_a / bev_b
+    int W, HW, resize, crop, batch, per_sample, n_blocks;
+};
+
+template <int CP, bool BF16>
+__global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t) {
+    typedef __attribute__((__ext_vector_type__(8))) float f32x8;
+    typedef __attribute__((__ext_vector_type__(8))) __bf16 bf16x8;
+    constexpr int MAX_S = CP / 6, GROUPS = CP / 3;
+    // (the workgroups of one sample read the same images: same id % 8 = same XCD = one L2 -- as in bev_tile_pair_kernel)
+    const int id = blockIdx.x, s_ = id >> 3;
+    const int smp = (s_ / t.n_blocks) * 8 + (id & 7), blk = s_ % t.n_blocks;
+    if (smp >= t.batch) return;
+    const salve_tile_aug_t a = t.aug[smp];
+    salve_tile_job_t ja[MAX_S], jb[MAX_S];
+    bool bad = (a.flags & ~(SALVE_TILE_HFLIP | SALVE_TILE_VFLIP)) != 0;
+#pragma unroll
+    for (int k = 0; k < MAX_S; k++) {
+        if (k < t.per_sample) {
+            ja[k] = t.jobs_a[(size_t)smp * t.per_sample + k];
+            jb[k] = t.jobs_b[(size_t)smp * t.per_sample + k];
+            bad |= ja[k].slot != smp || ja[k].chan < 0 || ja[k].chan % 3 != 0 || ja[k].chan + 3 > CP || ja[k].bev_offset < 0 || ja[k].bev_offset + t.HW > t.px_a;
+            bad |= jb[k].slot != smp || jb[k].chan < 0 || jb[k].chan % 3 != 0 || jb[k].chan + 3 > CP || jb[k].bev_offset < 0 || jb[k].bev_offset + t.HW > t.px_b;
+        } else {
+            ja[k].chan = jb[k].chan = -1;   // names no channel group
+            ja[k].bev_offset = jb[k].bev_offset = 0;
+        }
+    }
+    if (bad) {
+        if (t.status && blk == 0 && threadIdx.x == 0) atomicOr(t.status, SALVE_STATUS_BAD_TILE_JOB);
+        return;
+    }
+    const int idx = blk * 256 + threadIdx.x;
+    if (idx >= t.crop * t.crop) return;
+    const int i = idx / t.crop, j = idx % t.crop;
+    const int oy = min(max(a.crop_y, 0), t.resize - t.crop), ox = min(max(a.crop_x, 0), t.resize - t.crop);
+    const int si = (a.flags & SALVE_TILE_VFLIP) ? t.crop - 1 - i : i, sj = (a.flags & SALVE_TILE_HFLIP) ? t.crop - 1 - j : j;
+    const int4 cy = reinterpret_cast<const int4*>(t.coef_y)[si + oy];
+    const int4 cx = reinterpret_cast<const int4*>(t.coef_x)[sj + ox];
+    float v[CP];
+#pragma unroll
+    for (int c = 0; c < CP; c++) v[c] = 0.0f;
+#pragma unroll
+    for (int g = 0; g < GROUPS; g++) {   // channel group g = channels 3 g .. 3 g + 2: the image whose job names it (workgroup-uniform)
+        const uint32_t* img = nullptr;
+#pragma unroll
+        for (int k = 0; k < MAX_S; k++) {
+            if (ja[k].chan == 3 * g) img = t.bev_a + ja[k].bev_offset;
+            if (jb[k].chan == 3 * g) img = t.bev_b + jb[k].bev_offset;
+        }
+        if (img) tile_pixel(img, t.W, cy, cx, t.lut, &v[3 * g]);
+    }
+    const size_t px = ((size_t)smp * t.crop * t.crop + idx) * CP;
+    if (BF16) {
+        uint4* o = reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(t.out) + px);
+#pragma unroll
+        for (int c = 0; c < CP / 8; c++) {   // one rounding to nearest even (v_cvt_pk_bf16_f32), as conv_train_bf16.hip's epilogue
+            const f32x8 f = {v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6], v[8 * c + 7]};
+            o[c] = __builtin_bit_cast(uint4, __builtin_convertvector(f, bf16x8));
+        }
+    } else {
+        float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(t.out) + px);
+#pragma unroll
+        for (int c = 0; c < CP / 4; c++) o[c] = make_float4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
+    }
+}
+
 __global__ __launch_bounds__(256) void bev_export_kernel(const uint32_t* __restrict__ bev, size_t npx,
                                                          uint8_t* __restrict__ out) {
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -1501,6 +1585,45 @@ int salve_bev_tile_pairs(const uint32_t* bev_a, const uint32_t* bev_b, int32_t b
     dim3 g((unsigned)((xcd_group ? (n_pairs + 7) / 8 * 8 : n_pairs) * n_blocks));
     hipLaunchKernelGGL(bev_tile_pair_kernel, g, dim3(256), 0, (hipStream_t)stream, bev_a, bev_b, bev_w, jobs_a, jobs_b, coef_y, coef_x,
                        resize, crop, lut, reinterpret_cast<uint16_t*>(out), out_c, n_pairs, n_blocks, xcd_group, b_pretiled ? 1 : 0);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
+int salve_bev_train_tiles(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                          const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
+                          int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                          void* out, int32_t out_format, int32_t out_c, int32_t* status, void* stream) {
+    if (batch == 0) return SALVE_OK;
+    if (!bev_a || !bev_b || !jobs_a || !jobs_b || !aug || !coef_y || !coef_x || !lut || !out || batch < 0 || n_bev_a <= 0 || n_bev_b <= 0 ||
+        bev_h <= 0 || bev_w <= 0) {
+        salve_fail("salve_bev_train_tiles: null pointer or bad size");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (crop <= 0 || resize < crop) { salve_fail("salve_bev_train_tiles: need 0 < crop <= resize"); return SALVE_ERR_BAD_ARG; }
+    if (per_sample < 1 || per_sample > 3) { salve_fail("salve_bev_train_tiles: 1 to 3 images per sample and table"); return SALVE_ERR_BAD_ARG; }
+    if (out_c <= 0 || out_c % 8 != 0 || out_c < 6 * per_sample || out_c > 24) {
+        salve_fail("salve_bev_train_tiles: out_c must be a multiple of 8 that holds the sample's 6 * per_sample channels (8, 16 or 24)");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (out_format != SALVE_TILE_F32_NHWC && out_format != SALVE_TILE_BF16_NHWC) { salve_fail("salve_bev_train_tiles: unknown tile format"); return SALVE_ERR_BAD_ARG; }
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) { salve_fail("salve_bev_train_tiles: out must be 16-byte aligned"); return SALVE_ERR_BAD_ARG; }
+    if (batch > 65535) { salve_fail("at most 65535 samples per call"); return SALVE_ERR_BAD_ARG; }
+    const int n_blocks = (crop * crop + 255) / 256;
+    const TrainTiles t = {bev_a, bev_b, jobs_a, jobs_b, aug, coef_y, coef_x, lut, out, status, (long long)n_bev_a * bev_h * bev_w,
+                          (long long)n_bev_b * bev_h * bev_w, bev_w, bev_h * bev_w, resize, crop, batch, per_sample, n_blocks};
+    const dim3 g((unsigned)((batch + 7) / 8 * 8 * n_blocks));
+    const bool bf16 = out_format == SALVE_TILE_BF16_NHWC;
+    hipStream_t s = (hipStream_t)stream;
+    if (out_c == 8) {
+        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<8, true>), g, dim3(256), 0, s, t);
+        else hipLaunchKernelGGL((bev_train_tile_kernel<8, false>), g, dim3(256), 0, s, t);
+    } else if (out_c == 16) {
+        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<16, true>), g, dim3(256), 0, s, t);
+        else hipLaunchKernelGGL((bev_train_tile_kernel<16, false>), g, dim3(256), 0, s, t);
+    } else {
+        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<24, true>), g, dim3(256), 0, s, t);
+        else hipLaunchKernelGGL((bev_train_tile_kernel<24, false>), g, dim3(256), 0, s, t);
+    }
     SALVE_HIP_CHECK(hipGetLastError());
     return SALVE_OK;
 }

@@ -72,7 +72,7 @@ class Conv2dF32Function(torch.autograd.Function):
     dgrad is skipped when x needs no gradient."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int) -> Tensor:
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False) -> Tensor:
         for name, t in (("x", x), ("weight", weight)):
             if t.device.type != "cuda":
                 raise RuntimeError(f"Conv2dF32Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
@@ -81,7 +81,11 @@ class Conv2dF32Function(torch.autograd.Function):
                 raise RuntimeError(f"Conv2dF32Function: {name} must be float32 (training runs in the reference's fp32), got {t.dtype}")
         b, cin, h, w = x.shape
         cout, cin_w, kh, kw = weight.shape
-        if cin_w != cin:
+        if packed:   # x carries the weight's input channels zero-padded to a multiple of 8 already (forward_packed)
+            if cin != _pad8(cin_w):
+                raise RuntimeError(f"Conv2dF32Function: weight takes {cin_w} input channels, a packed x needs {_pad8(cin_w)}, got {cin}")
+            cin = cin_w
+        elif cin_w != cin:
             raise RuntimeError(f"Conv2dF32Function: weight takes {cin_w} input channels, x has {cin}")
         cp = _pad8(cin)
         ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
@@ -112,12 +116,12 @@ class Conv2dF32Function(torch.autograd.Function):
             dwk = torch.empty_like(wk)
             _run("salve_conv_f32_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
             dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
-def conv2d_f32(x: Tensor, conv: nn.Conv2d) -> Tensor:
+def conv2d_f32(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:
     assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
-    return Conv2dF32Function.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+    return Conv2dF32Function.apply(x, conv.weight, conv.stride[0], conv.padding[0], packed)
 
 
 class Conv2dBF16Function(torch.autograd.Function):
@@ -129,7 +133,7 @@ class Conv2dBF16Function(torch.autograd.Function):
     channels are zero-padded to a multiple of 8 as for Conv2dF32Function; its dgrad raises if asked."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int) -> Tensor:
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False) -> Tensor:
         for name, t, dt in (("x", x, torch.bfloat16), ("weight", weight, torch.float32)):
             if t.device.type != "cuda":
                 raise RuntimeError(f"Conv2dBF16Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
@@ -138,7 +142,11 @@ class Conv2dBF16Function(torch.autograd.Function):
                 raise RuntimeError(f"Conv2dBF16Function: {name} must be {dt} (bf16 activations, fp32 master weights), got {t.dtype}")
         b, cin, h, w = x.shape
         cout, cin_w, kh, kw = weight.shape
-        if cin_w != cin:
+        if packed:   # x carries the weight's input channels zero-padded to a multiple of 8 already (forward_packed)
+            if cin != _pad8(cin_w):
+                raise RuntimeError(f"Conv2dBF16Function: weight takes {cin_w} input channels, a packed x needs {_pad8(cin_w)}, got {cin}")
+            cin = cin_w
+        elif cin_w != cin:
             raise RuntimeError(f"Conv2dBF16Function: weight takes {cin_w} input channels, x has {cin}")
         cp = _pad8(cin)
         ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
@@ -169,12 +177,12 @@ class Conv2dBF16Function(torch.autograd.Function):
             dwk = torch.empty(wk.shape, dtype=torch.float32, device=gy.device)
             _run("salve_conv_bf16_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
             dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
-        return dx, dw, None, None
+        return dx, dw, None, None, None
 
 
-def conv2d_bf16(x: Tensor, conv: nn.Conv2d) -> Tensor:
+def conv2d_bf16(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:
     assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
-    return Conv2dBF16Function.apply(x, conv.weight, conv.stride[0], conv.padding[0])
+    return Conv2dBF16Function.apply(x, conv.weight, conv.stride[0], conv.padding[0], packed)
 
 
 TRAIN_PRECISIONS = ("fp32", "bf16")
@@ -373,19 +381,40 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
         if x1.device.type != "cuda":
             raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
         x = torch.cat(xs, dim=1)
-        bf16 = self._train_precision == "bf16"
-        if bf16:
+        if self._train_precision == "bf16":
             x = x.to(torch.bfloat16)
+        return self._from_stem(x, packed=False)
+
+    def forward_packed(self, x: Tensor) -> Tensor:
+        """`forward` on the input as the stem convolution reads it: x [B, H, W, Cp], contiguous NHWC, Cp = the 3 * images channels
+        in `forward`'s concatenation order zero-padded to a multiple of 8, in the training precision (float32 / bfloat16) -- what
+        salve_bev_train_tiles writes (salve_amd.train_render).  The same graph as `forward` from the stem on, without its torch.cat,
+        cast and padding copy: the same kernels on the same bytes, so logits and gradients are bit-identical."""
+        cp = _pad8(3 * num_input_images(self.modalities))
+        want = torch.bfloat16 if self._train_precision == "bf16" else torch.float32
+        if x.dim() != 4 or x.shape[3] != cp:
+            raise RuntimeError(f"forward_packed takes [B, H, W, {cp}] for modalities {self.modalities}, got {tuple(x.shape)}")
+        if x.dtype != want:
+            raise RuntimeError(f"forward_packed: train precision {self._train_precision} takes {want}, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
+        if not x.is_contiguous():
+            raise RuntimeError("forward_packed takes a contiguous NHWC tensor")
+        return self._from_stem(x.permute(0, 3, 1, 2), packed=True)   # (an NCHW view of the NHWC bytes: the stem uses them as they are)
+
+    def _from_stem(self, x: Tensor, packed: bool) -> Tensor:
+        bf16 = self._train_precision == "bf16"
         conv, bn = _conv(self._train_precision), (_bn_bf16 if bf16 else _bn)
         r = self.resnet
+        x = conv(x, self.conv1, True) if packed else conv(x, self.conv1)
         if self._train_norm == "hip" and (self.training or not torch.is_grad_enabled()):
-            x = r.maxpool(batch_norm_hip(r.bn1, conv(x, self.conv1), relu=True))
+            x = r.maxpool(batch_norm_hip(r.bn1, x, relu=True))
             block = _bottleneck_hip if r.block_kind == "bottleneck" else _basic_hip
             for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
                 for blk in layer:
                     x = block(blk, x, conv)
         else:
-            x = r.maxpool(F.relu(bn(r.bn1, conv(x, self.conv1))))
+            x = r.maxpool(F.relu(bn(r.bn1, x)))
             block = _bottleneck if r.block_kind == "bottleneck" else _basic
             for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
                 for blk in layer:

@@ -336,3 +336,23 @@ class BevRasteriser:
             )
         _lib.check(st, "salve_bev_tile_pairs")
         return out
+
+    def train_tiles(self, bev_a: torch.Tensor, bev_b: torch.Tensor, jobs_a: torch.Tensor, jobs_b: torch.Tensor, per_sample: int,
+                    aug: torch.Tensor, batch: int, out: torch.Tensor) -> torch.Tensor:
+        """The train transform of a whole batch in one launch (include/salve_hip.h: salve_bev_train_tiles): `out` is the trainable
+        model's packed input [batch, crop, crop, Cp], float32 or bfloat16, every channel written (padding channels zero).  bev_a / bev_b:
+        int32 [*, H, W] images; jobs_a / jobs_b: `upload_tile_jobs` tables, sample-major [batch][per_sample]; aug: TILE_AUG_DTYPE
+        bytes, one draw per sample.  Bad jobs are reported through the device status word (`check`)."""
+        Hb, Wb = self.bev_hw
+        if out.dtype not in (torch.float32, torch.bfloat16):
+            raise _lib.SalveHipError(f"train_tiles writes float32 or bfloat16, got {out.dtype}")
+        if not out.is_contiguous() or tuple(out.shape[:3]) != (batch, self.crop, self.crop):
+            raise _lib.SalveHipError(f"train_tiles: out must be contiguous [{batch}, {self.crop}, {self.crop}, Cp], got {tuple(out.shape)}")
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            st = self.lib.salve_bev_train_tiles(
+                p(bev_a), int(bev_a.numel() // (Hb * Wb)), p(bev_b), int(bev_b.numel() // (Hb * Wb)), Hb, Wb, p(jobs_a), p(jobs_b), per_sample,
+                p(aug), batch, p(self.coef_y), p(self.coef_x), self.resize, self.crop, p(self.lut), p(out),
+                _lib.TILE_F32_NHWC if out.dtype == torch.float32 else _lib.TILE_BF16_NHWC, int(out.shape[3]), status.ptr(self.device), self._stream())
+        _lib.check(st, "salve_bev_train_tiles")
+        return out

@@ -2,12 +2,14 @@
 
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
-                              [--norm {torch,hip}]
+                              [--norm {torch,hip}] [--render-from DIR]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
 convolutions, fp32 master weights, gradients and checkpoint); the default fp32 is the reference's.  --norm hip opts into the HIP
 BatchNorm with fused ReLU and residual add (same checkpoint); the default is torch's BatchNorm.  See salve_amd/training.py.
+--render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
+val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
 """
 
 from __future__ import annotations
@@ -34,6 +36,8 @@ def main(argv=None) -> None:
                     help="fp32 (default, the reference's) or bf16 mixed precision (fp32 master weights and checkpoint)")
     ap.add_argument("--norm", choices=("torch", "hip"), default="torch",
                     help="torch (default: nn.BatchNorm2d) or hip (BatchNorm with fused ReLU and residual add on the HIP kernels)")
+    ap.add_argument("--render-from", default=None, metavar="DIR",
+                    help="render the training batches on the GPU from DIR/panos_rgb.npy, panos_depth.npy, train.json, val.json")
     a = ap.parse_args(argv)
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     args = load_training_config(a.config)
@@ -47,7 +51,27 @@ def main(argv=None) -> None:
         args.layout_data_root = a.layout_data_root
     out = a.out or f"{args.model_save_dirpath}/{time.strftime('%Y_%m_%d_%H_%M_%S')}"
     logging.info(str(args))
-    results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm)
+    if a.render_from is not None:
+        import torch
+
+        from salve_amd import train_render
+
+        rgb, depth, examples = train_render.load_render_dir(a.render_from)
+        sources = {}
+        for split in ("train", "val"):
+            src = train_render.RenderedTrainSource(torch.device("cuda", torch.cuda.current_device()), args.modalities, pano_hw=rgb.shape[1:3],
+                                                   batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
+                                                   resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w))
+            if split == "train":
+                src.load_panos(rgb, depth)
+            else:   # the panoramas and their identity renders are on the device once
+                src.share_panos(sources["train"])
+            src.set_examples(*examples[split])
+            sources[split] = src
+        results = training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
+                                          norm=a.norm)
+    else:
+        results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm)
     logging.info(f"results in {out}: {results}")
 
 

@@ -2,7 +2,8 @@
 training convolutions.
 
 Same names as the reference: get_model, get_optimizer, poly_learning_rate, cross_entropy_forward, get_train_transform,
-get_dataloader, run_epoch, plus `train` (scripts/train.py:41-119's main).  The model is
+get_dataloader, run_epoch, plus `train` (scripts/train.py:41-119's main) and `train_rendered`, the same loop fed by batches
+rendered on the GPU (salve_amd.train_render) instead of the rendered dataset on disk.  The model is
 salve_amd.models.trainable.TrainableEarlyFusionCEResnet (its checkpoints load into the inference EarlyFusionCEResnet with
 strict=True).  salve_amd.train_utils stays inference-only and keeps refusing the train split: training is reached through this
 module (and `python -m salve_amd.train`) only.
@@ -81,6 +82,18 @@ def cross_entropy_forward(model: nn.Module, split: str, x1: Tensor, x2: Tensor, 
     return probs, loss
 
 
+def cross_entropy_forward_packed(model: nn.Module, split: str, x_packed: Tensor, is_match: Tensor) -> Tuple[Tensor, Tensor]:
+    """`cross_entropy_forward` for the packed input of salve_amd.train_render ([B, H, W, Cp], `model.forward_packed`)."""
+    if split == "train":
+        logits = model.forward_packed(x_packed)
+    else:
+        with torch.no_grad():
+            logits = model.forward_packed(x_packed)
+    probs = torch.nn.functional.softmax(logits.detach().clone(), dim=1)
+    loss = torch.nn.functional.cross_entropy(logits, is_match.squeeze())
+    return probs, loss
+
+
 def get_train_transform(args: TrainingConfig):
     """Resize -> random Crop -> random horizontal flip -> random vertical flip -> ToTensor -> Normalize for 2 / 4 / 6 images
     (salve/train_utils.py:63-124), on the GPU (transforms.TrainTransform)."""
@@ -124,7 +137,8 @@ def _unpack(args: TrainingConfig, example):
 
 def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
     """One pass over a split (scripts/train.py:169-278): train mode + Adam steps + the poly schedule for "train", eval mode
-    otherwise.  Returns {"avg_loss", "mAcc"}; as in the reference, avg_loss counts training batches only (0 for val)."""
+    otherwise.  Returns {"avg_loss", "mAcc"}; as in the reference, avg_loss counts training batches only (0 for val).
+    `data_loader`: a DataLoader over ZindData, or a train_render.RenderedTrainSource (2-tuples, through `model.forward_packed`)."""
     model.train() if split == "train" else model.eval()
     loss_sum, loss_n = 0.0, 0
     meter = ClassAccuracyMeter(args.num_ce_classes)
@@ -132,10 +146,14 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
     max_iter = args.num_epochs * len(data_loader)
     t0 = time.time()
     for it, example in enumerate(data_loader):
-        xs, is_match = _unpack(args, example)
-        xs = tuple(None if x is None else x.to(dev, non_blocking=True) for x in xs)
-        gt = is_match.to(dev, non_blocking=True)
-        probs, loss = cross_entropy_forward(model, split, *xs, gt)
+        if len(example) == 2:   # (x_packed, is_match) of a train_render.RenderedTrainSource: on the device, in the stem's layout
+            xs, gt = (example[0],), example[1]
+            probs, loss = cross_entropy_forward_packed(model, split, xs[0], gt)
+        else:
+            xs, is_match = _unpack(args, example)
+            xs = tuple(None if x is None else x.to(dev, non_blocking=True) for x in xs)
+            gt = is_match.to(dev, non_blocking=True)
+            probs, loss = cross_entropy_forward(model, split, *xs, gt)
         meter.update(torch.argmax(probs, dim=1).cpu().numpy(), gt.squeeze().cpu().numpy())
         current_iter = epoch * len(data_loader) + it + 1
         if split == "train":
@@ -169,8 +187,28 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    train_loader = get_dataloader(args, "train", seed=seed)
-    val_loader = get_dataloader(args, "val")
+    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm)
+
+
+def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
+                   precision: str = "fp32", norm: str = "torch") -> Dict[str, list]:
+    """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
+    split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON."""
+    _check_precision(precision)
+    _check_norm(norm)
+    get_train_transform(args)   # (the refusals of the on-disk path: photometric augmentation, crop-with-padding)
+    want = torch.bfloat16 if precision == "bf16" else torch.float32
+    for src in (train_source, val_source):
+        if src.dtype != want:
+            raise RuntimeError(f"the batch source yields {src.dtype}, training precision {precision} takes {want}")
+    np.random.seed(seed)
+    random.seed(seed)
+    torch.manual_seed(seed)
+    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm)
+
+
+def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str) -> Dict[str, list]:
+    """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources."""
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
     model = get_model(args, precision, norm)

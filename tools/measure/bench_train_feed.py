@@ -1,0 +1,198 @@
+"""Time the rendered training feed (salve_amd.train_render) beside the training step it feeds, on one MI355X:
+
+  * the source alone, per batch: host clock around one batch + synchronise, and HIP events around its scatter / densify / tile launches;
+    the tile launch also as a rate of algorithmic bytes (the batch tensor written + the BEV images of the batch read once);
+  * the training step (forward + backward + Adam) three ways, alternating step by step in one process: resident NCHW tensors through
+    `forward` (what tools/measure/bench_train.py times), the resident packed tensor through `forward_packed`, and a batch rendered by
+    the source through `forward_packed` (feed included);
+  * --disk N: end-to-end samples/s of `training.run_epoch` over N batches from the source and from the on-disk path -- the same
+    examples written once as JPEGs into a temporary ZindData tree (outside the timed region) and fed by `training.get_dataloader`.
+
+    python tools/measure/bench_train_feed.py [--configs 152:2,50:1] [--batch 256] [--modes bf16:hip,fp32:torch] [--steps 5] [--warmup 2]
+                                             [--panos 64] [--disk 0]
+
+Synthetic 1024 x 512 panoramas (as bench.py).  Medians; run the command twice for the spread.  Per-kernel times: a run of its own under
+`rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train_feed.py ...`.
+"""
+
+from __future__ import annotations
+
+import argparse
+import random
+import shutil
+import sys
+import tempfile
+import time
+from pathlib import Path
+from types import SimpleNamespace
+
+ROOT = Path(__file__).resolve().parents[2]
+sys.path.insert(0, str(ROOT))
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+from salve_amd import synthetic, train_render, training  # noqa: E402
+from salve_amd.models import trainable  # noqa: E402
+from salve_amd.training_config import TrainingConfig  # noqa: E402
+
+MODS = {1: ["floor_rgb_texture"], 2: ["ceiling_rgb_texture", "floor_rgb_texture"]}
+COPY_TBS = 5.3   # the measured float4 copy rate (profiles/r06_copy_sweep.txt)
+
+
+def med(v):
+    return sorted(v)[len(v) // 2]
+
+
+def config(layers: int, nm: int, batch: int, data_root: str = "") -> TrainingConfig:
+    return TrainingConfig(lr_annealing_strategy="poly", base_lr=1e-4, weight_decay=1e-4, num_ce_classes=2, print_every=10 ** 9, poly_lr_power=0.9,
+                          optimizer_algo="adam", num_layers=layers, pretrained=False, dataparallel=False, resize_h=234, resize_w=234, train_h=224,
+                          train_w=224, apply_photometric_augmentation=False, modalities=tuple(MODS[nm]), cfg_stem="feed", num_epochs=1, workers=0,
+                          batch_size=batch, data_root=data_root, layout_data_root="", model_save_dirpath="")
+
+
+def step(model, opt, fwd, y):
+    opt.zero_grad(set_to_none=True)
+    F.cross_entropy(fwd(), y).backward()
+    opt.step()
+
+
+def wall(fn) -> float:
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0
+
+
+def write_zind_tree(root: Path, src, n: int) -> None:
+    """Examples 0 .. n-1 of `src` as the reference's rendered dataset: {root}/{label}/{building}/pair_{k}___..._{surface}_rgb_floor_01_..._pano_{id}.jpg
+    (building 1208 is in the official train split).  The JPEGs are the source's own renders -- lossy, as the on-disk path's inputs are."""
+    from salve_amd.rasteriser import SURFACES, pack_hypotheses
+    from salve_amd.utils import image_io
+
+    ex, S = src.examples, len(src.surfaces)
+    surf = [SURFACES[s] for s in src.surfaces]
+    ident = src.ras.export_u8(src.ref_bev).cpu().numpy()
+    for lo in range(0, n, 64):
+        m = min(64, n - lo)
+        idx = np.arange(lo, lo + m)
+        rows = pack_hypotheses(np.repeat(ex["i1"][idx], S), np.tile(surf, m), np.repeat(ex["R"][idx], S, axis=0), np.repeat(ex["t"][idx], S, axis=0), np.ones(m * S))
+        bev, _ = src.ras.render(src.pano_rgb, src.pano_depth, src.ras.upload_hypotheses(rows), m * S)
+        posed = src.ras.export_u8(bev).cpu().numpy()
+        for k, j in enumerate(idx):
+            label = "gt_alignment_approx" if ex["is_match"][j] else "incorrect_alignment"
+            d = root / label / "1208"
+            d.mkdir(parents=True, exist_ok=True)
+            if S == 1:   # ZindData groups a pair's FOUR tiles, whichever modalities are read: the other surface's files exist, unread
+                other = "ceiling" if src.surfaces[0] == "floor" else "floor"
+                for pid in (2 * int(j), 2 * int(j) + 1):
+                    image_io.write_jpeg(str(d / f"pair_{j}___door_0_0_rotated_{other}_rgb_floor_01_partial_room_01_pano_{pid}.jpg"), posed[k])
+            for si, name in enumerate(src.surfaces):
+                stem = f"pair_{j}___door_0_0_rotated_{name}_rgb_floor_01_partial_room_01_pano_"
+                # (two distinct pano ids per pair; which tile the loader puts first does not matter to a timing)
+                image_io.write_jpeg(str(d / f"{stem}{2 * int(j)}.jpg"), posed[k * S + si])
+                image_io.write_jpeg(str(d / f"{stem}{2 * int(j) + 1}.jpg"), ident[int(ex["i2"][j]) * S + si])
+
+
+def main() -> None:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--configs", default="152:2,50:1", help="layers:surfaces, comma separated")
+    ap.add_argument("--batch", type=int, default=256)
+    ap.add_argument("--modes", default="bf16:hip,fp32:torch", help="precision:norm, comma separated")
+    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--panos", type=int, default=64)
+    ap.add_argument("--disk", type=int, default=0, help="batches of the end-to-end comparison with the on-disk path (0: skip)")
+    a = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("bench_train_feed.py needs the MI355X (a CPU run says nothing about it)")
+    dev = torch.device("cuda:0")
+    B, n_it = a.batch, a.warmup + a.steps
+    panos = synthetic.make_panos(a.panos)
+    rgb, depth = np.stack([p[0] for p in panos]), np.stack([p[1] for p in panos])
+    print(f"# {torch.cuda.get_device_name(dev)}; batch {B}, {a.panos} synthetic 1024 x 512 panoramas, median of {a.steps} after {a.warmup} warm-up; "
+          "step = forward + backward + Adam; variants alternate step by step", flush=True)
+    for cfg in a.configs.split(","):
+        layers, nm = (int(v) for v in cfg.split(":"))
+        for mode in a.modes.split(","):
+            prec, norm = mode.split(":")
+            n_ex = B * max(3 * n_it, a.disk)
+            hyp = synthetic.make_hypotheses(n_ex, a.panos)
+            labels = np.arange(n_ex, dtype=np.int64) % 2
+            src = train_render.RenderedTrainSource(dev, MODS[nm], batch_size=B, precision=prec, split="train", seed=0)
+            src.load_panos(rgb, depth)
+            src.set_examples(hyp, labels)
+            random.seed(0)
+            tag = f"resnet{layers} {6 * nm}ch batch {B} {prec} norm {norm}"
+
+            # ---- the source alone
+            it = iter(src)
+            src.timers, walls, splits = [], [], []
+            for i in range(n_it):
+                del src.timers[:]
+                box = []
+                walls.append(wall(lambda: box.append(next(it))))
+                splits.append({t: s.elapsed_time(e) for t, s, e in src.timers})
+            src.timers = None
+            x_packed, y = box[0][0], box[0][1].squeeze()
+            w = med(walls[a.warmup:]) * 1e3
+            sp = {t: med([s[t] for s in splits[a.warmup:]]) for t in ("scatter", "densify", "tiles")}
+            Hb, Wb = src.ras.bev_hw
+            tile_bytes = x_packed.numel() * x_packed.element_size() + 2 * B * nm * Hb * Wb * 4
+            print(f"{tag}: source alone {w:.2f} ms per batch (host clock); events: scatter {sp['scatter']:.2f}, densify {sp['densify']:.2f}, "
+                  f"tile launch {sp['tiles']:.3f} ms = {tile_bytes / 1e9:.3f} GB of algorithmic bytes at {tile_bytes / sp['tiles'] / 1e9:.2f} TB/s "
+                  f"({100 * tile_bytes / sp['tiles'] / 1e9 / COPY_TBS:.0f} % of the {COPY_TBS} TB/s copy rate)", flush=True)
+
+            # ---- the step, three ways
+            torch.manual_seed(0)
+            model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=MODS[nm])).to(dev).train()
+            model.set_train_precision(prec).set_train_norm(norm)
+            model = model.to(memory_format=torch.channels_last)
+            opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+            C = 6 * nm
+            xs = [x_packed[..., 3 * k:3 * k + 3].permute(0, 3, 1, 2).float().contiguous() for k in range(2 * nm)]   # the same batch as NCHW fp32
+            res = {"resident forward": [], "resident forward_packed": [], "fed forward_packed": []}
+
+            def fed():
+                xb, yb = next(it)
+                step(model, opt, lambda: model.forward_packed(xb), yb.squeeze())
+
+            for i in range(n_it):
+                res["resident forward"].append(wall(lambda: step(model, opt, lambda: model(*xs), y)))
+                res["resident forward_packed"].append(wall(lambda: step(model, opt, lambda: model.forward_packed(x_packed), y)))
+                res["fed forward_packed"].append(wall(fed))
+            m = {k: med(v[a.warmup:]) * 1e3 for k, v in res.items()}
+            print(f"{tag}: step on resident NCHW inputs through forward {m['resident forward']:.1f} ms ({B / m['resident forward'] * 1e3:.0f} samples/s); "
+                  f"resident packed input through forward_packed {m['resident forward_packed']:.1f} ms (cat + cast + pad copy: "
+                  f"{m['resident forward'] - m['resident forward_packed']:+.1f} ms); fed by the source {m['fed forward_packed']:.1f} ms "
+                  f"({B / m['fed forward_packed'] * 1e3:.0f} samples/s); feed / resident step = {w / m['resident forward']:.3f}", flush=True)
+            it.close()
+
+            # ---- end to end against the on-disk path
+            if a.disk > 0:
+                args = config(layers, nm, B)
+                n_disk = a.disk * B
+                tmp = Path(tempfile.mkdtemp(prefix="feed_zind_"))
+                try:
+                    write_zind_tree(tmp, src, n_disk)
+                    args.data_root = str(tmp)
+                    loader = training.get_dataloader(args, "train", seed=0)
+                    sub = train_render.RenderedTrainSource(dev, MODS[nm], batch_size=B, precision=prec, split="train", seed=0)
+                    sub.share_panos(src)
+                    sub.set_examples(synthetic.HypothesisTable(hyp.i1[:n_disk], hyp.i2[:n_disk], hyp.R[:n_disk], hyp.t[:n_disk], hyp.theta_deg[:n_disk]),
+                                     labels[:n_disk])
+                    assert len(loader) == len(sub) == a.disk, (len(loader), len(sub))
+                    t_r = wall(lambda: training.run_epoch(args, 0, model, sub, opt, "train"))
+                    t_d = wall(lambda: training.run_epoch(args, 0, model, loader, opt, "train"))
+                    print(f"{tag}: end to end over {a.disk} batches (run_epoch): rendered feed {n_disk / t_r:.0f} samples/s, on-disk path "
+                          f"(JPEG decode + per-example transform, num_workers 0) {n_disk / t_d:.0f} samples/s", flush=True)
+                finally:
+                    shutil.rmtree(tmp, ignore_errors=True)
+            del model, opt, xs, src, x_packed
+            torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
