@@ -42,7 +42,8 @@ typedef enum {
                                      given order), salve_bev_densify_tiles, a launch of >= 1025 renders keeps its dispatch order in the workspace's key image; unknown
                                      `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
-                                        additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug and salve_bev_train_tiles */
+                                        additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
+                                        salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -57,6 +58,8 @@ typedef enum {
                                           which are not implemented) -- that segment is not drawn */
 #define SALVE_STATUS_BAD_TILE_JOB 16 /* bev_train_tiles: a job names another sample, channels outside the sample, an image outside its array, or
                                         a draw carries unknown flag bits -- that sample is not written */
+#define SALVE_STATUS_BAD_PANO_SLOT 32 /* bev_pano_index_update: the slot list names a slot outside [0, n_panos) -- that entry is skipped, the
+                                         other listed slots are updated */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -120,6 +123,18 @@ size_t salve_bev_workspace_bytes(const salve_bev_config_t* cfg, int32_t n);
 size_t salve_bev_pano_index_bytes(const salve_bev_config_t* cfg, int32_t n_panos);
 int salve_bev_pano_index_build(const salve_bev_config_t* cfg, const uint16_t* pano_depth, int32_t n_panos, const double* sphere,
                                void* pano_index, size_t pano_index_bytes, void* stream);
+/* Rebuild the index of a LIST of slots of a resident pool of n_panos panoramas (a training run whose panorama set does not fit the
+ * device overwrites a few slots per batch).  Contract: pano_index was built or updated for these n_panos slots, and since then only the
+ * depth maps of the listed slots have changed; after the call the whole buffer is byte-identical to what salve_bev_pano_index_build
+ * writes for the current depth maps.  The work covers the listed slots only (their two range words, block boxes and group boxes): its
+ * cost does not depend on n_panos.  Ordered on `stream`; the library allocates nothing.
+ *   slots   device int32 [n_slots].  Device memory, so the kernels check every entry before forming an address: a slot outside
+ *           [0, n_panos) ORs SALVE_STATUS_BAD_PANO_SLOT into the status word and is skipped.  A slot listed twice is harmless.
+ *   status  device int32 status word or NULL
+ * SALVE_ERR_BAD_ARG on null or misaligned pointers, n_slots <= 0 or n_slots > n_panos; SALVE_ERR_WORKSPACE on a short index buffer. */
+int salve_bev_pano_index_update(const salve_bev_config_t* cfg, const uint16_t* pano_depth, int32_t n_panos, const double* sphere,
+                                void* pano_index, size_t pano_index_bytes, const int32_t* slots, int32_t n_slots, int32_t* status,
+                                void* stream);
 
 /*
  * Render n BEV texture maps.
@@ -268,7 +283,8 @@ int salve_bev_tiles_aug(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const
  * from disk).  Same 11-bit taps and LUT as salve_bev_tiles_aug: the fp32 values are bit-identical to its output, the bf16 values are
  * those rounded once to nearest even.
  *   bev_a / bev_b   two arrays of uint32 0x00BBGGRR images, n_bev_a / n_bev_b images of bev_h x bev_w (as for salve_bev_tile_pairs:
- *                   the batch's posed renders; the identity renders, one per panorama and surface)
+ *                   the batch's posed renders; the identity renders, one per panorama and surface).  Both are only read, so they
+ *                   may be the same array or overlap (a batch that renders its identity images behind its posed ones)
  *   jobs_a / jobs_b device salve_tile_job_t [batch][per_sample], sample-major: the per_sample (1..3: one per surface) images of
  *                   sample s from bev_a / bev_b.  .bev_offset = element offset of the image inside its array, .slot = s,
  *                   .chan = first of its 3 channels, a multiple of 3 with chan + 3 <= out_c

@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "salve_bn_bf16_forward",
     "salve_bn_bf16_backward",
     "salve_bev_train_tiles",
+    "salve_bev_pano_index_update",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -78,6 +79,7 @@ STATUS_FP16_RANGE = 2
 STATUS_BAD_HYPOTHESIS = 4
 STATUS_LAYOUT_THICKNESS = 8
 STATUS_BAD_TILE_JOB = 16
+STATUS_BAD_PANO_SLOT = 32
 
 
 class BevConfig(ctypes.Structure):
@@ -156,6 +158,8 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_pano_index_bytes.restype = sz
     lib.salve_bev_pano_index_build.argtypes = [ctypes.POINTER(BevConfig), vp, i32, vp, vp, sz, vp]
     lib.salve_bev_pano_index_build.restype = ctypes.c_int
+    lib.salve_bev_pano_index_update.argtypes = [ctypes.POINTER(BevConfig), vp, i32, vp, vp, sz, vp, i32, vp, vp]
+    lib.salve_bev_pano_index_update.restype = ctypes.c_int
     lib.salve_bev_render_batch.argtypes = [ctypes.POINTER(BevConfig), vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.salve_bev_render_batch.restype = ctypes.c_int
     lib.salve_bev_scatter.argtypes = [ctypes.POINTER(BevConfig), vp, vp, i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp]
@@ -244,6 +248,8 @@ def check_status_word(word: int, what: str) -> None:
     if word & STATUS_BAD_TILE_JOB:
         raise SalveHipError(f"{what}: a train-tile job names another sample, channels or an image outside its arrays (or a draw has unknown "
                             "flag bits); that sample was not written")
+    if word & STATUS_BAD_PANO_SLOT:
+        raise SalveHipError(f"{what}: a panorama-index update names a slot outside the resident pool; that slot's index was not rebuilt")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

@@ -1303,6 +1303,34 @@ int salve_bev_pano_index_build(const salve_bev_config_t* cfg, const uint16_t* pa
     return SALVE_OK;
 }
 
+int salve_bev_pano_index_update(const salve_bev_config_t* cfg, const uint16_t* pano_depth, int32_t n_panos, const double* sphere,
+                                void* pano_index, size_t pano_index_bytes, const int32_t* slots, int32_t n_slots, int32_t* status, void* stream) {
+    DevCfg d;
+    if (!make_devcfg(cfg, &d)) return SALVE_ERR_BAD_ARG;
+    if (n_panos <= 0 || !pano_depth || !sphere || !pano_index || ((uintptr_t)pano_index & 15) || !slots || ((uintptr_t)slots & 3) ||
+        ((uintptr_t)status & 3) || n_slots <= 0 || n_slots > n_panos) {
+        salve_fail("salve_bev_pano_index_update: null / unaligned pointer or bad count (1 <= n_slots <= n_panos)");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (pano_index_bytes < salve_bev_pano_index_bytes(cfg, n_panos)) { salve_fail("panorama index buffer too small"); return SALVE_ERR_WORKSPACE; }
+    hipStream_t s = (hipStream_t)stream;
+    const PanoGrid pg = pano_grid(d);
+    int* ranges = const_cast<int*>(index_ranges(d, pano_index, n_panos));
+    const long long waves = (long long)pg.entries() * 2 * n_slots;
+    if ((waves + 3) / 4 > 0x7FFFFFFFll) { salve_fail("too many slots for one index launch"); return SALVE_ERR_BAD_ARG; }
+    hipLaunchKernelGGL(bev_pano_index_reset_kernel, dim3((unsigned)((2 * (long long)n_slots + 255) / 256)), dim3(256), 0, s, slots, n_slots, n_panos, ranges,
+                       ranges + 2 * n_panos, status);
+    SALVE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bev_pano_index_update_kernel, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, s, d, pg, pano_depth, sphere,
+                       reinterpret_cast<float4*>(pano_index), ranges, ranges + 2 * n_panos, n_panos, slots, n_slots);
+    SALVE_HIP_CHECK(hipGetLastError());
+    const long long n_gb = (long long)pg.groups() * 2 * n_slots;
+    hipLaunchKernelGGL(bev_pano_group_update_kernel, dim3((unsigned)((n_gb + 255) / 256)), dim3(256), 0, s, pg, reinterpret_cast<const float4*>(pano_index),
+                       reinterpret_cast<float4*>(ranges + 4 * n_panos), n_panos, slots, n_slots);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
 // does a launch of n renders run its densify stage in cost order?  (both stages ask: the scatter sums the costs, the densify sorts them)
 static bool orders_renders(const DevCfg& d, int n, size_t npx) {
     return !(d.out_flags & 4) && n >= ORDER_MIN_RENDERS && (size_t)2 * n * sizeof(int32_t) <= npx * sizeof(uint32_t);

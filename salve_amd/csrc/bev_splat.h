@@ -65,15 +65,9 @@ __device__ __forceinline__ BackProj back_project(const DevCfg& c, uint32_t dep, 
     return o;
 }
 
-__global__ __launch_bounds__(256) void bev_pano_index_kernel(DevCfg c, PanoGrid pg, const uint16_t* __restrict__ depth,
-                                                             const double* __restrict__ sphere, float4* __restrict__ boxes,
-                                                             int* __restrict__ range_lo, int* __restrict__ range_hi, int n_panos) {
-    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per table entry
-    const int lane = threadIdx.x & 63;
-    const long long entries = (long long)pg.entries();
-    if (wv >= entries * 2 * n_panos) return;
-    const int ps = (int)(wv / entries);   // panorama * 2 + surface
-    const int e = (int)(wv % entries);
+// One table entry (panorama * 2 + surface `ps`, block `e`) by one wavefront: shared by the build of all panoramas and the update of a list of slots.
+__device__ __forceinline__ void pano_index_entry(const DevCfg& c, const PanoGrid& pg, const uint16_t* __restrict__ depth, const double* __restrict__ sphere,
+                                                 float4* __restrict__ boxes, int* __restrict__ range_lo, int* __restrict__ range_hi, int ps, int e, int lane) {
     const int pano = ps >> 1, surface = ps & 1;
     const int br = e / (pg.gpr * 64), bc = e % (pg.gpr * 64);
     const int vr = br * BLK_H + (lane >> 4), u = bc * BLK_W + (lane & 15);
@@ -97,7 +91,7 @@ __global__ __launch_bounds__(256) void bev_pano_index_kernel(DevCfg c, PanoGrid 
         xmax = fmaxf(xmax, __shfl_xor(xmax, off)); ymax = fmaxf(ymax, __shfl_xor(ymax, off));
     }
     if (lane == 0) {
-        boxes[wv] = make_float4(xmin, ymin, xmax, ymax);
+        boxes[(size_t)ps * pg.entries() + e] = make_float4(xmin, ymin, xmax, ymax);
         if (xmin <= xmax) {   // the range of groups that hold any point: [range_lo, range_hi)
             atomicMin(range_lo + ps, e >> 6);
             atomicMax(range_hi + ps, (e >> 6) + 1);
@@ -105,21 +99,76 @@ __global__ __launch_bounds__(256) void bev_pano_index_kernel(DevCfg c, PanoGrid 
     }
 }
 
+__global__ __launch_bounds__(256) void bev_pano_index_kernel(DevCfg c, PanoGrid pg, const uint16_t* __restrict__ depth,
+                                                             const double* __restrict__ sphere, float4* __restrict__ boxes,
+                                                             int* __restrict__ range_lo, int* __restrict__ range_hi, int n_panos) {
+    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per table entry
+    const long long entries = (long long)pg.entries();
+    if (wv >= entries * 2 * n_panos) return;
+    pano_index_entry(c, pg, depth, sphere, boxes, range_lo, range_hi, (int)(wv / entries), (int)(wv % entries), threadIdx.x & 63);
+}
+
+// salve_bev_pano_index_update: the same entries for a LIST of slots (device memory, so every kernel range-checks the slot before it forms an
+// address: a slot outside [0, n_panos) raises SALVE_STATUS_BAD_PANO_SLOT and is skipped).  Three launches in stream order -- the two range words
+// of the listed slots back to "empty", their block boxes, their group boxes -- whose cost depends on the list alone.  A slot listed twice is
+// written twice with the same values (the atomics are min / max: order-independent).
+__global__ __launch_bounds__(256) void bev_pano_index_reset_kernel(const int32_t* __restrict__ slots, int n_slots, int n_panos, int* __restrict__ range_lo,
+                                                                   int* __restrict__ range_hi, int32_t* __restrict__ status) {
+    const int i = blockIdx.x * 256 + threadIdx.x;   // one thread per (listed slot, surface)
+    if (i >= 2 * n_slots) return;
+    const int slot = slots[i >> 1];
+    if (slot < 0 || slot >= n_panos) {
+        if (status && (i & 1) == 0) atomicOr(status, SALVE_STATUS_BAD_PANO_SLOT);
+        return;
+    }
+    range_lo[2 * slot + (i & 1)] = 0x7F7F7F7F;   // as salve_bev_pano_index_build's memsets leave them
+    range_hi[2 * slot + (i & 1)] = 0;
+}
+
+__global__ __launch_bounds__(256) void bev_pano_index_update_kernel(DevCfg c, PanoGrid pg, const uint16_t* __restrict__ depth,
+                                                                    const double* __restrict__ sphere, float4* __restrict__ boxes,
+                                                                    int* __restrict__ range_lo, int* __restrict__ range_hi, int n_panos,
+                                                                    const int32_t* __restrict__ slots, int n_slots) {
+    const long long wv = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);   // one wavefront per table entry of a listed slot
+    const long long per_slot = (long long)pg.entries() * 2;
+    if (wv >= per_slot * n_slots) return;
+    const int slot = slots[wv / per_slot];   // wavefront-uniform
+    if (slot < 0 || slot >= n_panos) return;
+    const int r = (int)(wv % per_slot);
+    pano_index_entry(c, pg, depth, sphere, boxes, range_lo, range_hi, 2 * slot + (int)(r / (long long)pg.entries()), (int)(r % (long long)pg.entries()), threadIdx.x & 63);
+}
+
 // (r6) Second level of the index: the union box of every GROUP of 64 blocks.  A tile's workgroup tests the group boxes first -- all of them in one
 // pass, a box per thread -- and its wavefronts then visit only the groups that can reach the tile; before, every wavefront walked the whole
 // range of groups that hold points, one dependent LDS atomic + 1 KB box load + ballot per group (2048 x 1024 panoramas: 176 visits per tile and
 // render, 20 % of the kernel's time; a tile is reached by a sixth of them).
-__global__ __launch_bounds__(256) void bev_pano_group_kernel(PanoGrid pg, const float4* __restrict__ boxes, float4* __restrict__ gboxes, int n_ps) {
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    const long long groups = pg.groups();
-    if (i >= groups * n_ps) return;
-    const float4* b = boxes + (size_t)(i / groups) * pg.entries() + (size_t)(i % groups) * 64;
+// union box of group `grp` of (panorama, surface) `ps`
+__device__ __forceinline__ void pano_group_entry(const PanoGrid& pg, const float4* __restrict__ boxes, float4* __restrict__ gboxes, long long ps, long long grp) {
+    const float4* b = boxes + (size_t)ps * pg.entries() + (size_t)grp * 64;
     float xmin = 1e30f, ymin = 1e30f, xmax = -1e30f, ymax = -1e30f;
     for (int j = 0; j < 64; j++) {
         const float4 v = b[j];
         if (v.x <= v.z) { xmin = fminf(xmin, v.x); ymin = fminf(ymin, v.y); xmax = fmaxf(xmax, v.z); ymax = fmaxf(ymax, v.w); }
     }
-    gboxes[i] = make_float4(xmin, ymin, xmax, ymax);
+    gboxes[ps * pg.groups() + grp] = make_float4(xmin, ymin, xmax, ymax);
+}
+
+__global__ __launch_bounds__(256) void bev_pano_group_kernel(PanoGrid pg, const float4* __restrict__ boxes, float4* __restrict__ gboxes, int n_ps) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long groups = pg.groups();
+    if (i >= groups * n_ps) return;
+    pano_group_entry(pg, boxes, gboxes, i / groups, i % groups);
+}
+
+__global__ __launch_bounds__(256) void bev_pano_group_update_kernel(PanoGrid pg, const float4* __restrict__ boxes, float4* __restrict__ gboxes, int n_panos,
+                                                                    const int32_t* __restrict__ slots, int n_slots) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;   // one thread per group of a listed slot
+    const long long per_slot = (long long)pg.groups() * 2;
+    if (i >= per_slot * n_slots) return;
+    const int slot = slots[i / per_slot];
+    if (slot < 0 || slot >= n_panos) return;
+    const long long r = i % per_slot;
+    pano_group_entry(pg, boxes, gboxes, 2ll * slot + r / pg.groups(), r % pg.groups());
 }
 
 // can the box (pre-rotated frame) reach the tile [wx0, wx1] x [wy0, wy1] (posed frame) under the pose?  float32, conservative: centre + |R| half-extents

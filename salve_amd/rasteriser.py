@@ -162,6 +162,46 @@ class BevRasteriser:
         pano_depth._salve_pano_index = (buf, (pano_depth.data_ptr(), P, pano_depth._version))
         return buf
 
+    def pano_index_bytes(self, n_panos: int) -> int:
+        """Bytes of the panorama index of `n_panos` panoramas."""
+        nbytes = int(self.lib.salve_bev_pano_index_bytes(ctypes.byref(self.cfg), n_panos))
+        if nbytes == 0:
+            _lib.check(-1, "salve_bev_pano_index_bytes")
+        return nbytes
+
+    def update_panos(self, pano_rgb: torch.Tensor, pano_depth: torch.Tensor, slots_dev: torch.Tensor, rgb_rows_dev: torch.Tensor,
+                     depth_rows_dev: torch.Tensor) -> None:
+        """Overwrite slots of a resident panorama pool on the current stream: rows k of `rgb_rows_dev` (uint8 [n, H, W, 3]) and
+        `depth_rows_dev` (int16 bits [n, H, W]) go to slot slots_dev[k] (device int32 [n], distinct, inside the pool) of `pano_rgb` /
+        `pano_depth`, and the panorama index of exactly those slots is rebuilt (include/salve_hip.h: salve_bev_pano_index_update) -- work
+        that does not grow with the pool.  The index `pano_index` keeps with the depth tensor is then RE-KEYED to the tensor's new
+        version: the next scatter finds it, no full rebuild (which every other in-place write still gets) and no wait for the device.
+        A slot outside the pool is reported through the device status word (`check`) by the index update -- and by torch's own
+        index check in `index_copy_`."""
+        n = int(slots_dev.shape[0])
+        if slots_dev.dtype != torch.int32 or slots_dev.dim() != 1 or not slots_dev.is_contiguous():
+            raise _lib.SalveHipError(f"update_panos: slots must be a contiguous int32 vector, got {slots_dev.dtype} {tuple(slots_dev.shape)}")
+        if tuple(rgb_rows_dev.shape) != (n,) + tuple(pano_rgb.shape[1:]) or tuple(depth_rows_dev.shape) != (n,) + tuple(pano_depth.shape[1:]) \
+                or rgb_rows_dev.dtype != pano_rgb.dtype or depth_rows_dev.dtype != pano_depth.dtype:
+            raise _lib.SalveHipError(f"update_panos: {n} slots need rows of {(n,) + tuple(pano_rgb.shape[1:])} {pano_rgb.dtype} and "
+                                     f"{(n,) + tuple(pano_depth.shape[1:])} {pano_depth.dtype}, got {tuple(rgb_rows_dev.shape)} {rgb_rows_dev.dtype} and "
+                                     f"{tuple(depth_rows_dev.shape)} {depth_rows_dev.dtype}")
+        if n == 0:
+            return
+        P = int(pano_depth.shape[0])
+        if n > P:
+            raise _lib.SalveHipError(f"update_panos: {n} slots listed, the pool has {P}")
+        index = self.pano_index(pano_depth)   # (the index of the depth maps as they are now: built here on first use)
+        at = slots_dev.to(torch.int64)
+        pano_rgb.index_copy_(0, at, rgb_rows_dev)
+        pano_depth.index_copy_(0, at, depth_rows_dev)
+        with torch.cuda.device(self.device):
+            st = self.lib.salve_bev_pano_index_update(ctypes.byref(self.cfg), ctypes.c_void_p(pano_depth.data_ptr()), P,
+                                                      ctypes.c_void_p(self.sphere.data_ptr()), ctypes.c_void_p(index.data_ptr()), index.numel(),
+                                                      ctypes.c_void_p(slots_dev.data_ptr()), n, status.ptr(self.device), self._stream())
+        _lib.check(st, "salve_bev_pano_index_update")
+        pano_depth._salve_pano_index = (index, (pano_depth.data_ptr(), P, pano_depth._version))
+
     @staticmethod
     def drop_pano_index(pano_depth: torch.Tensor) -> None:
         if hasattr(pano_depth, "_salve_pano_index"):

@@ -2,7 +2,7 @@
 
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
-                              [--norm {torch,hip}] [--render-from DIR]
+                              [--norm {torch,hip}] [--render-from DIR [--identity {kept,batch}] [--resident-panos N]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
@@ -10,6 +10,9 @@ convolutions, fp32 master weights, gradients and checkpoint); the default fp32 i
 BatchNorm with fused ReLU and residual add (same checkpoint); the default is torch's BatchNorm.  See salve_amd/training.py.
 --render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
 val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
+--identity batch renders the identity images of a batch's second panoramas with the batch instead of keeping one per panorama;
+--resident-panos N (which selects --identity batch) memory-maps the two .npy files and keeps a pool of N panoramas on the device,
+uploaded as the batches need them: for panorama sets that do not fit in device memory.  N must be at least 2 x batch_size.
 """
 
 from __future__ import annotations
@@ -38,7 +41,19 @@ def main(argv=None) -> None:
                     help="torch (default: nn.BatchNorm2d) or hip (BatchNorm with fused ReLU and residual add on the HIP kernels)")
     ap.add_argument("--render-from", default=None, metavar="DIR",
                     help="render the training batches on the GPU from DIR/panos_rgb.npy, panos_depth.npy, train.json, val.json")
+    ap.add_argument("--identity", choices=("kept", "batch"), default=None,
+                    help="--render-from: keep one identity image per panorama (kept, the default) or render them with each batch (batch)")
+    ap.add_argument("--resident-panos", type=int, default=None, metavar="N",
+                    help="--render-from: keep a pool of N panoramas on the device and upload the others as batches need them (selects --identity batch)")
     a = ap.parse_args(argv)
+    if a.render_from is None and (a.identity is not None or a.resident_panos is not None):
+        raise SystemExit("--identity and --resident-panos belong to --render-from DIR")
+    if a.resident_panos is not None:
+        if a.identity == "kept":
+            raise SystemExit("--resident-panos keeps no identity image per panorama: it cannot be combined with --identity kept")
+        if a.resident_panos <= 0:
+            raise SystemExit(f"--resident-panos must be positive, got {a.resident_panos}")
+    identity = a.identity or ("batch" if a.resident_panos is not None else "kept")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     args = load_training_config(a.config)
     if a.epochs is not None:
@@ -56,15 +71,16 @@ def main(argv=None) -> None:
 
         from salve_amd import train_render
 
-        rgb, depth, examples = train_render.load_render_dir(a.render_from)
+        rgb, depth, examples = train_render.load_render_dir(a.render_from, mmap=a.resident_panos is not None)
         sources = {}
         for split in ("train", "val"):
             src = train_render.RenderedTrainSource(torch.device("cuda", torch.cuda.current_device()), args.modalities, pano_hw=rgb.shape[1:3],
                                                    batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
-                                                   resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w))
+                                                   resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
+                                                   identity=identity, resident_panos=a.resident_panos)
             if split == "train":
                 src.load_panos(rgb, depth)
-            else:   # the panoramas and their identity renders are on the device once
+            else:   # the panoramas (or their pool) and their identity renders are on the device once
                 src.share_panos(sources["train"])
             src.set_examples(*examples[split])
             sources[split] = src

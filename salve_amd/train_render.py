@@ -8,9 +8,15 @@ batches from the lossless BEV images instead: per batch one scatter + densify la
 (the identity renders of every panorama are made once and kept, as in salve_amd.pipeline) and ONE salve_bev_train_tiles launch
 that writes `[B, crop, crop, Cp]` in the training precision -- what `TrainableEarlyFusionCEResnet.forward_packed` takes.
 
+Two opt-in arguments take the feed beyond panorama sets that fit the device.  `identity="batch"` keeps no identity image per
+panorama: the identity renders of the batch's distinct second panoramas ride in the batch's own scatter / densify launch pair, behind
+the posed renders.  `resident_panos=N` keeps a pool of N panorama slots on the device: `PanoCache` plans, batch by batch, which
+panoramas of the host arrays (np.memmap included) are uploaded into which slots -- the victim is the panorama whose next use in the
+epoch lies furthest ahead -- and `BevRasteriser.update_panos` rebuilds the panorama index of the written slots only.
+
 Shuffle order and augmentation draws are those of `training.get_dataloader` + `transforms.TrainTransform`: the order of a
 `DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random`.
-The planning functions (`plan_epoch`, `plan_examples`, `check_launch`) are pure and need no device.
+The planning functions (`plan_epoch`, `plan_examples`, `check_launch`, `PanoCache`, `epoch_next_use`) are pure and need no device.
 """
 
 from __future__ import annotations
@@ -54,13 +60,17 @@ def batches_per_epoch(n: int, batch: int, split: str) -> int:
     return n // batch if split == "train" else (n + batch - 1) // batch
 
 
-def check_launch(batch_size: int, n_surfaces: int) -> None:
-    """A batch's posed renders go through ONE scatter / densify call."""
+def check_launch(batch_size: int, n_surfaces: int, identity_rows: int = 0) -> None:
+    """A batch's posed renders -- and, with identity="batch", the identity renders of up to `identity_rows` distinct second panoramas
+    behind them -- go through ONE scatter / densify call."""
     if batch_size <= 0:
         raise ValueError(f"batch size must be positive, got {batch_size}")
-    if batch_size * n_surfaces > MAX_RENDERS_PER_CALL:
-        raise RuntimeError(f"batch_size {batch_size} x {n_surfaces} surfaces = {batch_size * n_surfaces} renders per batch; the library "
-                           f"takes at most {MAX_RENDERS_PER_CALL} per call")
+    if identity_rows < 0:
+        raise ValueError(f"identity_rows must not be negative, got {identity_rows}")
+    n = (batch_size + identity_rows) * n_surfaces
+    if n > MAX_RENDERS_PER_CALL:
+        what = f"batch_size {batch_size}" if identity_rows == 0 else f"(batch_size {batch_size} + {identity_rows} identity panoramas)"
+        raise RuntimeError(f"{what} x {n_surfaces} surfaces = {n} renders per batch; the library takes at most {MAX_RENDERS_PER_CALL} per call")
 
 
 def train_surfaces(modalities: Sequence[str]) -> List[str]:
@@ -87,22 +97,112 @@ def plan_examples(hyp: HypothesisTable, is_match, n_panos: int) -> Dict[str, np.
     return {"i1": i1, "i2": i2, "R": R, "t": t, "swap": swap, "is_match": labels.astype(np.int64)}
 
 
+IDENTITIES = ("kept", "batch")
+NEVER = np.iinfo(np.int64).max   # next use of a panorama the rest of the epoch does not name
+
+
+def epoch_next_use(batch_panos: Sequence[np.ndarray], n_panos: int) -> Tuple[np.ndarray, List[np.ndarray]]:
+    """The next-use bookkeeping of one epoch whose batches name the DISTINCT panoramas `batch_panos[b]`: (`first`, `after`).
+    first[p] is the first batch that names panorama p (NEVER if none does), after[b][k] the next batch behind b that names
+    batch_panos[b][k] again.  A caller that walks the epoch keeps `next_use = first.copy()` and sets
+    `next_use[batch_panos[b]] = after[b]` once batch b is planned: next_use[p] is then, for every panorama batch b + 1 does not
+    name, the batch of its next use -- what `PanoCache.plan` ranks its victims by."""
+    nxt = np.full(n_panos, NEVER, dtype=np.int64)
+    after: List[np.ndarray] = [np.empty(0, dtype=np.int64)] * len(batch_panos)
+    for b in range(len(batch_panos) - 1, -1, -1):
+        after[b] = nxt[batch_panos[b]].copy()
+        nxt[batch_panos[b]] = b
+    return nxt, after
+
+
+class PanoCache:
+    """Which panorama lives in which slot of a resident pool of `capacity` slots (pure host code).  `plan` makes one batch's
+    panoramas resident: no two panoramas share a slot, a panorama of the current batch is never the victim, the uploads are exactly
+    the misses.  policy "furthest" (the product's): the victim is the resident panorama whose next use lies furthest ahead (one
+    without further use counts as never), ties broken by the lower panorama id -- the epoch's order is known before its first batch.
+    policy "lru" (kept for the test that compares the two): the least recently planned panorama.  Counters: hits, misses,
+    uploaded_bytes (misses x bytes_per_pano)."""
+
+    def __init__(self, n_panos: int, capacity: int, batch_size: int, bytes_per_pano: int = 0, policy: str = "furthest") -> None:
+        if policy not in ("furthest", "lru"):
+            raise ValueError(f"policy must be 'furthest' or 'lru', got {policy!r}")
+        if n_panos <= 0 or batch_size <= 0:
+            raise ValueError(f"n_panos and batch_size must be positive, got {n_panos} and {batch_size}")
+        need = min(2 * batch_size, n_panos)
+        if capacity < need:
+            raise ValueError(f"a pool of {capacity} panorama slots cannot hold one batch: batch size {batch_size} names up to {need} of the "
+                             f"{n_panos} panoramas at once (resident_panos must be at least {need})")
+        self.n_panos, self.capacity, self.policy, self.bytes_per_pano = int(n_panos), int(min(capacity, n_panos)), policy, int(bytes_per_pano)
+        self.slot_of = np.full(self.n_panos, -1, dtype=np.int64)
+        self.pano_in = np.full(self.capacity, -1, dtype=np.int64)
+        self.last_used = np.zeros(self.n_panos, dtype=np.int64)
+        self.clock = 0
+        self.hits = self.misses = self.uploaded_bytes = 0
+
+    def plan(self, batch_pano_ids, next_use: Optional[np.ndarray] = None) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
+        """(slot of every entry of `batch_pano_ids`, [(panorama, slot) to upload]) -- the uploads in panorama order.  `next_use`:
+        int64 [n_panos], the batch of every panorama's next use (`epoch_next_use`; None: nothing is known, every panorama counts as
+        never used again).  Entries of the current batch's own panoramas are not read."""
+        ids = np.asarray(batch_pano_ids, dtype=np.int64)
+        need = np.unique(ids)
+        if need.size and (int(need[0]) < 0 or int(need[-1]) >= self.n_panos):
+            raise ValueError(f"a batch names panorama {int(need[0]) if int(need[0]) < 0 else int(need[-1])}; the cache covers {self.n_panos}")
+        if need.size > self.capacity:
+            raise ValueError(f"a batch names {need.size} panoramas, the pool has {self.capacity} slots")
+        self.clock += 1
+        miss = need[self.slot_of[need] < 0]
+        self.hits += int(need.size - miss.size)
+        self.misses += int(miss.size)
+        self.uploaded_bytes += int(miss.size) * self.bytes_per_pano
+        slots = np.flatnonzero(self.pano_in < 0)[:miss.size]   # free slots first, the lowest first
+        if slots.size < miss.size:
+            mine = np.zeros(self.n_panos, dtype=bool)
+            mine[need] = True
+            cand = self.pano_in[(self.pano_in >= 0) & ~mine[np.maximum(self.pano_in, 0)]]   # resident, not of this batch
+            if self.policy == "lru":
+                order = np.lexsort((cand, self.last_used[cand]))
+            else:
+                far = np.full(cand.size, NEVER, dtype=np.int64) if next_use is None else np.asarray(next_use, dtype=np.int64)[cand]
+                order = np.lexsort((cand, -np.minimum(far, np.int64(2 ** 62))))   # furthest first (never = 2**62), then the lower id
+            victims = cand[order[:miss.size - slots.size]]
+            freed = np.sort(self.slot_of[victims])
+            self.slot_of[victims] = -1
+            slots = np.concatenate([slots, freed])
+        self.slot_of[miss] = slots
+        self.pano_in[slots] = miss
+        self.last_used[need] = self.clock
+        return self.slot_of[ids], [(int(p), int(sl)) for p, sl in zip(miss, slots)]
+
+
 class RenderedTrainSource:
     """Iterating yields `(x_packed, is_match)`: x_packed [B, crop, crop, Cp] float32 / bfloat16 on the device, is_match int64 [B, 1].
     One epoch per iteration; `len()` = batches per epoch.  Everything runs on the current stream.  The device status word is checked
-    once per epoch, after the last batch (a bad render row or tile job raises there)."""
+    once per epoch, after the last batch (a bad render row, tile job or pool slot raises there).
+
+    identity: "kept" (default) renders the identity image of every panorama once and keeps it; "batch" renders the identity images of
+    the batch's distinct second panoramas with the batch -- the same images, no P x S image array.  resident_panos: None (default)
+    uploads every panorama up front; an integer keeps a pool of that many panorama slots on the device, filled on first use from the
+    host arrays `load_panos` was given (needs identity="batch"; at least min(2 x batch_size, P) slots)."""
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
-                 crop_hw: Tuple[int, int] = (224, 224)) -> None:
+                 crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None) -> None:
         if split not in SPLITS:
             raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+        if identity not in IDENTITIES:
+            raise ValueError(f"identity must be one of {IDENTITIES}, got {identity!r}")
+        if resident_panos is not None:
+            if identity != "batch":
+                raise ValueError('resident_panos needs identity="batch": keeping an identity image per panorama is what does not fit')
+            if int(resident_panos) <= 0:
+                raise ValueError(f"resident_panos must be positive, got {resident_panos}")
         self.surfaces = train_surfaces(modalities)
-        check_launch(batch_size, len(self.surfaces))
+        check_launch(batch_size, len(self.surfaces), batch_size if identity == "batch" else 0)
         self.tf = TrainTransform(resize_hw, crop_hw)   # the draws (and the square / no-padding refusals); its kernels are not used
         self.split, self.batch_size = split, int(batch_size)
+        self.identity, self.resident_panos = identity, None if resident_panos is None else int(resident_panos)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
         self.out_c = (6 * len(self.surfaces) + 7) // 8 * 8
         self.gen = torch.Generator()
@@ -114,26 +214,70 @@ class RenderedTrainSource:
         self.pano_rgb = self.pano_depth = self.ref_bev = self.bev = None
         self.n_panos: Optional[int] = None
         self.examples: Optional[Dict[str, np.ndarray]] = None
+        self.pool: Optional[Dict] = None   # resident_panos: host arrays, PanoCache, pinned staging buffers -- shared by share_panos
         self.timers = None   # a list: every launch appends (tag, start event, end event) -- tools/measure/bench_train_feed.py
 
     # ------------------------------------------------------------------ panoramas
     def _refuse_if_too_large(self, need: int, what: str) -> None:
         free = int(torch.cuda.mem_get_info(self.device)[0])
         if need > free:
-            raise RuntimeError(f"{what} need {need} bytes of device memory, {free} are free: panorama sets that do not fit at once are not supported")
+            hint = ("a smaller --resident-panos pool fits" if self.resident_panos is not None else
+                    "panorama sets that do not fit at once train with --resident-panos N (which selects --identity batch)")
+            raise RuntimeError(f"{what} need {need} bytes of device memory, {free} are free: {hint}")
+
+    def _batch_images(self, n_slots: int) -> int:
+        """Images of one batch's buffer: the posed renders, and with identity="batch" the identity renders behind them."""
+        return (self.batch_size + (min(self.batch_size, n_slots) if self.identity == "batch" else 0)) * len(self.surfaces)
 
     def load_panos(self, rgb: np.ndarray, depth: np.ndarray) -> None:
-        """Upload P panoramas (uint8 [P, H, W, 3], uint16 [P, H, W]) and render their identity BEV images."""
-        self._refuse_if_too_large(int(rgb.nbytes) + int(depth.nbytes), f"{len(rgb)} panoramas")
-        self.set_panos(*self.ras.upload_panos(rgb, depth))
+        """P panoramas (uint8 [P, H, W, 3], uint16 [P, H, W]).  Default: upload them all (and, identity="kept", render their identity
+        BEV images).  resident_panos: keep the host arrays (np.memmap included) and upload nothing -- slots fill on first use."""
+        if self.resident_panos is None:
+            self._refuse_if_too_large(int(rgb.nbytes) + int(depth.nbytes), f"{len(rgb)} panoramas")
+            self.set_panos(*self.ras.upload_panos(rgb, depth))
+            return
+        H, W = self.ras.pano_hw
+        if rgb.dtype != np.uint8 or depth.dtype != np.uint16 or tuple(rgb.shape[1:]) != (H, W, 3) or tuple(depth.shape) != tuple(rgb.shape[:3]):
+            raise RuntimeError(f"panoramas must be uint8 [P, {H}, {W}, 3] and uint16 [P, {H}, {W}], got {rgb.dtype} {tuple(rgb.shape)} / "
+                               f"{depth.dtype} {tuple(depth.shape)}")
+        P, S = int(rgb.shape[0]), len(self.surfaces)
+        Hb, Wb = self.ras.bev_hw
+        try:
+            cache = PanoCache(P, self.resident_panos, self.batch_size, bytes_per_pano=H * W * 5)
+        except ValueError as e:
+            raise RuntimeError(str(e)) from None
+        n_slots, n_stage = cache.capacity, min(2 * self.batch_size, cache.capacity)
+        index_bytes = self.ras.pano_index_bytes(n_slots)
+        self._refuse_if_too_large((n_slots + n_stage) * H * W * 5 + index_bytes + self._batch_images(n_slots) * Hb * Wb * 4,
+                                  f"a pool of {n_slots} panorama slots, its index, one batch's uploads and one batch's BEV images")
+        # zero depth passes neither surface's z filter: an unfilled slot's index entries are empty boxes
+        self.pano_rgb = torch.zeros((n_slots, H, W, 3), dtype=torch.uint8, device=self.device)
+        self.pano_depth = torch.zeros((n_slots, H, W), dtype=torch.int16, device=self.device)
+        self.ras.pano_index(self.pano_depth)
+        # the host writes a staging buffer while an earlier copy may still read it: two buffers, an event each, waited on before the overwrite
+        stage = [{"rgb": torch.empty((n_stage, H, W, 3), dtype=torch.uint8).pin_memory(), "depth": torch.empty((n_stage, H, W), dtype=torch.int16).pin_memory(),
+                  "event": None} for _ in range(2)]
+        self.pool = {"rgb": rgb, "depth": depth, "cache": cache, "stage": stage, "turn": 0, "uploads": 0}
+        self.n_panos, self.examples, self.ref_bev = P, None, None
+        self.bev = torch.empty((self._batch_images(n_slots), Hb, Wb), dtype=torch.int32, device=self.device)
+        self.ras._workspace(self._batch_images(n_slots))
 
     def set_panos(self, rgb_dev: torch.Tensor, depth_dev: torch.Tensor) -> None:
-        """Panoramas on the device (as RenderVerifyPipeline.set_panos takes them); the identity render of every panorama and
-        surface is made once and kept."""
+        """Panoramas on the device (as RenderVerifyPipeline.set_panos takes them).  identity="kept": the identity render of every
+        panorama and surface is made once and kept; identity="batch": nothing is rendered here."""
+        if self.resident_panos is not None:
+            raise RuntimeError("resident_panos takes the panoramas as host arrays: load_panos(rgb, depth)")
         if tuple(rgb_dev.shape[1:3]) != tuple(self.ras.pano_hw) or tuple(depth_dev.shape[1:]) != tuple(self.ras.pano_hw):
             raise RuntimeError(f"panoramas must be {self.ras.pano_hw}, got {tuple(rgb_dev.shape[1:3])} / {tuple(depth_dev.shape[1:])}")
         P, S = int(rgb_dev.shape[0]), len(self.surfaces)
         Hb, Wb = self.ras.bev_hw
+        if self.identity == "batch":
+            self._refuse_if_too_large(self._batch_images(P) * Hb * Wb * 4, "the BEV images of one batch")
+            self.pano_rgb, self.pano_depth = rgb_dev.contiguous(), depth_dev.contiguous()
+            self.n_panos, self.examples, self.ref_bev = P, None, None
+            self.bev = torch.empty((self._batch_images(P), Hb, Wb), dtype=torch.int32, device=self.device)   # posed | identity renders of one batch
+            self.ras._workspace(self._batch_images(P))
+            return
         self._refuse_if_too_large((P + self.batch_size) * S * Hb * Wb * 4, f"the BEV images of {P} panoramas and one batch")
         self.pano_rgb, self.pano_depth = rgb_dev.contiguous(), depth_dev.contiguous()
         self.n_panos, self.examples = P, None
@@ -149,14 +293,27 @@ class RenderedTrainSource:
 
     def share_panos(self, other: "RenderedTrainSource") -> None:
         """Use the panoramas, identity renders and batch buffer `other` holds (the val source beside the train source: one copy on
-        the device; both run on the same stream, one batch at a time)."""
+        the device; both run on the same stream, one batch at a time).  With a resident pool the slots and their `PanoCache` are
+        shared too: whichever source is iterating plans with its own epoch's next uses."""
         if other.n_panos is None:
             raise RuntimeError("the other source has no panoramas yet")
         if (other.device, other.surfaces, other.ras.pano_hw, other.ras.bev_hw) != (self.device, self.surfaces, self.ras.pano_hw, self.ras.bev_hw) \
                 or other.batch_size < self.batch_size:
             raise RuntimeError("share_panos needs the same device, modalities and panorama size, and a batch size not above the other's")
+        if (other.identity, other.resident_panos) != (self.identity, self.resident_panos):
+            raise RuntimeError("share_panos needs the same identity and resident_panos arguments on both sources")
         self.pano_rgb, self.pano_depth, self.ref_bev, self.bev, self.n_panos, self.examples = (other.pano_rgb, other.pano_depth, other.ref_bev,
                                                                                                other.bev, other.n_panos, None)
+        self.pool = other.pool
+
+    @property
+    def cache(self) -> Optional[PanoCache]:
+        return None if self.pool is None else self.pool["cache"]
+
+    @property
+    def uploads(self) -> int:
+        """Panoramas uploaded into the pool so far (0 without one)."""
+        return 0 if self.pool is None else self.pool["uploads"]
 
     # ------------------------------------------------------------------ examples
     def set_examples(self, hyp: HypothesisTable, is_match) -> None:
@@ -179,25 +336,80 @@ class RenderedTrainSource:
         e0.record()
         return e1
 
-    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Render examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match)."""
+    def _make_resident(self, panos: np.ndarray, next_use: Optional[np.ndarray]) -> np.ndarray:
+        """Pool slot of every entry of `panos`; the misses are gathered into a pinned staging buffer, copied with one host-to-device
+        copy per array and written into their slots (BevRasteriser.update_panos), all on the current stream."""
+        pool = self.pool
+        slots, uploads = pool["cache"].plan(panos, next_use)
+        m = len(uploads)
+        if m == 0:
+            return slots
+        st = pool["stage"][pool["turn"]]
+        pool["turn"] ^= 1
+        if st["event"] is not None:
+            st["event"].synchronize()   # the copy that last read this buffer
+        rgb_np, depth_np = st["rgb"].numpy(), st["depth"].numpy().view(np.uint16)
+        for k, (p, _) in enumerate(uploads):
+            rgb_np[k] = pool["rgb"][p]
+            depth_np[k] = pool["depth"][p]
+        e1 = self._timed("upload")
+        with tracing.range("salve.pano_upload"):
+            rgb_rows = st["rgb"][:m].to(self.device, non_blocking=True)
+            depth_rows = st["depth"][:m].to(self.device, non_blocking=True)
+            slots_dev = torch.from_numpy(np.asarray([sl for _, sl in uploads], dtype=np.int32)).to(self.device)
+        st["event"] = torch.cuda.Event()
+        st["event"].record()
+        if e1 is not None:
+            e1.record()
+        e1 = self._timed("index update")
+        with tracing.range("salve.pano_update"):
+            self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows)
+        if e1 is not None:
+            e1.record()
+        pool["uploads"] += m
+        return slots
+
+    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Render examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  `next_use` (resident pool
+        only): the batch of every panorama's next use, for the planner (`epoch_next_use`)."""
         ex, S, B = self.examples, len(self.surfaces), len(idx)
         Hb, Wb = self.ras.bev_hw
         i1 = ex["i1"][idx]
-        # renders in the order of their panorama (as RenderVerifyPipeline.prepare issues them: the workgroups of one panorama run
-        # side by side and share its depth blocks through the L2s); the tile jobs name each sample's render by its rank
-        order = np.argsort(i1, kind="stable")
-        rank = np.empty(B, dtype=np.int64)
-        rank[order] = np.arange(B)
-        src = idx[order]
-        rows = pack_hypotheses(np.repeat(ex["i1"][src], S), np.tile([SURFACES[s] for s in self.surfaces], B), np.repeat(ex["R"][src], S, axis=0),
-                               np.repeat(ex["t"][src], S, axis=0), np.ones(B * S))
+        surf = [SURFACES[s] for s in self.surfaces]
         si = np.tile(np.arange(S, dtype=np.int64), B)
+        jobs = np.zeros((2, B * S), dtype=_lib.TILE_JOB_DTYPE)   # sample-major [B][S]: posed renders of this batch | identity renders
+        if self.identity == "kept":
+            # renders in the order of their panorama (as RenderVerifyPipeline.prepare issues them: the workgroups of one panorama run
+            # side by side and share its depth blocks through the L2s); the tile jobs name each sample's render by its rank
+            order = np.argsort(i1, kind="stable")
+            rank = np.empty(B, dtype=np.int64)
+            rank[order] = np.arange(B)
+            src = idx[order]
+            rows = pack_hypotheses(np.repeat(ex["i1"][src], S), np.tile(surf, B), np.repeat(ex["R"][src], S, axis=0),
+                                   np.repeat(ex["t"][src], S, axis=0), np.ones(B * S))
+            n, bev_b = B * S, self.ref_bev
+            jobs["bev_offset"][0] = (np.repeat(rank, S) * S + si) * (Hb * Wb)
+            jobs["bev_offset"][1] = (np.repeat(ex["i2"][idx], S) * S + si) * (Hb * Wb)
+        else:
+            # B posed renders and the identity renders of the U distinct second panoramas, ONE launch pair; a group of S renders per
+            # entry, the groups in the order of their panorama's slot (the pool's slot, or the panorama itself when all are resident)
+            uniq, inv = np.unique(ex["i2"][idx], return_inverse=True)
+            U = len(uniq)
+            pano = np.concatenate([i1, uniq])
+            where = pano if self.pool is None else self._make_resident(pano, next_use)
+            order = np.argsort(where, kind="stable")
+            rank = np.empty(B + U, dtype=np.int64)
+            rank[order] = np.arange(B + U)
+            R = np.concatenate([ex["R"][idx], np.tile(np.eye(2, dtype=np.float32), (U, 1, 1))])[order]
+            t = np.concatenate([ex["t"][idx], np.zeros((U, 2), np.float32)])[order]
+            posed = (np.arange(B + U) < B).astype(np.int32)[order]
+            rows = pack_hypotheses(np.repeat(where[order], S), np.tile(surf, B + U), np.repeat(R, S, axis=0), np.repeat(t, S, axis=0), np.repeat(posed, S))
+            n, bev_b = (B + U) * S, self.bev
+            jobs["bev_offset"][0] = (np.repeat(rank[:B], S) * S + si) * (Hb * Wb)
+            jobs["bev_offset"][1] = (np.repeat(rank[B + inv], S) * S + si) * (Hb * Wb)
+        check_launch(B, S, n // S - B)
         smp = np.repeat(np.arange(B, dtype=np.int64), S)
         swap = np.repeat(ex["swap"][idx], S)
-        jobs = np.zeros((2, B * S), dtype=_lib.TILE_JOB_DTYPE)   # sample-major [B][S]: posed renders of this batch | identity renders
-        jobs["bev_offset"][0] = (np.repeat(rank, S) * S + si) * (Hb * Wb)
-        jobs["bev_offset"][1] = (np.repeat(ex["i2"][idx], S) * S + si) * (Hb * Wb)
         jobs["slot"][:] = smp
         jobs["chan"][0] = 6 * si + 3 * swap
         jobs["chan"][1] = 6 * si + 3 * (1 - swap)
@@ -212,18 +424,18 @@ class RenderedTrainSource:
         labels = buf[o[2]:o[3]].view(torch.int64).view(B, 1)
         e1 = self._timed("scatter")
         with tracing.range("salve.scatter"):
-            self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:], B * S, self.bev)
+            self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:], n, self.bev)
         if e1 is not None:
             e1.record()
         e1 = self._timed("densify")
         with tracing.range("salve.densify"):
-            self.ras.densify(B * S, self.bev)
+            self.ras.densify(n, self.bev)
         if e1 is not None:
             e1.record()
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
         e1 = self._timed("tiles")
         with tracing.range("salve.train_tiles"):
-            self.ras.train_tiles(self.bev, self.ref_bev, jobs_a, jobs_b, S, buf[o[1]:o[2]], B, out)
+            self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, S, buf[o[1]:o[2]], B, out)   # (identity="batch": one buffer, only read)
         if e1 is not None:
             e1.record()
         return out, labels
@@ -235,11 +447,24 @@ class RenderedTrainSource:
         off = (self.tf.resize - self.tf.crop) // 2
         return [(off, off, False, False)] * n
 
+    def batch_panos(self, idx: np.ndarray) -> np.ndarray:
+        """The distinct panoramas examples `idx` name."""
+        return np.unique(np.concatenate([self.examples["i1"][idx], self.examples["i2"][idx]]))
+
     def __iter__(self):
         if self.examples is None:
             raise RuntimeError("set_examples first")
-        for idx in plan_epoch(len(self.examples["i1"]), self.batch_size, self.split, self.gen):
-            yield self.batch(idx, self.draws(len(idx)))
+        plan = plan_epoch(len(self.examples["i1"]), self.batch_size, self.split, self.gen)
+        if self.pool is None:
+            for idx in plan:
+                yield self.batch(idx, self.draws(len(idx)))
+        else:   # the epoch's order is known here, before its first batch: every panorama's next use, for the planner
+            panos = [self.batch_panos(idx) for idx in plan]
+            next_use, after = epoch_next_use(panos, self.n_panos)
+            for b, idx in enumerate(plan):
+                out = self.batch(idx, self.draws(len(idx)), next_use)
+                next_use[panos[b]] = after[b]
+                yield out
         status.check(self.device, f"rendered {self.split} batches")
 
 
@@ -262,14 +487,16 @@ def load_example_json(path: Path) -> Tuple[HypothesisTable, np.ndarray]:
     return table, np.asarray(d["is_match"], dtype=np.int64)
 
 
-def load_render_dir(path: str):
+def load_render_dir(path: str, mmap: bool = False):
     """(rgb uint8 [P, H, W, 3], depth uint16 [P, H, W], {"train" | "val": (HypothesisTable, labels)}) of a --render-from directory
-    (format: INTEGRATION.md).  A missing file ends the program with one line."""
+    (format: INTEGRATION.md).  A missing file ends the program with one line.  mmap: the two arrays are np.memmap views of their
+    files (only the headers are read here) -- for `RenderedTrainSource(resident_panos=N)`, which reads a panorama when it uploads it."""
     root = Path(path)
     for name in RENDER_DIR_FILES:
         if not (root / name).is_file():
             raise SystemExit(f"--render-from {root}: {name} is missing (expected {', '.join(RENDER_DIR_FILES)})")
-    rgb, depth = np.load(root / "panos_rgb.npy"), np.load(root / "panos_depth.npy")
+    mode = "r" if mmap else None
+    rgb, depth = np.load(root / "panos_rgb.npy", mmap_mode=mode), np.load(root / "panos_depth.npy", mmap_mode=mode)
     if rgb.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[3] != 3 or depth.dtype != np.uint16 or depth.shape != rgb.shape[:3]:
         raise SystemExit(f"--render-from {root}: panos_rgb.npy must be uint8 [P, H, W, 3] and panos_depth.npy uint16 [P, H, W], got "
                          f"{rgb.dtype} {rgb.shape} / {depth.dtype} {depth.shape}")

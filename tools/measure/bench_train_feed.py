@@ -9,7 +9,14 @@
     examples written once as JPEGs into a temporary ZindData tree (outside the timed region) and fed by `training.get_dataloader`.
 
     python tools/measure/bench_train_feed.py [--configs 152:2,50:1] [--batch 256] [--modes bf16:hip,fp32:torch] [--steps 5] [--warmup 2]
-                                             [--panos 64] [--disk 0]
+                                             [--panos 64] [--disk 0] [--identity {kept,batch}] [--resident-panos N]
+
+--identity batch and / or --resident-panos N switch to the comparison of the feed's modes instead: rows (a) identity
+"kept", everything resident (the default source: the yardstick), (b) identity "batch", everything resident, and with --resident-panos
+(c) a pool of N slots in its second epoch (steady state) and (d) in its first (cold fill) -- source alone with the event split (upload and
+index update beside scatter, densify, tiles), the host-to-device rate reached, the uploads per batch the planner makes (furthest next
+use) beside what LRU would make on the same epochs, and the step fed by each row beside the step on a resident batch.  --panos P must
+then be at least 4 x batch (so that a half-size pool misses); the P scenes are distinct (a few rooms, each turned by its own angle).
 
 Synthetic 1024 x 512 panoramas (as bench.py).  Medians; run the command twice for the spread.  Per-kernel times: a run of its own under
 `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train_feed.py ...`.
@@ -96,6 +103,192 @@ def write_zind_tree(root: Path, src, n: int) -> None:
                 image_io.write_jpeg(str(d / f"{stem}{2 * int(j) + 1}.jpg"), ident[int(ex["i2"][j]) * S + si])
 
 
+def distinct_panos(P: int, base: int = 64):
+    """P distinct 1024 x 512 scenes without P ray casts: `base` synthetic rooms, each also seen turned about the vertical axis (the
+    panorama and its depth map rolled by the same number of columns -- another room as far as the renderer is concerned)."""
+    rooms = synthetic.make_panos(min(P, base))
+    rgb = np.empty((P,) + rooms[0][0].shape, dtype=np.uint8)
+    depth = np.empty((P,) + rooms[0][1].shape, dtype=np.uint16)
+    for i in range(P):
+        r, turn = rooms[i % len(rooms)], (i // len(rooms)) * 61
+        rgb[i], depth[i] = np.roll(r[0], turn, axis=1), np.roll(r[1], turn, axis=1)
+    return rgb, depth
+
+
+def planned_uploads(hyp, P: int, pool: int, B: int, epochs: int, policy: str):
+    """Uploads per batch, per epoch, of a PanoCache with `policy` over the epochs a seed-0 train source runs."""
+    cache = train_render.PanoCache(P, pool, B, policy=policy)
+    gen = torch.Generator().manual_seed(0)
+    out = []
+    for _ in range(epochs):
+        plan = train_render.plan_epoch(len(hyp), B, "train", gen)
+        panos = [np.unique(np.concatenate([hyp.i1[idx], hyp.i2[idx]])) for idx in plan]
+        next_use, after = train_render.epoch_next_use(panos, P)
+        per = []
+        for b, need in enumerate(panos):
+            per.append(len(cache.plan(need, next_use)[1]))
+            next_use[need] = after[b]
+        out.append(per)
+    return out
+
+
+def cache_rows(a, dev) -> None:
+    """Rows (a)-(d) of DESIGN.md 4.11 (see the module docstring)."""
+    B, n_it, P = a.batch, a.warmup + a.steps, a.panos
+    if P < 4 * B:
+        sys.exit(f"--panos {P}: the comparison of the feed's modes needs at least 4 x batch = {4 * B} panoramas")
+    pool = a.resident_panos
+    t0 = time.perf_counter()
+    rgb, depth = distinct_panos(P)
+    pano_bytes = rgb[0].nbytes + depth[0].nbytes
+    print(f"# {torch.cuda.get_device_name(dev)}; batch {B}, {P} distinct synthetic 1024 x 512 panoramas ({time.perf_counter() - t0:.0f} s to make), "
+          f"pool {pool}, an epoch = {n_it} batches, median of {a.steps} after {a.warmup} warm-up; step = forward + backward + Adam; rows alternate "
+          "step by step", flush=True)
+    hyp = synthetic.make_hypotheses(B * n_it, P)
+    labels = np.arange(B * n_it, dtype=np.int64) % 2
+    if pool is not None:
+        for policy in ("furthest", "lru"):
+            per = planned_uploads(hyp, P, pool, B, 3, policy)
+            print(f"planned uploads per batch, {policy}: " + "; ".join(f"epoch {e + 1} mean {np.mean(v):.1f} (first batch {v[0]}, others {np.mean(v[1:]):.1f})"
+                                                                       for e, v in enumerate(per)), flush=True)
+    for cfg in a.configs.split(","):
+        layers, nm = (int(v) for v in cfg.split(":"))
+        for mode in a.modes.split(","):
+            prec, norm = mode.split(":")
+            tag = f"resnet{layers} {6 * nm}ch batch {B} {prec} norm {norm}"
+
+            def make(**kw):
+                s = train_render.RenderedTrainSource(dev, MODS[nm], batch_size=B, precision=prec, split="train", seed=0, **kw)
+                t1 = time.perf_counter()
+                s.load_panos(rgb, depth)
+                torch.cuda.synchronize()
+                print(f"{tag}: load_panos({kw or 'default'}) {time.perf_counter() - t1:.2f} s", flush=True)
+                s.set_examples(hyp, labels)
+                return s
+
+            rows = {"(a) kept, all resident": make()}
+            if a.identity == "batch" or pool is not None:
+                rows["(b) batch, all resident"] = make(identity="batch")
+            if pool is not None:
+                rows["(d) pool, first epoch"] = make(identity="batch", resident_panos=pool)
+            tags = ("upload", "index update", "scatter", "densify", "tiles")
+
+            def alone(names, its):
+                """Source alone: the named rows alternate batch by batch over one epoch each."""
+                walls, splits = {k: [] for k in names}, {k: [] for k in names}
+                for i in range(n_it):
+                    for k in names:
+                        src = rows[k]
+                        src.timers = []
+                        box = []
+                        walls[k].append(wall(lambda: box.append(next(its[k]))))
+                        sp = {t: 0.0 for t in tags}
+                        for t, s0, e0 in src.timers:
+                            sp[t] += s0.elapsed_time(e0)
+                        splits[k].append(sp)
+                        src.timers = None
+                        last[k] = box[0]
+                for k in names:
+                    w = med(walls[k][a.warmup:]) * 1e3
+                    sp = {t: med([s[t] for s in splits[k][a.warmup:]]) for t in tags}
+                    line = f"{tag}: {k}: source alone {w:.2f} ms per batch (host clock); events: " + ", ".join(f"{t} {sp[t]:.2f}" for t in tags) + " ms"
+                    if rows[k].pool is not None:
+                        line += f"; uploads so far {rows[k].uploads}"
+                    print(line, flush=True)
+                    res_alone[k] = w
+
+            last, res_alone = {}, {}
+            random.seed(0)
+            its = {k: iter(s) for k, s in rows.items()}
+            pool_key = "(d) pool, first epoch"
+            if pool is not None:
+                u0 = rows[pool_key].uploads
+            alone(list(rows), its)
+            if pool is not None:   # the H2D rate of the cold epoch, and the same source's second epoch = row (c)
+                src = rows[pool_key]
+                for it in its.values():
+                    for _ in it:   # (finish the epochs: the status check at their end)
+                        pass
+                cold = src.uploads - u0
+                print(f"{tag}: cold epoch uploaded {cold} panoramas = {cold * pano_bytes / 1e9:.2f} GB", flush=True)
+                rows["(c) pool, second epoch"] = rows.pop(pool_key)
+                # per-batch upload events with their byte counts: the host-to-device rate actually reached
+                rates = []
+                src.timers = []
+                it_c = iter(src)
+                walls_c, splits_c = [], []
+                for i in range(n_it):
+                    del src.timers[:]
+                    before = src.uploads
+                    box = []
+                    walls_c.append(wall(lambda: box.append(next(it_c))))
+                    sp = {t: 0.0 for t in tags}
+                    for t, s0, e0 in src.timers:
+                        sp[t] += s0.elapsed_time(e0)
+                    splits_c.append(sp)
+                    m = src.uploads - before
+                    if m and sp["upload"] > 0:
+                        rates.append((m, m * pano_bytes / sp["upload"] / 1e6))
+                    last["(c) pool, second epoch"] = box[0]
+                src.timers = None
+                w = med(walls_c[a.warmup:]) * 1e3
+                sp = {t: med([s[t] for s in splits_c[a.warmup:]]) for t in tags}
+                res_alone["(c) pool, second epoch"] = w
+                print(f"{tag}: (c) pool, second epoch: source alone {w:.2f} ms per batch (host clock); events: " + ", ".join(f"{t} {sp[t]:.2f}" for t in tags) +
+                      f" ms; uploads per batch {[m for m, _ in rates]}; host-to-device rate of the upload events (2 copies per batch, pinned) "
+                      f"{[round(r, 1) for _, r in rates]} GB/s, median {med([r for _, r in rates]) if rates else float('nan'):.1f} GB/s", flush=True)
+                for _ in it_c:
+                    pass
+
+            # ---- the step: resident packed batch, and fed by every row (the pool in its third epoch: steady), alternating
+            torch.manual_seed(0)
+            model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=MODS[nm])).to(dev).train()
+            model.set_train_precision(prec).set_train_norm(norm)
+            model = model.to(memory_format=torch.channels_last)
+            opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+            x_packed, y = last["(a) kept, all resident"][0].clone(), last["(a) kept, all resident"][1].squeeze().clone()
+            its = {k: iter(s) for k, s in rows.items()}
+            res = {k: [] for k in ["resident"] + list(rows)}
+
+            def fed(k):
+                xb, yb = next(its[k])
+                step(model, opt, lambda: model.forward_packed(xb), yb.squeeze())
+
+            for i in range(n_it):
+                res["resident"].append(wall(lambda: step(model, opt, lambda: model.forward_packed(x_packed), y)))
+                for k in rows:
+                    res[k].append(wall(lambda: fed(k)))
+            m = {k: med(v[a.warmup:]) * 1e3 for k, v in res.items()}
+            print(f"{tag}: step on a resident packed batch {m['resident']:.1f} ms; " +
+                  "; ".join(f"fed by {k} {m[k]:.1f} ms ({100 * (m[k] / m['resident'] - 1):+.1f} %, source alone / resident step = "
+                            f"{res_alone[k] / m['resident']:.3f})" for k in rows), flush=True)
+            if pool is not None:   # the cold fill under the step: a fresh pool, its first epoch
+                for it in its.values():
+                    it.close()
+                del rows["(c) pool, second epoch"]
+                fresh = make(identity="batch", resident_panos=pool)
+                it_d = iter(fresh)
+                cold_fed, resident = [], []
+                for i in range(n_it):
+                    resident.append(wall(lambda: step(model, opt, lambda: model.forward_packed(x_packed), y)))
+
+                    def fed_cold():
+                        xb, yb = next(it_d)
+                        step(model, opt, lambda: model.forward_packed(xb), yb.squeeze())
+
+                    cold_fed.append(wall(fed_cold))
+                r_, c_ = med(resident[a.warmup:]) * 1e3, med(cold_fed[a.warmup:]) * 1e3
+                print(f"{tag}: (d) pool, first epoch: fed step {c_:.1f} ms beside the resident step {r_:.1f} ms ({100 * (c_ / r_ - 1):+.1f} %); its first batch "
+                      f"(fills {min(pool, 2 * B)} slots at most) {cold_fed[0] * 1e3:.1f} ms", flush=True)
+                it_d.close()
+                del fresh
+            else:
+                for it in its.values():
+                    it.close()
+            del model, opt, rows, its, last, x_packed
+            torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="152:2,50:1", help="layers:surfaces, comma separated")
@@ -105,10 +298,15 @@ def main() -> None:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--panos", type=int, default=64)
     ap.add_argument("--disk", type=int, default=0, help="batches of the end-to-end comparison with the on-disk path (0: skip)")
+    ap.add_argument("--identity", choices=("kept", "batch"), default="kept", help="batch: compare the feed's modes (rows a, b) instead")
+    ap.add_argument("--resident-panos", type=int, default=None, help="pool size: compare the feed's modes (rows a-d) instead; needs --panos >= 4 x batch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_train_feed.py needs the MI355X (a CPU run says nothing about it)")
     dev = torch.device("cuda:0")
+    if a.identity == "batch" or a.resident_panos is not None:
+        cache_rows(a, dev)
+        return
     B, n_it = a.batch, a.warmup + a.steps
     panos = synthetic.make_panos(a.panos)
     rgb, depth = np.stack([p[0] for p in panos]), np.stack([p[1] for p in panos])
