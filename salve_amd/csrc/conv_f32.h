@@ -22,7 +22,7 @@ struct ConvF32Args {
     const float* bias;
     const float* res;      // [M][Cout] or nullptr
     float* out;            // [M][Cout]
-    const int32_t* ktab;   // one entry per 8 consecutive k: dy | dx << 8 | channel offset << 16
+    const int32_t* ktab;   // one entry per 8 consecutive k: dy | dx << 8 | channel offset << 16; a negative entry gathers zeros
     const float* in2;      // second point-wise source (projection shortcut) or nullptr
     int Hi, Wi, Cin, Ho, Wo, Cout, stride, pad, K, M, relu;
     int Hi2, Wi2, Cin2, stride2, nkt1;   // nkt1: k-tiles of the first source
@@ -43,11 +43,12 @@ __device__ __forceinline__ bool f32_tile(int id, int m_tiles, int n_tiles, int& 
 }
 
 // The 8 input channels of ktab entry e (tap dy, dx; channel offset) for the pixel whose tap (0, 0) is `pix` (at iy0, ix0),
-// zero outside the image.
+// zero outside the image.  A negative entry (bit 31: the training entries' K padding) reads nothing and gives zeros wherever
+// its tap would land: the test joins the bounds test, no load and no branch of its own.
 __device__ __forceinline__ void gather8(const ConvF32Args& p, long long pix, int iy0, int ix0, int32_t e, float4& v0, float4& v1) {
     const int dy = (int8_t)(e & 0xFF), dx = (int8_t)((e >> 8) & 0xFF), coff = (e >> 16) & 0xFFFF;
     v0 = v1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if ((unsigned)(iy0 + dy) < (unsigned)p.Hi && (unsigned)(ix0 + dx) < (unsigned)p.Wi) {
+    if (e >= 0 && (unsigned)(iy0 + dy) < (unsigned)p.Hi && (unsigned)(ix0 + dx) < (unsigned)p.Wi) {
         const float4* src = reinterpret_cast<const float4*>(p.in + pix + ((long long)dy * p.Wi + dx) * p.Cin + coff);
         v0 = src[0];
         v1 = src[1];
@@ -57,12 +58,12 @@ __device__ __forceinline__ void gather8(const ConvF32Args& p, long long pix, int
 // Backward-data of a stride-2 convolution as a gather (conv_train_f32.hip): the kernel's output pixel (y, x) is a pixel of dx, its
 // source image p.in is dy ([Hi, Wi] = the convolution's output), and ktab entry e names the forward tap (ky, kx) and a channel
 // offset of dy.  (iy0, ix0) = (y + pad, x + pad); the tap reads dy[(iy0 - ky) / 2][(ix0 - kx) / 2] when both divisions are
-// exact and inside dy, zero otherwise.  `pix` is the element offset of the sample's first dy pixel.
+// exact and inside dy, zero otherwise (and zero for a negative entry).  `pix` is the element offset of the sample's first dy pixel.
 __device__ __forceinline__ void gather8_dgrad_s2(const ConvF32Args& p, long long pix, int iy0, int ix0, int32_t e, float4& v0, float4& v1) {
     const int ky = (int8_t)(e & 0xFF), kx = (int8_t)((e >> 8) & 0xFF), coff = (e >> 16) & 0xFFFF;
     const int ty = iy0 - ky, tx = ix0 - kx;
     v0 = v1 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (ty >= 0 && tx >= 0 && !(ty & 1) && !(tx & 1) && (ty >> 1) < p.Hi && (tx >> 1) < p.Wi) {
+    if (e >= 0 && ty >= 0 && tx >= 0 && !(ty & 1) && !(tx & 1) && (ty >> 1) < p.Hi && (tx >> 1) < p.Wi) {
         const float4* src = reinterpret_cast<const float4*>(p.in + pix + ((long long)(ty >> 1) * p.Wi + (tx >> 1)) * p.Cin + coff);
         v0 = src[0];
         v1 = src[1];

@@ -8,8 +8,8 @@
 //            names the 16 source bytes of one k-table entry (8 channels of one tap) and global_load_lds_dwordx4 drops them into
 //            LDS, swizzled on the source side; taps outside the image read a zero page.  fp32 accumulation, ONE rounding to
 //            bf16 per output in the epilogue (a plain conversion: v_cvt_pk_bf16_f32, NaN stays NaN), no bias, no activation.
-//            The stems' K = 49 * Cin is padded to a multiple of 64 with zero weight columns whose table entries lie outside
-//            every image.
+//            The stems' K = 49 * Cin is padded to a multiple of 64 with zero weight columns whose table entries are negative:
+//            they read the zero page and no pixel.
 //   dgrad    stride 1: conv_bf16_kernel over dy with the weights transposed ([Cin][KH][KW][Cout]) and rotated by 180 degrees on the
 //            device, pad' = KH - 1 - pad.  Stride 2: the DGRAD_S2 gather of conv_f32.h -- the tap (ky, kx) of dx pixel (iy, ix)
 //            reads dy[(iy + pad - ky) / 2][(ix + pad - kx) / 2] when both divisions are exact, the zero page otherwise (the
@@ -44,13 +44,15 @@ constexpr int W_LDP = W_BP + 8;     // LDS row pitch in bf16 (80 B: the 16-byte 
 constexpr int W_TARGET_WG = 1024;   // workgroups a wgrad launch aims at; fixed, so the split is a function of the shape
 constexpr int W_MIN_TILES = 16;     // staged pixel tiles per split at least
 
+constexpr int32_t KTAB_PAD = INT32_MIN;   // a padding entry of the k table: negative, selects the zero page
+
 enum GemmMode { GATHER = 0, POINTWISE = 1, DGRAD_S2 = 2 };
 
 struct ConvBf16Args {
     const uint16_t* in;     // NHWC [.., Hi, Wi, Cin] bf16
     const uint16_t* w;      // [Cout][K] bf16
     uint16_t* out;          // [M][Cout] bf16
-    const int32_t* ktab;    // one entry per 8 consecutive k: dy | dx << 8 | channel offset << 16
+    const int32_t* ktab;    // one entry per 8 consecutive k: dy | dx << 8 | channel offset << 16; a negative entry reads the zero page
     const uint16_t* zeros;  // ZERO_BYTES of zeros
     int Hi, Wi, Cin, Ho, Wo, Cout, stride, pad, K, M;
     int m_tiles, n_tiles;
@@ -134,10 +136,10 @@ __global__ __launch_bounds__(G_THREADS, 2) void conv_bf16_kernel(ConvBf16Args p)
                     src = rowp[i] ? rowp[i] + kt * G_BK : p.zeros;
                 } else if (MODE == DGRAD_S2) {
                     const int ty = iy0[i] - ky, tx = ix0[i] - kx;
-                    const bool ok = !((ty | tx) & 1) && (unsigned)(ty >> 1) < (unsigned)p.Hi && (unsigned)(tx >> 1) < (unsigned)p.Wi;
+                    const bool ok = e >= 0 && !((ty | tx) & 1) && (unsigned)(ty >> 1) < (unsigned)p.Hi && (unsigned)(tx >> 1) < (unsigned)p.Wi;
                     src = ok ? rowp[i] + ((long long)(ty >> 1) * p.Wi + (tx >> 1)) * p.Cin + coff : p.zeros;
                 } else {
-                    const bool ok = (unsigned)(iy0[i] + ky) < (unsigned)p.Hi && (unsigned)(ix0[i] + kx) < (unsigned)p.Wi;
+                    const bool ok = e >= 0 && (unsigned)(iy0[i] + ky) < (unsigned)p.Hi && (unsigned)(ix0[i] + kx) < (unsigned)p.Wi;
                     src = ok ? rowp[i] + delta : p.zeros;
                 }
                 __builtin_amdgcn_global_load_lds((global_cptr)src, (lds_ptr)(As_ + i * 32 * G_BK), 16, 0, 0);
@@ -196,11 +198,12 @@ __global__ __launch_bounds__(G_THREADS, 2) void conv_bf16_kernel(ConvBf16Args p)
 }
 
 // One table entry per 8 consecutive k of a [rows][KH][KW][C] weight row: tap (ky, kx) | channel offset << 16.  Entries at and
-// beyond n_valid pad K to a multiple of 64: tap dy = -128 lies outside every image, so they read the zero page.
+// beyond n_valid pad K to a multiple of 64 (the stems): they are negative, which the kernel's source selection answers with the zero
+// page.  (A far tap is no padding: dy = -128 lies INSIDE an image of 129 rows or more, and 0 * inf is NaN.)
 __global__ __launch_bounds__(256) void ktab_bf16_kernel(int32_t* __restrict__ tab, int n_valid, int n_total, int C, int KW) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_total) return;
-    if (q >= n_valid) { tab[q] = 0x80; return; }
+    if (q >= n_valid) { tab[q] = KTAB_PAD; return; }
     const int c8 = q % (C / 8), kx = (q / (C / 8)) % KW, ky = q / ((C / 8) * KW);
     tab[q] = ky | (kx << 8) | ((c8 * 8) << 16);
 }

@@ -5,7 +5,7 @@
 //
 //   forward  conv_f32_kernel (conv_f32.h, the fp32 engine's implicit GEMM) with a zero bias, no residual, no ReLU.  The k table
 //            is built on the device from the descriptor; the stems' K = 49 * Cin (not a multiple of 32) is padded with zero
-//            weight columns whose table entries point outside the image.
+//            weight columns whose table entries are negative: they gather zeros and read no pixel.
 //   dgrad    stride 1: conv_f32_kernel over dy with the weights transposed ([Cin][KH][KW][Cout]) and rotated by 180 degrees,
 //            pad' = KH - 1 - pad.  Stride 2: conv_f32_kernel<.., DGRAD_S2> -- the tap (ky, kx) of dx pixel (iy, ix) reads
 //            dy[(iy + pad - ky) / 2][(ix + pad - kx) / 2] when both divisions are exact, zero otherwise (3/4 of its K terms are zero
@@ -30,14 +30,17 @@ constexpr int W_BP = 32;     // pixels per staged tile (the MFMA reduction)
 constexpr int W_TARGET_WG = 1024;   // workgroups a wgrad launch aims at (4 per CU); fixed, so the split is a function of the shape
 constexpr int W_MIN_TILES = 8;      // staged pixel tiles per split at least
 
+constexpr int32_t KTAB_PAD = INT32_MIN;   // a padding entry of the k table: negative (conv_f32.h: gather8)
+
 size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // One table entry per 8 consecutive k of a [rows][KH][KW][C] weight row: tap (ky, kx) | channel offset << 16.  Entries at and
-// beyond n_valid pad K to a multiple of 32: tap dy = -128 lies outside every image, so they gather zeros.
+// beyond n_valid pad K to a multiple of 32 (the stems): they are negative, which gather8 answers with zeros without reading the
+// image.  (A far tap is no padding: dy = -128 lies INSIDE an image of 129 rows or more, and 0 * inf is NaN.)
 __global__ __launch_bounds__(256) void ktab_kernel(int32_t* __restrict__ tab, int n_valid, int n_total, int C, int KW) {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (q >= n_total) return;
-    if (q >= n_valid) { tab[q] = 0x80; return; }
+    if (q >= n_valid) { tab[q] = KTAB_PAD; return; }
     const int c8 = q % (C / 8), kx = (q / (C / 8)) % KW, ky = q / ((C / 8) * KW);
     tab[q] = ky | (kx << 8) | ((c8 * 8) << 16);
 }
