@@ -1,7 +1,8 @@
 // conv_train_bf16.hip -- per-convolution bf16 entries for opt-in mixed-precision training of the verifier on gfx950 (MI355X):
 // forward, backward-data (dgrad) and backward-weight (wgrad) of one convolution, bf16 operands on the bf16 matrix cores with fp32
-// accumulation.  The same descriptors, layouts and refusals as the fp32 entries (conv_train_f32.hip); the caller keeps fp32
-// master weights and passes their bf16 copy (salve_amd/models/trainable.py: Conv2dBF16Function).
+// accumulation.  The same descriptors, layouts and refusals as the fp32 entries: both run conv_train.h's shape contract
+// (check_desc) and host drivers; this file holds the bf16 kernels and the bf16 precision policy.  The caller keeps fp32 master
+// weights and passes their bf16 copy (salve_amd/models/trainable.py: Conv2dBF16Function).
 //
 //   forward  conv_bf16_kernel: implicit GEMM, M = batch * Ho * Wo pixels, N = Cout, K = KH * KW * Cin, block tile 128 pixels x
 //            BN channels x 64 k, 4 waves, v_mfma_f32_16x16x32_bf16.  The staging is conv_igemm_kernel's (resnet.hip): each lane
@@ -16,14 +17,10 @@
 //            zero terms are multiplied).  The stem's dgrad is refused (SALVE_ERR_UNSUPPORTED).
 //   wgrad    wgrad_bf16_kernel: dW[Cout, K] = sum over the batch * Ho * Wo pixels of dy (x) x_patch with the pixels as the MFMA
 //            reduction; bf16 x bf16 products are exact in fp32.  The pixel range is split over workgroups into fp32 partial slabs
-//            that wgrad_bf16_combine_kernel sums in split order: no atomics, the same inputs give bit-identical dW, which stays
+//            that wgrad_combine_kernel sums in split order: no atomics, the same inputs give bit-identical dW, which stays
 //            fp32 throughout.  Both operands are transposed on their way into LDS (pixels along the LDS row), 4 pixels x 8
 //            channels per thread.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/salve_hip.h"
-#include "salve_common.h"
+#include "conv_train.h"
 
 namespace {
 
@@ -39,14 +36,8 @@ constexpr int G_THREADS = 256;   // 4 waves, 2 x 2 over the block tile
 constexpr int ZERO_BYTES = 256;  // the zero page of padding taps and of rows beyond M (>= 16 bytes)
 
 constexpr int W_BK = 128;           // k columns per wgrad workgroup
-constexpr int W_BP = 32;            // pixels per staged wgrad tile (the reduction of one MFMA)
 constexpr int W_LDP = W_BP + 8;     // LDS row pitch in bf16 (80 B: the 16-byte fragment reads of 16 rows hit 16 distinct slots)
-constexpr int W_TARGET_WG = 1024;   // workgroups a wgrad launch aims at; fixed, so the split is a function of the shape
 constexpr int W_MIN_TILES = 16;     // staged pixel tiles per split at least
-
-constexpr int32_t KTAB_PAD = INT32_MIN;   // a padding entry of the k table: negative, selects the zero page
-
-enum GemmMode { GATHER = 0, POINTWISE = 1, DGRAD_S2 = 2 };
 
 struct ConvBf16Args {
     const uint16_t* in;     // NHWC [.., Hi, Wi, Cin] bf16
@@ -197,41 +188,6 @@ __global__ __launch_bounds__(G_THREADS, 2) void conv_bf16_kernel(ConvBf16Args p)
     }
 }
 
-// One table entry per 8 consecutive k of a [rows][KH][KW][C] weight row: tap (ky, kx) | channel offset << 16.  Entries at and
-// beyond n_valid pad K to a multiple of 64 (the stems): they are negative, which the kernel's source selection answers with the zero
-// page.  (A far tap is no padding: dy = -128 lies INSIDE an image of 129 rows or more, and 0 * inf is NaN.)
-__global__ __launch_bounds__(256) void ktab_bf16_kernel(int32_t* __restrict__ tab, int n_valid, int n_total, int C, int KW) {
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n_total) return;
-    if (q >= n_valid) { tab[q] = KTAB_PAD; return; }
-    const int c8 = q % (C / 8), kx = (q / (C / 8)) % KW, ky = q / ((C / 8) * KW);
-    tab[q] = ky | (kx << 8) | ((c8 * 8) << 16);
-}
-
-// [Cout][K] -> [Cout][Kp] (columns K..Kp-1 zero): the stems' padded weight rows.
-__global__ __launch_bounds__(256) void pad_rows_bf16_kernel(const uint16_t* __restrict__ w, uint16_t* __restrict__ out, int rows, int K, int Kp) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)rows * Kp) return;
-    const int k = (int)(idx % Kp);
-    const long long r = idx / Kp;
-    out[idx] = k < K ? w[r * K + k] : (uint16_t)0;
-}
-
-// w [Cout][KH][KW][Cin] -> out [Cin][KH][KW][Cout], taps rotated by 180 degrees when rot (stride-1 dgrad) or kept (stride-2 gather).
-__global__ __launch_bounds__(256) void transpose_weights_bf16_kernel(const uint16_t* __restrict__ w, uint16_t* __restrict__ out, int Cout,
-                                                                     int KH, int KW, int Cin, int rot) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)Cout * KH * KW * Cin) return;
-    const int co = (int)(idx % Cout);
-    long long t = idx / Cout;
-    const int kx = (int)(t % KW);
-    t /= KW;
-    const int ky = (int)(t % KH);
-    const int ci = (int)(t / KH);
-    const int sy = rot ? KH - 1 - ky : ky, sx = rot ? KW - 1 - kx : kx;
-    out[idx] = w[(((long long)co * KH + sy) * KW + sx) * Cin + ci];
-}
-
 struct WgradBf16Args {
     const uint16_t* x;    // NHWC [B, Hi, Wi, Cin]
     const uint16_t* dy;   // NHWC [B, Ho, Wo, Cout]
@@ -355,76 +311,6 @@ __global__ __launch_bounds__(G_THREADS, 2) void wgrad_bf16_kernel(WgradBf16Args 
     }
 }
 
-// dW = slab 0 + slab 1 + ... in split order (one fixed fp32 summation order per element).
-__global__ __launch_bounds__(256) void wgrad_bf16_combine_kernel(const float* __restrict__ slabs, float* __restrict__ dw, long long n4, int splits) {
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= n4) return;
-    const float4* s = reinterpret_cast<const float4*>(slabs) + idx;
-    float4 a = s[0];
-    for (int k = 1; k < splits; k++) {
-        const float4 v = s[(long long)k * n4];
-        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
-    }
-    reinterpret_cast<float4*>(dw)[idx] = a;
-}
-
-// The fp32 entries' shape contract (conv_train_f32.hip: check_desc), word for word.
-int check_desc(const salve_conv_desc_t* d, const char* who) {
-    if (!d) { salve_fail(who); return SALVE_ERR_BAD_ARG; }
-    const bool k1 = d->KH == 1 && d->KW == 1 && d->pad == 0 && (d->stride == 1 || d->stride == 2);
-    const bool k3 = d->KH == 3 && d->KW == 3 && d->pad == 1 && (d->stride == 1 || d->stride == 2);
-    const bool k7 = d->KH == 7 && d->KW == 7 && d->pad == 3 && d->stride == 2;
-    if (!k1 && !k3 && !k7) { salve_fail("conv: only 1x1 (pad 0), 3x3 (pad 1) with stride 1 or 2 and the 7x7 / 2 / pad 3 stem are supported"); return SALVE_ERR_BAD_ARG; }
-    if (k7 ? (d->Cin != 8 && d->Cin != 16 && d->Cin != 24) : (d->Cin < 64 || d->Cin > 2048 || d->Cin % 64 != 0)) {
-        salve_fail("conv: Cin must be 64..2048 in steps of 64 (the 7x7 stem: 8, 16 or 24, the zero-padded 6 / 12 / 18 channels)");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (d->Cout < 64 || d->Cout > 2048 || d->Cout % 64 != 0) { salve_fail("conv: Cout must be 64..2048 in steps of 64"); return SALVE_ERR_BAD_ARG; }
-    if (d->batch <= 0 || d->Hi <= 0 || d->Wi <= 0 || d->Hi > 4096 || d->Wi > 4096) { salve_fail("conv: bad batch or input size"); return SALVE_ERR_BAD_ARG; }
-    if (d->Ho != (d->Hi + 2 * d->pad - d->KH) / d->stride + 1 || d->Wo != (d->Wi + 2 * d->pad - d->KW) / d->stride + 1 || d->Ho <= 0 || d->Wo <= 0) {
-        salve_fail("conv: Ho / Wo do not match the input size, kernel, stride and padding");
-        return SALVE_ERR_BAD_ARG;
-    }
-    const long long px = (long long)d->batch * (d->Hi > d->Ho ? (long long)d->Hi * d->Wi : (long long)d->Ho * d->Wo);
-    if (px > 0x7FFFFFFFll - 1024) { salve_fail("conv: batch too large"); return SALVE_ERR_BAD_ARG; }
-    return SALVE_OK;
-}
-
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-unsigned blocks256(long long n) { return (unsigned)((n + 255) / 256); }
-
-int wgrad_bco(const salve_conv_desc_t* d) { return d->Cout % 128 == 0 ? 128 : 64; }
-
-void wgrad_split(const salve_conv_desc_t* d, int& n_ptiles, int& tiles_per_split, int& splits, int& co_tiles, int& k_tiles) {
-    const long long P = (long long)d->batch * d->Ho * d->Wo;
-    const int K = d->KH * d->KW * d->Cin;
-    n_ptiles = (int)((P + W_BP - 1) / W_BP);
-    co_tiles = d->Cout / wgrad_bco(d);
-    k_tiles = (K + W_BK - 1) / W_BK;
-    int want = (W_TARGET_WG + co_tiles * k_tiles - 1) / (co_tiles * k_tiles);
-    const int most = (n_ptiles + W_MIN_TILES - 1) / W_MIN_TILES;
-    if (want > most) want = most;
-    if (want < 1) want = 1;
-    tiles_per_split = (n_ptiles + want - 1) / want;
-    splits = (n_ptiles + tiles_per_split - 1) / tiles_per_split;
-}
-
-// Workspace sections of the forward / dgrad passes: zero page | k table | packed weights.
-struct GemmWs {
-    size_t zeros, ktab, w, total;
-};
-
-GemmWs gemm_ws(int n_out, int K, bool packed_w) {
-    const int Kp = (K + G_BK - 1) / G_BK * G_BK;
-    GemmWs g;
-    g.zeros = 0;
-    g.ktab = ZERO_BYTES;
-    g.w = g.ktab + align256((size_t)(Kp / 8) * sizeof(int32_t));
-    g.total = g.w + (packed_w ? align256((size_t)n_out * Kp * sizeof(uint16_t)) : 0) + 256;   // + 256: the caller's pointer is aligned here
-    return g;
-}
-
 template <int BN, int MODE>
 int launch_bf16(const ConvBf16Args& a, hipStream_t s) {
     const long long grid = 8ll * ((a.m_tiles + 7) / 8) * a.n_tiles;
@@ -434,134 +320,52 @@ int launch_bf16(const ConvBf16Args& a, hipStream_t s) {
     return SALVE_OK;
 }
 
-int launch_gemm(ConvBf16Args& a, int mode, hipStream_t s) {
-    a.m_tiles = (int)(((long long)a.M + G_BM - 1) / G_BM);
-    const bool wide = a.Cout % 128 == 0;
-    a.n_tiles = a.Cout / (wide ? 128 : 64);
-    if (mode == POINTWISE) return wide ? launch_bf16<128, POINTWISE>(a, s) : launch_bf16<64, POINTWISE>(a, s);
-    if (mode == DGRAD_S2) return wide ? launch_bf16<128, DGRAD_S2>(a, s) : launch_bf16<64, DGRAD_S2>(a, s);
-    return wide ? launch_bf16<128, GATHER>(a, s) : launch_bf16<64, GATHER>(a, s);
-}
+struct BF16 {
+    typedef uint16_t T;
+    typedef ConvBf16Args Args;
+    typedef WgradBf16Args WgradArgs;
+    static constexpr int BK = G_BK;
+    static constexpr bool POINTWISE = true;   // a 1x1 / stride-1 pass reads its rows directly: no k table
+    static size_t head_bytes(int) { return ZERO_BYTES; }   // the zero page
+
+    static int launch_gemm(ConvBf16Args& a, void* head, int mode, hipStream_t s) {
+        a.zeros = static_cast<const uint16_t*>(head);
+        a.m_tiles = (int)(((long long)a.M + G_BM - 1) / G_BM);
+        const bool wide = a.Cout % 128 == 0;
+        a.n_tiles = a.Cout / (wide ? 128 : 64);
+        if (mode == POINTWISE) return wide ? launch_bf16<128, POINTWISE>(a, s) : launch_bf16<64, POINTWISE>(a, s);
+        if (mode == DGRAD_S2) return wide ? launch_bf16<128, DGRAD_S2>(a, s) : launch_bf16<64, DGRAD_S2>(a, s);
+        return wide ? launch_bf16<128, GATHER>(a, s) : launch_bf16<64, GATHER>(a, s);
+    }
+
+    static WgradTile wgrad_tile(const salve_conv_desc_t* d) { return {d->Cout % 128 == 0 ? 128 : 64, W_BK, W_MIN_TILES}; }
+    static void launch_wgrad(const WgradBf16Args& a, const WgradTile& t, dim3 grid, hipStream_t s) {
+        if (t.bco == 128) hipLaunchKernelGGL(wgrad_bf16_kernel<128>, grid, dim3(G_THREADS), 0, s, a);
+        else hipLaunchKernelGGL(wgrad_bf16_kernel<64>, grid, dim3(G_THREADS), 0, s, a);
+    }
+};
 
 }  // namespace
 
 extern "C" {
 
 size_t salve_conv_bf16_workspace_bytes(const salve_conv_desc_t* d, int32_t pass) {
-    if (check_desc(d, "salve_conv_bf16_workspace_bytes: null descriptor") != SALVE_OK) return 0;
-    const int K = d->KH * d->KW * d->Cin;
-    if (pass == SALVE_CONV_FWD) return gemm_ws(d->Cout, K, K % G_BK != 0).total;
-    if (pass == SALVE_CONV_DGRAD) {
-        if (d->KH == 7) { salve_fail("salve_conv_bf16: the stem's dgrad is not supported (the network input needs no gradient)"); return 0; }
-        return gemm_ws(d->Cin, d->KH * d->KW * d->Cout, true).total;
-    }
-    if (pass == SALVE_CONV_WGRAD) {
-        int n_ptiles, tps, splits, co_tiles, k_tiles;
-        wgrad_split(d, n_ptiles, tps, splits, co_tiles, k_tiles);
-        return (splits > 1 ? align256((size_t)splits * d->Cout * K * sizeof(float)) : 0) + 256;
-    }
-    salve_fail("salve_conv_bf16_workspace_bytes: pass must be SALVE_CONV_FWD, _DGRAD or _WGRAD");
-    return 0;
+    return conv_workspace_bytes<BF16>("salve_conv_bf16_workspace_bytes: null descriptor", d, pass);
 }
 
 int salve_conv_bf16_forward(const salve_conv_desc_t* d, const uint16_t* x, const uint16_t* w, uint16_t* y, void* ws, size_t ws_bytes,
                             void* stream) {
-    int st = check_desc(d, "salve_conv_bf16_forward: null descriptor");
-    if (st != SALVE_OK) return st;
-    if (!x || !w || !y || !ws || !aligned16(x) || !aligned16(w) || !aligned16(y)) {
-        salve_fail("salve_conv_bf16_forward: null or not 16-byte aligned pointer");
-        return SALVE_ERR_BAD_ARG;
-    }
-    const int K = d->KH * d->KW * d->Cin, Kp = (K + G_BK - 1) / G_BK * G_BK;
-    const GemmWs g = gemm_ws(d->Cout, K, K != Kp);
-    if (ws_bytes < g.total) { salve_fail("salve_conv_bf16_forward: workspace too small"); return SALVE_ERR_WORKSPACE; }
-    hipStream_t s = (hipStream_t)stream;
-    char* base = reinterpret_cast<char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    uint16_t* zeros = reinterpret_cast<uint16_t*>(base + g.zeros);
-    int32_t* ktab = reinterpret_cast<int32_t*>(base + g.ktab);
-    SALVE_HIP_CHECK(hipMemsetAsync(zeros, 0, ZERO_BYTES, s));
-    const bool pointwise = d->KH == 1 && d->stride == 1;
-    if (!pointwise) {
-        hipLaunchKernelGGL(ktab_bf16_kernel, dim3(blocks256(Kp / 8)), dim3(256), 0, s, ktab, K / 8, Kp / 8, d->Cin, d->KW);
-        SALVE_HIP_CHECK(hipGetLastError());
-    }
-    const uint16_t* wk = w;
-    if (K != Kp) {
-        uint16_t* wp = reinterpret_cast<uint16_t*>(base + g.w);
-        hipLaunchKernelGGL(pad_rows_bf16_kernel, dim3(blocks256((long long)d->Cout * Kp)), dim3(256), 0, s, w, wp, d->Cout, K, Kp);
-        SALVE_HIP_CHECK(hipGetLastError());
-        wk = wp;
-    }
-    ConvBf16Args a = {};
-    a.in = x; a.w = wk; a.out = y; a.ktab = ktab; a.zeros = zeros;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout;
-    a.stride = d->stride; a.pad = d->pad; a.K = Kp; a.M = (int)((long long)d->batch * d->Ho * d->Wo);
-    return launch_gemm(a, pointwise ? POINTWISE : GATHER, s);
+    return conv_forward<BF16>("salve_conv_bf16_forward: null descriptor", d, x, w, y, ws, ws_bytes, stream);
 }
 
 int salve_conv_bf16_backward_data(const salve_conv_desc_t* d, const uint16_t* dy, const uint16_t* w, uint16_t* dx, void* ws, size_t ws_bytes,
                                   void* stream) {
-    int st = check_desc(d, "salve_conv_bf16_backward_data: null descriptor");
-    if (st != SALVE_OK) return st;
-    if (d->KH == 7) { salve_fail("salve_conv_bf16_backward_data: the stem's dgrad is not supported (the network input needs no gradient)"); return SALVE_ERR_UNSUPPORTED; }
-    if (!dy || !w || !dx || !ws || !aligned16(dy) || !aligned16(w) || !aligned16(dx)) {
-        salve_fail("salve_conv_bf16_backward_data: null or not 16-byte aligned pointer");
-        return SALVE_ERR_BAD_ARG;
-    }
-    const int K = d->KH * d->KW * d->Cout;   // a multiple of 64: Cout is
-    const GemmWs g = gemm_ws(d->Cin, K, true);
-    if (ws_bytes < g.total) { salve_fail("salve_conv_bf16_backward_data: workspace too small"); return SALVE_ERR_WORKSPACE; }
-    hipStream_t s = (hipStream_t)stream;
-    char* base = reinterpret_cast<char*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    uint16_t* zeros = reinterpret_cast<uint16_t*>(base + g.zeros);
-    int32_t* ktab = reinterpret_cast<int32_t*>(base + g.ktab);
-    uint16_t* wt = reinterpret_cast<uint16_t*>(base + g.w);
-    const bool s2 = d->stride == 2, pointwise = d->KH == 1 && !s2;
-    SALVE_HIP_CHECK(hipMemsetAsync(zeros, 0, ZERO_BYTES, s));
-    if (!pointwise) {
-        hipLaunchKernelGGL(ktab_bf16_kernel, dim3(blocks256(K / 8)), dim3(256), 0, s, ktab, K / 8, K / 8, d->Cout, d->KW);
-        SALVE_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(transpose_weights_bf16_kernel, dim3(blocks256((long long)K * d->Cin)), dim3(256), 0, s, w, wt, d->Cout, d->KH, d->KW,
-                       d->Cin, s2 ? 0 : 1);
-    SALVE_HIP_CHECK(hipGetLastError());
-    ConvBf16Args a = {};
-    a.in = dy; a.w = wt; a.out = dx; a.ktab = ktab; a.zeros = zeros;
-    a.Hi = d->Ho; a.Wi = d->Wo; a.Cin = d->Cout; a.Ho = d->Hi; a.Wo = d->Wi; a.Cout = d->Cin;
-    a.stride = 1; a.pad = s2 ? d->pad : d->KH - 1 - d->pad;
-    a.K = K; a.M = (int)((long long)d->batch * d->Hi * d->Wi);
-    return launch_gemm(a, s2 ? DGRAD_S2 : (pointwise ? POINTWISE : GATHER), s);
+    return conv_backward_data<BF16>("salve_conv_bf16_backward_data: null descriptor", d, dy, w, dx, ws, ws_bytes, stream);
 }
 
 int salve_conv_bf16_backward_weight(const salve_conv_desc_t* d, const uint16_t* x, const uint16_t* dy, float* dw, void* ws, size_t ws_bytes,
                                     void* stream) {
-    int st = check_desc(d, "salve_conv_bf16_backward_weight: null descriptor");
-    if (st != SALVE_OK) return st;
-    if (!x || !dy || !dw || !ws || !aligned16(x) || !aligned16(dy) || !aligned16(dw)) {
-        salve_fail("salve_conv_bf16_backward_weight: null or not 16-byte aligned pointer");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (ws_bytes < salve_conv_bf16_workspace_bytes(d, SALVE_CONV_WGRAD)) { salve_fail("salve_conv_bf16_backward_weight: workspace too small"); return SALVE_ERR_WORKSPACE; }
-    int n_ptiles, tps, splits, co_tiles, k_tiles;
-    wgrad_split(d, n_ptiles, tps, splits, co_tiles, k_tiles);
-    const int K = d->KH * d->KW * d->Cin;
-    hipStream_t s = (hipStream_t)stream;
-    float* slabs = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    WgradBf16Args a;
-    a.x = x; a.dy = dy; a.out = splits > 1 ? slabs : dw;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Cin = d->Cin; a.Ho = d->Ho; a.Wo = d->Wo; a.Cout = d->Cout; a.KW = d->KW;
-    a.stride = d->stride; a.pad = d->pad; a.K = K; a.P = (int)((long long)d->batch * d->Ho * d->Wo);
-    a.n_ptiles = n_ptiles; a.tiles_per_split = tps; a.co_tiles = co_tiles;
-    const dim3 grid((unsigned)(co_tiles * k_tiles), (unsigned)splits);
-    if (wgrad_bco(d) == 128) hipLaunchKernelGGL(wgrad_bf16_kernel<128>, grid, dim3(G_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(wgrad_bf16_kernel<64>, grid, dim3(G_THREADS), 0, s, a);
-    SALVE_HIP_CHECK(hipGetLastError());
-    if (splits > 1) {
-        const long long n4 = (long long)d->Cout * K / 4;
-        hipLaunchKernelGGL(wgrad_bf16_combine_kernel, dim3(blocks256(n4)), dim3(256), 0, s, slabs, dw, n4, splits);
-        SALVE_HIP_CHECK(hipGetLastError());
-    }
-    return SALVE_OK;
+    return conv_backward_weight<BF16>("salve_conv_bf16_backward_weight: null descriptor", d, x, dy, dw, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -50,10 +50,11 @@ def _pack_weight(w: Tensor, cp: int) -> Tensor:
     return _nhwc(w, cp)
 
 
-def _run(fn: str, desc: "_lib.ConvDesc", pass_: int, a: Tensor, b: Tensor, out: Tensor) -> None:
+def _run(prefix: str, entry: str, desc: "_lib.ConvDesc", pass_: int, a: Tensor, b: Tensor, out: Tensor) -> None:
+    """One `prefix`_`entry` call (salve_conv_f32 / salve_conv_bf16; forward / backward_data / backward_weight) on `prefix`'s workspace."""
     lib = _lib.load()
-    ws_query = lib.salve_conv_bf16_workspace_bytes if fn.startswith("salve_conv_bf16_") else lib.salve_conv_f32_workspace_bytes
-    nbytes = int(ws_query(ctypes.byref(desc), pass_))
+    fn = f"{prefix}_{entry}"
+    nbytes = int(getattr(lib, prefix + "_workspace_bytes")(ctypes.byref(desc), pass_))
     if nbytes == 0:
         raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
     ws = torch.empty(nbytes, dtype=torch.uint8, device=a.device)
@@ -63,37 +64,40 @@ def _run(fn: str, desc: "_lib.ConvDesc", pass_: int, a: Tensor, b: Tensor, out: 
     _lib.check(st, fn)
 
 
-class Conv2dF32Function(torch.autograd.Function):
-    """y = conv2d(x, weight, stride, padding) without bias, in fp32 on the HIP entries (forward / dgrad / wgrad).
+class _Conv2dFunction(torch.autograd.Function):
+    """y = conv2d(x, weight, stride, padding) without bias on the HIP entries (forward / dgrad / wgrad): the one body of
+    Conv2dF32Function and Conv2dBF16Function, which set `prefix` (the entries), `act` (the dtype of x, y, dx and of the weight as
+    the kernels read it) and `why` (for the dtype refusal).  The weight is always the fp32 parameter and dW always fp32.
 
-    x: fp32 CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: fp32 CUDA torch layout
-    [Cout, Cin, KH, KW].  Returns channels_last fp32 [B, Cout, Ho, Wo].  Input channels that are not a multiple of 8 (the stem's
-    6 / 12 / 18) are zero-padded here; the stem's dgrad is never needed (the network input takes no gradient) and raises if asked.
-    dgrad is skipped when x needs no gradient."""
+    x: CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: torch layout [Cout, Cin, KH, KW].
+    Returns channels_last [B, Cout, Ho, Wo].  Input channels that are not a multiple of 8 (the stem's 6 / 12 / 18) are zero-padded
+    here; the stem's dgrad is never needed (the network input takes no gradient) and raises if asked.  dgrad is skipped when x
+    needs no gradient."""
 
     @staticmethod
     def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False) -> Tensor:
-        for name, t in (("x", x), ("weight", weight)):
+        cls = ctx._forward_cls   # the class `apply` was called on
+        who = cls.__name__
+        for name, t, dt in (("x", x, cls.act), ("weight", weight, torch.float32)):
             if t.device.type != "cuda":
-                raise RuntimeError(f"Conv2dF32Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
-                                   "(no CPU fallback)")
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"Conv2dF32Function: {name} must be float32 (training runs in the reference's fp32), got {t.dtype}")
+                raise RuntimeError(f"{who}: {name} is on {t.device}; the training convolutions run on the HIP device only (no CPU fallback)")
+            if t.dtype != dt:
+                raise RuntimeError(f"{who}: {name} must be {dt} ({cls.why}), got {t.dtype}")
         b, cin, h, w = x.shape
         cout, cin_w, kh, kw = weight.shape
         if packed:   # x carries the weight's input channels zero-padded to a multiple of 8 already (forward_packed)
             if cin != _pad8(cin_w):
-                raise RuntimeError(f"Conv2dF32Function: weight takes {cin_w} input channels, a packed x needs {_pad8(cin_w)}, got {cin}")
+                raise RuntimeError(f"{who}: weight takes {cin_w} input channels, a packed x needs {_pad8(cin_w)}, got {cin}")
             cin = cin_w
         elif cin_w != cin:
-            raise RuntimeError(f"Conv2dF32Function: weight takes {cin_w} input channels, x has {cin}")
+            raise RuntimeError(f"{who}: weight takes {cin_w} input channels, x has {cin}")
         cp = _pad8(cin)
         ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
         desc = _lib.ConvDesc(b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
         xn = _nhwc(x.detach(), cp)
-        wk = _pack_weight(weight.detach(), cp)
-        y = torch.empty((b, cout, ho, wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
-        _run("salve_conv_f32_forward", desc, _lib.CONV_FWD, xn, wk, y)
+        wk = _pack_weight(weight.detach().to(cls.act), cp)   # (bf16: cast once per forward, the copy is saved for the backward pass)
+        y = torch.empty((b, cout, ho, wo), dtype=cls.act, device=x.device, memory_format=torch.channels_last)
+        _run(cls.prefix, "forward", desc, _lib.CONV_FWD, xn, wk, y)
         ctx.save_for_backward(xn, wk)
         ctx.desc = (b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
         ctx.cin = cin
@@ -101,83 +105,39 @@ class Conv2dF32Function(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gy: Tensor):
+        cls = ctx._forward_cls
         xn, wk = ctx.saved_tensors
         desc = _lib.ConvDesc(*ctx.desc)
         b, h, w, cp = ctx.desc[:4]
-        gyn = gy.float().permute(0, 2, 3, 1).contiguous()   # NHWC [B, Ho, Wo, Cout]
+        gyn = gy.to(cls.act).permute(0, 2, 3, 1).contiguous()   # NHWC [B, Ho, Wo, Cout]
         dx = dw = None
         if ctx.needs_input_grad[0]:
             if cp != ctx.cin:
-                raise RuntimeError("Conv2dF32Function: no input gradient for the stem (its input channels are zero-padded)")
-            dxn = torch.empty((b, h, w, cp), dtype=torch.float32, device=gy.device)
-            _run("salve_conv_f32_backward_data", desc, _lib.CONV_DGRAD, gyn, wk, dxn)
+                raise RuntimeError(f"{cls.__name__}: no input gradient for the stem (its input channels are zero-padded)")
+            dxn = torch.empty((b, h, w, cp), dtype=cls.act, device=gy.device)
+            _run(cls.prefix, "backward_data", desc, _lib.CONV_DGRAD, gyn, wk, dxn)
             dx = dxn.permute(0, 3, 1, 2)   # channels_last view
         if ctx.needs_input_grad[1]:
-            dwk = torch.empty_like(wk)
-            _run("salve_conv_f32_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
+            dwk = torch.empty(wk.shape, dtype=torch.float32, device=gy.device)   # (never accumulated in bf16)
+            _run(cls.prefix, "backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
             dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
         return dx, dw, None, None, None
+
+
+class Conv2dF32Function(_Conv2dFunction):
+    """The convolution in fp32, the reference's precision: fp32 x, y, dx and weights on salve_conv_f32_*."""
+    prefix, act, why = "salve_conv_f32", torch.float32, "training runs in the reference's fp32"
+
+
+class Conv2dBF16Function(_Conv2dFunction):
+    """The convolution in bf16 mixed precision: bf16 x, y and dx, a bf16 copy of the fp32 master weight, fp32 accumulation and fp32
+    dW on salve_conv_bf16_*."""
+    prefix, act, why = "salve_conv_bf16", torch.bfloat16, "bf16 activations, fp32 master weights"
 
 
 def conv2d_f32(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:
     assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
     return Conv2dF32Function.apply(x, conv.weight, conv.stride[0], conv.padding[0], packed)
-
-
-class Conv2dBF16Function(torch.autograd.Function):
-    """y = conv2d(x, weight, stride, padding) without bias, bf16 operands on the HIP bf16 entries, fp32 accumulation.
-
-    x: bf16 CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: the fp32 master weight,
-    torch layout [Cout, Cin, KH, KW], packed and cast to bf16 once per forward (the bf16 copy is saved for the backward pass).
-    Returns channels_last bf16 [B, Cout, Ho, Wo].  Backward: bf16 dx, fp32 dW (never accumulated in bf16).  The stem's input
-    channels are zero-padded to a multiple of 8 as for Conv2dF32Function; its dgrad raises if asked."""
-
-    @staticmethod
-    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False) -> Tensor:
-        for name, t, dt in (("x", x, torch.bfloat16), ("weight", weight, torch.float32)):
-            if t.device.type != "cuda":
-                raise RuntimeError(f"Conv2dBF16Function: {name} is on {t.device}; the training convolutions run on the HIP device only "
-                                   "(no CPU fallback)")
-            if t.dtype != dt:
-                raise RuntimeError(f"Conv2dBF16Function: {name} must be {dt} (bf16 activations, fp32 master weights), got {t.dtype}")
-        b, cin, h, w = x.shape
-        cout, cin_w, kh, kw = weight.shape
-        if packed:   # x carries the weight's input channels zero-padded to a multiple of 8 already (forward_packed)
-            if cin != _pad8(cin_w):
-                raise RuntimeError(f"Conv2dBF16Function: weight takes {cin_w} input channels, a packed x needs {_pad8(cin_w)}, got {cin}")
-            cin = cin_w
-        elif cin_w != cin:
-            raise RuntimeError(f"Conv2dBF16Function: weight takes {cin_w} input channels, x has {cin}")
-        cp = _pad8(cin)
-        ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
-        desc = _lib.ConvDesc(b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
-        xn = _nhwc(x.detach(), cp)
-        wk = _pack_weight(weight.detach().to(torch.bfloat16), cp)
-        y = torch.empty((b, cout, ho, wo), dtype=torch.bfloat16, device=x.device, memory_format=torch.channels_last)
-        _run("salve_conv_bf16_forward", desc, _lib.CONV_FWD, xn, wk, y)
-        ctx.save_for_backward(xn, wk)
-        ctx.desc = (b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
-        ctx.cin = cin
-        return y
-
-    @staticmethod
-    def backward(ctx, gy: Tensor):
-        xn, wk = ctx.saved_tensors
-        desc = _lib.ConvDesc(*ctx.desc)
-        b, h, w, cp = ctx.desc[:4]
-        gyn = gy.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()   # NHWC [B, Ho, Wo, Cout]
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            if cp != ctx.cin:
-                raise RuntimeError("Conv2dBF16Function: no input gradient for the stem (its input channels are zero-padded)")
-            dxn = torch.empty((b, h, w, cp), dtype=torch.bfloat16, device=gy.device)
-            _run("salve_conv_bf16_backward_data", desc, _lib.CONV_DGRAD, gyn, wk, dxn)
-            dx = dxn.permute(0, 3, 1, 2)   # channels_last view
-        if ctx.needs_input_grad[1]:
-            dwk = torch.empty(wk.shape, dtype=torch.float32, device=gy.device)
-            _run("salve_conv_bf16_backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
-            dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
-        return dx, dw, None, None, None
 
 
 def conv2d_bf16(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:

@@ -36,12 +36,12 @@ _hip_conv = {"fp32": trainable.conv2d_f32, "bf16": trainable.conv2d_bf16}
 _conv_attr = {"fp32": "conv2d_f32", "bf16": "conv2d_bf16"}
 
 
-def _timed_run(fn, desc, pass_, a, b, out):
+def _timed_run(prefix, entry, desc, pass_, a, b, out):
     s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     s.record()
-    _hip_run(fn, desc, pass_, a, b, out)
+    _hip_run(prefix, entry, desc, pass_, a, b, out)
     e.record()
-    _events.append((fn, s, e))
+    _events.append((f"{prefix}_{entry}", s, e))
 
 
 def _timed_run_bn(fn, desc, pass_, ptrs, device):
