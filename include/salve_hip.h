@@ -43,7 +43,7 @@ typedef enum {
                                      `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
-                                        salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT) */
+                                        salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -60,6 +60,8 @@ typedef enum {
                                         a draw carries unknown flag bits -- that sample is not written */
 #define SALVE_STATUS_BAD_PANO_SLOT 32 /* bev_pano_index_update: the slot list names a slot outside [0, n_panos) -- that entry is skipped, the
                                          other listed slots are updated */
+#define SALVE_STATUS_BAD_LAYOUT 64 /* layout_pose: an image record names a panorama outside [0, n_panos), offsets outside the output capacities,
+                                      or a posed coordinate lies beyond 2^24 pixels -- that image's record is written empty, the others are posed */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -228,6 +230,43 @@ typedef struct {
 } salve_layout_t;
 int salve_layout_rasterise(const salve_layout_t* layouts, int32_t n, const int32_t* poly_xy, const int32_t* segs, int32_t img_h,
                            int32_t img_w, uint32_t* out, int32_t* status, void* stream);
+
+/* The host chain in front of salve_layout_rasterise, on the device (additive within ABI 7): n layout images posed from panorama
+ * geometry that stays resident as flat tables, ONE launch per batch.  It stands behind rasterize_room_layout_pair's
+ * `i2Ti1.transform_from` of panorama 1's room and W/D/O vertices (salve/utils/bev_rendering_utils.py:82, 90; panorama 2's own
+ * layout, :96, is the identity record R = I, t = 0, s = 1), the HoHoNet -> ZInD factor 1.5 (:127, :149), and
+ * `bevimg_Sim2_world.transform_from` followed by np.round (:187-188, :214-215).
+ *   room_xy / room_off   device double [n_room_xy, 2] in metres in each panorama's own frame, CSR offsets int64 [n_panos + 1]; rooms
+ *                        are stored closed (first vertex repeated); a panorama without a room has no vertex and gives an empty image
+ *   wdo_xy / wdo_type / wdo_off   device double [n_wdo, 2, 2], uint8 [n_wdo] (0 windows, 1 doors, 2 openings), CSR offsets int64
+ *                        [n_panos + 1]; per panorama in drawing order (doors, windows, openings)
+ *   recs                 device salve_layout_pose_t [n]: the image's panorama, its pose -- R (row-major) and t are float32 and are widened
+ *                        to double, s is a double (Sim2 stores them so) -- and the first vertex / segment of its output; the host
+ *                        computes the offsets (a running sum of the panoramas' counts): there is no device scan
+ *   bev_tx, bev_ty, bev_scale   -xlims[0], -ylims[0], 1 / meters_per_px of the BEV window;  line_width: W/D/O thickness in pixels
+ *   layouts, poly_xy, segs      OUT: exactly the tables salve_layout_rasterise reads (colour 0x00BBGGRR: windows 0x0000ff, doors
+ *                        0x00ff00, openings 0xff0000); poly_cap vertices / seg_cap segments of capacity; 8-byte aligned
+ * Per coordinate, in fp64, one rounding per operation and in the host's order: x' = x * R00 + y * R01 (y' = x * R10 + y * R11), + t,
+ * * s, * 1.5, + bev_t, * bev_scale, round half to even, narrowed to int32.  (numpy's `@` may fuse the first multiply-add; the results
+ * can then differ in the last bit of the fp64 intermediate, which changes a pixel coordinate only within an ulp of a half-pixel tie:
+ * the contract is the integer tables -- DESIGN.md 4.13.)
+ * The record table is device memory, so the kernel checks it before it forms an address: a record whose panorama lies outside
+ * [0, n_panos), whose output would leave the capacities, whose panorama's offsets leave the tables, or a coordinate that is not
+ * finite or beyond 2^24 pixels (pack_layouts' limit) ORs SALVE_STATUS_BAD_LAYOUT into `status` (device int32 or NULL) and that
+ * image's record is written empty (n_poly = n_seg = 0); the other images are written.
+ * SALVE_ERR_BAD_ARG on null pointers, misaligned tables, n < 0, n > 65535, n_panos <= 0, non-positive capacities, a non-finite BEV
+ * parameter.  The thin-contour variant (render_mask=False) is not posed here. */
+typedef struct {
+    int32_t pano;               /* panorama whose layout is drawn */
+    int32_t poly_off, seg_off;  /* first vertex in poly_xy / first segment in segs of this image */
+    int32_t reserved;
+    float R[4], t[2];           /* i2Ti1's rotation (row-major) and translation, as Sim2 stores them */
+    double s;                   /* i2Ti1's scale */
+} salve_layout_pose_t;
+int salve_layout_pose(const double* room_xy, const int64_t* room_off, int64_t n_room_xy, const double* wdo_xy, const uint8_t* wdo_type,
+                      const int64_t* wdo_off, int64_t n_wdo, int32_t n_panos, const salve_layout_pose_t* recs, int32_t n,
+                      double bev_tx, double bev_ty, double bev_scale, int32_t line_width, salve_layout_t* layouts, int32_t* poly_xy,
+                      int32_t poly_cap, int32_t* segs, int32_t seg_cap, int32_t* status, void* stream);
 
 /* BEV uint32 -> uint8 [n, bev_h, bev_w, 3], the array render_bev_image returns (bev_rendering_utils.py:328). */
 int salve_bev_export_u8(const uint32_t* bev, int32_t n, int32_t bev_h, int32_t bev_w, uint8_t* out, void* stream);

@@ -69,6 +69,7 @@ EXPORTED_SYMBOLS = (
     "salve_bn_bf16_backward",
     "salve_bev_train_tiles",
     "salve_bev_pano_index_update",
+    "salve_layout_pose",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -80,6 +81,7 @@ STATUS_BAD_HYPOTHESIS = 4
 STATUS_LAYOUT_THICKNESS = 8
 STATUS_BAD_TILE_JOB = 16
 STATUS_BAD_PANO_SLOT = 32
+STATUS_BAD_LAYOUT = 64
 
 
 class BevConfig(ctypes.Structure):
@@ -104,9 +106,11 @@ HYP_DTYPE = np.dtype(
 )
 TILE_JOB_DTYPE = np.dtype([("bev_offset", "<i8"), ("slot", "<i4"), ("chan", "<i4")])
 LAYOUT_DTYPE = np.dtype([("n_poly", "<i4"), ("poly_off", "<i4"), ("n_seg", "<i4"), ("seg_off", "<i4")])
+LAYOUT_POSE_DTYPE = np.dtype([("pano", "<i4"), ("poly_off", "<i4"), ("seg_off", "<i4"), ("reserved", "<i4"), ("R", "<f4", (4,)), ("t", "<f4", (2,)),
+                              ("s", "<f8")])
 TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 TILE_HFLIP, TILE_VFLIP = 1, 2
-assert HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
+assert LAYOUT_POSE_DTYPE.itemsize == 48 and HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
 
 # salve_conv_f32_* / salve_conv_bf16_* passes (include/salve_hip.h: SALVE_CONV_*)
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
@@ -176,6 +180,9 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_keys_from_pixels.restype = ctypes.c_int
     lib.salve_layout_rasterise.argtypes = [vp, i32, vp, vp, i32, i32, vp, vp, vp]
     lib.salve_layout_rasterise.restype = ctypes.c_int
+    f64, i64 = ctypes.c_double, ctypes.c_int64
+    lib.salve_layout_pose.argtypes = [vp, vp, i64, vp, vp, vp, i64, i32, vp, i32, f64, f64, f64, i32, vp, vp, i32, vp, i32, vp, vp]
+    lib.salve_layout_pose.restype = ctypes.c_int
     lib.salve_bev_export_u8.argtypes = [vp, i32, i32, i32, vp, vp]
     lib.salve_bev_export_u8.restype = ctypes.c_int
     lib.salve_bev_tiles.argtypes = [vp, i32, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp]
@@ -250,6 +257,9 @@ def check_status_word(word: int, what: str) -> None:
                             "flag bits); that sample was not written")
     if word & STATUS_BAD_PANO_SLOT:
         raise SalveHipError(f"{what}: a panorama-index update names a slot outside the resident pool; that slot's index was not rebuilt")
+    if word & STATUS_BAD_LAYOUT:
+        raise SalveHipError(f"{what}: a layout image record names a panorama outside the layout tables or output outside its tables, or a "
+                            "posed coordinate lies more than 2^24 pixels away; that layout image is empty")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

@@ -414,3 +414,100 @@ extern "C" int salve_layout_rasterise(const salve_layout_t* layouts, int32_t n, 
     SALVE_HIP_CHECK(hipGetLastError());
     return SALVE_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ posing on the device
+// salve_layout_pose: the host chain of salve_amd/layout.py in front of the rasteriser -- Sim2.transform_from of the panorama's
+// room and W/D/O vertices (bev_rendering_utils.py:82, 90; the identity for :96), x 1.5 (:127, :149), bevimg_Sim2_world and
+// np.round (:187-188, :214-215) -- for n images whose geometry is resident as flat per-panorama tables.  One workgroup per image,
+// one thread per room vertex or W/D/O end point; every product and sum is a separate fp64 operation in the host's order (this
+// file is compiled with -ffp-contract=off).  The record table is device memory: everything is range-checked before an address
+// is formed.
+namespace {
+
+constexpr int POSE_THREADS = 64;
+constexpr double POSE_LIMIT = 16777216.0;   // 2^24 pixels: pack_layouts' limit
+
+struct PoseXf {
+    double r00, r01, r10, r11, tx, ty, s, bx, by, bs;
+};
+
+// -> false if the pixel coordinate is not finite or lies beyond 2^24 (the pair is then stored as 0, 0)
+__device__ __forceinline__ bool pose_point(const PoseXf& f, double x, double y, int2& out) {
+    double px = x * f.r00 + y * f.r01, py = x * f.r10 + y * f.r11;   // point_cloud @ R.T, un-fused
+    px = px + f.tx; py = py + f.ty;
+    px = px * f.s; py = py * f.s;
+    px = px * 1.5; py = py * 1.5;                                   // HOHO_S_ZIND_SCALE_FACTOR
+    px = px + f.bx; py = py + f.by;                                 // bevimg_Sim2_world: rotation I, + t, * s
+    px = px * f.bs; py = py * f.bs;
+    px = rint(px); py = rint(py);                                   // np.round: half to even
+    const bool ok = fabs(px) <= POSE_LIMIT && fabs(py) <= POSE_LIMIT;   // (false for NaN)
+    out = ok ? make_int2((int)px, (int)py) : make_int2(0, 0);
+    return ok;
+}
+
+__global__ __launch_bounds__(POSE_THREADS) void layout_pose_kernel(const double* __restrict__ room_xy, const int64_t* __restrict__ room_off,
+                                                                   long long n_room_xy, const double* __restrict__ wdo_xy,
+                                                                   const uint8_t* __restrict__ wdo_type, const int64_t* __restrict__ wdo_off,
+                                                                   long long n_wdo, int n_panos, const salve_layout_pose_t* __restrict__ recs,
+                                                                   double bx, double by, double bs, int line_width,
+                                                                   salve_layout_t* __restrict__ layouts, int32_t* __restrict__ poly_xy, int poly_cap,
+                                                                   int32_t* __restrict__ segs, int seg_cap, int32_t* __restrict__ status) {
+    const int img = blockIdx.x, tid = threadIdx.x;
+    const salve_layout_pose_t rec = recs[img];
+    bool bad = rec.pano < 0 || rec.pano >= n_panos || rec.poly_off < 0 || rec.seg_off < 0 || rec.poly_off > poly_cap || rec.seg_off > seg_cap;
+    long long v0 = 0, nv = 0, w0 = 0, nw = 0;
+    if (!bad) {
+        v0 = room_off[rec.pano]; nv = room_off[rec.pano + 1] - v0;
+        w0 = wdo_off[rec.pano];  nw = wdo_off[rec.pano + 1] - w0;
+        bad = v0 < 0 || nv < 0 || v0 + nv > n_room_xy || w0 < 0 || nw < 0 || w0 + nw > n_wdo ||
+              nv > (long long)poly_cap - rec.poly_off || nw > (long long)seg_cap - rec.seg_off;
+    }
+    if (bad) { nv = 0; nw = 0; }   // (uniform over the workgroup: every thread read the same record)
+    const PoseXf f = {(double)rec.R[0], (double)rec.R[1], (double)rec.R[2], (double)rec.R[3], (double)rec.t[0], (double)rec.t[1], rec.s, bx, by, bs};
+    int far = 0;
+    for (long long k = tid; k < nv; k += POSE_THREADS) {                 // room vertices
+        int2 p;
+        far |= !pose_point(f, room_xy[2 * (v0 + k)], room_xy[2 * (v0 + k) + 1], p);
+        *reinterpret_cast<int2*>(poly_xy + 2 * ((long long)rec.poly_off + k)) = p;
+    }
+    for (long long k = tid; k < 2 * nw; k += POSE_THREADS) {             // W/D/O end points: segment k / 2, end k & 1
+        const long long sg = k >> 1;
+        const int e = (int)(k & 1);
+        int2 p;
+        far |= !pose_point(f, wdo_xy[4 * (w0 + sg) + 2 * e], wdo_xy[4 * (w0 + sg) + 2 * e + 1], p);
+        int32_t* q = segs + 8 * ((long long)rec.seg_off + sg);
+        *reinterpret_cast<int2*>(q + 2 * e) = p;
+        // x1, y1, x2, y2, colour 0x00BBGGRR (windows red, doors green, openings blue), thickness, 0, 0
+        const unsigned ty = wdo_type[w0 + sg];
+        *reinterpret_cast<int2*>(q + 4 + 2 * e) = e ? make_int2(0, 0) : make_int2(ty < 3u ? (int)(0xffu << (8u * ty)) : 0, line_width);
+        far |= ty >= 3u;
+    }
+    const int any_far = __syncthreads_or(far);
+    if (tid == 0) {
+        const bool empty = bad || any_far;
+        layouts[img] = salve_layout_t{empty ? 0 : (int32_t)nv, bad ? 0 : rec.poly_off, empty ? 0 : (int32_t)nw, bad ? 0 : rec.seg_off};
+        if (empty && status) atomicOr(status, SALVE_STATUS_BAD_LAYOUT);
+    }
+}
+
+}  // namespace
+
+extern "C" int salve_layout_pose(const double* room_xy, const int64_t* room_off, int64_t n_room_xy, const double* wdo_xy, const uint8_t* wdo_type,
+                                 const int64_t* wdo_off, int64_t n_wdo, int32_t n_panos, const salve_layout_pose_t* recs, int32_t n,
+                                 double bev_tx, double bev_ty, double bev_scale, int32_t line_width, salve_layout_t* layouts, int32_t* poly_xy,
+                                 int32_t poly_cap, int32_t* segs, int32_t seg_cap, int32_t* status, void* stream) {
+    const auto finite = [](double v) { return v - v == 0.0; };   // false for NaN and the infinities
+    const uintptr_t align = (uintptr_t)room_xy | (uintptr_t)room_off | (uintptr_t)wdo_xy | (uintptr_t)wdo_off | (uintptr_t)recs | (uintptr_t)poly_xy |
+                            (uintptr_t)segs | (uintptr_t)layouts;
+    if (!room_xy || !room_off || !wdo_xy || !wdo_type || !wdo_off || !recs || !layouts || !poly_xy || !segs || (align & 7) || n < 0 || n > 65535 ||
+        n_panos <= 0 || n_room_xy < 0 || n_wdo < 0 || poly_cap <= 0 || seg_cap <= 0 || !finite(bev_tx) || !finite(bev_ty) || !finite(bev_scale)) {
+        salve_fail("salve_layout_pose: null or misaligned pointer, n outside 0..65535, no panorama, non-positive capacity or non-finite BEV parameter");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (n == 0) return SALVE_OK;
+    hipLaunchKernelGGL(layout_pose_kernel, dim3((unsigned)n), dim3(POSE_THREADS), 0, (hipStream_t)stream, room_xy, room_off, (long long)n_room_xy,
+                       wdo_xy, wdo_type, wdo_off, (long long)n_wdo, (int)n_panos, recs, bev_tx, bev_ty, bev_scale, (int)line_width, layouts, poly_xy,
+                       (int)poly_cap, segs, (int)seg_cap, status);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}

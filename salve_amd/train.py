@@ -10,6 +10,7 @@ convolutions, fp32 master weights, gradients and checkpoint); the default fp32 i
 BatchNorm with fused ReLU and residual add (same checkpoint); the default is torch's BatchNorm.  See salve_amd/training.py.
 --render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
 val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
+A configuration whose modalities include "layout" also needs DIR/layouts.npz: the layouts are posed and drawn on the GPU.
 --identity batch renders the identity images of a batch's second panoramas with the batch instead of keeping one per panorama;
 --resident-panos N (which selects --identity batch) memory-maps the two .npy files and keeps a pool of N panoramas on the device,
 uploaded as the batches need them: for panorama sets that do not fit in device memory.  N must be at least 2 x batch_size.
@@ -72,12 +73,13 @@ def main(argv=None) -> None:
         from salve_amd import train_render
 
         rgb, depth, examples = train_render.load_render_dir(a.render_from, mmap=a.resident_panos is not None)
+        layouts = train_render.load_render_layouts(a.render_from, len(rgb)) if "layout" in set(args.modalities) else None
         sources = {}
         for split in ("train", "val"):
             src = train_render.RenderedTrainSource(torch.device("cuda", torch.cuda.current_device()), args.modalities, pano_hw=rgb.shape[1:3],
                                                    batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
                                                    resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
-                                                   identity=identity, resident_panos=a.resident_panos)
+                                                   identity=identity, resident_panos=a.resident_panos, layouts=layouts)
             if split == "train":
                 src.load_panos(rgb, depth)
             else:   # the panoramas (or their pool) and their identity renders are on the device once

@@ -8,6 +8,11 @@ batches from the lossless BEV images instead: per batch one scatter + densify la
 (the identity renders of every panorama are made once and kept, as in salve_amd.pipeline) and ONE salve_bev_train_tiles launch
 that writes `[B, crop, crop, Cp]` in the training precision -- what `TrainableEarlyFusionCEResnet.forward_packed` takes.
 
+The layout modality (`layouts=PanoLayouts`) rides along: the panoramas' rooms and W/D/Os stay on the device as flat tables, a batch's
+record table goes up with its one upload, ONE salve_layout_pose launch poses the batch's layouts and ONE salve_layout_rasterise launch
+draws them into the image arrays the tile jobs index, behind the texture renders; the train-tile launch then takes one more image per
+sample.  Layout alone renders no texture map and uploads no panorama.
+
 Two opt-in arguments take the feed beyond panorama sets that fit the device.  `identity="batch"` keeps no identity image per
 panorama: the identity renders of the batch's distinct second panoramas ride in the batch's own scatter / densify launch pair, behind
 the posed renders.  `resident_panos=N` keeps a pool of N panorama slots on the device: `PanoCache` plans, batch by batch, which
@@ -35,6 +40,7 @@ from salve_amd.synthetic import HypothesisTable
 from salve_amd.transforms import TrainTransform
 
 MAX_RENDERS_PER_CALL = 65535   # include/salve_hip.h: renders per scatter / densify call
+MAX_LAYOUTS_PER_LAUNCH = 65535  # include/salve_hip.h: images per salve_layout_pose / salve_layout_rasterise call
 SPLITS = ("train", "val")
 
 
@@ -60,9 +66,10 @@ def batches_per_epoch(n: int, batch: int, split: str) -> int:
     return n // batch if split == "train" else (n + batch - 1) // batch
 
 
-def check_launch(batch_size: int, n_surfaces: int, identity_rows: int = 0) -> None:
+def check_launch(batch_size: int, n_surfaces: int, identity_rows: int = 0, layout: bool = False) -> None:
     """A batch's posed renders -- and, with identity="batch", the identity renders of up to `identity_rows` distinct second panoramas
-    behind them -- go through ONE scatter / densify call."""
+    behind them -- go through ONE scatter / densify call; with `layout`, its layout images (one per sample and identity panorama) go
+    through ONE pose / rasterise call of the same limit."""
     if batch_size <= 0:
         raise ValueError(f"batch size must be positive, got {batch_size}")
     if identity_rows < 0:
@@ -71,12 +78,17 @@ def check_launch(batch_size: int, n_surfaces: int, identity_rows: int = 0) -> No
     if n > MAX_RENDERS_PER_CALL:
         what = f"batch_size {batch_size}" if identity_rows == 0 else f"(batch_size {batch_size} + {identity_rows} identity panoramas)"
         raise RuntimeError(f"{what} x {n_surfaces} surfaces = {n} renders per batch; the library takes at most {MAX_RENDERS_PER_CALL} per call")
+    if layout and batch_size + identity_rows > MAX_LAYOUTS_PER_LAUNCH:
+        raise RuntimeError(f"batch_size {batch_size} + {identity_rows} identity panoramas = {batch_size + identity_rows} layout images per batch; "
+                           f"the library takes at most {MAX_LAYOUTS_PER_LAUNCH} per call")
 
 
-def train_surfaces(modalities: Sequence[str]) -> List[str]:
-    if "layout" in set(modalities):
-        raise RuntimeError('RenderedTrainSource does not render the "layout" modality (floor, ceiling, ceiling + floor only): train it from '
-                           "the rendered dataset on disk")
+def train_surfaces(modalities: Sequence[str], with_layouts: bool = False) -> List[str]:
+    """The texture surfaces of a configuration's modalities.  "layout" is served only when the panoramas' layouts are given
+    (`RenderedTrainSource(layouts=...)`): alone (no surface) or behind ceiling + floor."""
+    if "layout" in set(modalities) and not with_layouts:
+        raise RuntimeError('RenderedTrainSource does not render the "layout" modality (floor, ceiling, ceiling + floor only) without the '
+                           "panoramas' layouts (layouts=PanoLayouts; --render-from: layouts.npz): train it from the rendered dataset on disk")
     return surfaces_for(modalities)
 
 
@@ -179,6 +191,8 @@ class RenderedTrainSource:
     One epoch per iteration; `len()` = batches per epoch.  Everything runs on the current stream.  The device status word is checked
     once per epoch, after the last batch (a bad render row, tile job or pool slot raises there).
 
+    layouts: salve_amd.layout.PanoLayouts of the same panoramas -- required iff the modalities include "layout" (["layout"] alone: no
+    texture map is rendered and no panorama uploaded; ceiling + floor + layout: 18 channels, the layout pair behind the texture maps).
     identity: "kept" (default) renders the identity image of every panorama once and keeps it; "batch" renders the identity images of
     the batch's distinct second panoramas with the batch -- the same images, no P x S image array.  resident_panos: None (default)
     uploads every panorama up front; an integer keeps a pool of that many panorama slots on the device, filled on first use from the
@@ -186,7 +200,7 @@ class RenderedTrainSource:
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
-                 crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None) -> None:
+                 crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None) -> None:
         if split not in SPLITS:
             raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
         if precision not in ("fp32", "bf16"):
@@ -198,13 +212,16 @@ class RenderedTrainSource:
                 raise ValueError('resident_panos needs identity="batch": keeping an identity image per panorama is what does not fit')
             if int(resident_panos) <= 0:
                 raise ValueError(f"resident_panos must be positive, got {resident_panos}")
-        self.surfaces = train_surfaces(modalities)
-        check_launch(batch_size, len(self.surfaces), batch_size if identity == "batch" else 0)
+        self.surfaces = train_surfaces(modalities, with_layouts=layouts is not None)
+        self.has_layout = "layout" in set(modalities)
+        self.layouts = layouts if self.has_layout else None   # salve_amd.layout.PanoLayouts, indexed by panorama
+        self.per_sample = len(self.surfaces) + (1 if self.has_layout else 0)   # images per sample and array: texture maps, then the layout
+        check_launch(batch_size, len(self.surfaces), batch_size if identity == "batch" else 0, layout=self.has_layout)
         self.tf = TrainTransform(resize_hw, crop_hw)   # the draws (and the square / no-padding refusals); its kernels are not used
         self.split, self.batch_size = split, int(batch_size)
         self.identity, self.resident_panos = identity, None if resident_panos is None else int(resident_panos)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
-        self.out_c = (6 * len(self.surfaces) + 7) // 8 * 8
+        self.out_c = (6 * self.per_sample + 7) // 8 * 8
         self.gen = torch.Generator()
         self.gen.manual_seed(seed)
         self.device = torch.device(device)
@@ -212,6 +229,8 @@ class RenderedTrainSource:
         status.check(self.device, "a launch issued before this RenderedTrainSource was created")
         self.ras = BevRasteriser(self.device, pano_hw=pano_hw, resize=self.tf.resize, crop=self.tf.crop)
         self.pano_rgb = self.pano_depth = self.ref_bev = self.bev = None
+        self.lay = None           # layout.DeviceLayouts: the resident tables and one batch's output tables
+        self.lay_base = (0, 0)    # first layout image inside self.bev / self.ref_bev: they lie behind the texture renders
         self.n_panos: Optional[int] = None
         self.examples: Optional[Dict[str, np.ndarray]] = None
         self.pool: Optional[Dict] = None   # resident_panos: host arrays, PanoCache, pinned staging buffers -- shared by share_panos
@@ -229,9 +248,43 @@ class RenderedTrainSource:
         """Images of one batch's buffer: the posed renders, and with identity="batch" the identity renders behind them."""
         return (self.batch_size + (min(self.batch_size, n_slots) if self.identity == "batch" else 0)) * len(self.surfaces)
 
+    def _layout_images(self, n_slots: int) -> int:
+        """Layout images of one batch's buffer: one per sample, and with identity="batch" one per distinct second panorama."""
+        return (self.batch_size + (min(self.batch_size, n_slots) if self.identity == "batch" else 0)) if self.has_layout else 0
+
+    def layout_bases(self, P: int, n_slots: int) -> Tuple[int, int]:
+        """First layout image inside (the batch's array, the kept identity array): behind the texture renders of each."""
+        S = len(self.surfaces)
+        return (self._batch_images(n_slots) if self.identity == "batch" else self.batch_size * S), P * S
+
+    def _alloc_images(self, P: int, n_slots: int) -> None:
+        """self.bev (one batch: texture renders | layout images) and, identity="kept", self.ref_bev (P x S identity renders | P identity
+        layout images, drawn here once); the layout tables go to the device."""
+        S = len(self.surfaces)
+        Hb, Wb = self.ras.bev_hw
+        self.lay_base = self.layout_bases(P, n_slots)
+        self.bev = torch.empty((self.lay_base[0] + self._layout_images(n_slots), Hb, Wb), dtype=torch.int32, device=self.device)
+        self.ref_bev = torch.empty((P * self.per_sample, Hb, Wb), dtype=torch.int32, device=self.device) if self.identity == "kept" else None
+        if not self.has_layout:
+            return
+        from salve_amd import layout as layout_mod
+
+        if self.layouts.P != P:
+            raise RuntimeError(f"the layout tables hold {self.layouts.P} panoramas, {P} panoramas are loaded")
+        self.lay = layout_mod.DeviceLayouts(self.layouts, self.device, max(1, self._layout_images(n_slots)))
+        if self.identity == "kept":
+            with tracing.range("salve.identity_layouts"):
+                for lo in range(0, P, self.lay.n_max):
+                    ids = np.arange(lo, min(lo + self.lay.n_max, P))
+                    self.lay.draw(layout_mod.pose_records(self.layouts, ids), self.ref_bev[P * S + lo:])
+
     def load_panos(self, rgb: np.ndarray, depth: np.ndarray) -> None:
         """P panoramas (uint8 [P, H, W, 3], uint16 [P, H, W]).  Default: upload them all (and, identity="kept", render their identity
-        BEV images).  resident_panos: keep the host arrays (np.memmap included) and upload nothing -- slots fill on first use."""
+        BEV images).  resident_panos: keep the host arrays (np.memmap included) and upload nothing -- slots fill on first use.
+        Layout alone: only P is taken from the arrays, nothing is uploaded."""
+        if not self.surfaces:
+            self._set_no_panos(int(rgb.shape[0]))
+            return
         if self.resident_panos is None:
             self._refuse_if_too_large(int(rgb.nbytes) + int(depth.nbytes), f"{len(rgb)} panoramas")
             self.set_panos(*self.ras.upload_panos(rgb, depth))
@@ -248,7 +301,7 @@ class RenderedTrainSource:
             raise RuntimeError(str(e)) from None
         n_slots, n_stage = cache.capacity, min(2 * self.batch_size, cache.capacity)
         index_bytes = self.ras.pano_index_bytes(n_slots)
-        self._refuse_if_too_large((n_slots + n_stage) * H * W * 5 + index_bytes + self._batch_images(n_slots) * Hb * Wb * 4,
+        self._refuse_if_too_large((n_slots + n_stage) * H * W * 5 + index_bytes + (self._batch_images(n_slots) + self._layout_images(n_slots)) * Hb * Wb * 4,
                                   f"a pool of {n_slots} panorama slots, its index, one batch's uploads and one batch's BEV images")
         # zero depth passes neither surface's z filter: an unfilled slot's index entries are empty boxes
         self.pano_rgb = torch.zeros((n_slots, H, W, 3), dtype=torch.uint8, device=self.device)
@@ -258,13 +311,24 @@ class RenderedTrainSource:
         stage = [{"rgb": torch.empty((n_stage, H, W, 3), dtype=torch.uint8).pin_memory(), "depth": torch.empty((n_stage, H, W), dtype=torch.int16).pin_memory(),
                   "event": None} for _ in range(2)]
         self.pool = {"rgb": rgb, "depth": depth, "cache": cache, "stage": stage, "turn": 0, "uploads": 0}
-        self.n_panos, self.examples, self.ref_bev = P, None, None
-        self.bev = torch.empty((self._batch_images(n_slots), Hb, Wb), dtype=torch.int32, device=self.device)
+        self.n_panos, self.examples = P, None
+        self._alloc_images(P, n_slots)
         self.ras._workspace(self._batch_images(n_slots))
+
+    def _set_no_panos(self, P: int) -> None:
+        """Layout alone: P panoramas are known by their layouts only; no texture map is rendered, so none is uploaded and a resident
+        pool has nothing to hold."""
+        Hb, Wb = self.ras.bev_hw
+        self._refuse_if_too_large((self._layout_images(P) + (P if self.identity == "kept" else 0)) * Hb * Wb * 4, "the layout images")
+        self.n_panos, self.examples = P, None
+        self._alloc_images(P, P)
 
     def set_panos(self, rgb_dev: torch.Tensor, depth_dev: torch.Tensor) -> None:
         """Panoramas on the device (as RenderVerifyPipeline.set_panos takes them).  identity="kept": the identity render of every
         panorama and surface is made once and kept; identity="batch": nothing is rendered here."""
+        if not self.surfaces:
+            self._set_no_panos(int(rgb_dev.shape[0]))
+            return
         if self.resident_panos is not None:
             raise RuntimeError("resident_panos takes the panoramas as host arrays: load_panos(rgb, depth)")
         if tuple(rgb_dev.shape[1:3]) != tuple(self.ras.pano_hw) or tuple(depth_dev.shape[1:]) != tuple(self.ras.pano_hw):
@@ -272,24 +336,23 @@ class RenderedTrainSource:
         P, S = int(rgb_dev.shape[0]), len(self.surfaces)
         Hb, Wb = self.ras.bev_hw
         if self.identity == "batch":
-            self._refuse_if_too_large(self._batch_images(P) * Hb * Wb * 4, "the BEV images of one batch")
+            self._refuse_if_too_large((self._batch_images(P) + self._layout_images(P)) * Hb * Wb * 4, "the BEV images of one batch")
             self.pano_rgb, self.pano_depth = rgb_dev.contiguous(), depth_dev.contiguous()
-            self.n_panos, self.examples, self.ref_bev = P, None, None
-            self.bev = torch.empty((self._batch_images(P), Hb, Wb), dtype=torch.int32, device=self.device)   # posed | identity renders of one batch
+            self.n_panos, self.examples = P, None
+            self._alloc_images(P, P)   # posed | identity renders of one batch (| its layout images)
             self.ras._workspace(self._batch_images(P))
             return
-        self._refuse_if_too_large((P + self.batch_size) * S * Hb * Wb * 4, f"the BEV images of {P} panoramas and one batch")
+        self._refuse_if_too_large((P + self.batch_size) * self.per_sample * Hb * Wb * 4, f"the BEV images of {P} panoramas and one batch")
         self.pano_rgb, self.pano_depth = rgb_dev.contiguous(), depth_dev.contiguous()
         self.n_panos, self.examples = P, None
         rows = pack_hypotheses(np.repeat(np.arange(P), S), np.tile([SURFACES[s] for s in self.surfaces], P),
                                np.tile(np.eye(2, dtype=np.float32), (P * S, 1, 1)), np.zeros((P * S, 2), np.float32), np.zeros(P * S))
         rows_dev = self.ras.upload_hypotheses(rows)
-        self.ref_bev = torch.empty((P * S, Hb, Wb), dtype=torch.int32, device=self.device)
+        self._alloc_images(P, P)   # one batch's posed renders; the identity renders of every panorama
         with tracing.range("salve.identity_renders"):
             for lo in range(0, P * S, 256):
                 n = min(256, P * S - lo)
                 self.ras.render(self.pano_rgb, self.pano_depth, rows_dev[lo * _lib.HYP_DTYPE.itemsize:], n, self.ref_bev[lo:lo + n])
-        self.bev = torch.empty((self.batch_size * S, Hb, Wb), dtype=torch.int32, device=self.device)   # one batch's posed renders
 
     def share_panos(self, other: "RenderedTrainSource") -> None:
         """Use the panoramas, identity renders and batch buffer `other` holds (the val source beside the train source: one copy on
@@ -297,14 +360,15 @@ class RenderedTrainSource:
         shared too: whichever source is iterating plans with its own epoch's next uses."""
         if other.n_panos is None:
             raise RuntimeError("the other source has no panoramas yet")
-        if (other.device, other.surfaces, other.ras.pano_hw, other.ras.bev_hw) != (self.device, self.surfaces, self.ras.pano_hw, self.ras.bev_hw) \
+        if (other.device, other.surfaces, other.has_layout, other.ras.pano_hw, other.ras.bev_hw) != \
+                (self.device, self.surfaces, self.has_layout, self.ras.pano_hw, self.ras.bev_hw) \
                 or other.batch_size < self.batch_size:
             raise RuntimeError("share_panos needs the same device, modalities and panorama size, and a batch size not above the other's")
         if (other.identity, other.resident_panos) != (self.identity, self.resident_panos):
             raise RuntimeError("share_panos needs the same identity and resident_panos arguments on both sources")
         self.pano_rgb, self.pano_depth, self.ref_bev, self.bev, self.n_panos, self.examples = (other.pano_rgb, other.pano_depth, other.ref_bev,
                                                                                                other.bev, other.n_panos, None)
-        self.pool = other.pool
+        self.pool, self.lay, self.lay_base, self.layouts = other.pool, other.lay, other.lay_base, other.layouts
 
     @property
     def cache(self) -> Optional[PanoCache]:
@@ -372,12 +436,59 @@ class RenderedTrainSource:
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Render examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  `next_use` (resident pool
         only): the batch of every panorama's next use, for the planner (`epoch_next_use`)."""
-        ex, S, B = self.examples, len(self.surfaces), len(idx)
+        B, S, K = len(idx), len(self.surfaces), self.per_sample
+        jobs, aug, rows, lay_recs, n = self.batch_tables(idx, draws, next_use)
+        bev_b = self.ref_bev if self.identity == "kept" else self.bev
+        # ONE upload per batch; every table starts on a multiple of 16 bytes (the 40-byte render rows come last)
+        # (the 48-byte layout records hold a double: every table in front of them is a multiple of 8 bytes long)
+        parts = [jobs.view(np.uint8).reshape(-1), aug.view(np.uint8), self.examples["is_match"][idx].view(np.uint8), rows.view(np.uint8),
+                 lay_recs.view(np.uint8)]
+        buf = torch.from_numpy(np.concatenate(parts)).to(self.device)
+        o = np.cumsum([0] + [p.nbytes for p in parts])
+        jobs_a, jobs_b = buf[:o[1] // 2], buf[o[1] // 2:o[1]]
+        labels = buf[o[2]:o[3]].view(torch.int64).view(B, 1)
+        if S:   # (layout alone: no texture map, as RenderVerifyPipeline)
+            e1 = self._timed("scatter")
+            with tracing.range("salve.scatter"):
+                self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:o[4]], n, self.bev)
+            if e1 is not None:
+                e1.record()
+            e1 = self._timed("densify")
+            with tracing.range("salve.densify"):
+                self.ras.densify(n, self.bev)
+            if e1 is not None:
+                e1.record()
+        if self.has_layout:
+            e1 = self._timed("layout pose")
+            with tracing.range("salve.layout_pose"):
+                self.lay.pose(buf[o[4]:], len(lay_recs))
+            if e1 is not None:
+                e1.record()
+            e1 = self._timed("layout rasterise")
+            with tracing.range("salve.layout_rasterise"):
+                self.lay.rasterise(len(lay_recs), self.bev[self.lay_base[0]:])
+            if e1 is not None:
+                e1.record()
+        out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
+        e1 = self._timed("tiles")
+        with tracing.range("salve.train_tiles"):
+            self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, K, buf[o[1]:o[2]], B, out)   # (identity="batch": one buffer, only read)
+        if e1 is not None:
+            e1.record()
+        return out, labels
+
+    def batch_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None):
+        """The host tables of one batch: (tile jobs [2][B][K], draws [B], render rows, layout pose records, renders).  Host arithmetic,
+        except that a resident pool uploads its misses here (`_make_resident`)."""
+        ex, S, B, K = self.examples, len(self.surfaces), len(idx), self.per_sample
         Hb, Wb = self.ras.bev_hw
         i1 = ex["i1"][idx]
         surf = [SURFACES[s] for s in self.surfaces]
         si = np.tile(np.arange(S, dtype=np.int64), B)
-        jobs = np.zeros((2, B * S), dtype=_lib.TILE_JOB_DTYPE)   # sample-major [B][S]: posed renders of this batch | identity renders
+        # sample-major [B][K]: posed renders of this batch | identity renders; a sample's layout image (K = S + 1) is its last job
+        jobs = np.zeros((2, B, K), dtype=_lib.TILE_JOB_DTYPE)
+        tex = lambda v: np.asarray(v).reshape(B, S)
+        lay_recs = np.zeros(0, dtype=_lib.LAYOUT_POSE_DTYPE)
         if self.identity == "kept":
             # renders in the order of their panorama (as RenderVerifyPipeline.prepare issues them: the workgroups of one panorama run
             # side by side and share its depth blocks through the L2s); the tile jobs name each sample's render by its rank
@@ -387,9 +498,13 @@ class RenderedTrainSource:
             src = idx[order]
             rows = pack_hypotheses(np.repeat(ex["i1"][src], S), np.tile(surf, B), np.repeat(ex["R"][src], S, axis=0),
                                    np.repeat(ex["t"][src], S, axis=0), np.ones(B * S))
-            n, bev_b = B * S, self.ref_bev
-            jobs["bev_offset"][0] = (np.repeat(rank, S) * S + si) * (Hb * Wb)
-            jobs["bev_offset"][1] = (np.repeat(ex["i2"][idx], S) * S + si) * (Hb * Wb)
+            n = B * S
+            jobs["bev_offset"][0, :, :S] = tex((np.repeat(rank, S) * S + si) * (Hb * Wb))
+            jobs["bev_offset"][1, :, :S] = tex((np.repeat(ex["i2"][idx], S) * S + si) * (Hb * Wb))
+            if self.has_layout:   # sample k's posed layout is image k of the batch's; panorama i2's own layout was drawn when the layouts were loaded
+                lay_recs = self._layout_records(i1, ex["R"][idx], ex["t"][idx], 0)
+                jobs["bev_offset"][0, :, S] = (self.lay_base[0] + np.arange(B)) * (Hb * Wb)
+                jobs["bev_offset"][1, :, S] = (self.lay_base[1] + ex["i2"][idx]) * (Hb * Wb)
         else:
             # B posed renders and the identity renders of the U distinct second panoramas, ONE launch pair; a group of S renders per
             # entry, the groups in the order of their panorama's slot (the pool's slot, or the panorama itself when all are resident)
@@ -404,41 +519,30 @@ class RenderedTrainSource:
             t = np.concatenate([ex["t"][idx], np.zeros((U, 2), np.float32)])[order]
             posed = (np.arange(B + U) < B).astype(np.int32)[order]
             rows = pack_hypotheses(np.repeat(where[order], S), np.tile(surf, B + U), np.repeat(R, S, axis=0), np.repeat(t, S, axis=0), np.repeat(posed, S))
-            n, bev_b = (B + U) * S, self.bev
-            jobs["bev_offset"][0] = (np.repeat(rank[:B], S) * S + si) * (Hb * Wb)
-            jobs["bev_offset"][1] = (np.repeat(rank[B + inv], S) * S + si) * (Hb * Wb)
-        check_launch(B, S, n // S - B)
-        smp = np.repeat(np.arange(B, dtype=np.int64), S)
-        swap = np.repeat(ex["swap"][idx], S)
-        jobs["slot"][:] = smp
-        jobs["chan"][0] = 6 * si + 3 * swap
-        jobs["chan"][1] = 6 * si + 3 * (1 - swap)
+            n = (B + U) * S
+            jobs["bev_offset"][0, :, :S] = tex((np.repeat(rank[:B], S) * S + si) * (Hb * Wb))
+            jobs["bev_offset"][1, :, :S] = tex((np.repeat(rank[B + inv], S) * S + si) * (Hb * Wb))
+            if self.has_layout:   # B posed layouts and the U distinct identity layouts behind them, ONE pose and ONE rasterise launch
+                lay_recs = self._layout_records(np.concatenate([i1, uniq]), ex["R"][idx], ex["t"][idx], U)
+                jobs["bev_offset"][0, :, S] = (self.lay_base[0] + np.arange(B)) * (Hb * Wb)
+                jobs["bev_offset"][1, :, S] = (self.lay_base[0] + B + inv) * (Hb * Wb)
+        check_launch(B, S, (n // S - B) if S else (len(lay_recs) - B), layout=self.has_layout)
+        swap = ex["swap"][idx]
+        jobs["slot"][:] = np.arange(B, dtype=np.int64)[None, :, None]
+        jobs["chan"][0] = 6 * np.arange(K)[None, :] + 3 * swap[:, None]   # the layout pair follows the texture maps (zind_data.py:26)
+        jobs["chan"][1] = 6 * np.arange(K)[None, :] + 3 * (1 - swap)[:, None]
         aug = np.zeros(B, dtype=_lib.TILE_AUG_DTYPE)
         for k, (cy, cx, hflip, vflip) in enumerate(draws):
             aug[k] = (cy, cx, (_lib.TILE_HFLIP if hflip else 0) | (_lib.TILE_VFLIP if vflip else 0), 0)
-        # ONE upload per batch; every table starts on a multiple of 16 bytes (the 40-byte render rows come last)
-        parts = [jobs.view(np.uint8).reshape(-1), aug.view(np.uint8), ex["is_match"][idx].view(np.uint8), rows.view(np.uint8)]
-        buf = torch.from_numpy(np.concatenate(parts)).to(self.device)
-        o = np.cumsum([0] + [p.nbytes for p in parts])
-        jobs_a, jobs_b = buf[:o[1] // 2], buf[o[1] // 2:o[1]]
-        labels = buf[o[2]:o[3]].view(torch.int64).view(B, 1)
-        e1 = self._timed("scatter")
-        with tracing.range("salve.scatter"):
-            self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:], n, self.bev)
-        if e1 is not None:
-            e1.record()
-        e1 = self._timed("densify")
-        with tracing.range("salve.densify"):
-            self.ras.densify(n, self.bev)
-        if e1 is not None:
-            e1.record()
-        out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
-        e1 = self._timed("tiles")
-        with tracing.range("salve.train_tiles"):
-            self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, S, buf[o[1]:o[2]], B, out)   # (identity="batch": one buffer, only read)
-        if e1 is not None:
-            e1.record()
-        return out, labels
+        return jobs, aug, rows, lay_recs, n
+
+    def _layout_records(self, pano: np.ndarray, R: np.ndarray, t: np.ndarray, n_identity: int) -> np.ndarray:
+        """salve_layout_pose_t rows of a batch: its posed layouts under (R, t) (alignment hypotheses are SE(2): scale 1), then
+        `n_identity` panoramas' own layouts -- indexed by PANORAMA, not by pool slot: the layout tables are fully resident."""
+        from salve_amd import layout as layout_mod
+
+        return layout_mod.pose_records(self.layouts, pano, np.concatenate([R, np.zeros((n_identity, 2, 2), np.float32)]),
+                                       np.concatenate([t, np.zeros((n_identity, 2), np.float32)]), None, np.arange(len(pano)) < len(R))
 
     def draws(self, n: int) -> List[Tuple[int, int, bool, bool]]:
         """train: `TrainTransform.draw()` per example, from Python's `random`; val: the centre crop, no flips (ValTestTransform)."""
@@ -470,6 +574,7 @@ class RenderedTrainSource:
 
 # ---------------------------------------------------------------------------------------------------- --render-from DIR
 RENDER_DIR_FILES = ("panos_rgb.npy", "panos_depth.npy", "train.json", "val.json")
+LAYOUTS_FILE = "layouts.npz"   # the optional fifth file: read only when the configuration's modalities include "layout"
 
 
 def load_example_json(path: Path) -> Tuple[HypothesisTable, np.ndarray]:
@@ -501,3 +606,21 @@ def load_render_dir(path: str, mmap: bool = False):
         raise SystemExit(f"--render-from {root}: panos_rgb.npy must be uint8 [P, H, W, 3] and panos_depth.npy uint16 [P, H, W], got "
                          f"{rgb.dtype} {rgb.shape} / {depth.dtype} {depth.shape}")
     return rgb, depth, {split: load_example_json(root / f"{split}.json") for split in SPLITS}
+
+
+def load_render_layouts(path: str, n_panos: int):
+    """The `layout.PanoLayouts` of a --render-from directory's optional fifth file, layouts.npz (format: INTEGRATION.md), for
+    configurations whose modalities include "layout".  A missing or malformed file, or tables for another number of panoramas than
+    the panorama arrays hold, ends the program with one line."""
+    from salve_amd.layout import PanoLayouts
+
+    root = Path(path)
+    if not (root / LAYOUTS_FILE).is_file():
+        raise SystemExit(f'--render-from {root}: {LAYOUTS_FILE} is missing (the "layout" modality needs it beside {", ".join(RENDER_DIR_FILES)})')
+    try:
+        layouts = PanoLayouts.load(root / LAYOUTS_FILE)
+    except Exception as e:   # (a truncated or foreign file raises whatever numpy's reader raises)
+        raise SystemExit(f"--render-from {root}: {LAYOUTS_FILE}: {e}") from None
+    if layouts.P != n_panos:
+        raise SystemExit(f"--render-from {root}: {LAYOUTS_FILE} holds the layouts of {layouts.P} panoramas, panos_rgb.npy holds {n_panos}")
+    return layouts

@@ -9,7 +9,7 @@
     examples written once as JPEGs into a temporary ZindData tree (outside the timed region) and fed by `training.get_dataloader`.
 
     python tools/measure/bench_train_feed.py [--configs 152:2,50:1] [--batch 256] [--modes bf16:hip,fp32:torch] [--steps 5] [--warmup 2]
-                                             [--panos 64] [--disk 0] [--identity {kept,batch}] [--resident-panos N]
+                                             [--panos 64] [--disk 0] [--identity {kept,batch}] [--resident-panos N] [--layout]
 
 --identity batch and / or --resident-panos N switch to the comparison of the feed's modes instead: rows (a) identity
 "kept", everything resident (the default source: the yardstick), (b) identity "batch", everything resident, and with --resident-panos
@@ -17,6 +17,11 @@
 index update beside scatter, densify, tiles), the host-to-device rate reached, the uploads per batch the planner makes (furthest next
 use) beside what LRU would make on the same epochs, and the step fed by each row beside the step on a resident batch.  --panos P must
 then be at least 4 x batch (so that a half-size pool misses); the P scenes are distinct (a few rooms, each turned by its own angle).
+
+--layout switches to the layout modality with synthetic layouts (salve_amd/synthetic_layouts.py): per batch the HIP
+events of the pose / rasterise / tile launches, the source alone, and the fed step beside the resident step for ResNet-50 on layout
+alone (6 channels) and ResNet-152 on ceiling + floor + layout (18 channels), bf16 + hip norm -- and, as the yardstick of posing on the
+device, the SAME batch posed by the existing host path (`pack_layouts` of 2 x batch specs, its upload included).
 
 Synthetic 1024 x 512 panoramas (as bench.py).  Medians; run the command twice for the spread.  Per-kernel times: a run of its own under
 `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train_feed.py ...`.
@@ -289,6 +294,93 @@ def cache_rows(a, dev) -> None:
             torch.cuda.empty_cache()
 
 
+def layout_rows(a, dev) -> None:
+    """The layout modality of the feed (see the module docstring)."""
+    from salve_amd import layout, synthetic_layouts
+    from salve_amd.common.sim2 import Sim2
+
+    B, n_it, P = a.batch, a.warmup + a.steps, a.panos
+    layouts = synthetic_layouts.make_layouts(P, seed=0)
+    panos = synthetic.make_panos(P)
+    rgb, depth = np.stack([p[0] for p in panos]), np.stack([p[1] for p in panos])
+    hyp = synthetic.make_hypotheses(B * 3 * n_it, P)
+    labels = np.arange(len(hyp), dtype=np.int64) % 2
+    print(f"# {torch.cuda.get_device_name(dev)}; batch {B}, {P} synthetic panoramas with synthetic layouts ({int(layouts.room_count.sum())} room vertices, "
+          f"{int(layouts.wdo_count.sum())} W/D/Os), median of {a.steps} after {a.warmup} warm-up; step = forward + backward + Adam, bf16 + hip norm; "
+          "variants alternate step by step", flush=True)
+
+    # ---- posing one batch: the existing host path against the device path, the same B posed + B identity layouts
+    gen = torch.Generator().manual_seed(0)
+    plan = train_render.plan_epoch(len(hyp), B, "train", gen)[:n_it]
+    dl = layout.DeviceLayouts(layouts, dev, 2 * B)
+    host, host_pack, dev_host, dev_event = [], [], [], []
+    for idx in plan:
+        def host_path():
+            specs = [layouts.spec(int(hyp.i1[j]), Sim2(hyp.R[j], hyp.t[j], 1.0)) for j in idx] + [layouts.spec(int(hyp.i2[j])) for j in idx]
+            t1 = time.perf_counter()
+            packed = layout.pack_layouts(specs, dev)
+            torch.cuda.synchronize()
+            host_pack.append(time.perf_counter() - t1)
+            return packed
+        host.append(wall(host_path))
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def device_path():
+            recs = layout.pose_records(layouts, np.concatenate([hyp.i1[idx], hyp.i2[idx]]), np.concatenate([hyp.R[idx], hyp.R[idx]]),
+                                       np.concatenate([hyp.t[idx], hyp.t[idx]]), None, np.arange(2 * B) < B)
+            recs_dev = torch.from_numpy(recs.view(np.uint8)).to(dev)
+            e0.record()
+            dl.pose(recs_dev, 2 * B)
+            e1.record()
+        dev_host.append(wall(device_path))
+        dev_event.append(e0.elapsed_time(e1))
+    h, hp, d, de = (med(v[a.warmup:]) * 1e3 for v in (host, host_pack, dev_host, [x / 1e3 for x in dev_event]))
+    print(f"posing 2 x {B} layouts: host path (specs + pack_layouts + upload) {h:.2f} ms per batch (pack_layouts + upload alone {hp:.2f} ms); device path "
+          f"(records + upload + salve_layout_pose, host clock) {d:.3f} ms, its launch {de * 1e3:.1f} us (HIP events); host / device = {h / d:.0f} x", flush=True)
+    del dl
+
+    for layers, mods in ((50, ["layout"]), (152, ["ceiling_rgb_texture", "floor_rgb_texture", "layout"])):
+        tag = f"resnet{layers} {6 * len(mods)}ch batch {B} bf16 norm hip"
+        src = train_render.RenderedTrainSource(dev, mods, batch_size=B, precision="bf16", split="train", seed=0, layouts=layouts)
+        src.load_panos(rgb, depth)
+        src.set_examples(hyp, labels)
+        random.seed(0)
+        it = iter(src)
+        src.timers, walls, splits = [], [], []
+        for i in range(n_it):
+            del src.timers[:]
+            box = []
+            walls.append(wall(lambda: box.append(next(it))))
+            splits.append({t: s0.elapsed_time(e0) for t, s0, e0 in src.timers})
+        src.timers = None
+        x_packed, y = box[0][0].clone(), box[0][1].squeeze().clone()
+        w = med(walls[a.warmup:]) * 1e3
+        tags = [t for t in ("scatter", "densify", "layout pose", "layout rasterise", "tiles") if t in splits[0]]
+        print(f"{tag}: source alone {w:.2f} ms per batch (host clock); events: " +
+              ", ".join(f"{t} {med([s_[t] for s_ in splits[a.warmup:]]):.3f}" for t in tags) + " ms", flush=True)
+        torch.manual_seed(0)
+        model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=mods)).to(dev).train()
+        model.set_train_precision("bf16").set_train_norm("hip")
+        model = model.to(memory_format=torch.channels_last)
+        opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+        res = {"resident": [], "fed": []}
+
+        def fed():
+            xb, yb = next(it)
+            step(model, opt, lambda: model.forward_packed(xb), yb.squeeze())
+
+        for i in range(n_it):
+            res["resident"].append(wall(lambda: step(model, opt, lambda: model.forward_packed(x_packed), y)))
+            res["fed"].append(wall(fed))
+        m = {k: med(v[a.warmup:]) * 1e3 for k, v in res.items()}
+        print(f"{tag}: step on a resident packed batch {m['resident']:.1f} ms ({B / m['resident'] * 1e3:.0f} samples/s); fed by the source {m['fed']:.1f} ms "
+              f"({B / m['fed'] * 1e3:.0f} samples/s, {100 * (m['fed'] / m['resident'] - 1):+.1f} %); source alone / resident step = {w / m['resident']:.3f}",
+              flush=True)
+        it.close()
+        del model, opt, src, x_packed
+        torch.cuda.empty_cache()
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--configs", default="152:2,50:1", help="layers:surfaces, comma separated")
@@ -300,10 +392,14 @@ def main() -> None:
     ap.add_argument("--disk", type=int, default=0, help="batches of the end-to-end comparison with the on-disk path (0: skip)")
     ap.add_argument("--identity", choices=("kept", "batch"), default="kept", help="batch: compare the feed's modes (rows a, b) instead")
     ap.add_argument("--resident-panos", type=int, default=None, help="pool size: compare the feed's modes (rows a-d) instead; needs --panos >= 4 x batch")
+    ap.add_argument("--layout", action="store_true", help="the layout modality: device posing against the host path, ResNet-50 6ch and ResNet-152 18ch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_train_feed.py needs the MI355X (a CPU run says nothing about it)")
     dev = torch.device("cuda:0")
+    if a.layout:
+        layout_rows(a, dev)
+        return
     if a.identity == "batch" or a.resident_panos is not None:
         cache_rows(a, dev)
         return
