@@ -114,6 +114,7 @@ class BevRasteriser:
         self.lut = torch.from_numpy(normalisation_lut()).to(self.device)
         self._ws_slots = {}   # workspaces by slot: a caller that keeps two batches in flight alternates `ws_slot`
         self.ws_slot = 0
+        self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> ctypes.c_void_p:
@@ -155,6 +156,7 @@ class BevRasteriser:
         if nbytes == 0:
             _lib.check(-1, "salve_bev_pano_index_bytes")
         buf = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.index_builds += 1
         with torch.cuda.device(self.device):
             st = self.lib.salve_bev_pano_index_build(ctypes.byref(self.cfg), ctypes.c_void_p(pano_depth.data_ptr()), P,
                                                      ctypes.c_void_p(self.sphere.data_ptr()), ctypes.c_void_p(buf.data_ptr()), nbytes, self._stream())
@@ -170,14 +172,18 @@ class BevRasteriser:
         return nbytes
 
     def update_panos(self, pano_rgb: torch.Tensor, pano_depth: torch.Tensor, slots_dev: torch.Tensor, rgb_rows_dev: torch.Tensor,
-                     depth_rows_dev: torch.Tensor) -> None:
+                     depth_rows_dev: torch.Tensor, index: Optional[torch.Tensor] = None) -> None:
         """Overwrite slots of a resident panorama pool on the current stream: rows k of `rgb_rows_dev` (uint8 [n, H, W, 3]) and
         `depth_rows_dev` (int16 bits [n, H, W]) go to slot slots_dev[k] (device int32 [n], distinct, inside the pool) of `pano_rgb` /
         `pano_depth`, and the panorama index of exactly those slots is rebuilt (include/salve_hip.h: salve_bev_pano_index_update) -- work
         that does not grow with the pool.  The index `pano_index` keeps with the depth tensor is then RE-KEYED to the tensor's new
         version: the next scatter finds it, no full rebuild (which every other in-place write still gets) and no wait for the device.
         A slot outside the pool is reported through the device status word (`check`) by the index update -- and by torch's own
-        index check in `index_copy_`."""
+        index check in `index_copy_`.
+        It runs on the current stream: a caller with a stream of its own wraps the call in `torch.cuda.stream(...)`.  `index`: the pool's own index
+        buffer (what `pano_index` returned for `pano_depth`), for a caller that writes slots from another thread than the one that
+        scatters: neither this call nor a `scatter(..., index=)` then LOOKS the index up by the tensor's version, so a scatter issued
+        between the slot writes and the re-key can never see a stale key and rebuild the whole pool's index."""
         n = int(slots_dev.shape[0])
         if slots_dev.dtype != torch.int32 or slots_dev.dim() != 1 or not slots_dev.is_contiguous():
             raise _lib.SalveHipError(f"update_panos: slots must be a contiguous int32 vector, got {slots_dev.dtype} {tuple(slots_dev.shape)}")
@@ -191,7 +197,10 @@ class BevRasteriser:
         P = int(pano_depth.shape[0])
         if n > P:
             raise _lib.SalveHipError(f"update_panos: {n} slots listed, the pool has {P}")
-        index = self.pano_index(pano_depth)   # (the index of the depth maps as they are now: built here on first use)
+        if index is None:
+            index = self.pano_index(pano_depth)   # (the index of the depth maps as they are now: built here on first use)
+        elif index.numel() != self.pano_index_bytes(P) or index.device != pano_depth.device:
+            raise _lib.SalveHipError(f"update_panos: the index buffer holds {index.numel()} bytes, a pool of {P} slots needs {self.pano_index_bytes(P)}")
         at = slots_dev.to(torch.int64)
         pano_rgb.index_copy_(0, at, rgb_rows_dev)
         pano_depth.index_copy_(0, at, depth_rows_dev)
@@ -247,12 +256,14 @@ class BevRasteriser:
         return out_bev, dbg
 
     def scatter(self, pano_rgb: torch.Tensor, pano_depth: torch.Tensor, hyps_dev: torch.Tensor, n: int, out_bev: torch.Tensor,
-                in_window: Optional[torch.Tensor] = None) -> None:
+                in_window: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None) -> None:
         """First half of `render`: the sparse images (z-order winners' colours) into `out_bev`, the occupancy bitmaps into the
         workspace.  `in_window` (int32 [n]) receives the number of points inside the window per render (0 => the reference
-        writes no tile, bev_rendering_utils.py:279, 623-627)."""
+        writes no tile, bev_rendering_utils.py:279, 623-627).  `index`: the panorama index to use as it is (see `update_panos`);
+        default: the one `pano_index` keeps with the depth tensor."""
         ws = self._workspace(n)
-        index = self.pano_index(pano_depth)
+        if index is None:
+            index = self.pano_index(pano_depth)
         with torch.cuda.device(self.device):
             st = self.lib.salve_bev_scatter(
                 ctypes.byref(self.cfg), ctypes.c_void_p(pano_rgb.data_ptr()), ctypes.c_void_p(pano_depth.data_ptr()),

@@ -2,7 +2,7 @@
 
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
-                              [--norm {torch,hip}] [--render-from DIR [--identity {kept,batch}] [--resident-panos N]]
+                              [--norm {torch,hip}] [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
@@ -14,6 +14,8 @@ A configuration whose modalities include "layout" also needs DIR/layouts.npz: th
 --identity batch renders the identity images of a batch's second panoramas with the batch instead of keeping one per panorama;
 --resident-panos N (which selects --identity batch) memory-maps the two .npy files and keeps a pool of N panoramas on the device,
 uploaded as the batches need them: for panorama sets that do not fit in device memory.  N must be at least 2 x batch_size.
+--prefetch (with --resident-panos N, N at least 4 x batch_size) uploads the next batch's missing panoramas on a second stream while the
+current batch trains: the same batches, the uploads hidden under the step.
 """
 
 from __future__ import annotations
@@ -46,6 +48,8 @@ def main(argv=None) -> None:
                     help="--render-from: keep one identity image per panorama (kept, the default) or render them with each batch (batch)")
     ap.add_argument("--resident-panos", type=int, default=None, metavar="N",
                     help="--render-from: keep a pool of N panoramas on the device and upload the others as batches need them (selects --identity batch)")
+    ap.add_argument("--prefetch", action="store_true",
+                    help="--resident-panos: upload the next batch's missing panoramas beside the training step (N at least 4 x batch size)")
     a = ap.parse_args(argv)
     if a.render_from is None and (a.identity is not None or a.resident_panos is not None):
         raise SystemExit("--identity and --resident-panos belong to --render-from DIR")
@@ -54,6 +58,11 @@ def main(argv=None) -> None:
             raise SystemExit("--resident-panos keeps no identity image per panorama: it cannot be combined with --identity kept")
         if a.resident_panos <= 0:
             raise SystemExit(f"--resident-panos must be positive, got {a.resident_panos}")
+    if a.prefetch:
+        if a.identity == "kept":
+            raise SystemExit("--prefetch uploads into the --resident-panos pool: it cannot be combined with --identity kept")
+        if a.resident_panos is None:
+            raise SystemExit("--prefetch belongs to --resident-panos N: without a pool nothing is uploaded per batch")
     identity = a.identity or ("batch" if a.resident_panos is not None else "kept")
     logging.basicConfig(level=logging.INFO, format="%(asctime)s %(message)s")
     args = load_training_config(a.config)
@@ -79,7 +88,7 @@ def main(argv=None) -> None:
             src = train_render.RenderedTrainSource(torch.device("cuda", torch.cuda.current_device()), args.modalities, pano_hw=rgb.shape[1:3],
                                                    batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
                                                    resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
-                                                   identity=identity, resident_panos=a.resident_panos, layouts=layouts)
+                                                   identity=identity, resident_panos=a.resident_panos, layouts=layouts, prefetch=a.prefetch)
             if split == "train":
                 src.load_panos(rgb, depth)
             else:   # the panoramas (or their pool) and their identity renders are on the device once

@@ -17,7 +17,9 @@ Two opt-in arguments take the feed beyond panorama sets that fit the device.  `i
 panorama: the identity renders of the batch's distinct second panoramas ride in the batch's own scatter / densify launch pair, behind
 the posed renders.  `resident_panos=N` keeps a pool of N panorama slots on the device: `PanoCache` plans, batch by batch, which
 panoramas of the host arrays (np.memmap included) are uploaded into which slots -- the victim is the panorama whose next use in the
-epoch lies furthest ahead -- and `BevRasteriser.update_panos` rebuilds the panorama index of the written slots only.
+epoch lies furthest ahead -- and `BevRasteriser.update_panos` rebuilds the panorama index of the written slots only.  `prefetch=True`
+(with a pool) does that one batch ahead, off the training step's path: worker threads gather the next batch's missed rows and the
+copies, slot writes and index update run on a copy stream of the pool's own while the current batch trains.
 
 Shuffle order and augmentation draws are those of `training.get_dataloader` + `transforms.TrainTransform`: the order of a
 `DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random`.
@@ -27,6 +29,8 @@ The planning functions (`plan_epoch`, `plan_examples`, `check_launch`, `PanoCach
 from __future__ import annotations
 
 import json
+import time
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -110,6 +114,7 @@ def plan_examples(hyp: HypothesisTable, is_match, n_panos: int) -> Dict[str, np.
 
 
 IDENTITIES = ("kept", "batch")
+MAX_GATHER_THREADS = 8   # prefetch: host threads that gather a batch's missed rows (a fixed small number, never the machine's CPU count)
 NEVER = np.iinfo(np.int64).max   # next use of a panorama the rest of the epoch does not name
 
 
@@ -135,12 +140,17 @@ class PanoCache:
     policy "lru" (kept for the test that compares the two): the least recently planned panorama.  Counters: hits, misses,
     uploaded_bytes (misses x bytes_per_pano)."""
 
-    def __init__(self, n_panos: int, capacity: int, batch_size: int, bytes_per_pano: int = 0, policy: str = "furthest") -> None:
+    def __init__(self, n_panos: int, capacity: int, batch_size: int, bytes_per_pano: int = 0, policy: str = "furthest", prefetch: bool = False) -> None:
         if policy not in ("furthest", "lru"):
             raise ValueError(f"policy must be 'furthest' or 'lru', got {policy!r}")
         if n_panos <= 0 or batch_size <= 0:
             raise ValueError(f"n_panos and batch_size must be positive, got {n_panos} and {batch_size}")
         need = min(2 * batch_size, n_panos)
+        if prefetch and capacity < min(4 * batch_size, n_panos):
+            # the batch in flight and the batch being uploaded are pinned at once, up to 2 x batch_size panoramas each
+            raise ValueError(f"a pool of {capacity} panorama slots cannot hold two batches: with prefetch the batch in flight and the next one are "
+                             f"pinned at once, batch size {batch_size} names up to {min(4 * batch_size, n_panos)} of the {n_panos} panoramas in two "
+                             f"batches (resident_panos must be at least {min(4 * batch_size, n_panos)})")
         if capacity < need:
             raise ValueError(f"a pool of {capacity} panorama slots cannot hold one batch: batch size {batch_size} names up to {need} of the "
                              f"{n_panos} panoramas at once (resident_panos must be at least {need})")
@@ -150,19 +160,31 @@ class PanoCache:
         self.last_used = np.zeros(self.n_panos, dtype=np.int64)
         self.clock = 0
         self.hits = self.misses = self.uploaded_bytes = 0
+        self._last = None
 
-    def plan(self, batch_pano_ids, next_use: Optional[np.ndarray] = None) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
+    def plan(self, batch_pano_ids, next_use: Optional[np.ndarray] = None, keep=None) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
         """(slot of every entry of `batch_pano_ids`, [(panorama, slot) to upload]) -- the uploads in panorama order.  `next_use`:
         int64 [n_panos], the batch of every panorama's next use (`epoch_next_use`; None: nothing is known, every panorama counts as
-        never used again).  Entries of the current batch's own panoramas are not read."""
+        never used again).  Entries of the current batch's own panoramas are not read.  `keep`: panorama ids that must not be chosen as
+        victims either (the batch in flight, when this one is planned ahead of it); the ranking of the others is unchanged, and too few
+        victims outside `keep` and the batch is a ValueError, raised before anything is changed."""
         ids = np.asarray(batch_pano_ids, dtype=np.int64)
         need = np.unique(ids)
         if need.size and (int(need[0]) < 0 or int(need[-1]) >= self.n_panos):
             raise ValueError(f"a batch names panorama {int(need[0]) if int(need[0]) < 0 else int(need[-1])}; the cache covers {self.n_panos}")
         if need.size > self.capacity:
             raise ValueError(f"a batch names {need.size} panoramas, the pool has {self.capacity} slots")
-        self.clock += 1
         miss = need[self.slot_of[need] < 0]
+        if keep is not None:
+            kept = np.unique(np.asarray(keep, dtype=np.int64))
+            if kept.size and (int(kept[0]) < 0 or int(kept[-1]) >= self.n_panos):
+                raise ValueError(f"keep names panorama {int(kept[0]) if int(kept[0]) < 0 else int(kept[-1])}; the cache covers {self.n_panos}")
+            pinned = np.union1d(need, kept)
+            room = self.capacity - int((self.slot_of[pinned] >= 0).sum())   # free slots + residents that may be evicted
+            if miss.size > room:
+                raise ValueError(f"a batch misses {miss.size} panoramas, but only {room} of the pool's {self.capacity} slots are free or hold a "
+                                 f"panorama outside this batch and the {kept.size} kept ones: no kept panorama is evicted (a larger pool is needed)")
+        self.clock += 1
         self.hits += int(need.size - miss.size)
         self.misses += int(miss.size)
         self.uploaded_bytes += int(miss.size) * self.bytes_per_pano
@@ -170,6 +192,8 @@ class PanoCache:
         if slots.size < miss.size:
             mine = np.zeros(self.n_panos, dtype=bool)
             mine[need] = True
+            if keep is not None:
+                mine[kept] = True
             cand = self.pano_in[(self.pano_in >= 0) & ~mine[np.maximum(self.pano_in, 0)]]   # resident, not of this batch
             if self.policy == "lru":
                 order = np.lexsort((cand, self.last_used[cand]))
@@ -182,8 +206,33 @@ class PanoCache:
             slots = np.concatenate([slots, freed])
         self.slot_of[miss] = slots
         self.pano_in[slots] = miss
+        self._last = (need, self.last_used[need].copy())   # what `forget` needs to take this plan back
         self.last_used[need] = self.clock
         return self.slot_of[ids], [(int(p), int(sl)) for p, sl in zip(miss, slots)]
+
+    def lookup(self, pano_ids) -> np.ndarray:
+        """Slot of every entry of `pano_ids`, all of them resident (planned earlier): no counter moves."""
+        slots = self.slot_of[np.asarray(pano_ids, dtype=np.int64)]
+        if slots.size and int(slots.min()) < 0:
+            raise ValueError("lookup of a panorama that is not resident: plan the batch first")
+        return slots
+
+    def forget(self, uploads: Sequence[Tuple[int, int]]) -> None:
+        """Take back the MOST RECENT `plan` call, whose `uploads` [(panorama, slot)] did not happen: their slots are free again (the
+        victims stay evicted), and hits, misses, uploaded_bytes, the clock and the batch's last-use stamps are what they were before
+        it, so that the state matches what was uploaded and hits + misses still counts the panoramas of the plans that stand."""
+        if self._last is None or any(self.slot_of[p] != sl or self.pano_in[sl] != p for p, sl in uploads) \
+                or not np.isin([p for p, _ in uploads], self._last[0]).all():
+            raise ValueError("forget takes back the most recent plan only, with the uploads that plan returned")
+        need, stamps = self._last
+        for p, sl in uploads:
+            self.slot_of[p], self.pano_in[sl] = -1, -1
+        self.hits -= int(need.size) - len(uploads)
+        self.misses -= len(uploads)
+        self.uploaded_bytes -= len(uploads) * self.bytes_per_pano
+        self.last_used[need] = stamps
+        self.clock -= 1
+        self._last = None
 
 
 class RenderedTrainSource:
@@ -196,11 +245,14 @@ class RenderedTrainSource:
     identity: "kept" (default) renders the identity image of every panorama once and keeps it; "batch" renders the identity images of
     the batch's distinct second panoramas with the batch -- the same images, no P x S image array.  resident_panos: None (default)
     uploads every panorama up front; an integer keeps a pool of that many panorama slots on the device, filled on first use from the
-    host arrays `load_panos` was given (needs identity="batch"; at least min(2 x batch_size, P) slots)."""
+    host arrays `load_panos` was given (needs identity="batch"; at least min(2 x batch_size, P) slots).
+    prefetch (needs resident_panos; at least min(4 x batch_size, P) slots): while batch b trains, batch b + 1's misses are gathered by
+    `gather_threads` host threads and uploaded on a copy stream the pool owns; the batches are the same."""
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
-                 crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None) -> None:
+                 crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None,
+                 prefetch: bool = False, gather_threads: int = 4) -> None:
         if split not in SPLITS:
             raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
         if precision not in ("fp32", "bf16"):
@@ -212,6 +264,11 @@ class RenderedTrainSource:
                 raise ValueError('resident_panos needs identity="batch": keeping an identity image per panorama is what does not fit')
             if int(resident_panos) <= 0:
                 raise ValueError(f"resident_panos must be positive, got {resident_panos}")
+        if prefetch and resident_panos is None:
+            raise ValueError("prefetch needs resident_panos: without a pool every panorama is resident and nothing is uploaded per batch")
+        if not 1 <= int(gather_threads) <= MAX_GATHER_THREADS:
+            raise ValueError(f"gather_threads must be 1 .. {MAX_GATHER_THREADS}, got {gather_threads}")
+        self.prefetch, self.gather_threads = bool(prefetch), int(gather_threads)
         self.surfaces = train_surfaces(modalities, with_layouts=layouts is not None)
         self.has_layout = "layout" in set(modalities)
         self.layouts = layouts if self.has_layout else None   # salve_amd.layout.PanoLayouts, indexed by panorama
@@ -296,21 +353,32 @@ class RenderedTrainSource:
         P, S = int(rgb.shape[0]), len(self.surfaces)
         Hb, Wb = self.ras.bev_hw
         try:
-            cache = PanoCache(P, self.resident_panos, self.batch_size, bytes_per_pano=H * W * 5)
+            cache = PanoCache(P, self.resident_panos, self.batch_size, bytes_per_pano=H * W * 5, prefetch=self.prefetch)
         except ValueError as e:
             raise RuntimeError(str(e)) from None
         n_slots, n_stage = cache.capacity, min(2 * self.batch_size, cache.capacity)
         index_bytes = self.ras.pano_index_bytes(n_slots)
-        self._refuse_if_too_large((n_slots + n_stage) * H * W * 5 + index_bytes + (self._batch_images(n_slots) + self._layout_images(n_slots)) * Hb * Wb * 4,
-                                  f"a pool of {n_slots} panorama slots, its index, one batch's uploads and one batch's BEV images")
+        # (prefetch: the rows of the batch ahead are allocated on the copy stream, those of an epoch's first batch on the compute stream, and
+        # the caching allocator keeps the two streams' blocks apart: two batches' upload rows and their int64 slot lists can be held at once)
+        n_rows = 2 * n_stage if self.prefetch else n_stage
+        self._refuse_if_too_large((n_slots + n_rows) * H * W * 5 + n_rows * 12 + index_bytes
+                                  + (self._batch_images(n_slots) + self._layout_images(n_slots)) * Hb * Wb * 4,
+                                  f"a pool of {n_slots} panorama slots, its index, {'two batches' if self.prefetch else 'one batch'}'s uploads and one batch's BEV images")
         # zero depth passes neither surface's z filter: an unfilled slot's index entries are empty boxes
         self.pano_rgb = torch.zeros((n_slots, H, W, 3), dtype=torch.uint8, device=self.device)
         self.pano_depth = torch.zeros((n_slots, H, W), dtype=torch.int16, device=self.device)
-        self.ras.pano_index(self.pano_depth)
+        index = self.ras.pano_index(self.pano_depth)
         # the host writes a staging buffer while an earlier copy may still read it: two buffers, an event each, waited on before the overwrite
         stage = [{"rgb": torch.empty((n_stage, H, W, 3), dtype=torch.uint8).pin_memory(), "depth": torch.empty((n_stage, H, W), dtype=torch.int16).pin_memory(),
                   "event": None} for _ in range(2)]
         self.pool = {"rgb": rgb, "depth": depth, "cache": cache, "stage": stage, "turn": 0, "uploads": 0}
+        if self.prefetch and self.surfaces:
+            # the pool owns its index buffer and its copy stream: the uploads of the batch ahead run there, beside the step.
+            # "done": the event behind the last batch's last launch; "pending": the upload job in flight, if any; "iteration": the token of
+            # the iteration that plans the pool; "wait_s": host seconds the loop has waited for upload jobs so far
+            for st in stage:
+                st["slots"] = torch.empty(n_stage, dtype=torch.int32).pin_memory()
+            self.pool.update(index=index, stream=torch.cuda.Stream(self.device), done=None, pending=None, iteration=None, wait_s=0.0)
         self.n_panos, self.examples = P, None
         self._alloc_images(P, n_slots)
         self.ras._workspace(self._batch_images(n_slots))
@@ -366,6 +434,8 @@ class RenderedTrainSource:
             raise RuntimeError("share_panos needs the same device, modalities and panorama size, and a batch size not above the other's")
         if (other.identity, other.resident_panos) != (self.identity, self.resident_panos):
             raise RuntimeError("share_panos needs the same identity and resident_panos arguments on both sources")
+        if other.prefetch != self.prefetch:
+            raise RuntimeError("share_panos needs the same prefetch argument on both sources")
         self.pano_rgb, self.pano_depth, self.ref_bev, self.bev, self.n_panos, self.examples = (other.pano_rgb, other.pano_depth, other.ref_bev,
                                                                                                other.bev, other.n_panos, None)
         self.pool, self.lay, self.lay_base, self.layouts = other.pool, other.lay, other.lay_base, other.layouts
@@ -427,17 +497,129 @@ class RenderedTrainSource:
             e1.record()
         e1 = self._timed("index update")
         with tracing.range("salve.pano_update"):
-            self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows)
+            self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows, index=pool.get("index"))
         if e1 is not None:
             e1.record()
         pool["uploads"] += m
         return slots
 
-    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    # ------------------------------------------------------------------ prefetch
+    def _gather_rows(self, st: Dict, uploads: Sequence[Tuple[int, int]], lo: int, hi: int) -> None:
+        """Rows lo .. hi - 1 of a job's missed panoramas from the host arrays into the pinned staging buffer (one gather thread's share;
+        numpy copies rows of this size with the GIL released)."""
+        pool = self.pool
+        rgb_np, depth_np = st["rgb"].numpy(), st["depth"].numpy().view(np.uint16)
+        for k in range(lo, hi):
+            p = uploads[k][0]
+            rgb_np[k] = pool["rgb"][p]
+            depth_np[k] = pool["depth"][p]
+
+    def _upload_job(self, st: Dict, uploads: Sequence[Tuple[int, int]], after: Optional[torch.cuda.Event], gatherers: ThreadPoolExecutor):
+        """Worker thread: gather the missed rows (split over the gather threads), then enqueue the two copies, the slot writes and the
+        index update on the pool's copy stream -- behind `after`, the event of the last batch that may still read a victim's slot.
+        Returns the event behind the index update: what the compute stream waits on before it reads the slots."""
+        pool, m, T = self.pool, len(uploads), self.gather_threads
+        if st["event"] is not None:
+            st["event"].synchronize()   # the copy that last read this buffer
+        cuts = [m * t // T for t in range(T + 1)]
+        shares = [gatherers.submit(self._gather_rows, st, uploads, cuts[t], cuts[t + 1]) for t in range(T) if cuts[t + 1] > cuts[t]]
+        errors = [f.exception() for f in shares]   # (every thread has left the buffer before the first failure is raised)
+        for e in errors:
+            if e is not None:
+                raise e
+        st["slots"].numpy()[:m] = [sl for _, sl in uploads]
+        with torch.cuda.stream(pool["stream"]):
+            if after is not None:
+                pool["stream"].wait_event(after)
+            with tracing.range("salve.pano_upload"):   # (no `timers` entry: the caller that reads them does not know when this thread records)
+                rgb_rows = st["rgb"][:m].to(self.device, non_blocking=True)
+                depth_rows = st["depth"][:m].to(self.device, non_blocking=True)
+                slots_dev = st["slots"][:m].to(self.device, non_blocking=True)
+            st["event"] = torch.cuda.Event()
+            st["event"].record()
+            with tracing.range("salve.pano_update"):
+                self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows, index=pool["index"])
+            ready = torch.cuda.Event()
+            ready.record()
+        return ready
+
+    def _prefetch(self, panos: np.ndarray, next_use: np.ndarray, keep: np.ndarray, after: Optional[torch.cuda.Event], worker: ThreadPoolExecutor,
+                  gatherers: ThreadPoolExecutor) -> Dict:
+        """Plan the batch ahead (its victims spare `keep`, the batch in flight) and start its upload; the job is the pool's `pending`."""
+        pool = self.pool
+        _, uploads = pool["cache"].plan(panos, next_use, keep=keep)
+        job = {"uploads": uploads, "future": None}
+        if uploads:
+            st = pool["stage"][pool["turn"]]
+            pool["turn"] ^= 1
+            job["future"] = worker.submit(self._upload_job, st, uploads, after, gatherers)
+        pool["pending"] = job
+        return job
+
+    def _drain(self, raise_errors: bool = False) -> Optional[torch.cuda.Event]:
+        """Complete the pool's outstanding upload job, if any: join its worker and count its uploads; returns the event behind its index
+        update.  A job that failed is taken back from the `PanoCache` (its slots are free again: the state matches what was uploaded) and
+        the copy stream is synchronised; its exception is raised here only with `raise_errors` (the loop that needs the batch)."""
+        pool = self.pool
+        job = pool["pending"]
+        if job is None or job["future"] is None:
+            pool["pending"] = None
+            return None
+        t0 = time.perf_counter()
+        error = job["future"].exception()   # joins the worker; an interrupt of THIS thread leaves the job pending, to be completed later
+        pool["wait_s"] += time.perf_counter() - t0
+        pool["pending"] = None
+        if error is not None:   # the worker's own exception: nothing of the job's upload counts
+            pool["cache"].forget(job["uploads"])
+            pool["stream"].synchronize()
+            if raise_errors:
+                raise error
+            return None
+        pool["uploads"] += len(job["uploads"])
+        return job["future"].result()
+
+    def _iter_prefetch(self, plan: List[np.ndarray]):
+        """The epoch with the uploads one batch ahead: batch 0 is made resident on the compute stream as without prefetch; right behind
+        batch b's launches batch b + 1 is planned and its upload started.  The copy stream writes only slots that neither batch b nor
+        batch b + 1 names, behind the event of batch b - 1's last launch (the last batch of the epoch before, for b = 0)."""
+        pool = self.pool
+        self._drain()   # another iteration on this pool (the other source's, or one of this source's left suspended) may have a job out
+        pool["stream"].synchronize()
+        mine = pool["iteration"] = object()   # one iteration at a time plans this pool: one that was suspended meanwhile refuses to go on
+        panos = [self.batch_panos(idx) for idx in plan]
+        next_use, after = epoch_next_use(panos, self.n_panos)
+        worker, gatherers = ThreadPoolExecutor(1, "salve-upload"), ThreadPoolExecutor(self.gather_threads, "salve-gather")
+        job = None
+        try:
+            for b, idx in enumerate(plan):
+                if pool["iteration"] is not mine:
+                    raise RuntimeError("another iteration over this resident pool was started while this one was suspended: with prefetch the "
+                                       "pool serves one iteration at a time (finish or close an epoch before the next begins)")
+                if job is not None:
+                    ready = self._drain(raise_errors=True)
+                    if ready is not None:
+                        torch.cuda.current_stream(self.device).wait_event(ready)
+                out = self.batch(idx, self.draws(len(idx)), next_use, planned=job is not None)
+                next_use[panos[b]] = after[b]
+                before, pool["done"] = pool["done"], torch.cuda.Event()
+                pool["done"].record()
+                job = self._prefetch(panos[b + 1], next_use, panos[b], before, worker, gatherers) if b + 1 < len(plan) else None
+                yield out
+        finally:   # closed or dropped mid-epoch, or an exception: nothing stays in flight, the cache matches the slots
+            if pool["iteration"] is mine:
+                self._drain()
+            worker.shutdown(wait=True)
+            gatherers.shutdown(wait=True)
+            if pool["iteration"] is mine:
+                pool["stream"].synchronize()
+
+    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None,
+              planned: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """Render examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  `next_use` (resident pool
-        only): the batch of every panorama's next use, for the planner (`epoch_next_use`)."""
+        only): the batch of every panorama's next use, for the planner (`epoch_next_use`).  `planned`: the batch's panoramas were made
+        resident ahead (prefetch): their slots are looked up, nothing is planned or uploaded here."""
         B, S, K = len(idx), len(self.surfaces), self.per_sample
-        jobs, aug, rows, lay_recs, n = self.batch_tables(idx, draws, next_use)
+        jobs, aug, rows, lay_recs, n = self.batch_tables(idx, draws, next_use, planned)
         bev_b = self.ref_bev if self.identity == "kept" else self.bev
         # ONE upload per batch; every table starts on a multiple of 16 bytes (the 40-byte render rows come last)
         # (the 48-byte layout records hold a double: every table in front of them is a multiple of 8 bytes long)
@@ -450,7 +632,8 @@ class RenderedTrainSource:
         if S:   # (layout alone: no texture map, as RenderVerifyPipeline)
             e1 = self._timed("scatter")
             with tracing.range("salve.scatter"):
-                self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:o[4]], n, self.bev)
+                self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:o[4]], n, self.bev,
+                                 index=None if self.pool is None else self.pool.get("index"))
             if e1 is not None:
                 e1.record()
             e1 = self._timed("densify")
@@ -477,7 +660,7 @@ class RenderedTrainSource:
             e1.record()
         return out, labels
 
-    def batch_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None):
+    def batch_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None, planned: bool = False):
         """The host tables of one batch: (tile jobs [2][B][K], draws [B], render rows, layout pose records, renders).  Host arithmetic,
         except that a resident pool uploads its misses here (`_make_resident`)."""
         ex, S, B, K = self.examples, len(self.surfaces), len(idx), self.per_sample
@@ -511,7 +694,7 @@ class RenderedTrainSource:
             uniq, inv = np.unique(ex["i2"][idx], return_inverse=True)
             U = len(uniq)
             pano = np.concatenate([i1, uniq])
-            where = pano if self.pool is None else self._make_resident(pano, next_use)
+            where = pano if self.pool is None else self.pool["cache"].lookup(pano) if planned else self._make_resident(pano, next_use)
             order = np.argsort(where, kind="stable")
             rank = np.empty(B + U, dtype=np.int64)
             rank[order] = np.arange(B + U)
@@ -562,6 +745,8 @@ class RenderedTrainSource:
         if self.pool is None:
             for idx in plan:
                 yield self.batch(idx, self.draws(len(idx)))
+        elif "stream" in self.pool:
+            yield from self._iter_prefetch(plan)
         else:   # the epoch's order is known here, before its first batch: every panorama's next use, for the planner
             panos = [self.batch_panos(idx) for idx in plan]
             next_use, after = epoch_next_use(panos, self.n_panos)

@@ -9,7 +9,7 @@
     examples written once as JPEGs into a temporary ZindData tree (outside the timed region) and fed by `training.get_dataloader`.
 
     python tools/measure/bench_train_feed.py [--configs 152:2,50:1] [--batch 256] [--modes bf16:hip,fp32:torch] [--steps 5] [--warmup 2]
-                                             [--panos 64] [--disk 0] [--identity {kept,batch}] [--resident-panos N] [--layout]
+                                             [--panos 64] [--disk 0] [--identity {kept,batch}] [--resident-panos N [--prefetch]] [--layout]
 
 --identity batch and / or --resident-panos N switch to the comparison of the feed's modes instead: rows (a) identity
 "kept", everything resident (the default source: the yardstick), (b) identity "batch", everything resident, and with --resident-panos
@@ -17,6 +17,13 @@
 index update beside scatter, densify, tiles), the host-to-device rate reached, the uploads per batch the planner makes (furthest next
 use) beside what LRU would make on the same epochs, and the step fed by each row beside the step on a resident batch.  --panos P must
 then be at least 4 x batch (so that a half-size pool misses); the P scenes are distinct (a few rooms, each turned by its own angle).
+--prefetch adds row (e): the same pool with prefetch=True (the pool must hold 4 x batch).  A prefetched upload hides under
+the step that FOLLOWS its submission, so row (e) is not part of the step-by-step alternation (there four other rows' steps would run before
+its next batch is asked for, and its upload would land under them): it is timed over CONSECUTIVE steps of whole epochs, the way training
+consumes it -- every step ends with `loss.item()` as training.run_epoch's does, the device is synchronised once, behind the epoch --
+with three kinds of epoch alternating epoch by epoch in one process: the resident batch, row (c) (the same pool size without prefetch: the
+yardstick) and row (e).  The first round (the pools' cold fill) is dropped.  Reported per kind: the median step behind an epoch's first, the
+first step (made resident serially in both rows), the epoch's time per batch, and for (e) the host time its loop spent waiting for upload jobs.
 
 --layout switches to the layout modality with synthetic layouts (salve_amd/synthetic_layouts.py): per batch the HIP
 events of the pose / rasterise / tile launches, the source alone, and the fed step beside the resident step for ResNet-50 on layout
@@ -121,8 +128,10 @@ def distinct_panos(P: int, base: int = 64):
 
 
 def planned_uploads(hyp, P: int, pool: int, B: int, epochs: int, policy: str):
-    """Uploads per batch, per epoch, of a PanoCache with `policy` over the epochs a seed-0 train source runs."""
-    cache = train_render.PanoCache(P, pool, B, policy=policy)
+    """Uploads per batch, per epoch, of a PanoCache with `policy` over the epochs a seed-0 train source runs ("ahead": furthest next use
+    planned one batch ahead, the batch in flight kept -- what prefetch=True plans)."""
+    ahead = policy == "ahead"
+    cache = train_render.PanoCache(P, pool, B, policy="furthest" if ahead else policy, prefetch=ahead)
     gen = torch.Generator().manual_seed(0)
     out = []
     for _ in range(epochs):
@@ -131,10 +140,54 @@ def planned_uploads(hyp, P: int, pool: int, B: int, epochs: int, policy: str):
         next_use, after = train_render.epoch_next_use(panos, P)
         per = []
         for b, need in enumerate(panos):
-            per.append(len(cache.plan(need, next_use)[1]))
+            per.append(len(cache.plan(need, next_use, keep=panos[b - 1] if ahead and b else None)[1]))
             next_use[need] = after[b]
         out.append(per)
     return out
+
+
+def sustained(a, tag, model, opt, x_packed, y, src_c, src_e, n_it) -> None:
+    """Rows (c) and (e) and the resident batch over consecutive steps of whole epochs, the kinds alternating epoch by epoch (module docstring)."""
+    kinds = {"resident": None, "(c) pool": src_c, "(e) pool + prefetch": src_e}
+    steps, firsts, epochs, waits = ({k: [] for k in kinds} for _ in range(4))
+    for r in range(1 + a.rounds):
+        for k, src in kinds.items():
+            it = None if src is None else iter(src)
+            w0 = 0.0 if src is None or "wait_s" not in src.pool else src.pool["wait_s"]
+            torch.cuda.synchronize()
+            t0 = t_prev = time.perf_counter()
+            per = []
+            for i in range(n_it):
+                xb, yb = (x_packed, y) if it is None else next(it)
+                opt.zero_grad(set_to_none=True)
+                loss = F.cross_entropy(model.forward_packed(xb), yb.squeeze())
+                loss.backward()
+                opt.step()
+                loss.item()   # (what training.run_epoch does every step: the compute stream is waited for, the copy stream is not)
+                t = time.perf_counter()
+                per.append(t - t_prev)
+                t_prev = t
+            if it is not None:
+                for _ in it:   # (the status check behind the epoch)
+                    pass
+            torch.cuda.synchronize()
+            total = time.perf_counter() - t0
+            if r:   # the first round fills the pools
+                steps[k] += per[1:]
+                firsts[k].append(per[0])
+                epochs[k].append(total / n_it)
+                waits[k].append(0.0 if src is None or "wait_s" not in src.pool else (src.pool["wait_s"] - w0) / (n_it - 1))
+    res = med(steps["resident"]) * 1e3
+    for k in kinds:
+        m = med(steps[k]) * 1e3
+        line = (f"{tag}: consecutive steps, {a.rounds} epochs of {n_it}: {k}: median step behind the first {m:.1f} ms ({100 * (m / res - 1):+.1f} % over the "
+                f"resident step; min {min(steps[k]) * 1e3:.1f}, max {max(steps[k]) * 1e3:.1f}), first step of an epoch {med(firsts[k]) * 1e3:.1f} ms, epoch per batch "
+                + " / ".join(f"{v * 1e3:.1f}" for v in epochs[k]) + " ms")
+        if kinds[k] is not None and "wait_s" in kinds[k].pool:
+            line += "; host wait for the upload job per prefetched batch " + " / ".join(f"{v * 1e3:.2f}" for v in waits[k]) + " ms"
+        if kinds[k] is not None:
+            line += f"; uploads so far {kinds[k].uploads}"
+        print(line, flush=True)
 
 
 def cache_rows(a, dev) -> None:
@@ -152,7 +205,7 @@ def cache_rows(a, dev) -> None:
     hyp = synthetic.make_hypotheses(B * n_it, P)
     labels = np.arange(B * n_it, dtype=np.int64) % 2
     if pool is not None:
-        for policy in ("furthest", "lru"):
+        for policy in ("furthest", "lru") + (("ahead",) if a.prefetch else ()):
             per = planned_uploads(hyp, P, pool, B, 3, policy)
             print(f"planned uploads per batch, {policy}: " + "; ".join(f"epoch {e + 1} mean {np.mean(v):.1f} (first batch {v[0]}, others {np.mean(v[1:]):.1f})"
                                                                        for e, v in enumerate(per)), flush=True)
@@ -270,6 +323,9 @@ def cache_rows(a, dev) -> None:
             if pool is not None:   # the cold fill under the step: a fresh pool, its first epoch
                 for it in its.values():
                     it.close()
+                if a.prefetch:
+                    sustained(a, tag, model, opt, x_packed, y, rows["(c) pool, second epoch"],
+                              make(identity="batch", resident_panos=pool, prefetch=True, gather_threads=a.gather_threads), n_it)
                 del rows["(c) pool, second epoch"]
                 fresh = make(identity="batch", resident_panos=pool)
                 it_d = iter(fresh)
@@ -392,11 +448,16 @@ def main() -> None:
     ap.add_argument("--disk", type=int, default=0, help="batches of the end-to-end comparison with the on-disk path (0: skip)")
     ap.add_argument("--identity", choices=("kept", "batch"), default="kept", help="batch: compare the feed's modes (rows a, b) instead")
     ap.add_argument("--resident-panos", type=int, default=None, help="pool size: compare the feed's modes (rows a-d) instead; needs --panos >= 4 x batch")
+    ap.add_argument("--prefetch", action="store_true", help="with --resident-panos N (N >= 4 x batch): add row (e), the pool with prefetch=True")
+    ap.add_argument("--rounds", type=int, default=4, help="--prefetch: epochs of consecutive steps timed per kind (one more, the first, is dropped)")
+    ap.add_argument("--gather-threads", type=int, default=4, help="--prefetch: host threads that gather the missed rows (1 .. 8)")
     ap.add_argument("--layout", action="store_true", help="the layout modality: device posing against the host path, ResNet-50 6ch and ResNet-152 18ch")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_train_feed.py needs the MI355X (a CPU run says nothing about it)")
     dev = torch.device("cuda:0")
+    if a.prefetch and a.resident_panos is None:
+        sys.exit("--prefetch belongs to --resident-panos N")
     if a.layout:
         layout_rows(a, dev)
         return
