@@ -43,7 +43,8 @@ typedef enum {
                                      `flags` / `out_flags` bits are refused with SALVE_ERR_BAD_ARG (ABI 5 ignored them);
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
-                                        salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT) */
+                                        salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
+                                        salve_adam_step */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -571,6 +572,58 @@ int salve_bn_bf16_forward(const salve_bn_desc_t* d, const uint16_t* x, const uin
 int salve_bn_bf16_backward(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* gamma,
                            const float* save_mean, const float* save_invstd, uint16_t* dx, uint16_t* dres, float* dgamma, float* dbeta, void* ws,
                            size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Adam over every parameter tensor in one launch, with the bf16 copy of a weight written alongside (additive within ABI 7):
+ * opt-in.  The reference trains with torch.optim.Adam(lr, weight_decay) (salve/train_utils.py:173-180) under a poly schedule
+ * that changes lr every iteration (scripts/train.py).  This entry performs one step of that optimiser (amsgrad=False,
+ * maximize=False, L2 weight decay added to the gradient) for a list of fp32 tensors (salve_amd/optim.py: HipAdam; the default
+ * stays torch.optim.Adam).
+ *   Table:   device salve_adam_segment_t [n_segments], one record per parameter tensor, 8-byte aligned:
+ *              param, grad, exp_avg, exp_avg_sq   device float [n], 4-byte aligned (16-byte aligned tensors take the 16-byte
+ *                                                 path); param, exp_avg and exp_avg_sq are updated in place, grad is read only
+ *              shadow_bf16                        NULL, or device uint16_t [n]: receives the new param as bf16 bit patterns,
+ *                                                 rounded to nearest even (+-inf kept, NaN stored as 0x7FC0)
+ *              n                                  elements (64-bit)
+ *              step_size                          lr / (1 - beta1^t), t = this tensor's step count after the step
+ *              sqrt_bc2                           sqrt(1 - beta2^t)
+ *              beta1, beta2, eps, weight_decay    the group's hyperparameters
+ *              one_minus_beta1, one_minus_beta2   1 - beta1, 1 - beta2
+ *            The scalars are per segment (torch keeps a step count per parameter, groups may differ in lr); the caller computes
+ *            each in double and rounds it to float once.  Nothing is a compiled constant: lr changes every step.
+ *   Chunks:  device salve_adam_chunk_t [n_chunks], one per workgroup: `segment` indexes the table, `offset` is the first element
+ *            of the chunk, a multiple of SALVE_ADAM_CHUNK below that segment's n; the chunk ends SALVE_ADAM_CHUNK elements later
+ *            or at n.  A segment of n elements takes ceil(n / SALVE_ADAM_CHUNK) chunks, each listed once (a chunk listed twice
+ *            is a race; an element no chunk covers is not updated).
+ *   Update:  g += weight_decay * p (skipped for weight_decay == 0); m += (1 - beta1) * (g - m); v = v * beta2 + (1 - beta2) * g * g;
+ *            p -= step_size * m / (sqrt(v) / sqrt_bc2 + eps).  fp32, in the operation order of torch's fp32 Adam on the CPU (its
+ *            three fused multiply-adds included; sqrt and the divisions correctly rounded), no atomics: the same inputs give
+ *            bit-identical outputs.  One launch, whatever n_segments; n_chunks == 0 launches nothing.
+ *   Checks:  SALVE_ERR_BAD_ARG on a null table, a null chunk map with n_chunks > 0, negative counts or misaligned tables.  The
+ *            tables live on the device, so their contents can be checked only through host_table / host_chunk_map: host copies
+ *            of the same bytes (e.g. the staging buffer), either may be NULL.  With host_table, a segment with a null or
+ *            misaligned pointer or n < 0 is SALVE_ERR_BAD_ARG; with both, so is a chunk that names a segment outside the table or
+ *            an offset that is negative, not a multiple of SALVE_ADAM_CHUNK or not below its segment's n.  On the device a chunk
+ *            outside its table or segment is skipped, and no chunk reaches past its segment's n.
+ *   The caller owns every buffer; the library allocates nothing and keeps nothing.  The launch is asynchronous on `stream`: the
+ *   device tables must stay unchanged until it has run (the host copies are read before the call returns).
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_ADAM_CHUNK 4096   /* elements a workgroup updates */
+typedef struct {
+    float* param;
+    const float* grad;
+    float* exp_avg;
+    float* exp_avg_sq;
+    uint16_t* shadow_bf16;
+    int64_t n;
+    float step_size, sqrt_bc2, beta1, beta2, eps, weight_decay, one_minus_beta1, one_minus_beta2;
+} salve_adam_segment_t; /* 80 bytes */
+typedef struct {
+    int32_t segment, reserved;
+    int64_t offset;
+} salve_adam_chunk_t; /* 16 bytes */
+int salve_adam_step(const salve_adam_segment_t* table, int32_t n_segments, const salve_adam_chunk_t* chunk_map, int32_t n_chunks,
+                    const salve_adam_segment_t* host_table, const salve_adam_chunk_t* host_chunk_map, void* stream);
 
 #ifdef __cplusplus
 }

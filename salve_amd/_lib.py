@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = (
     "salve_bev_train_tiles",
     "salve_bev_pano_index_update",
     "salve_layout_pose",
+    "salve_adam_step",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -134,6 +135,14 @@ class BnDesc(ctypes.Structure):
     _fields_ = [("rows", ctypes.c_int32), ("C", ctypes.c_int32), ("flags", ctypes.c_int32), ("eps", ctypes.c_float),
                 ("momentum", ctypes.c_float)]
 
+
+# salve_adam_step tables (include/salve_hip.h: salve_adam_segment_t, salve_adam_chunk_t, SALVE_ADAM_CHUNK)
+ADAM_CHUNK = 4096
+ADAM_SEGMENT_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<u8"), ("exp_avg_sq", "<u8"), ("shadow_bf16", "<u8"), ("n", "<i8"),
+                               ("step_size", "<f4"), ("sqrt_bc2", "<f4"), ("beta1", "<f4"), ("beta2", "<f4"), ("eps", "<f4"),
+                               ("weight_decay", "<f4"), ("one_minus_beta1", "<f4"), ("one_minus_beta2", "<f4")])
+ADAM_CHUNK_DTYPE = np.dtype([("segment", "<i4"), ("reserved", "<i4"), ("offset", "<i8")])
+assert ADAM_SEGMENT_DTYPE.itemsize == 80 and ADAM_CHUNK_DTYPE.itemsize == 16
 
 _lib = None
 
@@ -231,6 +240,8 @@ def load() -> ctypes.CDLL:
     for name in ("salve_bn_f32_backward", "salve_bn_bf16_backward"):   # d, dy, x, y, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta
         getattr(lib, name).argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 10 + [vp, sz, vp]
         getattr(lib, name).restype = ctypes.c_int
+    lib.salve_adam_step.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.salve_adam_step.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

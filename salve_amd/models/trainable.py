@@ -13,6 +13,10 @@ Opt-in HIP BatchNorm (`set_train_norm("hip")`): every BatchNorm runs on salve_am
 `BatchNormHipFunction`, with the ReLU and the residual add that follow it fused in, forward and backward, in either precision;
 in bf16 no cast remains around BatchNorm.  torch's BatchNorm stays the default.
 
+With the opt-in HIP Adam (salve_amd/optim.py: HipAdam, `--optim hip`) the bf16 convolutions read the bf16 copy of a weight that
+the optimiser's step wrote, instead of casting the fp32 master on every call, while that copy is provably current
+(`optim.current_shadow`); otherwise they cast as before.  The same bits either way.
+
 `TrainableEarlyFusionCEResnet` subclasses `EarlyFusionCEResnet`: the same parameters and buffers under the same names, so state
 dicts move between the two with strict=True, and a checkpoint trained here loads into the inference model (fp16 or fp32 engine).
 There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
@@ -29,6 +33,7 @@ from torch import Tensor, nn
 
 from salve_amd import _lib
 from salve_amd.models.early_fusion import EarlyFusionCEResnet, num_input_images
+from salve_amd.optim import GENERATION_ATTR, current_shadow
 
 
 def _pad8(c: int) -> int:
@@ -72,10 +77,10 @@ class _Conv2dFunction(torch.autograd.Function):
     x: CUDA [B, Cin, H, W] (channels_last memory is used as is; other layouts are copied); weight: torch layout [Cout, Cin, KH, KW].
     Returns channels_last [B, Cout, Ho, Wo].  Input channels that are not a multiple of 8 (the stem's 6 / 12 / 18) are zero-padded
     here; the stem's dgrad is never needed (the network input takes no gradient) and raises if asked.  dgrad is skipped when x
-    needs no gradient."""
+    needs no gradient.  shadow: None, or the weight already in `act` (same shape), used instead of casting it."""
 
     @staticmethod
-    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False) -> Tensor:
+    def forward(ctx, x: Tensor, weight: Tensor, stride: int, padding: int, packed: bool = False, shadow: Optional[Tensor] = None) -> Tensor:
         cls = ctx._forward_cls   # the class `apply` was called on
         who = cls.__name__
         for name, t, dt in (("x", x, cls.act), ("weight", weight, torch.float32)):
@@ -95,17 +100,27 @@ class _Conv2dFunction(torch.autograd.Function):
         ho, wo = (h + 2 * padding - kh) // stride + 1, (w + 2 * padding - kw) // stride + 1
         desc = _lib.ConvDesc(b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
         xn = _nhwc(x.detach(), cp)
-        wk = _pack_weight(weight.detach().to(cls.act), cp)   # (bf16: cast once per forward, the copy is saved for the backward pass)
+        if shadow is not None and (shadow.dtype != cls.act or shadow.shape != weight.shape or shadow.device != weight.device):
+            raise RuntimeError(f"{who}: the weight's {cls.act} copy must have its shape and device, got {shadow.dtype} {tuple(shadow.shape)} on {shadow.device}")
+        # bf16: cast once per forward, unless the optimiser left a current copy behind (salve_amd.optim.current_shadow: the same bits);
+        # the packed copy is saved for the backward pass (for a 1 x 1 kernel it is a view of `shadow`, which the next optimiser step
+        # rewrites in place: backward checks the copy's step count)
+        wk = _pack_weight(weight.detach().to(cls.act) if shadow is None else shadow, cp)
         y = torch.empty((b, cout, ho, wo), dtype=cls.act, device=x.device, memory_format=torch.channels_last)
         _run(cls.prefix, "forward", desc, _lib.CONV_FWD, xn, wk, y)
         ctx.save_for_backward(xn, wk)
         ctx.desc = (b, h, w, cp, ho, wo, cout, kh, kw, stride, padding)
         ctx.cin = cin
+        ctx.shadow = shadow
+        ctx.shadow_generation = None if shadow is None else getattr(shadow, GENERATION_ATTR, None)
         return y
 
     @staticmethod
     def backward(ctx, gy: Tensor):
         cls = ctx._forward_cls
+        if ctx.shadow is not None and getattr(ctx.shadow, GENERATION_ATTR, None) != ctx.shadow_generation:
+            raise RuntimeError(f"{cls.__name__}: the optimiser has stepped since this forward pass and rewritten the weight copy it saved; "
+                               "call backward before optimizer.step()")
         xn, wk = ctx.saved_tensors
         desc = _lib.ConvDesc(*ctx.desc)
         b, h, w, cp = ctx.desc[:4]
@@ -121,7 +136,7 @@ class _Conv2dFunction(torch.autograd.Function):
             dwk = torch.empty(wk.shape, dtype=torch.float32, device=gy.device)   # (never accumulated in bf16)
             _run(cls.prefix, "backward_weight", desc, _lib.CONV_WGRAD, xn, gyn, dwk)
             dw = dwk[..., :ctx.cin].permute(0, 3, 1, 2).contiguous()
-        return dx, dw, None, None, None
+        return dx, dw, None, None, None, None
 
 
 class Conv2dF32Function(_Conv2dFunction):
@@ -131,7 +146,8 @@ class Conv2dF32Function(_Conv2dFunction):
 
 class Conv2dBF16Function(_Conv2dFunction):
     """The convolution in bf16 mixed precision: bf16 x, y and dx, a bf16 copy of the fp32 master weight, fp32 accumulation and fp32
-    dW on salve_conv_bf16_*."""
+    dW on salve_conv_bf16_*.  The copy is cast here, or is `shadow`: the one HipAdam's step wrote (`conv2d_bf16` passes it while
+    it is current)."""
     prefix, act, why = "salve_conv_bf16", torch.bfloat16, "bf16 activations, fp32 master weights"
 
 
@@ -142,7 +158,7 @@ def conv2d_f32(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:
 
 def conv2d_bf16(x: Tensor, conv: nn.Conv2d, packed: bool = False) -> Tensor:
     assert conv.bias is None and conv.dilation == (1, 1) and conv.groups == 1
-    return Conv2dBF16Function.apply(x, conv.weight, conv.stride[0], conv.padding[0], packed)
+    return Conv2dBF16Function.apply(x, conv.weight, conv.stride[0], conv.padding[0], packed, current_shadow(conv.weight))
 
 
 TRAIN_PRECISIONS = ("fp32", "bf16")

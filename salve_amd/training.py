@@ -29,6 +29,7 @@ from torch import Tensor, nn
 
 from salve_amd.evaluate import ClassAccuracyMeter
 from salve_amd.models.trainable import TRAIN_NORMS, TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
+from salve_amd.optim import OPTIMS, HipAdam
 from salve_amd.training_config import TrainingConfig
 
 CRIT_ACC_STAT = "val_mAcc"   # scripts/train.py:85: the checkpoint-selection criterion
@@ -44,6 +45,11 @@ def _check_norm(norm: str) -> None:
         raise ValueError(f"training norm must be one of {TRAIN_NORMS}, got {norm!r}")
 
 
+def _check_optim(optim: str) -> None:
+    if optim not in OPTIMS:
+        raise ValueError(f"training optimiser must be one of {OPTIMS}, got {optim!r}")
+
+
 def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch") -> nn.Module:
     """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored.
     precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision).
@@ -56,9 +62,15 @@ def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch"
     return model.set_train_precision(precision).set_train_norm(norm).cuda()
 
 
-def get_optimizer(args: TrainingConfig, model: nn.Module) -> torch.optim.Optimizer:
-    """Adam(lr=base_lr, weight_decay) -- the only algorithm the reference knows (salve/train_utils.py:173-180)."""
+def get_optimizer(args: TrainingConfig, model: nn.Module, optim: str = "torch") -> torch.optim.Optimizer:
+    """Adam(lr=base_lr, weight_decay) -- the only algorithm the reference knows (salve/train_utils.py:173-180).
+    optim: "torch" (torch.optim.Adam) or "hip" (opt-in: salve_amd.optim.HipAdam, the same update in one HIP launch, the same
+    state and state dict; for a model that trains in bf16 it also keeps the convolution weights' bf16 copies current)."""
+    _check_optim(optim)
     if args.optimizer_algo == "adam":
+        if optim == "hip":
+            return HipAdam(model.parameters(), lr=args.base_lr, weight_decay=args.weight_decay,
+                           bf16_shadow=getattr(model, "train_precision", "fp32") == "bf16")
         return torch.optim.Adam(model.parameters(), lr=args.base_lr, weight_decay=args.weight_decay)
     raise RuntimeError("Unknown optimizer")
 
@@ -175,27 +187,29 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
 
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
-          norm: str = "torch") -> Dict[str, list]:
+          norm: str = "torch", optim: str = "torch") -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
     checkpoint's state dict (strict).  precision: "fp32" (default) or "bf16" -- the checkpoint is fp32 either way (fp32 master
     weights), with the same keys.  norm: "torch" (default) or "hip", the fused HIP BatchNorm -- same parameters, buffers and
-    checkpoint."""
+    checkpoint.  optim: "torch" (default) or "hip", HipAdam -- the checkpoint's "optimizer" entry keeps torch.optim.Adam's format."""
     _check_precision(precision)
     _check_norm(norm)
+    _check_optim(optim)
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm)
+    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim)
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
-                   precision: str = "fp32", norm: str = "torch") -> Dict[str, list]:
+                   precision: str = "fp32", norm: str = "torch", optim: str = "torch") -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
     split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON."""
     _check_precision(precision)
     _check_norm(norm)
+    _check_optim(optim)
     get_train_transform(args)   # (the refusals of the on-disk path: photometric augmentation, crop-with-padding)
     want = torch.bfloat16 if precision == "bf16" else torch.float32
     for src in (train_source, val_source):
@@ -204,10 +218,11 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm)
+    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim)
 
 
-def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str) -> Dict[str, list]:
+def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str,
+         optim: str = "torch") -> Dict[str, list]:
     """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources."""
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
@@ -216,7 +231,7 @@ def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_
         from salve_amd import train_utils
 
         train_utils.load_model_checkpoint(init_ckpt, model, args)
-    optimizer = get_optimizer(args, model)
+    optimizer = get_optimizer(args, model, optim)
     out = Path(results_dir)
     out.mkdir(parents=True, exist_ok=True)
     results: Dict[str, list] = defaultdict(list)

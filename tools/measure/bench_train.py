@@ -4,10 +4,15 @@ beside it, in the same process and alternating (context only: the product never 
 the reference's fp32 step and the opt-in bf16 mixed-precision step (TrainableEarlyFusionCEResnet.set_train_precision) one after
 the other in the same process; the torch step of a precision runs F.conv2d in that precision.  --norm torch,hip times the step
 with torch's BatchNorm and with the opt-in fused HIP BatchNorm (TrainableEarlyFusionCEResnet.set_train_norm), alternating the two
-step by step inside the same process; the event split then also reports the time inside the salve_bn_* calls.
+step by step inside the same process; the event split then also reports the time inside the salve_bn_* calls.  --optim
+torch,fused,hip times the step with torch.optim.Adam (the default), torch.optim.Adam(fused=True) and the opt-in HipAdam
+(salve_amd/optim.py; with bf16 it also writes the convolution weights' bf16 copies), each on its own copy of the model (a
+weight's bf16 copy belongs to the parameter, so the variants cannot share one), alternating step by step.  Without hip in the
+list the model's weights are converted to channels_last as before; with it every variant keeps the contiguous weights that
+training.get_model creates (HipAdam refuses non-contiguous parameters), so those lines are not comparable with earlier tables.
 
     python tools/measure/bench_train.py [--configs 50:1,152:2] [--batches 64,256] [--steps 3] [--warmup 1] [--hw 224]
-                                        [--precision fp32,bf16] [--norm torch,hip]
+                                        [--precision fp32,bf16] [--norm torch,hip] [--optim torch,fused,hip]
 
 Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_train.py ...` on its own.
 """
@@ -15,6 +20,7 @@ Per-kernel times: run this under `rocprofv3 --kernel-trace --stats -- python too
 from __future__ import annotations
 
 import argparse
+import copy
 import sys
 import time
 from pathlib import Path
@@ -27,6 +33,7 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 from salve_amd.models import trainable  # noqa: E402
+from salve_amd.optim import HipAdam  # noqa: E402
 
 MODS = {1: ["floor_rgb_texture"], 2: ["ceiling_rgb_texture", "floor_rgb_texture"], 3: ["ceiling_rgb_texture", "floor_rgb_texture", "layout"]}
 _events = []
@@ -91,7 +98,11 @@ def main() -> None:
     ap.add_argument("--no-torch", action="store_true", help="skip the F.conv2d comparison")
     ap.add_argument("--precision", default="fp32", help="training precisions, comma separated: fp32, bf16")
     ap.add_argument("--norm", default="torch", help="BatchNorm implementations, comma separated: torch, hip (alternated step by step)")
+    ap.add_argument("--optim", default="torch", help="optimisers, comma separated: torch, fused (torch's fused=True), hip (alternated step by step)")
     a = ap.parse_args()
+    optims = a.optim.split(",")
+    if not optims or any(o not in ("torch", "fused", "hip") for o in optims):
+        ap.error("--optim takes a comma-separated list of torch, fused, hip")
     precs = a.precision.split(",")
     if not precs or any(p not in trainable.TRAIN_PRECISIONS for p in precs):
         ap.error(f"--precision takes a comma-separated list of {trainable.TRAIN_PRECISIONS}")
@@ -108,32 +119,39 @@ def main() -> None:
             torch.manual_seed(0)
             model = trainable.TrainableEarlyFusionCEResnet(layers, False, 2, SimpleNamespace(modalities=MODS[nm])).to(dev).train()
             model.set_train_precision(prec)
-            model = model.to(memory_format=torch.channels_last)
-            opt = torch.optim.Adam(model.parameters(), lr=1e-4)
+            if "hip" not in optims:   # HipAdam takes contiguous parameters, as training.get_model creates them: with it in the list
+                model = model.to(memory_format=torch.channels_last)   # every variant keeps them, so the variants differ in the optimiser only
+            variants = []   # (optimiser name, its model, its optimiser)
+            for o in optims:
+                mo = model if o == optims[-1] else copy.deepcopy(model)
+                variants.append((o, mo, HipAdam(mo.parameters(), lr=1e-4, bf16_shadow=prec == "bf16") if o == "hip" else
+                                 torch.optim.Adam(mo.parameters(), lr=1e-4, fused=True if o == "fused" else None)))
             xs = [torch.randn(batch, 3, a.hw, a.hw, device=dev) for _ in range(2 * nm)]
             y = torch.randint(0, 2, (batch,), device=dev)
             impls = [("hip", _hip_conv[prec])] + ([] if a.no_torch else [("torch", _torch_conv)])
-            res = {(norm, k): [] for norm in norms for k, _ in impls}
-            split = {norm: [] for norm in norms}
+            res = {(o, norm, k): [] for o in optims for norm in norms for k, _ in impls}
+            split = {(o, norm): [] for o in optims for norm in norms}
             for i in range(a.warmup + a.steps):
-                for norm in norms:
-                    model.set_train_norm(norm)
-                    for name, impl in impls:
-                        dt, _, _ = timed(model, opt, xs, y, impl, False, prec)
-                        if i >= a.warmup:
-                            res[(norm, name)].append(dt)
+                for o, model, opt in variants:
+                    for norm in norms:
+                        model.set_train_norm(norm)
+                        for name, impl in impls:
+                            dt, _, _ = timed(model, opt, xs, y, impl, False, prec)
+                            if i >= a.warmup:
+                                res[(o, norm, name)].append(dt)
             for i in range(a.steps):   # separate steps with an event pair around every HIP convolution (and HIP BatchNorm) call
-                for norm in norms:
-                    model.set_train_norm(norm)
-                    split[norm].append(timed(model, opt, xs, y, _hip_conv[prec], True, prec))
+                for o, model, opt in variants:
+                    for norm in norms:
+                        model.set_train_norm(norm)
+                        split[(o, norm)].append(timed(model, opt, xs, y, _hip_conv[prec], True, prec))
             setattr(trainable, _conv_attr[prec], _hip_conv[prec])
             trainable._run = _hip_run
             trainable._run_bn = _hip_run_bn
             med = {k: sorted(v)[len(v) // 2] for k, v in res.items()}
-            for norm in norms:
-                sp = sorted(split[norm], key=lambda t: t[0])[len(split[norm]) // 2]
-                step_s = med[(norm, "hip")]
-                tag = ("" if prec == "fp32" else f" {prec}") + ("" if norms == ["torch"] else f" norm {norm}")
+            for o, norm in ((o, norm) for o in optims for norm in norms):
+                sp = sorted(split[(o, norm)], key=lambda t: t[0])[len(split[(o, norm)]) // 2]
+                step_s = med[(o, norm, "hip")]
+                tag = ("" if prec == "fp32" else f" {prec}") + ("" if norms == ["torch"] else f" norm {norm}") + ("" if optims == ["torch"] else f" optim {o}")
                 bn = sp[2].get("bn", 0.0)
                 line = (f"resnet{layers} {6 * nm}ch batch {batch}{tag}: step {step_s * 1e3:.1f} ms ({batch / step_s:.0f} samples/s); "
                         f"HIP convolutions {sp[1] * 1e3:.1f} ms of a {sp[0] * 1e3:.1f} ms event-split step "
@@ -142,16 +160,20 @@ def main() -> None:
                 if norm == "hip":
                     line += f"HIP BatchNorm {bn * 1e3:.1f} ms, "
                 line += f"torch + host {(sp[0] - sp[1] - bn) * 1e3:.1f} ms"
-                if (norm, "torch") in med:
-                    line += f"; same step with F.conv2d: {med[(norm, 'torch')] * 1e3:.1f} ms ({batch / med[(norm, 'torch')]:.0f} samples/s)"
-                fp32_step[(layers, nm, batch, prec, norm)] = step_s
-                if prec != "fp32" and (layers, nm, batch, "fp32", norm) in fp32_step:
-                    line += f"; {step_s / fp32_step[(layers, nm, batch, 'fp32', norm)]:.2f} x the fp32 step's time"
-                if norm != "torch" and (norm, "hip") in med and ("torch", "hip") in med:
-                    line += f"; {step_s / med[('torch', 'hip')]:.2f} x the torch-norm step's time"
+                if (o, norm, "torch") in med:
+                    line += f"; same step with F.conv2d: {med[(o, norm, 'torch')] * 1e3:.1f} ms ({batch / med[(o, norm, 'torch')]:.0f} samples/s)"
+                fp32_step[(layers, nm, batch, prec, norm, o)] = step_s
+                if prec != "fp32" and (layers, nm, batch, "fp32", norm, o) in fp32_step:
+                    line += f"; {step_s / fp32_step[(layers, nm, batch, 'fp32', norm, o)]:.2f} x the fp32 step's time"
+                if norm != "torch" and (o, "torch", "hip") in med:
+                    line += f"; {step_s / med[(o, 'torch', 'hip')]:.2f} x the torch-norm step's time"
+                if o != "torch" and ("torch", norm, "hip") in med:
+                    line += f"; {step_s / med[('torch', norm, 'hip')]:.3f} x the torch.optim.Adam step's time"
+                if o == "torch" and optims != ["torch"]:
+                    v = res[(o, norm, "hip")]
+                    line += f"; its steps {min(v) * 1e3:.1f} .. {max(v) * 1e3:.1f} ms"
                 print(line, flush=True)
-            model.set_train_norm("torch")
-            del model, opt, xs
+            del variants, model, opt, xs
             torch.cuda.empty_cache()
 
 
