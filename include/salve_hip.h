@@ -44,7 +44,7 @@ typedef enum {
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
                                         salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
-                                        salve_adam_step */
+                                        salve_adam_step, salve_head_* (the training classifier head) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -624,6 +624,60 @@ typedef struct {
 } salve_adam_chunk_t; /* 16 bytes */
 int salve_adam_step(const salve_adam_segment_t* table, int32_t n_segments, const salve_adam_chunk_t* chunk_map, int32_t n_chunks,
                     const salve_adam_segment_t* host_table, const salve_adam_chunk_t* host_chunk_map, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The classifier head of a training step with its loss and accuracy counts on the device (additive within ABI 7): opt-in, fp32
+ * and bf16.  The reference ends its network in resnet.avgpool, flatten and fc (salve/models/early_fusion.py:78-83), forms
+ * softmax probabilities on a clone of the logits and the cross-entropy loss (salve/train_utils.py:18-41), and feeds the arg-max
+ * of the probabilities to a per-class accuracy meter on the host (salve/utils/avg_meter.py: intersection / target counts per
+ * class).  These entries compute all of that in one forward call and its gradient in one backward call
+ * (salve_amd/models/trainable.py: ClassifierHeadHipFunction, salve_amd/evaluate.py: DeviceClassMeter; the default stays torch).
+ *   Layout:  x and dx [B, HW, C], the channel innermost (NHWC), fp32 or bf16 bit patterns (uint16_t), device pointers, 16-byte
+ *            aligned.  weight [K, C] and bias [K] (fc), pooled [B, C], logits, probs, dlogits [B, K], dw [K, C], db [K]: device
+ *            float, always fp32 (weight and pooled 16-byte aligned).  target: device int64 [B].  loss, grad_loss: one device float.
+ *   Shapes:  1 <= B <= 65535, 1 <= HW <= 1024, C a multiple of 8 from 8 to 4096, 2 <= K <= 16 (SALVE_HEAD_MAX_CLASSES); flags 0 or
+ *            SALVE_HEAD_ACCUMULATE_LOSS.  Anything else, a misaligned or null pointer included: SALVE_ERR_BAD_ARG before any
+ *            launch, and 0 workspace bytes for a refused descriptor or pass.
+ *   forward: pooled = the mean over HW (summed in fp32, divided by HW once); logits = pooled . weight^T + bias; probs = the
+ *            max-subtracted softmax of the logits; loss = the mean over the batch of -log_softmax[target] (cross_entropy's default
+ *            reduction).  The meter record (may be NULL: no counts) is updated in place: total[c] += rows whose target is c,
+ *            correct[c] += those whose prediction is c too -- the prediction is the arg-max of the probs just written, the first
+ *            index winning a tie, as torch.argmax(probs, 1) -- and, with SALVE_HEAD_ACCUMULATE_LOSS only, loss_sum +=
+ *            (double)loss * B and loss_rows += B.  A row whose target lies outside [0, K) contributes no loss, no gradient and no
+ *            count, increments bad_targets and indexes nothing.  A NaN in x reaches loss and loss_sum as NaN.
+ *   backward (from the forward's pooled and probs): dlogits = (probs - onehot(target)) * (*grad_loss / B), dw = dlogits^T . pooled,
+ *            db = the column sums of dlogits, dx = (dlogits . weight) / HW broadcast over the HW rows, rounded once for bf16.
+ *   Arithmetic: fp32 sums for pooled, logits, dw, db and dx; the few scalars per row (softmax, the row's loss, dlogits) and the sum
+ *            of the row losses are formed in double and rounded to fp32 once.  Every reduction (over HW, over C, over B, into the
+ *            record) has a fixed order and there are no floating-point atomics: the same inputs give bit-identical results.
+ *            Element offsets are 64-bit.
+ *   Workspace: salve_head_workspace_bytes(d, pass) bytes of device memory; it holds nothing from one call to the next.  The caller
+ *            owns every buffer and zeroes the meter record when a pass begins.  Asynchronous on `stream`; calls on one stream update
+ *            the record one after the other.  All other outputs are overwritten.
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_HEAD_MAX_CLASSES 16
+typedef struct {
+    int32_t B, HW, C, K, flags;
+} salve_head_desc_t;
+typedef struct {
+    int64_t total[SALVE_HEAD_MAX_CLASSES];
+    int64_t correct[SALVE_HEAD_MAX_CLASSES];
+    double loss_sum;
+    int64_t loss_rows;
+    int64_t bad_targets;
+} salve_head_meter_t; /* 280 bytes */
+#define SALVE_HEAD_ACCUMULATE_LOSS 1 /* add this batch to loss_sum / loss_rows (training batches) */
+#define SALVE_HEAD_FWD 0
+#define SALVE_HEAD_BWD 1
+size_t salve_head_workspace_bytes(const salve_head_desc_t* d, int32_t pass);
+int salve_head_f32_forward(const salve_head_desc_t* d, const float* x, const float* weight, const float* bias, const int64_t* target, float* pooled,
+                           float* logits, float* probs, float* loss, salve_head_meter_t* meter, void* ws, size_t ws_bytes, void* stream);
+int salve_head_bf16_forward(const salve_head_desc_t* d, const uint16_t* x, const float* weight, const float* bias, const int64_t* target, float* pooled,
+                            float* logits, float* probs, float* loss, salve_head_meter_t* meter, void* ws, size_t ws_bytes, void* stream);
+int salve_head_f32_backward(const salve_head_desc_t* d, const float* pooled, const float* probs, const int64_t* target, const float* weight,
+                            const float* grad_loss, float* dlogits, float* dw, float* db, float* dx, void* ws, size_t ws_bytes, void* stream);
+int salve_head_bf16_backward(const salve_head_desc_t* d, const float* pooled, const float* probs, const int64_t* target, const float* weight,
+                             const float* grad_loss, float* dlogits, float* dw, float* db, uint16_t* dx, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

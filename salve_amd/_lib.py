@@ -71,6 +71,11 @@ EXPORTED_SYMBOLS = (
     "salve_bev_pano_index_update",
     "salve_layout_pose",
     "salve_adam_step",
+    "salve_head_workspace_bytes",
+    "salve_head_f32_forward",
+    "salve_head_f32_backward",
+    "salve_head_bf16_forward",
+    "salve_head_bf16_backward",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -143,6 +148,23 @@ ADAM_SEGMENT_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<
                                ("weight_decay", "<f4"), ("one_minus_beta1", "<f4"), ("one_minus_beta2", "<f4")])
 ADAM_CHUNK_DTYPE = np.dtype([("segment", "<i4"), ("reserved", "<i4"), ("offset", "<i8")])
 assert ADAM_SEGMENT_DTYPE.itemsize == 80 and ADAM_CHUNK_DTYPE.itemsize == 16
+
+# salve_head_* (include/salve_hip.h: SALVE_HEAD_*, salve_head_desc_t, salve_head_meter_t): the training classifier head.  It stands
+# behind the reference's avgpool + flatten + fc (salve/models/early_fusion.py:78-83), its softmax and cross-entropy
+# (salve/train_utils.py:18-41) and its per-class accuracy meter (salve/utils/avg_meter.py)
+HEAD_MAX_CLASSES = 16
+HEAD_ACCUMULATE_LOSS = 1
+HEAD_FWD, HEAD_BWD = 0, 1
+HEAD_METER_DTYPE = np.dtype([("total", "<i8", (HEAD_MAX_CLASSES,)), ("correct", "<i8", (HEAD_MAX_CLASSES,)), ("loss_sum", "<f8"), ("loss_rows", "<i8"),
+                             ("bad_targets", "<i8")])
+assert HEAD_METER_DTYPE.itemsize == 280
+
+
+class HeadDesc(ctypes.Structure):
+    """salve_head_desc_t"""
+
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "HW", "C", "K", "flags")]
+
 
 _lib = None
 
@@ -242,6 +264,14 @@ def load() -> ctypes.CDLL:
         getattr(lib, name).restype = ctypes.c_int
     lib.salve_adam_step.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     lib.salve_adam_step.restype = ctypes.c_int
+    lib.salve_head_workspace_bytes.argtypes = [ctypes.POINTER(HeadDesc), i32]
+    lib.salve_head_workspace_bytes.restype = sz
+    for name in ("salve_head_f32_forward", "salve_head_bf16_forward"):   # d, x, weight, bias, target, pooled, logits, probs, loss, meter
+        getattr(lib, name).argtypes = [ctypes.POINTER(HeadDesc)] + [vp] * 9 + [vp, sz, vp]
+        getattr(lib, name).restype = ctypes.c_int
+    for name in ("salve_head_f32_backward", "salve_head_bf16_backward"):   # d, pooled, probs, target, weight, grad_loss, dlogits, dw, db, dx
+        getattr(lib, name).argtypes = [ctypes.POINTER(HeadDesc)] + [vp] * 9 + [vp, sz, vp]
+        getattr(lib, name).restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

@@ -20,6 +20,7 @@ from typing import Any, Dict, List, Optional, Sequence
 import numpy as np
 import torch
 
+from salve_amd import _lib
 from salve_amd.utils import pr_utils
 
 
@@ -55,6 +56,35 @@ class ClassAccuracyMeter:
     def get_metrics(self):
         accs = self.correct / (self.total + 1e-10)
         return accs, float(np.mean(accs))
+
+
+class DeviceClassMeter:
+    """ClassAccuracyMeter's counts and run_epoch's loss sum kept ON THE DEVICE: it owns the record (include/salve_hip.h:
+    salve_head_meter_t) that the HIP classifier head (salve_amd/models/trainable.py: ClassifierHeadHipFunction) updates batch by
+    batch, so that a pass over a split reads the device once, at its end, instead of twice per batch."""
+
+    def __init__(self, num_classes: int, device) -> None:
+        if not 2 <= int(num_classes) <= _lib.HEAD_MAX_CLASSES:
+            raise ValueError(f"DeviceClassMeter counts 2 to {_lib.HEAD_MAX_CLASSES} classes, got {num_classes}")
+        self.num_classes = int(num_classes)
+        self.record = torch.zeros(_lib.HEAD_METER_DTYPE.itemsize // 8, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        """Zero the record, on the current stream (no synchronisation)."""
+        self.record.zero_()
+
+    def read(self):
+        """(class accuracies, their mean, average loss): the ONE device-to-host copy.  The accuracies are
+        ClassAccuracyMeter.get_metrics' formula (epsilon 1e-10), the average loss is loss_sum / loss_rows over the batches that
+        were accumulated (0.0 if none).  Raises if a target outside [0, num_classes) was met: such rows were left out."""
+        rec = self.record.cpu().numpy().view(_lib.HEAD_METER_DTYPE)[0]
+        bad = int(rec["bad_targets"])
+        if bad != 0:
+            raise RuntimeError(f"{bad} targets lie outside [0, {self.num_classes}): those rows were left out of the loss, its gradient and the counts")
+        k = self.num_classes
+        accs = rec["correct"][:k].astype(np.float64) / (rec["total"][:k].astype(np.float64) + 1e-10)
+        rows = int(rec["loss_rows"])
+        return accs, float(np.mean(accs)), (float(rec["loss_sum"]) / rows if rows else 0.0)
 
 
 def save_edge_classifications_to_disk(serialization_save_dir: str, batch_idx: int, y_hat: torch.Tensor, y_true: torch.Tensor,

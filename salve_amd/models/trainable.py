@@ -17,6 +17,11 @@ With the opt-in HIP Adam (salve_amd/optim.py: HipAdam, `--optim hip`) the bf16 c
 the optimiser's step wrote, instead of casting the fp32 master on every call, while that copy is provably current
 (`optim.current_shadow`); otherwise they cast as before.  The same bits either way.
 
+Opt-in HIP classifier head (`set_train_head("hip")`, `forward_loss` / `forward_packed_loss`): average pool, fc, softmax,
+cross-entropy and the accuracy counts run on salve_amd/csrc/head_train.hip (salve_head_*) through `ClassifierHeadHipFunction`, one
+fused forward and one fused backward, with the loss and the counts accumulated in a device record (salve_amd.evaluate.
+DeviceClassMeter) so that an epoch never waits for the device between batches.  torch's head stays the default.
+
 `TrainableEarlyFusionCEResnet` subclasses `EarlyFusionCEResnet`: the same parameters and buffers under the same names, so state
 dicts move between the two with strict=True, and a checkpoint trained here loads into the inference model (fp16 or fp32 engine).
 There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
@@ -263,6 +268,81 @@ def batch_norm_hip(bn: nn.BatchNorm2d, x: Tensor, residual: Optional[Tensor] = N
                                       relu, bn.eps, bn.momentum, training)
 
 
+TRAIN_HEADS = ("torch", "hip")
+_HEAD_ENTRY = {torch.float32: "salve_head_f32", torch.bfloat16: "salve_head_bf16"}
+
+
+def _run_head(fn: str, desc: "_lib.HeadDesc", pass_: int, ptrs, device) -> None:
+    """One salve_head_* call: `ptrs` are the entry's pointer arguments in order (tensors or None)."""
+    lib = _lib.load()
+    nbytes = int(lib.salve_head_workspace_bytes(ctypes.byref(desc), pass_))
+    if nbytes == 0:
+        raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    args = [ctypes.c_void_p(None if t is None else t.data_ptr()) for t in ptrs]
+    st = getattr(lib, fn)(ctypes.byref(desc), *args, ctypes.c_void_p(ws.data_ptr()), nbytes, ctypes.c_void_p(stream))
+    _lib.check(st, fn)
+
+
+class ClassifierHeadHipFunction(torch.autograd.Function):
+    """loss, probs, logits = the classifier head on the HIP entries (salve_head_*), forward and backward: average pool over H x W,
+    fc, max-subtracted softmax, cross_entropy(logits, target) with its default mean reduction, and the per-class accuracy counts.
+
+    x: the last block's output, fp32 or bf16 CUDA [B, C, H, W] (channels_last memory is used as is; other layouts are copied);
+    weight [K, C], bias [K]: fc's fp32 parameters; target: int64 CUDA [B]; record: None or a DeviceClassMeter's record, updated in
+    place on the stream (counts always; the loss sum only with accumulate_loss).  Returns (loss, probs, logits): loss a 0-dim fp32
+    tensor with a gradient towards x, weight and bias; probs and logits [B, K] fp32, not differentiable.  Nothing here reads the
+    device: a target outside [0, K) is counted in the record (DeviceClassMeter.read raises) and contributes nothing."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, weight: Tensor, bias: Tensor, target: Tensor, record: Optional[Tensor], accumulate_loss: bool):
+        if x.dtype not in _HEAD_ENTRY:
+            raise RuntimeError(f"ClassifierHeadHipFunction: x must be float32 or bfloat16, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError(f"ClassifierHeadHipFunction: x is on {x.device}; the HIP head runs on the HIP device only (no CPU fallback)")
+        if x.dim() != 4:
+            raise RuntimeError(f"ClassifierHeadHipFunction: x must be [B, C, H, W], got {tuple(x.shape)}")
+        b, c, h, w = x.shape
+        k = weight.shape[0]
+        for name, t, dt, shape in (("weight", weight, torch.float32, (k, c)), ("bias", bias, torch.float32, (k,)), ("target", target, torch.int64, (b,)),
+                                   ("record", record, torch.int64, (_lib.HEAD_METER_DTYPE.itemsize // 8,))):
+            if t is None and name == "record":
+                continue
+            if t.device != x.device:
+                raise RuntimeError(f"ClassifierHeadHipFunction: {name} is on {t.device}, x on {x.device} (no CPU fallback)")
+            if t.dtype != dt or tuple(t.shape) != shape:
+                raise RuntimeError(f"ClassifierHeadHipFunction: {name} must be {dt} {list(shape)}, got {t.dtype} {list(t.shape)}")
+        if record is not None and not record.is_contiguous():
+            raise RuntimeError("ClassifierHeadHipFunction: the meter record must be contiguous")
+        xn = _nhwc(x.detach(), c)
+        weight, bias, target = weight.detach().contiguous(), bias.detach().contiguous(), target.contiguous()
+        pooled = torch.empty((b, c), dtype=torch.float32, device=x.device)
+        logits = torch.empty((b, k), dtype=torch.float32, device=x.device)
+        probs = torch.empty((b, k), dtype=torch.float32, device=x.device)
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        desc = (b, h * w, c, k, _lib.HEAD_ACCUMULATE_LOSS if accumulate_loss else 0)
+        _run_head(_HEAD_ENTRY[x.dtype] + "_forward", _lib.HeadDesc(*desc), _lib.HEAD_FWD,
+                  (xn, weight, bias, target, pooled, logits, probs, loss, record), x.device)
+        ctx.save_for_backward(pooled, probs, target, weight)
+        ctx.desc, ctx.hw, ctx.act = desc, (h, w), x.dtype
+        ctx.mark_non_differentiable(probs, logits)
+        return loss, probs, logits
+
+    @staticmethod
+    def backward(ctx, g_loss: Tensor, g_probs, g_logits):
+        pooled, probs, target, weight = ctx.saved_tensors
+        b, _, c, k, _ = ctx.desc
+        g = g_loss.detach().to(torch.float32).reshape(()).contiguous()
+        dxn = torch.empty((b, ctx.hw[0], ctx.hw[1], c), dtype=ctx.act, device=pooled.device)
+        dlogits = torch.empty((b, k), dtype=torch.float32, device=pooled.device)
+        dw = torch.empty((k, c), dtype=torch.float32, device=pooled.device)
+        db = torch.empty((k,), dtype=torch.float32, device=pooled.device)
+        _run_head(_HEAD_ENTRY[ctx.act] + "_backward", _lib.HeadDesc(*ctx.desc), _lib.HEAD_BWD,
+                  (pooled, probs, target, weight, g, dlogits, dw, db, dxn), pooled.device)
+        return dxn.permute(0, 3, 1, 2), dw, db, None, None, None
+
+
 def _conv(precision: str):
     """The convolution of a training precision, looked up at call time (tools/measure/bench_train.py swaps these functions)."""
     return conv2d_bf16 if precision == "bf16" else conv2d_f32
@@ -320,10 +400,16 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     `set_train_norm("hip")` opts into the HIP BatchNorm: one fused operation per BatchNorm (bn + relu after the stem, conv1 and
     conv2, plain bn on the downsample branch, bn + add + relu at the end of a block), in fp32 and in bf16 (no casts around
     BatchNorm then).  Train mode uses batch statistics; eval mode under torch.no_grad() (the validation pass) the eval form; eval
-    mode with gradients enabled runs the torch path, which has a backward pass.  The same parameters and buffers either way."""
+    mode with gradients enabled runs the torch path, which has a backward pass.  The same parameters and buffers either way.
+
+    `set_train_head("hip")` opts into the HIP classifier head for `forward_loss` / `forward_packed_loss`, which return (probs,
+    loss): the last block's output goes through ClassifierHeadHipFunction (average pool, fc, softmax, cross-entropy and the
+    accuracy counts in one forward and one backward, in fp32 and in bf16) instead of torch's avgpool / flatten / cast / fc /
+    softmax / cross_entropy.  `forward` and `forward_packed`, which return logits, run torch's head in both settings."""
 
     _train_precision = "fp32"
     _train_norm = "torch"
+    _train_head = "torch"
 
     def set_train_precision(self, precision: str) -> "TrainableEarlyFusionCEResnet":
         """"fp32" (the default, the reference's precision) or "bf16" (opt-in mixed precision).  Returns self."""
@@ -348,24 +434,46 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     def train_norm(self) -> str:
         return self._train_norm
 
+    def set_train_head(self, head: str) -> "TrainableEarlyFusionCEResnet":
+        """"torch" (the default: avgpool, fc, softmax and cross_entropy as separate torch operations) or "hip" (opt-in:
+        ClassifierHeadHipFunction) for `forward_loss` / `forward_packed_loss`.  Returns self."""
+        if head not in TRAIN_HEADS:
+            raise ValueError(f"training head must be one of {TRAIN_HEADS}, got {head!r}")
+        self._train_head = head
+        return self
+
+    @property
+    def train_head(self) -> str:
+        return self._train_head
+
     def forward(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor] = None, x4: Optional[Tensor] = None, x5: Optional[Tensor] = None,
                 x6: Optional[Tensor] = None) -> Tensor:
+        return self._from_stem(self._cat(self._images(x1, x2, x3, x4, x5, x6)), packed=False)
+
+    def _images(self, x1, x2, x3, x4, x5, x6):
         n = num_input_images(self.modalities)
         xs = [x1, x2, x3, x4, x5, x6][:n]
         if any(x is None for x in xs):
             raise RuntimeError(f"{n} input images are required for modalities {self.modalities}")
         if x1.device.type != "cuda":
             raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
+        return xs
+
+    def _cat(self, xs) -> Tensor:
         x = torch.cat(xs, dim=1)
         if self._train_precision == "bf16":
             x = x.to(torch.bfloat16)
-        return self._from_stem(x, packed=False)
+        return x
 
     def forward_packed(self, x: Tensor) -> Tensor:
         """`forward` on the input as the stem convolution reads it: x [B, H, W, Cp], contiguous NHWC, Cp = the 3 * images channels
         in `forward`'s concatenation order zero-padded to a multiple of 8, in the training precision (float32 / bfloat16) -- what
         salve_bev_train_tiles writes (salve_amd.train_render).  The same graph as `forward` from the stem on, without its torch.cat,
         cast and padding copy: the same kernels on the same bytes, so logits and gradients are bit-identical."""
+        return self._from_stem(self._packed(x), packed=True)
+
+    def _packed(self, x: Tensor) -> Tensor:
+        """forward_packed's input checked, as the NCHW view of its NHWC bytes (the stem uses them as they are)."""
         cp = _pad8(3 * num_input_images(self.modalities))
         want = torch.bfloat16 if self._train_precision == "bf16" else torch.float32
         if x.dim() != 4 or x.shape[3] != cp:
@@ -376,9 +484,45 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
             raise RuntimeError("TrainableEarlyFusionCEResnet runs on the HIP device only (no CPU fallback)")
         if not x.is_contiguous():
             raise RuntimeError("forward_packed takes a contiguous NHWC tensor")
-        return self._from_stem(x.permute(0, 3, 1, 2), packed=True)   # (an NCHW view of the NHWC bytes: the stem uses them as they are)
+        return x.permute(0, 3, 1, 2)
+
+    def forward_loss(self, x1: Tensor, x2: Tensor, x3: Optional[Tensor], x4: Optional[Tensor], x5: Optional[Tensor], x6: Optional[Tensor],
+                     is_match: Tensor, meters=None, accumulate_loss: bool = False):
+        """(softmax probabilities [B, K], cross-entropy loss) of a batch, as training.cross_entropy_forward forms them.  With head
+        "torch": `forward`'s graph followed by softmax on a detached clone of the logits and F.cross_entropy(logits,
+        is_match.squeeze()) -- the present results; `meters` must be None (the host meter is the caller's).  With head "hip": the
+        trunk's output through ClassifierHeadHipFunction; meters: None or a salve_amd.evaluate.DeviceClassMeter, whose counts this
+        batch is added to on the device (and, with accumulate_loss, its loss sum).  The caller chooses the gradient mode."""
+        return self._loss(self._cat(self._images(x1, x2, x3, x4, x5, x6)), False, is_match, meters, accumulate_loss)
+
+    def forward_packed_loss(self, x_packed: Tensor, is_match: Tensor, meters=None, accumulate_loss: bool = False):
+        """`forward_loss` on `forward_packed`'s input: the same kernels on the same bytes, so the results are bit-identical."""
+        return self._loss(self._packed(x_packed), True, is_match, meters, accumulate_loss)
+
+    def _loss(self, x: Tensor, packed: bool, is_match: Tensor, meters, accumulate_loss: bool):
+        if self._train_head == "hip":
+            record = None
+            if meters is not None:
+                if meters.num_classes != self.fc.out_features:
+                    raise RuntimeError(f"the meter counts {meters.num_classes} classes, the model has {self.fc.out_features}")
+                record = meters.record
+            loss, probs, _ = ClassifierHeadHipFunction.apply(self._features(x, packed), self.fc.weight, self.fc.bias, is_match.reshape(-1), record,
+                                                             bool(accumulate_loss))
+            return probs, loss
+        if meters is not None:
+            raise RuntimeError("a DeviceClassMeter is updated by the HIP head only: set_train_head(\"hip\")")
+        logits = self._from_stem(x, packed)
+        probs = F.softmax(logits.detach().clone(), dim=1)
+        return probs, F.cross_entropy(logits, is_match.squeeze())
 
     def _from_stem(self, x: Tensor, packed: bool) -> Tensor:
+        x = torch.flatten(self.resnet.avgpool(self._features(x, packed)), 1)
+        if self._train_precision == "bf16":
+            x = x.float()
+        return self.fc(x)
+
+    def _features(self, x: Tensor, packed: bool) -> Tensor:
+        """The last block's output [B, C, H, W] in the training precision."""
         bf16 = self._train_precision == "bf16"
         conv, bn = _conv(self._train_precision), (_bn_bf16 if bf16 else _bn)
         r = self.resnet
@@ -395,7 +539,4 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
             for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
                 for blk in layer:
                     x = block(blk, x, conv, bn)
-        x = torch.flatten(r.avgpool(x), 1)
-        if bf16:
-            x = x.float()
-        return self.fc(x)
+        return x

@@ -2,14 +2,17 @@
 
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
-                              [--norm {torch,hip}] [--optim {torch,hip}] [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]]]
+                              [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}]
+                              [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
 convolutions, fp32 master weights, gradients and checkpoint); the default fp32 is the reference's.  --norm hip opts into the HIP
 BatchNorm with fused ReLU and residual add (same checkpoint); the default is torch's BatchNorm.  --optim hip opts into HipAdam
 (salve_amd/optim.py): torch.optim.Adam's update in one HIP launch per step, which with --precision bf16 also writes the
-convolution weights' bf16 copies; the checkpoint's "optimizer" entry keeps torch's format.  See salve_amd/training.py.
+convolution weights' bf16 copies; the checkpoint's "optimizer" entry keeps torch's format.  --head hip opts into the fused HIP
+classifier head (average pool, fc, softmax, cross-entropy, accuracy counts): loss and accuracy are accumulated on the device and
+read once per pass, so the host never waits for the device between batches; the default is torch's head.  See salve_amd/training.py.
 --render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
 val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
 A configuration whose modalities include "layout" also needs DIR/layouts.npz: the layouts are posed and drawn on the GPU.
@@ -46,6 +49,8 @@ def main(argv=None) -> None:
                     help="torch (default: nn.BatchNorm2d) or hip (BatchNorm with fused ReLU and residual add on the HIP kernels)")
     ap.add_argument("--optim", choices=("torch", "hip"), default="torch",
                     help="torch (default: torch.optim.Adam) or hip (the same update in one HIP launch; with bf16 it also writes the weights' bf16 copies)")
+    ap.add_argument("--head", default="torch",
+                    help="torch (default: avgpool, fc, softmax, cross_entropy) or hip (one fused HIP forward and backward; loss and accuracy stay on the device)")
     ap.add_argument("--render-from", default=None, metavar="DIR",
                     help="render the training batches on the GPU from DIR/panos_rgb.npy, panos_depth.npy, train.json, val.json")
     ap.add_argument("--identity", choices=("kept", "batch"), default=None,
@@ -55,6 +60,7 @@ def main(argv=None) -> None:
     ap.add_argument("--prefetch", action="store_true",
                     help="--resident-panos: upload the next batch's missing panoramas beside the training step (N at least 4 x batch size)")
     a = ap.parse_args(argv)
+    training._check_head(a.head)
     if a.render_from is None and (a.identity is not None or a.resident_panos is not None):
         raise SystemExit("--identity and --resident-panos belong to --render-from DIR")
     if a.resident_panos is not None:
@@ -100,9 +106,10 @@ def main(argv=None) -> None:
             src.set_examples(*examples[split])
             sources[split] = src
         results = training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
-                                          norm=a.norm, optim=a.optim)
+                                          norm=a.norm, optim=a.optim, head=a.head)
     else:
-        results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim)
+        results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
+                                 head=a.head)
     logging.info(f"results in {out}: {results}")
 
 

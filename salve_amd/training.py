@@ -27,8 +27,8 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
-from salve_amd.evaluate import ClassAccuracyMeter
-from salve_amd.models.trainable import TRAIN_NORMS, TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
+from salve_amd.evaluate import ClassAccuracyMeter, DeviceClassMeter
+from salve_amd.models.trainable import TRAIN_HEADS, TRAIN_NORMS, TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
 from salve_amd.optim import OPTIMS, HipAdam
 from salve_amd.training_config import TrainingConfig
 
@@ -50,16 +50,24 @@ def _check_optim(optim: str) -> None:
         raise ValueError(f"training optimiser must be one of {OPTIMS}, got {optim!r}")
 
 
-def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch") -> nn.Module:
+def _check_head(head: str) -> None:
+    if head not in TRAIN_HEADS:
+        raise ValueError(f"training head must be one of {TRAIN_HEADS}, got {head!r}")
+
+
+def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch", head: str = "torch") -> nn.Module:
     """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored.
     precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision).
-    norm: "torch" (nn.BatchNorm2d) or "hip" (opt-in fused HIP BatchNorm: TrainableEarlyFusionCEResnet.set_train_norm)."""
+    norm: "torch" (nn.BatchNorm2d) or "hip" (opt-in fused HIP BatchNorm: TrainableEarlyFusionCEResnet.set_train_norm).
+    head: "torch" (avgpool, fc, softmax, cross_entropy) or "hip" (opt-in fused HIP classifier head with the loss and the accuracy
+    counts kept on the device: TrainableEarlyFusionCEResnet.set_train_head)."""
     _check_precision(precision)
     _check_norm(norm)
+    _check_head(head)
     if not torch.cuda.is_available():
         raise RuntimeError("salve_amd.training needs the HIP device (no CPU fallback)")
     model = TrainableEarlyFusionCEResnet(args.num_layers, args.pretrained, args.num_ce_classes, args)
-    return model.set_train_precision(precision).set_train_norm(norm).cuda()
+    return model.set_train_precision(precision).set_train_norm(norm).set_train_head(head).cuda()
 
 
 def get_optimizer(args: TrainingConfig, model: nn.Module, optim: str = "torch") -> torch.optim.Optimizer:
@@ -81,9 +89,13 @@ def poly_learning_rate(base_lr: float, curr_iter: int, max_iter: int, power: flo
 
 
 def cross_entropy_forward(model: nn.Module, split: str, x1: Tensor, x2: Tensor, x3: Optional[Tensor], x4: Optional[Tensor],
-                          x5: Optional[Tensor], x6: Optional[Tensor], is_match: Tensor) -> Tuple[Tensor, Tensor]:
+                          x5: Optional[Tensor], x6: Optional[Tensor], is_match: Tensor, meters: Optional[DeviceClassMeter] = None,
+                          accumulate_loss: bool = False) -> Tuple[Tensor, Tensor]:
     """(softmax probabilities, cross-entropy loss) as salve/train_utils.py:18-41: with gradients for split == "train", under
-    torch.no_grad() otherwise."""
+    torch.no_grad() otherwise.  A model whose head is "hip" goes through its `forward_loss` (meters, accumulate_loss: see there)."""
+    if getattr(model, "train_head", "torch") == "hip":
+        with torch.set_grad_enabled(split == "train" and torch.is_grad_enabled()):
+            return model.forward_loss(x1, x2, x3, x4, x5, x6, is_match, meters=meters, accumulate_loss=accumulate_loss)
     if split == "train":
         logits = model(x1, x2, x3, x4, x5, x6)
     else:
@@ -94,8 +106,12 @@ def cross_entropy_forward(model: nn.Module, split: str, x1: Tensor, x2: Tensor, 
     return probs, loss
 
 
-def cross_entropy_forward_packed(model: nn.Module, split: str, x_packed: Tensor, is_match: Tensor) -> Tuple[Tensor, Tensor]:
+def cross_entropy_forward_packed(model: nn.Module, split: str, x_packed: Tensor, is_match: Tensor, meters: Optional[DeviceClassMeter] = None,
+                                 accumulate_loss: bool = False) -> Tuple[Tensor, Tensor]:
     """`cross_entropy_forward` for the packed input of salve_amd.train_render ([B, H, W, Cp], `model.forward_packed`)."""
+    if getattr(model, "train_head", "torch") == "hip":
+        with torch.set_grad_enabled(split == "train" and torch.is_grad_enabled()):
+            return model.forward_packed_loss(x_packed, is_match, meters=meters, accumulate_loss=accumulate_loss)
     if split == "train":
         logits = model.forward_packed(x_packed)
     else:
@@ -150,7 +166,10 @@ def _unpack(args: TrainingConfig, example):
 def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
     """One pass over a split (scripts/train.py:169-278): train mode + Adam steps + the poly schedule for "train", eval mode
     otherwise.  Returns {"avg_loss", "mAcc"}; as in the reference, avg_loss counts training batches only (0 for val).
-    `data_loader`: a DataLoader over ZindData, or a train_render.RenderedTrainSource (2-tuples, through `model.forward_packed`)."""
+    `data_loader`: a DataLoader over ZindData, or a train_render.RenderedTrainSource (2-tuples, through `model.forward_packed`).
+    A model whose head is "hip" runs `_run_epoch_device`: the same pass without a wait for the device between batches."""
+    if getattr(model, "train_head", "torch") == "hip":
+        return _run_epoch_device(args, epoch, model, data_loader, optimizer, split)
     model.train() if split == "train" else model.eval()
     loss_sum, loss_n = 0.0, 0
     meter = ClassAccuracyMeter(args.num_ce_classes)
@@ -186,30 +205,67 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
     return {"avg_loss": loss_sum / loss_n if loss_n else 0.0, "mAcc": float(mAcc)}
 
 
+def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
+    """`run_epoch` for a model with the HIP head: the loss sum and the per-class counts live in a DeviceClassMeter that the head's
+    forward updates, so no batch copies anything to the host -- the host enqueues batch after batch and reads the meter once at the
+    end of the pass.  Only the iterations that log (`it % print_every == 0`, training) read their loss.  Same schedule, same
+    returned dict."""
+    model.train() if split == "train" else model.eval()
+    dev = next(model.parameters()).device
+    meter = DeviceClassMeter(args.num_ce_classes, dev)
+    max_iter = args.num_epochs * len(data_loader)
+    t0 = time.time()
+    train = split == "train"
+    for it, example in enumerate(data_loader):
+        if len(example) == 2:
+            probs, loss = cross_entropy_forward_packed(model, split, example[0], example[1], meters=meter, accumulate_loss=train)
+        else:
+            xs, is_match = _unpack(args, example)
+            xs = tuple(None if x is None else x.to(dev, non_blocking=True) for x in xs)
+            probs, loss = cross_entropy_forward(model, split, *xs, is_match.to(dev, non_blocking=True), meters=meter, accumulate_loss=train)
+        current_iter = epoch * len(data_loader) + it + 1
+        if train:
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            if args.lr_annealing_strategy == "poly":   # decayed after the step, as the reference does
+                lr = poly_learning_rate(args.base_lr, current_iter, max_iter, power=args.poly_lr_power)
+                for group in optimizer.param_groups:
+                    group["lr"] = lr
+            if it % max(1, args.print_every) == 0:
+                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f} ({time.time() - t0:.1f} s)")
+    accs, mAcc, avg_loss = meter.read()
+    logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
+    return {"avg_loss": avg_loss, "mAcc": float(mAcc)}
+
+
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
-          norm: str = "torch", optim: str = "torch") -> Dict[str, list]:
+          norm: str = "torch", optim: str = "torch", head: str = "torch") -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
     checkpoint's state dict (strict).  precision: "fp32" (default) or "bf16" -- the checkpoint is fp32 either way (fp32 master
     weights), with the same keys.  norm: "torch" (default) or "hip", the fused HIP BatchNorm -- same parameters, buffers and
-    checkpoint.  optim: "torch" (default) or "hip", HipAdam -- the checkpoint's "optimizer" entry keeps torch.optim.Adam's format."""
+    checkpoint.  optim: "torch" (default) or "hip", HipAdam -- the checkpoint's "optimizer" entry keeps torch.optim.Adam's format.
+    head: "torch" (default) or "hip", the fused HIP classifier head with loss and accuracy on the device -- same results JSON."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
+    _check_head(head)
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim)
+    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim, head)
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
-                   precision: str = "fp32", norm: str = "torch", optim: str = "torch") -> Dict[str, list]:
+                   precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch") -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
     split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
+    _check_head(head)
     get_train_transform(args)   # (the refusals of the on-disk path: photometric augmentation, crop-with-padding)
     want = torch.bfloat16 if precision == "bf16" else torch.float32
     for src in (train_source, val_source):
@@ -218,15 +274,15 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim)
+    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)
 
 
 def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str,
-         optim: str = "torch") -> Dict[str, list]:
+         optim: str = "torch", head: str = "torch") -> Dict[str, list]:
     """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources."""
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
-    model = get_model(args, precision, norm)
+    model = get_model(args, precision, norm, head)
     if init_ckpt:
         from salve_amd import train_utils
 
