@@ -44,7 +44,7 @@ typedef enum {
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
                                         salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
-                                        salve_adam_step, salve_head_* (the training classifier head) */
+                                        salve_adam_step, salve_head_* (the training classifier head), salve_bev_jpeg_roundtrip */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -678,6 +678,33 @@ int salve_head_f32_backward(const salve_head_desc_t* d, const float* pooled, con
                             const float* grad_loss, float* dlogits, float* dw, float* db, float* dx, void* ws, size_t ws_bytes, void* stream);
 int salve_head_bf16_backward(const salve_head_desc_t* d, const float* pooled, const float* probs, const int64_t* target, const float* weight,
                              const float* grad_loss, float* dlogits, float* dw, float* db, uint16_t* dx, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The reference's JPEG hop on the device (additive within ABI 7): opt-in.  The reference writes every BEV render and layout image
+ * with imageio.imwrite(path.jpg) -- Pillow over libjpeg: baseline, quality 75, 4:2:0 (bev_rendering_utils.py:629-630) -- and its
+ * data set decodes the files again (zind_data.py:306-315).  salve_bev_jpeg_roundtrip replaces n images by decode(encode(image))
+ * with libjpeg's defaults, bit for bit, without an entropy coder or a file (quantised coefficients of 8-bit baseline data always fit
+ * the code range, so the decoded pixels depend on the coefficients alone).
+ *   Layout:  bev_in, bev_out: device uint32 [n, h, w] holding 0x00BBGGRR -- salve_bev_densify's out_bev, salve_layout_rasterise's
+ *            out, what every tile entry reads.  bev_out == bev_in is allowed (no other overlap); the top byte is written as 0.
+ *            qtab: HOST uint16 [2][64], the luma and the chroma quantisation table in natural (row-major) order, read before
+ *            the call returns (salve_amd/jpeg.py: quality_tables).
+ *   Stages:  RGB -> YCbCr (16-bit fixed point); right / bottom edges replicated to whole blocks as libjpeg does it (chroma: rows to
+ *            a whole row group and columns to whole blocks before downsampling, the downsampled rows to whole blocks after it); h2v2
+ *            downsampling with the alternating 1, 2 bias; slow-integer forward DCT of the level-shifted samples; quantisation by
+ *            q << 3, magnitude rounded half up, sign restored (exact 32-bit integer division); dequantisation; slow-integer inverse
+ *            DCT with its range limit; h2v2 "fancy" triangle upsampling (replication where the image is at most 4 pixels wide, as
+ *            libjpeg); YCbCr -> RGB with the range limit.  Integer arithmetic only, no atomics, one writer per output: the same
+ *            inputs give the same bits.  Offsets are 64-bit.
+ *   Checks:  SALVE_ERR_BAD_ARG (and 0 workspace bytes from the size query) on null pointers, n <= 0, n > 65535, h or w outside
+ *            [1, 4096], a table entry outside [1, 255], images that are not 4-byte aligned, a workspace smaller than
+ *            salve_bev_jpeg_roundtrip_workspace_bytes(n, h, w) or not 16-byte aligned.
+ *   Workspace: the decoded luma and half-resolution chroma planes, 1.5 bytes per pixel of the images rounded up to whole 16 x 16
+ *            MCUs; it holds nothing from one call to the next.  Two launches, asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------------ */
+size_t salve_bev_jpeg_roundtrip_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int salve_bev_jpeg_roundtrip(const uint32_t* bev_in, uint32_t* bev_out, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, void* ws,
+                             size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -76,6 +76,8 @@ EXPORTED_SYMBOLS = (
     "salve_head_f32_backward",
     "salve_head_bf16_forward",
     "salve_head_bf16_backward",
+    "salve_bev_jpeg_roundtrip_workspace_bytes",
+    "salve_bev_jpeg_roundtrip",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -272,6 +274,10 @@ def load() -> ctypes.CDLL:
     for name in ("salve_head_f32_backward", "salve_head_bf16_backward"):   # d, pooled, probs, target, weight, grad_loss, dlogits, dw, db, dx
         getattr(lib, name).argtypes = [ctypes.POINTER(HeadDesc)] + [vp] * 9 + [vp, sz, vp]
         getattr(lib, name).restype = ctypes.c_int
+    lib.salve_bev_jpeg_roundtrip_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.salve_bev_jpeg_roundtrip_workspace_bytes.restype = sz
+    lib.salve_bev_jpeg_roundtrip.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]   # bev_in, bev_out, n, h, w, HOST qtab, ws, ws_bytes, stream
+    lib.salve_bev_jpeg_roundtrip.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

@@ -1,5 +1,5 @@
 """python -m salve_amd.check_checkpoint <train_ckpt.pth> [--layers 152] [--modalities ceiling_rgb_texture,floor_rgb_texture] [--tiles DIR] [-n 64]
-                                   [--precision fp16|fp32]
+                                   [--precision fp16|fp32] [--jpeg-quality Q]
 
 What fp16 storage costs THIS checkpoint: loads a reference-format checkpoint (`{"state_dict": ...}`, optional `module.` prefix --
 scripts/train.py:97-107, loaded strictly as salve/train_utils.py:229-242 does), runs N tile sets through the HIP engine (fp16
@@ -22,6 +22,11 @@ with textured regions, the input the verifier actually sees.
 reference's own precision): the tiles stay fp32 (no fp16 cast of the files' tiles; rendered tile sets come from the fp32 pipeline), the
 float32 evaluation sees the same fp32 tiles, and the contract is north_star's ABSOLUTE one:
     |logit error| <= 1e-3   and   equal arg-max,   at any logit magnitude.
+
+--jpeg-quality Q (rendered tile sets only; the reference's files: 75) renders the same tile sets a second time through the reference's
+JPEG round trip on the device (RenderVerifyPipeline(jpeg_quality=Q)) and prints, beside the numbers above, how far the engine's logits
+move between the lossless and the round-tripped tiles: max |logit difference| and the number of arg-max flips.  A report, not part
+of the contract: the exit code does not depend on it.
 
 This module is a CHECK beside the product path, never part of it: the float32 evaluation below exists only to be compared with.
 """
@@ -144,13 +149,14 @@ def _tiles_from_dir_f32(tile_dir: str, n_images: int, n_sets: int, device) -> to
     return torch.cat(sets)
 
 
-def _rendered_tiles(model, n_sets: int, device, precision: str = "fp16") -> torch.Tensor:
+def _rendered_tiles(model, n_sets: int, device, precision: str = "fp16", jpeg_quality=None) -> torch.Tensor:
     """Tile sets rendered by the fused pipeline from seeded synthetic panoramas (cluttered scene) and random hypotheses: fp16 NHWC, or
-    with precision="fp32" fp32 NCHW (the fp32 pipeline's tiles)."""
+    with precision="fp32" fp32 NCHW (the fp32 pipeline's tiles).  jpeg_quality: the same sets after the reference's JPEG round trip."""
     from salve_amd import synthetic
     from salve_amd.pipeline import RenderVerifyPipeline
 
-    pipe = RenderVerifyPipeline(model, device, chunk=None, overlap=False, streams=1, n_hypotheses=n_sets, precision=precision)
+    pipe = RenderVerifyPipeline(model, device, chunk=None, overlap=False, streams=1, n_hypotheses=n_sets, precision=precision,
+                                jpeg_quality=jpeg_quality)
     P = 8
     panos = [synthetic.make_pano(i, scene="cluttered") for i in range(P)]
     pipe.load_panos(np.stack([p[0] for p in panos]), np.stack([p[1] for p in panos]))
@@ -204,6 +210,28 @@ def run_f32(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 
     return compare(got, ref, absolute=True)
 
 
+def jpeg_shift(model, lossless: torch.Tensor, roundtripped: torch.Tensor, precision: str = "fp16") -> dict:
+    """How far the engine's logits move between lossless tiles and the same tiles after the JPEG round trip (both as `_rendered_tiles`
+    gives them): {"n", "max_abs_dlogit", "argmax_flips"}."""
+    with torch.no_grad():
+        if precision == "fp32":
+            prev = model.precision
+            model.set_precision("fp32")
+            try:
+                a, b = (model(*([t[:, 3 * k:3 * k + 3].contiguous() for k in range(model.num_images)] + [None] * (6 - model.num_images))).float().cpu()
+                        for t in (lossless, roundtripped))
+            finally:
+                model.set_precision(prev)
+        else:
+            a, b = (model.forward_nhwc(t.contiguous()).float().cpu() for t in (lossless, roundtripped))
+    return {"n": int(a.shape[0]), "max_abs_dlogit": float((a - b).abs().max()), "argmax_flips": int((a.argmax(1) != b.argmax(1)).sum())}
+
+
+def report_jpeg_shift(st: dict, quality: int) -> str:
+    return (f"  JPEG round trip (quality {quality}) against lossless tiles: max |logit difference| {st['max_abs_dlogit']:.3e}, "
+            f"arg-max flips {st['argmax_flips']} / {st['n']}   (a report, not part of the contract)")
+
+
 def main(argv: List[str] = None) -> int:
     ap = argparse.ArgumentParser(prog="python -m salve_amd.check_checkpoint", description=__doc__.split("\n\n")[1])
     ap.add_argument("checkpoint", help="train_ckpt.pth: a dict with 'state_dict' (scripts/train.py:97-107)")
@@ -214,7 +242,13 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--precision", choices=("fp16", "fp32"), default="fp16",
                     help="verifier engine to check: fp16 (the default engine; relative contract) or fp32 (the reference's precision; absolute 1e-3)")
+    ap.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
+                    help="also report how far the logits move when the rendered tiles take the reference's JPEG round trip at quality Q (its files: 75)")
     args = ap.parse_args(argv)
+    if args.jpeg_quality is not None and args.tiles:
+        raise SystemExit("check_checkpoint: --jpeg-quality compares rendered tile sets; tiles from --tiles DIR have been through their files already")
+    if args.jpeg_quality is not None and not 1 <= args.jpeg_quality <= 100:
+        raise SystemExit(f"check_checkpoint: --jpeg-quality must be 1 .. 100, got {args.jpeg_quality}")
 
     from salve_amd.models.early_fusion import EarlyFusionCEResnet
     from salve_amd.train_utils import load_model_checkpoint
@@ -234,6 +268,9 @@ def main(argv: List[str] = None) -> int:
         st = run(model, tiles, dev)
     print(report(st, f"{args.checkpoint} (ResNet-{args.layers}, {model.num_images} images per set, {'fp32 engine, ' if args.precision == 'fp32' else ''}"
                      f"{'tiles from ' + args.tiles if args.tiles else 'tile sets rendered from synthetic panoramas'})"))
+    if args.jpeg_quality is not None:
+        shifted = _rendered_tiles(model, args.n, dev, args.precision, jpeg_quality=args.jpeg_quality)
+        print(report_jpeg_shift(jpeg_shift(model, tiles, shifted, args.precision), args.jpeg_quality))
     return 0 if st["contract_holds"] else 1
 
 

@@ -1,4 +1,5 @@
-"""Fused render -> verify pipeline: alignment hypotheses in, verifier logits out, no JPEG hop.
+"""Fused render -> verify pipeline: alignment hypotheses in, verifier logits out, no JPEG file (`jpeg_quality=` reproduces the
+reference's JPEG round trip on the device instead: DESIGN.md 4.17).
 
 This is the MI355X counterpart of running the reference's two drivers back to back --
 scripts/render_dataset_bev.py:91-117 (one `generate_texture_maps_for_pair` per hypothesis x surface) and
@@ -94,13 +95,17 @@ class RenderVerifyPipeline:
 
     def __init__(self, model, device: torch.device, pano_hw: Tuple[int, int] = (512, 1024), chunk: Optional[int] = None,
                  overlap: bool = True, streams: int = 3, n_hypotheses: Optional[int] = None, fuse_tiles: bool = True,
-                 precision: str = "fp16") -> None:
+                 precision: str = "fp16", jpeg_quality: Optional[int] = None) -> None:
         """chunk: hypotheses per render / verify launch.  None (default): chosen by `pick_launch` from the HBM that is free now --
         the whole shard of `n_hypotheses` rows in one launch if its workspaces fit LAUNCH_HBM_FRACTION of it (a shard of 4096
         hypotheses needs 57 GB with one surface / ResNet-50, 80 GB with two / ResNet-152, of 288), else the fewest equal launches.
         precision: "fp16" (default: fp16 NHWC tiles, the fp16 verifier engine) or "fp32" -- the reference's precision: fp32 NCHW tiles
         [chunk, 3 n, 224, 224] (salve_bev_tiles, SALVE_TILE_F32_NCHW: the same LUT values, not rounded to fp16) into the fp32 engine.
-        fp32 renders its tiles with launches of their own (fuse_tiles is forced off) and does not support the layout modality."""
+        fp32 renders its tiles with launches of their own (fuse_tiles is forced off) and does not support the layout modality.
+        jpeg_quality: None (default): the tiles come from the lossless renders.  An integer (the reference's files: 75): every render and
+        layout image goes through the reference's JPEG round trip on the device first (BevRasteriser.jpeg_roundtrip; the posed images
+        per launch, the kept identity images once), so the tiles equal those of the files scripts/test.py reads; the tiles then come
+        from launches of their own (fuse_tiles is forced off).  Both precisions."""
         self.device = torch.device(device)
         if precision not in ("fp16", "fp32"):
             raise ValueError(f"precision must be 'fp16' or 'fp32', got {precision!r}")
@@ -111,7 +116,8 @@ class RenderVerifyPipeline:
         self.model = model
         # fuse_tiles (default): the densify kernel writes every render's verifier tile itself (salve_bev_densify_tiles); False: densify, then
         # salve_bev_tile_pairs in a launch of its own (the form of rounds 2-5; same bits: tests/test_gpu_rasteriser.py)
-        self.fuse_tiles = bool(fuse_tiles) and precision == "fp16"
+        self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
+        self.fuse_tiles = bool(fuse_tiles) and precision == "fp16" and self.jpeg_quality is None
         self.surfaces = surfaces_for(model.modalities)
         self.has_layout = "layout" in set(model.modalities)
         if precision == "fp32" and self.has_layout:
@@ -201,6 +207,8 @@ class RenderVerifyPipeline:
                 n = min(256, P * S - lo)
                 self.ras.render_counted(self.pano_rgb, self.pano_depth, hd[lo * _lib.HYP_DTYPE.itemsize:], n, self.ref_bev[lo:lo + n],
                                         self.ref_in_window[lo:lo + n])
+        if self.jpeg_quality is not None:   # the kept identity renders take the file hop once
+            self.ras.jpeg_roundtrip(self.ref_bev, self.jpeg_quality, out=self.ref_bev)
         # the identity images' Resize + Crop, once per (panorama, surface): every hypothesis that names the panorama as its second
         # one then only normalises them (salve_bev_tile_pairs, b_pretiled)
         self.ref_tiles = self.ras.pretile(self.ref_bev)
@@ -284,6 +292,8 @@ class RenderVerifyPipeline:
             # pano i2's own layout does not depend on the hypothesis: drawn, resized and cropped once per panorama (like the
             # identity texture maps), then only normalised by the pair kernel
             ident = layout_mod.rasterise_layouts(layouts.identity, self.device)
+            if self.jpeg_quality is not None:
+                ident = self.ras.jpeg_roundtrip(ident, self.jpeg_quality, out=ident)
             prepared["layout_ref_tiles"] = self.ras.pretile(ident)
             prepared["layouts"] = layout_mod.pack_layouts(layouts.posed, self.device)   # hypothesis order: image j of the table
             base = 6 * S
@@ -335,6 +345,9 @@ class RenderVerifyPipeline:
                     self.ras.densify(n * S, bev)
             if e1 is not None:
                 e1.record()
+            if self.jpeg_quality is not None:
+                with tracing.range("salve.jpeg"):
+                    self.ras.jpeg_roundtrip(bev[:n * S], self.jpeg_quality, out=bev[:n * S])
             if self.precision == "fp32":
                 with tracing.range("salve.tiles"):
                     # fp32 NCHW tiles of the posed renders (this chunk's images) and of the identity renders (ref_bev), in the channel
@@ -352,6 +365,8 @@ class RenderVerifyPipeline:
             with tracing.range("salve.layout"):
                 lbev = self.layout_bevs[buf]
                 prepared["layouts"].rasterise(lo, n, lbev)
+                if self.jpeg_quality is not None:
+                    self.ras.jpeg_roundtrip(lbev[:n], self.jpeg_quality, out=lbev[:n])
                 self.ras.tile_pairs(lbev, prepared["jobsL1"][lo * jb:], prepared["layout_ref_tiles"], prepared["jobsL2"][lo * jb:], n, tiles,
                                     self.engine.in_channels, pretiled=True)
 

@@ -115,6 +115,8 @@ class BevRasteriser:
         self._ws_slots = {}   # workspaces by slot: a caller that keeps two batches in flight alternates `ws_slot`
         self.ws_slot = 0
         self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
+        self._jpeg_ws = {}      # jpeg_roundtrip's workspaces by stream: callers on different streams never share one
+        self._jpeg_tables = {}  # quality -> uint16 [2, 64] (host)
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> ctypes.c_void_p:
@@ -344,6 +346,43 @@ class BevRasteriser:
         with torch.cuda.device(self.device):
             st = self.lib.salve_bev_export_u8(ctypes.c_void_p(bev.data_ptr()), n, Hb, Wb, ctypes.c_void_p(out.data_ptr()), self._stream())
         _lib.check(st, "salve_bev_export_u8")
+        return out
+
+    JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip: images per library call (bounds its workspace: 1.5 bytes per padded pixel)
+
+    def jpeg_roundtrip(self, bev: torch.Tensor, quality: int = 75, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n, H, W] images (0x00BBGGRR: BEV renders, layout images) -> what the reference's file hop makes of them: Pillow's
+        `save(quality=quality)` and decode (bev_rendering_utils.py:629-630 -> zind_data.py:306-315), bit for bit, on the current stream
+        (include/salve_hip.h: salve_bev_jpeg_roundtrip).  `out`: default a new tensor; `out=bev` works in place."""
+        if bev.dim() != 3 or bev.dtype != torch.int32 or not bev.is_contiguous() or bev.device != self.device:
+            raise _lib.SalveHipError(f"jpeg_roundtrip takes contiguous int32 [n, H, W] images on {self.device}, got {bev.dtype} {tuple(bev.shape)}")
+        if out is None:
+            out = torch.empty_like(bev)
+        elif out.shape != bev.shape or out.dtype != bev.dtype or not out.is_contiguous() or out.device != bev.device:
+            raise _lib.SalveHipError(f"jpeg_roundtrip: out must match the images ({bev.dtype} {tuple(bev.shape)}), got {out.dtype} {tuple(out.shape)}")
+        n, h, w = (int(v) for v in bev.shape)
+        if n == 0:
+            return out
+        q = int(quality)
+        if q not in self._jpeg_tables:
+            from salve_amd.jpeg import quality_tables
+
+            self._jpeg_tables[q] = np.ascontiguousarray(quality_tables(q), dtype=np.uint16)
+        qtab = self._jpeg_tables[q]
+        per = min(n, self.JPEG_IMAGES_PER_CALL)
+        need = self.lib.salve_bev_jpeg_roundtrip_workspace_bytes(per, h, w)
+        if need == 0:
+            _lib.check(-1, "salve_bev_jpeg_roundtrip_workspace_bytes")
+        stream = torch.cuda.current_stream(self.device)
+        ws = self._jpeg_ws.get(stream.cuda_stream)
+        if ws is None or ws.numel() < need:   # (allocated under the stream that uses it: the caching allocator orders its reuse against that stream)
+            ws = self._jpeg_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for lo in range(0, n, per):
+                m = min(per, n - lo)
+                st = self.lib.salve_bev_jpeg_roundtrip(ctypes.c_void_p(bev[lo:].data_ptr()), ctypes.c_void_p(out[lo:].data_ptr()), m, h, w,
+                                                       qtab.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
+                _lib.check(st, "salve_bev_jpeg_roundtrip")
         return out
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:

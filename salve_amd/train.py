@@ -3,7 +3,7 @@
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}]
-                              [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]]]
+                              [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]] [--jpeg-quality Q]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
 model_save_dirpath / a time stamp, as the reference does).  --precision bf16 opts into mixed precision (bf16 activations and
@@ -21,6 +21,8 @@ A configuration whose modalities include "layout" also needs DIR/layouts.npz: th
 uploaded as the batches need them: for panorama sets that do not fit in device memory.  N must be at least 2 x batch_size.
 --prefetch (with --resident-panos N, N at least 4 x batch_size) uploads the next batch's missing panoramas on a second stream while the
 current batch trains: the same batches, the uploads hidden under the step.
+--jpeg-quality Q (with --render-from; the reference's files: 75) puts every rendered image through the reference's JPEG round trip on
+the GPU before it is tiled: the batches of the rendered dataset on disk, without the files.
 """
 
 from __future__ import annotations
@@ -59,8 +61,15 @@ def main(argv=None) -> None:
                     help="--render-from: keep a pool of N panoramas on the device and upload the others as batches need them (selects --identity batch)")
     ap.add_argument("--prefetch", action="store_true",
                     help="--resident-panos: upload the next batch's missing panoramas beside the training step (N at least 4 x batch size)")
+    ap.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
+                    help="--render-from: JPEG round trip of every rendered image on the GPU at quality Q (the reference writes its tiles at 75)")
     a = ap.parse_args(argv)
     training._check_head(a.head)
+    if a.jpeg_quality is not None:
+        if a.render_from is None:
+            raise SystemExit("--jpeg-quality belongs to --render-from DIR (a rendered dataset on disk already holds JPEG files)")
+        if not 1 <= a.jpeg_quality <= 100:
+            raise SystemExit(f"--jpeg-quality must be 1 .. 100, got {a.jpeg_quality}")
     if a.render_from is None and (a.identity is not None or a.resident_panos is not None):
         raise SystemExit("--identity and --resident-panos belong to --render-from DIR")
     if a.resident_panos is not None:
@@ -98,7 +107,8 @@ def main(argv=None) -> None:
             src = train_render.RenderedTrainSource(torch.device("cuda", torch.cuda.current_device()), args.modalities, pano_hw=rgb.shape[1:3],
                                                    batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
                                                    resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
-                                                   identity=identity, resident_panos=a.resident_panos, layouts=layouts, prefetch=a.prefetch)
+                                                   identity=identity, resident_panos=a.resident_panos, layouts=layouts, prefetch=a.prefetch,
+                                                   jpeg_quality=a.jpeg_quality)
             if split == "train":
                 src.load_panos(rgb, depth)
             else:   # the panoramas (or their pool) and their identity renders are on the device once
@@ -106,7 +116,7 @@ def main(argv=None) -> None:
             src.set_examples(*examples[split])
             sources[split] = src
         results = training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
-                                          norm=a.norm, optim=a.optim, head=a.head)
+                                          norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality)
     else:
         results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
                                  head=a.head)

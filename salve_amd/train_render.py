@@ -247,12 +247,16 @@ class RenderedTrainSource:
     uploads every panorama up front; an integer keeps a pool of that many panorama slots on the device, filled on first use from the
     host arrays `load_panos` was given (needs identity="batch"; at least min(2 x batch_size, P) slots).
     prefetch (needs resident_panos; at least min(4 x batch_size, P) slots): while batch b trains, batch b + 1's misses are gathered by
-    `gather_threads` host threads and uploaded on a copy stream the pool owns; the batches are the same."""
+    `gather_threads` host threads and uploaded on a copy stream the pool owns; the batches are the same.
+    jpeg_quality: None (default): the tiles come from the lossless images.  An integer (the reference's files: 75): every render and
+    layout image takes the reference's JPEG round trip on the device (BevRasteriser.jpeg_roundtrip) between densify / rasterise and the
+    train-tile launch -- kept identity images once, everything else with its batch -- so the batches equal the on-disk DataLoader's
+    (DESIGN.md 4.17).  It runs on the compute stream: prefetch and the resident pool are unaffected."""
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
                  crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None,
-                 prefetch: bool = False, gather_threads: int = 4) -> None:
+                 prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None) -> None:
         if split not in SPLITS:
             raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
         if precision not in ("fp32", "bf16"):
@@ -269,6 +273,7 @@ class RenderedTrainSource:
         if not 1 <= int(gather_threads) <= MAX_GATHER_THREADS:
             raise ValueError(f"gather_threads must be 1 .. {MAX_GATHER_THREADS}, got {gather_threads}")
         self.prefetch, self.gather_threads = bool(prefetch), int(gather_threads)
+        self.jpeg_quality = None if jpeg_quality is None else int(jpeg_quality)
         self.surfaces = train_surfaces(modalities, with_layouts=layouts is not None)
         self.has_layout = "layout" in set(modalities)
         self.layouts = layouts if self.has_layout else None   # salve_amd.layout.PanoLayouts, indexed by panorama
@@ -334,6 +339,7 @@ class RenderedTrainSource:
                 for lo in range(0, P, self.lay.n_max):
                     ids = np.arange(lo, min(lo + self.lay.n_max, P))
                     self.lay.draw(layout_mod.pose_records(self.layouts, ids), self.ref_bev[P * S + lo:])
+                self._jpeg(self.ref_bev[P * S:P * S + P])
 
     def load_panos(self, rgb: np.ndarray, depth: np.ndarray) -> None:
         """P panoramas (uint8 [P, H, W, 3], uint16 [P, H, W]).  Default: upload them all (and, identity="kept", render their identity
@@ -421,6 +427,7 @@ class RenderedTrainSource:
             for lo in range(0, P * S, 256):
                 n = min(256, P * S - lo)
                 self.ras.render(self.pano_rgb, self.pano_depth, rows_dev[lo * _lib.HYP_DTYPE.itemsize:], n, self.ref_bev[lo:lo + n])
+            self._jpeg(self.ref_bev[:P * S])
 
     def share_panos(self, other: "RenderedTrainSource") -> None:
         """Use the panoramas, identity renders and batch buffer `other` holds (the val source beside the train source: one copy on
@@ -436,6 +443,8 @@ class RenderedTrainSource:
             raise RuntimeError("share_panos needs the same identity and resident_panos arguments on both sources")
         if other.prefetch != self.prefetch:
             raise RuntimeError("share_panos needs the same prefetch argument on both sources")
+        if other.jpeg_quality != self.jpeg_quality:
+            raise RuntimeError("share_panos needs the same jpeg_quality argument on both sources (the kept identity images are shared)")
         self.pano_rgb, self.pano_depth, self.ref_bev, self.bev, self.n_panos, self.examples = (other.pano_rgb, other.pano_depth, other.ref_bev,
                                                                                                other.bev, other.n_panos, None)
         self.pool, self.lay, self.lay_base, self.layouts = other.pool, other.lay, other.lay_base, other.layouts
@@ -462,6 +471,16 @@ class RenderedTrainSource:
         return 0 if self.examples is None else batches_per_epoch(len(self.examples["i1"]), self.batch_size, self.split)
 
     # ------------------------------------------------------------------ batches
+    def _jpeg(self, images: torch.Tensor) -> None:
+        """The reference's JPEG round trip of `images`, in place, if this source was asked for it."""
+        if self.jpeg_quality is None or images.shape[0] == 0:
+            return
+        e1 = self._timed("jpeg")
+        with tracing.range("salve.jpeg"):
+            self.ras.jpeg_roundtrip(images, self.jpeg_quality, out=images)
+        if e1 is not None:
+            e1.record()
+
     def _timed(self, tag: str):
         if self.timers is None:
             return None
@@ -641,6 +660,7 @@ class RenderedTrainSource:
                 self.ras.densify(n, self.bev)
             if e1 is not None:
                 e1.record()
+            self._jpeg(self.bev[:n])
         if self.has_layout:
             e1 = self._timed("layout pose")
             with tracing.range("salve.layout_pose"):
@@ -652,6 +672,7 @@ class RenderedTrainSource:
                 self.lay.rasterise(len(lay_recs), self.bev[self.lay_base[0]:])
             if e1 is not None:
                 e1.record()
+            self._jpeg(self.bev[self.lay_base[0]:self.lay_base[0] + len(lay_recs)])
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
         e1 = self._timed("tiles")
         with tracing.range("salve.train_tiles"):

@@ -259,9 +259,12 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
-                   precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch") -> Dict[str, list]:
+                   precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch",
+                   jpeg_quality: Optional[int] = None) -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
-    split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON."""
+    split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON.  jpeg_quality: the
+    sources' own argument (the reference's JPEG round trip of every rendered image, on the device); the two sources must agree, and
+    an integer given here must be what they were built with."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
@@ -271,6 +274,10 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
     for src in (train_source, val_source):
         if src.dtype != want:
             raise RuntimeError(f"the batch source yields {src.dtype}, training precision {precision} takes {want}")
+    built = (getattr(train_source, "jpeg_quality", None), getattr(val_source, "jpeg_quality", None))
+    if built[0] != built[1] or (jpeg_quality is not None and built[0] != int(jpeg_quality)):
+        raise RuntimeError(f"the batch sources were built with jpeg_quality {built[0]} (train) and {built[1]} (val), "
+                           f"train_rendered was asked for {jpeg_quality}: build both with the same value")
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
