@@ -44,7 +44,8 @@ typedef enum {
                                      7: the fp32 verifier handle family salve_resnet_f32_* (the fp16 engine's calls and flags unchanged);
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
                                         salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
-                                        salve_adam_step, salve_head_* (the training classifier head), salve_bev_jpeg_roundtrip */
+                                        salve_adam_step, salve_head_* (the training classifier head), salve_bev_jpeg_roundtrip, salve_bev_jpeg_encode
+                                        (with salve_bev_jpeg_encode_workspace_bytes / _max_bytes) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -705,6 +706,41 @@ int salve_head_bf16_backward(const salve_head_desc_t* d, const float* pooled, co
 size_t salve_bev_jpeg_roundtrip_workspace_bytes(int32_t n, int32_t h, int32_t w);
 int salve_bev_jpeg_roundtrip(const uint32_t* bev_in, uint32_t* bev_out, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, void* ws,
                              size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The reference's JPEG FILES from the device (additive within ABI 7): opt-in.  salve_bev_jpeg_encode leaves, for each of n images,
+ * the entropy-coded scan of the file Pillow's `save(path, quality=q)` writes (libjpeg: baseline, 4:2:0, the standard Huffman
+ * tables of ITU-T T.81 Annex K, one interleaved scan, no restart interval), byte for byte: the forward chain of
+ * salve_bev_jpeg_roundtrip (the same device functions), then jchuff.c's encode_one_block -- DC differences per component in scan
+ * order, (run, size) symbols in zigzag order with ZRL and EOB, bits most significant first, the last byte padded with 1-bits, a
+ * 0x00 stuffed behind every 0xFF.  The file is header + scan + FF D9; the 623 header bytes depend on h, w and the tables only and
+ * are the host's (salve_amd/jpeg.py: file_header, file_bytes).
+ *   bev         device uint32 [n, h, w] holding 0x00BBGGRR, as for salve_bev_jpeg_roundtrip; only read
+ *   qtab        HOST uint16 [2][64], luma and chroma table in natural order, read before the call returns
+ *   scan        device bytes: image i's scan starts at scan + i * scan_stride (stuffed and padded; no header, no EOI)
+ *   scan_bytes  device int32 [n]: the scan's length in bytes
+ *   Capacity:   salve_bev_jpeg_encode_max_bytes(h, w) bounds the scan of ANY content: a block codes to at most 11 + 11 bits of DC
+ *               (the longest DC code plus category 11's value bits) and 63 x (16 + 10) bits of AC (the longest AC code plus category
+ *               10's value bits per coefficient; with table entries >= 1, 8-bit samples give no larger category, and a ZRL's 11 bits
+ *               per 16 zeros and the EOB cost less than the coefficients they replace), 1660 bits; six blocks per 16 x 16 MCU are 1245
+ *               bytes, and stuffing at most doubles them: 2490 bytes per MCU, rounded up to a multiple of 4.  A caller may pass a
+ *               SMALLER scan_stride (real scans are a small fraction of the bound).  If image i needs more than scan_stride bytes,
+ *               scan_bytes[i] still holds the NEEDED length, nothing is written outside the image's slot, no status bit is set and
+ *               the other images are complete: the caller sees scan_bytes[i] > scan_stride and encodes that image another way.
+ *               Bytes of a slot beyond the scan's length are not written.
+ *   Checks:     SALVE_ERR_BAD_ARG (and 0 from the two size queries) on null pointers, n <= 0, n > 65535, h or w outside [1, 4096],
+ *               a table entry outside [1, 255], bev or scan_bytes not 4-byte aligned, a workspace smaller than
+ *               salve_bev_jpeg_encode_workspace_bytes(n, h, w) or not 16-byte aligned, scan_stride 0 or not a multiple of 4.
+ *   Workspace:  per block 128 bytes of coefficients (int16, zigzag order, MCU-interleaved) and a 4-byte length / bit offset; the
+ *               unstuffed bit stream at its bound (1245 bytes per MCU); a counter per 1024 bytes of it.  About 2.1 MB per 501 x 501
+ *               image.  It needs no initialisation and holds nothing from one call to the next.
+ *   Eight launches, asynchronous on `stream`.  32-bit integer arithmetic, vector stores and vector atomics (bit-wise OR into zeroed
+ *   words: no dependence on order): the same input gives the same bytes.
+ * ------------------------------------------------------------------------------------------------ */
+size_t salve_bev_jpeg_encode_workspace_bytes(int32_t n, int32_t h, int32_t w);
+size_t salve_bev_jpeg_encode_max_bytes(int32_t h, int32_t w);
+int salve_bev_jpeg_encode(const uint32_t* bev, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, uint8_t* scan, size_t scan_stride,
+                          int32_t* scan_bytes, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

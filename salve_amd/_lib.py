@@ -78,6 +78,9 @@ EXPORTED_SYMBOLS = (
     "salve_head_bf16_backward",
     "salve_bev_jpeg_roundtrip_workspace_bytes",
     "salve_bev_jpeg_roundtrip",
+    "salve_bev_jpeg_encode_workspace_bytes",
+    "salve_bev_jpeg_encode_max_bytes",
+    "salve_bev_jpeg_encode",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -278,6 +281,12 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_jpeg_roundtrip_workspace_bytes.restype = sz
     lib.salve_bev_jpeg_roundtrip.argtypes = [vp, vp, i32, i32, i32, vp, vp, sz, vp]   # bev_in, bev_out, n, h, w, HOST qtab, ws, ws_bytes, stream
     lib.salve_bev_jpeg_roundtrip.restype = ctypes.c_int
+    lib.salve_bev_jpeg_encode_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.salve_bev_jpeg_encode_workspace_bytes.restype = sz
+    lib.salve_bev_jpeg_encode_max_bytes.argtypes = [i32, i32]
+    lib.salve_bev_jpeg_encode_max_bytes.restype = sz
+    lib.salve_bev_jpeg_encode.argtypes = [vp, i32, i32, i32, vp, vp, sz, vp, vp, sz, vp]   # bev, n, h, w, HOST qtab, scan, scan_stride, scan_bytes, ws, ws_bytes, stream
+    lib.salve_bev_jpeg_encode.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

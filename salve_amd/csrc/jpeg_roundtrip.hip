@@ -31,61 +31,10 @@
 #include <stdint.h>
 
 #include "../../include/salve_hip.h"
+#include "jpeg_forward.h"   // the forward chain, shared with jpeg_encode.hip
 #include "salve_common.h"
 
 namespace {
-
-constexpr int JPEG_THREADS = 256;
-constexpr int MCUS = 4;            // MCUs of a workgroup, side by side
-constexpr int TW = 16 * MCUS;      // its luma tile: 16 rows of TW samples
-constexpr int SY = TW + 1;         // LDS row strides (odd: the column passes of a block's eight threads fall on different banks)
-constexpr int SC = TW / 2 + 1;
-constexpr int MAX_DIM = 4096, MAX_IMAGES = 65535;
-
-constexpr int CONST_BITS = 13, PASS1_BITS = 2;
-constexpr int F_0_298631336 = 2446, F_0_390180644 = 3196, F_0_541196100 = 4433, F_0_765366865 = 6270;
-constexpr int F_0_899976223 = 7373, F_1_175875602 = 9633, F_1_501321110 = 12299, F_1_847759065 = 15137;
-constexpr int F_1_961570560 = 16069, F_2_053119869 = 16819, F_2_562915447 = 20995, F_3_072711026 = 25172;
-
-struct QTables {
-    uint16_t q[2][64];   // luma, chroma; natural order
-};
-
-__device__ __forceinline__ int descale(int x, int n) { return (x + (1 << (n - 1))) >> n; }
-
-// jccolor.c: rgb_ycc_convert (every sum is positive: the shifts are plain)
-__device__ __forceinline__ void rgb_to_ycc(uint32_t p, int& y, int& cb, int& cr) {
-    const int r = p & 255, g = (p >> 8) & 255, b = (p >> 16) & 255;
-    y = (19595 * r + 38470 * g + 7471 * b + 32768) >> 16;
-    cb = (-11059 * r - 21709 * g + 32768 * b + (128 << 16) + 32767) >> 16;
-    cr = (32768 * r - 27439 * g - 5329 * b + (128 << 16) + 32767) >> 16;
-}
-
-// jfdctint.c: one 1-D pass of jpeg_fdct_islow, in place
-template <bool SECOND>
-__device__ __forceinline__ void fdct_1d(int* d) {
-    const int t0 = d[0] + d[7], t7 = d[0] - d[7], t1 = d[1] + d[6], t6 = d[1] - d[6];
-    const int t2 = d[2] + d[5], t5 = d[2] - d[5], t3 = d[3] + d[4], t4 = d[3] - d[4];
-    const int t10 = t0 + t3, t13 = t0 - t3, t11 = t1 + t2, t12 = t1 - t2;
-    constexpr int n = SECOND ? CONST_BITS + PASS1_BITS : CONST_BITS - PASS1_BITS;
-    d[0] = SECOND ? descale(t10 + t11, PASS1_BITS) : (t10 + t11) * (1 << PASS1_BITS);
-    d[4] = SECOND ? descale(t10 - t11, PASS1_BITS) : (t10 - t11) * (1 << PASS1_BITS);
-    int z1 = (t12 + t13) * F_0_541196100;
-    d[2] = descale(z1 + t13 * F_0_765366865, n);
-    d[6] = descale(z1 + t12 * (-F_1_847759065), n);
-    z1 = t4 + t7;
-    int z2 = t5 + t6, z3 = t4 + t6, z4 = t5 + t7;
-    const int z5 = (z3 + z4) * F_1_175875602;
-    const int u4 = t4 * F_0_298631336, u5 = t5 * F_2_053119869, u6 = t6 * F_3_072711026, u7 = t7 * F_1_501321110;
-    z1 *= -F_0_899976223;
-    z2 *= -F_2_562915447;
-    z3 = z3 * (-F_1_961570560) + z5;
-    z4 = z4 * (-F_0_390180644) + z5;
-    d[7] = descale(u4 + z1 + z3, n);
-    d[5] = descale(u5 + z2 + z4, n);
-    d[3] = descale(u6 + z2 + z3, n);
-    d[1] = descale(u7 + z1 + z4, n);
-}
 
 // jidctint.c: one 1-D pass of jpeg_idct_islow, in place, descaled by n bits (its zero-AC short cuts give what these formulas give)
 __device__ __forceinline__ void idct_1d(int* d, int n) {
@@ -144,48 +93,14 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_blocks_kernel(const uint32_
     const uint32_t* img = in + (int64_t)blockIdx.z * h * w;
     if (tid < 128) s_q[tid >> 6][tid & 63] = qt.q[tid >> 6][tid & 63];
 
-    {   // colour conversion, edge replication and chroma downsampling: one 2 x 2 quad per thread
-        const int qx = tid & 31, qy = tid >> 5;
-        const int x0 = gx0 + 2 * qx, y0 = gy0 + 2 * qy;
-        const int X0 = min(x0, w - 1), X1 = min(x0 + 1, w - 1);
-        const int Y0 = min(y0, h - 1), Y1 = min(y0 + 1, h - 1);
-        uint32_t p00 = img[(int64_t)Y0 * w + X0], p01 = img[(int64_t)Y0 * w + X1];
-        uint32_t p10 = img[(int64_t)Y1 * w + X0], p11 = img[(int64_t)Y1 * w + X1];
-        int ya, yb, yc, yd, cb[4], cr[4];
-        rgb_to_ycc(p00, ya, cb[0], cr[0]);
-        rgb_to_ycc(p01, yb, cb[1], cr[1]);
-        rgb_to_ycc(p10, yc, cb[2], cr[2]);
-        rgb_to_ycc(p11, yd, cb[3], cr[3]);
-        s_y[(2 * qy) * SY + 2 * qx] = ya - 128;
-        s_y[(2 * qy) * SY + 2 * qx + 1] = yb - 128;
-        s_y[(2 * qy + 1) * SY + 2 * qx] = yc - 128;
-        s_y[(2 * qy + 1) * SY + 2 * qx + 1] = yd - 128;
-        // chroma rows below the image repeat the last DOWNSAMPLED row: the box over rows 2 (ch - 1) and min(2 ch - 1, h - 1)
-        const int ch = (h + 1) >> 1;
-        const int cye = min(y0 >> 1, ch - 1);
-        const int C0 = 2 * cye, C1 = min(2 * cye + 1, h - 1);
-        if (C0 != Y0 || C1 != Y1) {
-            int unused;
-            rgb_to_ycc(img[(int64_t)C0 * w + X0], unused, cb[0], cr[0]);
-            rgb_to_ycc(img[(int64_t)C0 * w + X1], unused, cb[1], cr[1]);
-            rgb_to_ycc(img[(int64_t)C1 * w + X0], unused, cb[2], cr[2]);
-            rgb_to_ycc(img[(int64_t)C1 * w + X1], unused, cb[3], cr[3]);
-        }
-        const int bias = 1 + ((x0 >> 1) & 1);   // 1, 2, 1, 2 ... from the row's first chroma sample
-        s_c[0][qy * SC + qx] = ((cb[0] + cb[1] + cb[2] + cb[3] + bias) >> 2) - 128;
-        s_c[1][qy * SC + qx] = ((cr[0] + cr[1] + cr[2] + cr[3] + bias) >> 2) - 128;
-    }
+    jpeg_stage_quad(img, h, w, gx0, gy0, tid, s_y, s_c);   // colour conversion, edge replication and chroma downsampling
     __syncthreads();
 
     // eight threads per block: blocks 0 .. 15 luma (MCU m: 4 m .. 4 m + 3, row-major inside the MCU), 16 .. 19 Cb, 20 .. 23 Cr
-    const int blk = tid >> 3, r = tid & 7;
-    const bool working = blk < 6 * MCUS;
-    const bool luma = blk < 4 * MCUS;
-    const int m = luma ? blk >> 2 : (blk - 4 * MCUS) & (MCUS - 1);
-    const int comp = luma ? 0 : 1 + ((blk - 4 * MCUS) >> 2);          // 0 Y, 1 Cb, 2 Cr
-    const int by = luma ? (blk >> 1) & 1 : 0, bx = luma ? blk & 1 : 0;
-    const int stride = luma ? SY : SC;
-    int* base = luma ? s_y + (by * 8) * SY + m * 16 + bx * 8 : s_c[working ? comp - 1 : 0] + m * 8;
+    const JpegBlockMap map(tid);
+    const int r = map.r, m = map.m, comp = map.comp, by = map.by, bx = map.bx, stride = map.stride;
+    const bool working = map.working, luma = map.luma;
+    int* base = map.base(s_y, s_c);
     const int* q = s_q[luma ? 0 : 1];
     int d[8];
     if (working) {   // forward pass 1: rows
@@ -203,9 +118,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_blocks_kernel(const uint32_
 #pragma unroll
         for (int k = 0; k < 8; k++) {
             const int qk = q[k * 8 + r];
-            const uint32_t qv = (uint32_t)qk << 3;
-            const uint32_t mag = ((uint32_t)(d[k] < 0 ? -d[k] : d[k]) + (qv >> 1)) / qv;   // exact 32-bit division
-            d[k] = (d[k] < 0 ? -(int)mag : (int)mag) * qk;
+            d[k] = jpeg_quantise(d[k], qk) * qk;
         }
         idct_1d(d, CONST_BITS - PASS1_BITS);
 #pragma unroll
@@ -276,14 +189,12 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixels_kernel(const uint8_t
     }
 }
 
-bool good_shape(int32_t n, int32_t h, int32_t w) { return n > 0 && n <= MAX_IMAGES && h >= 1 && h <= MAX_DIM && w >= 1 && w <= MAX_DIM; }
-
 }  // namespace
 
 extern "C" {
 
 size_t salve_bev_jpeg_roundtrip_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    if (!good_shape(n, h, w)) {
+    if (!jpeg_good_shape(n, h, w)) {
         salve_fail("salve_bev_jpeg_roundtrip_workspace_bytes: n outside 1..65535 or h / w outside 1..4096");
         return 0;
     }
@@ -294,7 +205,7 @@ size_t salve_bev_jpeg_roundtrip_workspace_bytes(int32_t n, int32_t h, int32_t w)
 int salve_bev_jpeg_roundtrip(const uint32_t* bev_in, uint32_t* bev_out, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, void* ws,
                              size_t ws_bytes, void* stream) {
     if (!bev_in || !bev_out || !qtab || !ws) { salve_fail("salve_bev_jpeg_roundtrip: null pointer"); return SALVE_ERR_BAD_ARG; }
-    if (!good_shape(n, h, w)) { salve_fail("salve_bev_jpeg_roundtrip: n outside 1..65535 or h / w outside 1..4096"); return SALVE_ERR_BAD_ARG; }
+    if (!jpeg_good_shape(n, h, w)) { salve_fail("salve_bev_jpeg_roundtrip: n outside 1..65535 or h / w outside 1..4096"); return SALVE_ERR_BAD_ARG; }
     if (((uintptr_t)bev_in | (uintptr_t)bev_out) & 3) { salve_fail("salve_bev_jpeg_roundtrip: the images must be 4-byte aligned"); return SALVE_ERR_BAD_ARG; }
     QTables qt;
     for (int i = 0; i < 128; i++) {

@@ -1,8 +1,10 @@
-"""The quantisation tables of the reference's JPEG hop.
+"""The quantisation tables of the reference's JPEG hop, and the file around a device-coded scan.
 
 The reference writes every BEV render with `imageio.imwrite(path.jpg, img)` (bev_rendering_utils.py:629-630) -- Pillow's encoder
 over libjpeg at quality 75, baseline, 4:2:0 -- and reads the file back (zind_data.py:306-315).  `BevRasteriser.jpeg_roundtrip`
 reproduces decode(encode(img)) on the device (salve_amd/csrc/jpeg_roundtrip.hip); the tables it divides by come from here.
+`BevRasteriser.jpeg_encode` leaves the entropy-coded scan of that very file (salve_amd/csrc/jpeg_encode.hip); `file_bytes` puts
+Pillow's header in front of it and the end marker behind it.
 Pure host arithmetic, no device.
 """
 
@@ -42,3 +44,95 @@ def quality_tables(quality: int) -> np.ndarray:
     tables -- (entry * scale + 50) / 100, clamped to 1..255 -- i.e. the tables of Pillow's `save(path, quality=quality)`."""
     scale = quality_scaling(quality)
     return np.stack([np.clip((t * scale + 50) // 100, 1, 255) for t in (STD_LUMA, STD_CHROMA)]).astype(np.uint16)
+
+
+# ---------------------------------------------------------------------------------------------------- the file around the scan
+# ITU-T T.81 Annex K.3, tables K.3 - K.6: the Huffman tables libjpeg's jpeg_set_defaults installs and Pillow's default
+# (optimize=False) writes.  BITS: the number of codes of each length 1 .. 16; HUFFVAL: the symbols in code order.
+BITS_DC_LUMA = (0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0)
+HUFFVAL_DC_LUMA = (
+    0x00, 0x01, 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x08, 0x09, 0x0a, 0x0b)
+
+BITS_AC_LUMA = (0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 125)
+HUFFVAL_AC_LUMA = (
+    0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07,
+    0x22, 0x71, 0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0,
+    0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28,
+    0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48, 0x49,
+    0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69,
+    0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89,
+    0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7,
+    0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3, 0xc4, 0xc5,
+    0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
+    0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa)
+
+BITS_DC_CHROMA = (0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0)
+HUFFVAL_DC_CHROMA = (
+    0x00, 0x01, 0x02, 0x03, 0x04, 0x05, 0x06, 0x07, 0x08, 0x09, 0x0a, 0x0b)
+
+BITS_AC_CHROMA = (0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 119)
+HUFFVAL_AC_CHROMA = (
+    0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71,
+    0x13, 0x22, 0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0,
+    0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26,
+    0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
+    0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68,
+    0x69, 0x6a, 0x73, 0x74, 0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87,
+    0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5,
+    0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
+    0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
+    0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8,
+    0xf9, 0xfa)
+
+
+def huffman_codes(bits, huffval) -> np.ndarray:
+    """uint32 [256]: code << 5 | length of every symbol of a table (0: not a symbol), by T.81 Annex C -- the codes of one length are
+    consecutive, the first code of the next length is the successor shifted left.  The layout the device coder's tables have."""
+    out = np.zeros(256, dtype=np.uint32)
+    code, k = 0, 0
+    for length in range(1, 17):
+        for _ in range(bits[length - 1]):
+            out[huffval[k]] = (code << 5) | length
+            code += 1
+            k += 1
+        code <<= 1
+    return out
+
+
+DC_CODES = np.stack([huffman_codes(BITS_DC_LUMA, HUFFVAL_DC_LUMA), huffman_codes(BITS_DC_CHROMA, HUFFVAL_DC_CHROMA)])   # [luma, chroma][category]
+AC_CODES = np.stack([huffman_codes(BITS_AC_LUMA, HUFFVAL_AC_LUMA), huffman_codes(BITS_AC_CHROMA, HUFFVAL_AC_CHROMA)])   # [luma, chroma][run << 4 | size]
+
+# natural (row-major) index of zigzag position k (T.81 figure A.6)
+ZIGZAG = np.array(sorted(range(64), key=lambda i: (i // 8 + i % 8, (i // 8) if (i // 8 + i % 8) % 2 else (i % 8))), dtype=np.int64)
+
+HEADER_BYTES = 623
+
+
+def _segment(marker: int, payload: bytes) -> bytes:
+    return bytes([0xFF, marker]) + (len(payload) + 2).to_bytes(2, "big") + payload
+
+
+def file_header(h: int, w: int, quality: int) -> bytes:
+    """The 623 bytes Pillow's `Image.fromarray(rgb).save(path, quality=quality)` writes in front of the entropy-coded scan of an
+    h x w RGB image: SOI, APP0 (JFIF 1.01, no units, density 1 x 1), the two quantisation tables in zigzag order, SOF0 (4:2:0),
+    the four standard Huffman tables, SOS."""
+    h, w = int(h), int(w)
+    if not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"a JPEG file holds 1..65535 rows and columns, got {h} x {w}")
+    qt = quality_tables(quality)
+    out = b"\xff\xd8" + _segment(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for k in range(2):
+        out += _segment(0xDB, bytes([k]) + bytes(int(v) for v in qt[k][ZIGZAG]))
+    out += _segment(0xC0, bytes([8]) + h.to_bytes(2, "big") + w.to_bytes(2, "big") + bytes([3, 1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1]))
+    for ident, bits, vals in ((0x00, BITS_DC_LUMA, HUFFVAL_DC_LUMA), (0x10, BITS_AC_LUMA, HUFFVAL_AC_LUMA),
+                              (0x01, BITS_DC_CHROMA, HUFFVAL_DC_CHROMA), (0x11, BITS_AC_CHROMA, HUFFVAL_AC_CHROMA)):
+        out += _segment(0xC4, bytes([ident]) + bytes(bits) + bytes(vals))
+    out += _segment(0xDA, bytes([3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 0x3F, 0]))
+    assert len(out) == HEADER_BYTES
+    return out
+
+
+def file_bytes(scan: bytes, h: int, w: int, quality: int) -> bytes:
+    """The whole file around an entropy-coded scan (BevRasteriser.jpeg_encode's bytes of one image): header + scan + EOI."""
+    return file_header(h, w, quality) + bytes(scan) + b"\xff\xd9"

@@ -116,6 +116,7 @@ class BevRasteriser:
         self.ws_slot = 0
         self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
         self._jpeg_ws = {}      # jpeg_roundtrip's workspaces by stream: callers on different streams never share one
+        self._jpeg_encode_ws = {}   # jpeg_encode's, likewise
         self._jpeg_tables = {}  # quality -> uint16 [2, 64] (host)
 
     # ------------------------------------------------------------------ helpers
@@ -384,6 +385,56 @@ class BevRasteriser:
                                                        qtab.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
                 _lib.check(st, "salve_bev_jpeg_roundtrip")
         return out
+
+    JPEG_STRIDE_FRACTION = 8   # jpeg_encode's default slot: 1 / 8 of salve_bev_jpeg_encode_max_bytes (see its docstring)
+
+    def jpeg_encode(self, bev: torch.Tensor, quality: int = 75, stride: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """int32 [n, H, W] images (0x00BBGGRR) -> (scan uint8 [n, stride], nbytes int32 [n]), both on the device: scan[i, :nbytes[i]] is
+        the entropy-coded segment of the file Pillow's `save(path, quality=quality)` writes for image i, byte for byte
+        (include/salve_hip.h: salve_bev_jpeg_encode); `salve_amd.jpeg.file_bytes` puts the header and the end marker around it.
+        `stride`: bytes per image slot, a multiple of 4.  The default is 1 / 8 of the proven bound for any content (2490 bytes per
+        16 x 16 MCU): 318 720 bytes at 501 x 501, where at quality 75 the test table's render-like textured disc needs 66 KB, its layout
+        image 14 KB and full-frame noise 154 KB (300 KB at quality 95; the synthetic scenes' renders have not been sized on their own).  An image that needs more reports it: nbytes[i] > stride holds the NEEDED length, its slot
+        is incomplete, and the caller encodes that image another way (or again with a larger stride); the other images are whole.
+        The bytes of a slot beyond nbytes[i] are not written (the array is not initialised).  On the current stream; batches of at
+        most 1024 images per library call, one workspace per stream."""
+        if bev.dim() != 3 or bev.dtype != torch.int32 or not bev.is_contiguous() or bev.device != self.device:
+            raise _lib.SalveHipError(f"jpeg_encode takes contiguous int32 [n, H, W] images on {self.device}, got {bev.dtype} {tuple(bev.shape)}")
+        n, h, w = (int(v) for v in bev.shape)
+        bound = self.lib.salve_bev_jpeg_encode_max_bytes(h, w)
+        if bound == 0:
+            _lib.check(-1, "salve_bev_jpeg_encode_max_bytes")
+        if stride is None:
+            stride = (bound // self.JPEG_STRIDE_FRACTION + 3) // 4 * 4
+        stride = int(stride)
+        if stride <= 0 or stride % 4:
+            raise _lib.SalveHipError(f"jpeg_encode: stride must be a positive multiple of 4, got {stride}")
+        scan = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
+        nbytes = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return scan, nbytes
+        q = int(quality)
+        if q not in self._jpeg_tables:
+            from salve_amd.jpeg import quality_tables
+
+            self._jpeg_tables[q] = np.ascontiguousarray(quality_tables(q), dtype=np.uint16)
+        qtab = self._jpeg_tables[q]
+        per = min(n, self.JPEG_IMAGES_PER_CALL)
+        need = self.lib.salve_bev_jpeg_encode_workspace_bytes(per, h, w)
+        if need == 0:
+            _lib.check(-1, "salve_bev_jpeg_encode_workspace_bytes")
+        stream = torch.cuda.current_stream(self.device)
+        ws = self._jpeg_encode_ws.get(stream.cuda_stream)
+        if ws is None or ws.numel() < need:   # (allocated under the stream that uses it, as jpeg_roundtrip's)
+            ws = self._jpeg_encode_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for lo in range(0, n, per):
+                m = min(per, n - lo)
+                st = self.lib.salve_bev_jpeg_encode(ctypes.c_void_p(bev[lo:].data_ptr()), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
+                                                    ctypes.c_void_p(scan[lo:].data_ptr()), stride, ctypes.c_void_p(nbytes[lo:].data_ptr()),
+                                                    ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
+                _lib.check(st, "salve_bev_jpeg_encode")
+        return scan, nbytes
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:
         """Tile jobs naming image `bev_index` of a BEV array -- or, with pretiled, of an array of TILE_U8X4 images."""

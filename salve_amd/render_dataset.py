@@ -20,11 +20,45 @@ import numpy as np
 import torch
 
 from salve_amd import ingest
+from salve_amd import jpeg as jpeg_file
 from salve_amd.dataset.zind_partition import DATASET_SPLITS
 from salve_amd.rasteriser import SURFACES, BevRasteriser, pack_hypotheses
 from salve_amd.utils import image_io
 
 SURFACE_TYPES = ("floor", "ceiling")  # scripts/render_dataset_bev.py:91
+JPEG_QUALITY = 75   # image_io.write_jpeg's (imageio's default)
+
+
+def _check_jpeg_route(jpeg: str) -> None:
+    if jpeg not in ("host", "device"):
+        raise ValueError(f"jpeg must be 'host' or 'device', got {jpeg!r}")
+
+
+def _device_jpegs(ras: BevRasteriser, bev: torch.Tensor, stride: Optional[int]) -> List[object]:
+    """Per image of `bev` (int32 [n, H, W]) what `_write_tile` writes: the entropy-coded scan as bytes, coded on the device
+    (BevRasteriser.jpeg_encode) -- the download is ONE 2-D copy of [n, longest scan] bytes, not the pixels -- or, for an image that
+    did not fit its slot, the uint8 [H, W, 3] pixels for the host encoder (the same file by construction)."""
+    scan, nbytes = ras.jpeg_encode(bev, JPEG_QUALITY, stride)
+    lens = nbytes.cpu().numpy()
+    fits = lens <= scan.shape[1]
+    longest = int(lens[fits].max()) if fits.any() else 0
+    host = scan[:, :longest].cpu().numpy()
+    out: List[object] = [host[i, :lens[i]].tobytes() if fits[i] else None for i in range(len(lens))]
+    late = np.flatnonzero(~fits)
+    if len(late):
+        pixels = ras.export_u8(bev[torch.from_numpy(late).to(bev.device)]).cpu().numpy()
+        for k, i in enumerate(late):
+            out[i] = pixels[k]
+    return out
+
+
+def _write_tile(path: str, tile, hw: Tuple[int, int]) -> None:
+    """`tile`: uint8 [H, W, 3] pixels (encoded here by Pillow) or the scan bytes of `_device_jpegs` (only wrapped and written)."""
+    if isinstance(tile, bytes):
+        with open(path, "wb") as f:
+            f.write(jpeg_file.file_bytes(tile, hw[0], hw[1], JPEG_QUALITY))
+    else:
+        image_io.write_jpeg(path, tile)
 
 
 def available_floors(hypotheses_save_root: str, building_id: str) -> List[str]:
@@ -37,12 +71,16 @@ def available_floors(hypotheses_save_root: str, building_id: str) -> List[str]:
 def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypotheses_save_root: str, raw_dataset_dir: str,
                                 building_id: str, floor_id: str, layout_save_root: Optional[str], render_modalities: List[str],
                                 multiprocess_building_panos: bool = False, num_processes: int = 1, device=None, batch: int = 256,
-                                floor_pose_graph=None) -> int:
+                                floor_pose_graph=None, jpeg: str = "host", jpeg_stride: Optional[int] = None) -> int:
     """All floor + ceiling texture maps of one floor (scripts/render_dataset_bev.py:34-117).  `multiprocess_building_panos`
     and `num_processes` are accepted for signature compatibility; the parallelism is the GPU's.  Returns the number of
     JPEG files written.
     The "layout" modality needs the floor's pose graph with room layouts and W/D/O objects (the reference loads it with
-    hnet_prediction_loader, :61-75, which is outside this path): pass it as `floor_pose_graph`."""
+    hnet_prediction_loader, :61-75, which is outside this path): pass it as `floor_pose_graph`.
+    jpeg: "host" (default) downloads every image's pixels and encodes them with Pillow; "device" codes the files' entropy-coded scans
+    on the GPU (BevRasteriser.jpeg_encode), downloads those and only writes bytes -- the same files, byte for byte.  `jpeg_stride`:
+    the device route's bytes per image slot (default: jpeg_encode's); an image that needs more takes the host route."""
+    _check_jpeg_route(jpeg)
     if "layout" in render_modalities and floor_pose_graph is None:
         raise NotImplementedError("the layout modality needs `floor_pose_graph` (loading inferred layouts is outside this path)")
     hyps = ingest.load_floor_hypotheses(hypotheses_save_root, building_id, floor_id)
@@ -51,7 +89,7 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
     img_fpaths = ingest.floor_pano_fpaths(raw_dataset_dir, building_id)
     written = 0
     if "layout" in render_modalities:
-        written += _render_floor_layouts(hyps, img_fpaths, layout_save_root, floor_pose_graph, device)
+        written += _render_floor_layouts(hyps, img_fpaths, layout_save_root, floor_pose_graph, device, jpeg, jpeg_stride)
     if "rgb_texture" not in render_modalities:
         return written
     names = {s: hyps.tile_paths(bev_save_root, img_fpaths, s) for s in SURFACE_TYPES}  # (tile of i1, tile of i2)
@@ -66,7 +104,8 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
     Hb, Wb = ras.bev_hw
 
     def render(rows: List[Tuple[int, str, np.ndarray, np.ndarray, int]]):
-        """rows of (store index, surface, R, t, apply_pose) -> (uint8 [n,H,W,3] on the host, in-window point counts)."""
+        """rows of (store index, surface, R, t, apply_pose) -> (per image what `_write_tile` takes -- uint8 [H,W,3] on the host, or
+        with jpeg="device" its scan bytes --, in-window point counts)."""
         out, cnts = [], []
         for lo in range(0, len(rows), batch):
             part = rows[lo:lo + batch]
@@ -75,10 +114,10 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
             counts = torch.zeros(len(part), dtype=torch.int32, device=dev)
             bev = torch.empty((len(part), Hb, Wb), dtype=torch.int32, device=dev)
             ras.render_counted(store.rgb, store.depth, ras.upload_hypotheses(h), len(part), bev, counts)
-            out.append(ras.export_u8(bev).cpu().numpy())
+            out.extend(ras.export_u8(bev).cpu().numpy() if jpeg == "host" else _device_jpegs(ras, bev, jpeg_stride))
             cnts.append(counts.cpu().numpy())
             ras.check(f"render_building_floor_pairs({building_id}, {floor_id})")   # before any of these images is written to disk
-        return np.concatenate(out), np.concatenate(cnts)
+        return out, np.concatenate(cnts)
 
     eye, zero = np.eye(2, dtype=np.float32), np.zeros(2, dtype=np.float32)
     # pano i2 is rendered at identity (bev_rendering_utils.py:455): once per (pano, surface)
@@ -92,13 +131,14 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
             continue  # render_bev_pair -> (None, None): nothing is written for this pair and surface
         fp1, fp2 = names[s][j]
         os.makedirs(os.path.dirname(fp1), exist_ok=True)
-        image_io.write_jpeg(fp1, posed_img[k])
-        image_io.write_jpeg(fp2, img2)
+        _write_tile(fp1, posed_img[k], (Hb, Wb))
+        _write_tile(fp2, img2, (Hb, Wb))
         written += 2
     return written
 
 
-def _render_floor_layouts(hyps, img_fpaths: Dict[int, str], layout_save_root: str, floor_pose_graph, device) -> int:
+def _render_floor_layouts(hyps, img_fpaths: Dict[int, str], layout_save_root: str, floor_pose_graph, device, jpeg: str = "host",
+                          jpeg_stride: Optional[int] = None) -> int:
     """Layout tiles of every hypothesis of a floor in one launch (bev_rendering_utils.py:632-663: `floor` names only, skip if
     both files exist).  The layout of pano i2 does not depend on the hypothesis: rendered once per panorama."""
     from salve_amd import layout
@@ -118,26 +158,30 @@ def _render_floor_layouts(hyps, img_fpaths: Dict[int, str], layout_save_root: st
         ident_of.setdefault(int(hyps.i2[j]), s2)
     ident_ids = sorted(ident_of)
     imgs = layout.rasterise_layouts(specs + [ident_of[p] for p in ident_ids], dev)
-    u8 = BevRasteriser(dev).export_u8(imgs).cpu().numpy()
+    ras = BevRasteriser(dev)
+    u8 = ras.export_u8(imgs).cpu().numpy() if jpeg == "host" else _device_jpegs(ras, imgs, jpeg_stride)
+    hw = (int(imgs.shape[1]), int(imgs.shape[2]))
     written = 0
     for k, j in enumerate(todo):
         fp1, fp2 = paths[j]
         os.makedirs(os.path.dirname(fp1), exist_ok=True)
-        image_io.write_jpeg(fp1, u8[k])
-        image_io.write_jpeg(fp2, u8[len(todo) + ident_ids.index(int(hyps.i2[j]))])
+        _write_tile(fp1, u8[k], hw)
+        _write_tile(fp2, u8[len(todo) + ident_ids.index(int(hyps.i2[j]))], hw)
         written += 2
     return written
 
 
 def render_pairs(num_processes: int, depth_save_root: str, bev_save_root: str, raw_dataset_dir: str, hypotheses_save_root: str,
                  layout_save_root: Optional[str], render_modalities: List[str], split: Optional[str], building_id: Optional[str],
-                 multiprocess_building_panos: bool = False, device=None, rank: int = 0, world: int = 1) -> int:
+                 multiprocess_building_panos: bool = False, device=None, rank: int = 0, world: int = 1, jpeg: str = "host") -> int:
     """All floors of a split's buildings, or of one building (scripts/render_dataset_bev.py:120-191): exactly one of
     `split` / `building_id`; building 1348 is skipped (two panoramas share an id, :160-162).
     world > 1: one process per GPU.  The reference hands its (building, floor) work list to a multiprocessing.Pool
     (`p.starmap(render_building_floor_pairs, args)`, :186-188); here rank r takes items r, r + world, ... of the same list (round
     robin: buildings differ a lot in size, neighbours in the sorted list less so) and writes their files -- the items are
-    independent, nothing is exchanged.  Returns the number of JPEG files THIS rank wrote."""
+    independent, nothing is exchanged.  Returns the number of JPEG files THIS rank wrote.  `jpeg`: as for
+    render_building_floor_pairs (the layout modality's pose graph is not loaded on this path)."""
+    _check_jpeg_route(jpeg)
     if building_id is not None and split is not None:
         raise ValueError("Either `split` or `building_id` should be provided, but not both.")
     if not 0 <= rank < world:
@@ -145,7 +189,7 @@ def render_pairs(num_processes: int, depth_save_root: str, bev_save_root: str, r
     written = 0
     for bid, floor_id in floor_work_list(hypotheses_save_root, split, building_id)[rank::world]:
         written += render_building_floor_pairs(depth_save_root, bev_save_root, hypotheses_save_root, raw_dataset_dir, bid, floor_id,
-                                               layout_save_root, render_modalities, multiprocess_building_panos, num_processes, device)
+                                               layout_save_root, render_modalities, multiprocess_building_panos, num_processes, device, jpeg=jpeg)
     return written
 
 
