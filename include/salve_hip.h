@@ -45,7 +45,8 @@ typedef enum {
                                         additive within 7: salve_conv_f32_* (training convolutions), salve_bev_tiles_aug, salve_bev_train_tiles and
                                         salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
                                         salve_adam_step, salve_head_* (the training classifier head), salve_bev_jpeg_roundtrip, salve_bev_jpeg_encode
-                                        (with salve_bev_jpeg_encode_workspace_bytes / _max_bytes) */
+                                        (with salve_bev_jpeg_encode_workspace_bytes / _max_bytes), salve_bev_jpeg_decode (with
+                                        salve_bev_jpeg_decode_workspace_bytes and the SALVE_JPEG_* bits of its per-image status) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -741,6 +742,72 @@ size_t salve_bev_jpeg_encode_workspace_bytes(int32_t n, int32_t h, int32_t w);
 size_t salve_bev_jpeg_encode_max_bytes(int32_t h, int32_t w);
 int salve_bev_jpeg_encode(const uint32_t* bev, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, uint8_t* scan, size_t scan_stride,
                           int32_t* scan_bytes, void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The tile data set's JPEG FILES decoded on the device, in whole batches (additive within ABI 7): opt-in.  The reference trains and
+ * evaluates from rendered tiles on disk and decodes every file with Pillow (zind_data.py:306-315).  salve_bev_jpeg_decode decodes n
+ * images of ONE size that SHARE their tables -- baseline: 8-bit, three components, 4:2:0, one interleaved scan (MCU = Y0 Y1 Y2 Y3 Cb
+ * Cr), no restart interval -- to the pixels Pillow's decoder gives (libjpeg: slow-integer inverse DCT, fancy upsampling), bit for bit.
+ * The host parses the headers (salve_amd/jpeg.py: parse_file) and hands over the entropy-coded scans as they stand in the files.
+ *   scans        device bytes, scans_size of them.  Image i is the stuffed, padded scan at scans + scan_offset[i], scan_bytes[i] long:
+ *                no header, no EOI, any byte alignment.  The caller leaves SALVE_JPEG_SCAN_PADDING (16) bytes behind the last scan:
+ *                scan_offset[i] + scan_bytes[i] + 16 <= scans_size for every image, else the image is not read at all and reports
+ *                SALVE_JPEG_BAD_SLOT.  (The decoder itself reads no byte at or behind scan_offset[i] + scan_bytes[i].)
+ *   scan_offset  device int64 [n];  scan_bytes  device int32 [n] (0 is allowed: the image reports SALVE_JPEG_TRUNCATED)
+ *   qtab         HOST uint16 [2][64]: the luma and the chroma quantisation table of the files' DQT segments in NATURAL order
+ *   huffman      HOST bytes [4][272]: DC luma, AC luma, DC chroma, AC chroma, each the 16 BITS and 256 HUFFVAL bytes of a DHT segment
+ *                (HUFFVAL zero-filled behind its last symbol).  Both are read before the call returns.
+ *   bev_out      device uint32 [n, h, w], 0x00BBGGRR: what every tile entry reads
+ *   image_status device int32 [n]: 0, or the SALVE_JPEG_* bits of what was wrong with the image's scan.  Always written.
+ *   Entropy stage (ITU-T T.81 F.2.2), one wavefront per image: the lanes stage the scan into LDS in coalesced runs; the 0x00 stuffed
+ *                behind a 0xFF is dropped inline; the symbol loop is wave-uniform; codes are looked up in a 9-bit look-ahead table in
+ *                LDS, longer ones by the maxcode walk; DC category plus value bits with the EXTEND rule and a predictor per component
+ *                across the whole scan; (run, size) symbols with ZRL and EOB in zigzag order; every block leaves as one coalesced
+ *                128-byte store of int16 coefficients into the workspace.
+ *   Inverse stage: dequantisation and the two inverse DCT passes into the planes of salve_bev_jpeg_roundtrip, then its pixel launch
+ *                unchanged (the same device functions).  The blocks of an edge MCU that lie outside the image are decoded and ignored.
+ *   Malformed input: no scan makes the kernels read or write out of bounds, loop without end or fault.  The byte position is bounded
+ *                by scan_bytes[i], the coefficient index by 63, the DC category by 11 and the predictor by +-2047; a code that is not
+ *                in the table is rejected; every turn of the symbol loop consumes at least one bit or ends.  Each failure sets a bit:
+ *                  SALVE_JPEG_BAD_CODE      a bit pattern that is no code of its table
+ *                  SALVE_JPEG_COEF_OVERRUN  a run that passes coefficient 63
+ *                  SALVE_JPEG_TRUNCATED     the scan ended before the last MCU
+ *                  SALVE_JPEG_DC_RANGE      a DC category above 11 or a DC predictor outside +-2047
+ *                  SALVE_JPEG_LEFTOVER      more than 7 bits left behind the last MCU, or pad bits that are not all 1
+ *                  SALVE_JPEG_MARKER        0xFF followed by anything but 0x00 inside the scan, or as its last byte
+ *                  SALVE_JPEG_BAD_SLOT      offset / length outside the scan buffer and its padding
+ *                A failing image keeps the coefficients it had decoded, every later one is zero, and it still goes through the inverse
+ *                stage; the other images of the call are unaffected, and the device status word is not touched.
+ *   Parity with Pillow is claimed for streams whose coefficients came from an 8-bit image (every real encoder's output); for other
+ *                well-formed streams the output is deterministic only.
+ *   Checks:      SALVE_ERR_BAD_ARG (and 0 from the size query) on null pointers, n <= 0, n > 65535, h or w outside [1, 4096], a
+ *                quantisation entry outside [1, 255], a BITS array that over-subscribes the code space or sums past 256, scans_size
+ *                below 16, scan_offset not 8-byte or scan_bytes / bev_out / image_status not 4-byte aligned, a workspace smaller than
+ *                salve_bev_jpeg_decode_workspace_bytes(n, h, w) or not 16-byte aligned.
+ *   Workspace:   the planes (1.5 bytes per pixel of the images rounded up to whole 16 x 16 MCUs) and 768 bytes of coefficients per
+ *                MCU: 1.2 MB per 501 x 501 image.  It needs no initialisation and holds nothing from one call to the next.
+ *   stages:      SALVE_JPEG_STAGES_ALL for a decode.  SALVE_JPEG_STAGE_ENTROPY alone runs the first launch only (scans -> coefficients in
+ *                the workspace, image_status written; bev_out untouched); SALVE_JPEG_STAGE_INVERSE alone runs the other two on the
+ *                coefficients the last entropy stage left in the SAME workspace for the same n, h, w (image_status untouched): a caller
+ *                can put events between the stages (tools/measure/bench_tile_files.py).  Any other value: SALVE_ERR_BAD_ARG.
+ *   Three launches, asynchronous on `stream`.  Integer arithmetic and plain stores only, one writer per output: the same input
+ *   gives the same bits.  Offsets are 64-bit.
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_JPEG_SCAN_PADDING 16
+#define SALVE_JPEG_STAGE_ENTROPY 1u
+#define SALVE_JPEG_STAGE_INVERSE 2u
+#define SALVE_JPEG_STAGES_ALL 3u
+#define SALVE_JPEG_BAD_CODE 1u
+#define SALVE_JPEG_COEF_OVERRUN 2u
+#define SALVE_JPEG_TRUNCATED 4u
+#define SALVE_JPEG_DC_RANGE 8u
+#define SALVE_JPEG_LEFTOVER 16u
+#define SALVE_JPEG_MARKER 32u
+#define SALVE_JPEG_BAD_SLOT 64u
+size_t salve_bev_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w);
+int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes, int32_t n, int32_t h,
+                          int32_t w, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws,
+                          size_t ws_bytes, uint32_t stages, void* stream);
 
 #ifdef __cplusplus
 }

@@ -81,11 +81,14 @@ EXPORTED_SYMBOLS = (
     "salve_bev_jpeg_encode_workspace_bytes",
     "salve_bev_jpeg_encode_max_bytes",
     "salve_bev_jpeg_encode",
+    "salve_bev_jpeg_decode_workspace_bytes",
+    "salve_bev_jpeg_decode",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
 RESNET_NO_PROJ_FUSE, RESNET_NO_CHAIN, RESNET_CHAIN_EXPAND_ONLY, RESNET_CHAIN_16_WAVES, RESNET_CHAIN_NO_SPLIT = 32, 64, 128, 256, 512
 RESNET_CHAIN_STORE_ALL, RESNET_NO_TRANSPOSED_TILES, RESNET_NO_NEXT_FUSE = 1024, 2048, 4096
+JPEG_STAGE_ENTROPY, JPEG_STAGE_INVERSE, JPEG_STAGES_ALL = 1, 2, 3   # salve_bev_jpeg_decode's `stages`
 STATUS_WALK_FAILED = 1
 STATUS_FP16_RANGE = 2
 STATUS_BAD_HYPOTHESIS = 4
@@ -287,6 +290,11 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_jpeg_encode_max_bytes.restype = sz
     lib.salve_bev_jpeg_encode.argtypes = [vp, i32, i32, i32, vp, vp, sz, vp, vp, sz, vp]   # bev, n, h, w, HOST qtab, scan, scan_stride, scan_bytes, ws, ws_bytes, stream
     lib.salve_bev_jpeg_encode.restype = ctypes.c_int
+    lib.salve_bev_jpeg_decode_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.salve_bev_jpeg_decode_workspace_bytes.restype = sz
+    # scans, scans_size, scan_offset, scan_bytes, n, h, w, HOST qtab, HOST huffman, bev_out, image_status, ws, ws_bytes, stages, stream
+    lib.salve_bev_jpeg_decode.argtypes = [vp, sz, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
+    lib.salve_bev_jpeg_decode.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

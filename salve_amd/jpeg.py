@@ -4,11 +4,15 @@ The reference writes every BEV render with `imageio.imwrite(path.jpg, img)` (bev
 over libjpeg at quality 75, baseline, 4:2:0 -- and reads the file back (zind_data.py:306-315).  `BevRasteriser.jpeg_roundtrip`
 reproduces decode(encode(img)) on the device (salve_amd/csrc/jpeg_roundtrip.hip); the tables it divides by come from here.
 `BevRasteriser.jpeg_encode` leaves the entropy-coded scan of that very file (salve_amd/csrc/jpeg_encode.hip); `file_bytes` puts
-Pillow's header in front of it and the end marker behind it.
+Pillow's header in front of it and the end marker behind it.  `parse_file` goes the other way for `BevRasteriser.jpeg_decode`
+(salve_amd/csrc/jpeg_decode.hip): size, tables and the scan's place in a file from disk.
 Pure host arithmetic, no device.
 """
 
 from __future__ import annotations
+
+import re
+from typing import Dict, NamedTuple
 
 import numpy as np
 
@@ -136,3 +140,153 @@ def file_header(h: int, w: int, quality: int) -> bytes:
 def file_bytes(scan: bytes, h: int, w: int, quality: int) -> bytes:
     """The whole file around an entropy-coded scan (BevRasteriser.jpeg_encode's bytes of one image): header + scan + EOI."""
     return file_header(h, w, quality) + bytes(scan) + b"\xff\xd9"
+
+
+# ---------------------------------------------------------------------------------------------------- reading a file's header
+class Unsupported(ValueError):
+    """A file outside what `BevRasteriser.jpeg_decode` takes (baseline, 8-bit, three components, 4:2:0, one interleaved scan, no
+    restart interval): the caller decodes it on the host."""
+
+
+class ParsedFile(NamedTuple):
+    h: int
+    w: int
+    qtab: np.ndarray          # uint16 [2, 64], natural order: the luma component's table, the chroma components' table
+    huffman: np.ndarray       # uint8 [4, 272]: DC luma, AC luma, DC chroma, AC chroma; each 16 BITS + 256 HUFFVAL (zero-filled)
+    scan_offset: int          # the entropy-coded scan is data[scan_offset : scan_offset + scan_bytes] (stuffed, padded; no EOI)
+    scan_bytes: int
+    header_key: bytes         # the bytes before the scan: files with equal keys share size and tables and may go into one call
+
+
+HUFFMAN_TABLE_BYTES = 272
+SCAN_PADDING = 16             # include/salve_hip.h: SALVE_JPEG_SCAN_PADDING
+_MARKER_IN_SCAN = re.compile(rb"\xff[^\x00]")   # inside entropy-coded data every 0xFF is followed by a stuffed 0x00
+# include/salve_hip.h: SALVE_JPEG_*, the bits of salve_bev_jpeg_decode's per-image status
+STATUS_BITS = {1: "a bit pattern that is no Huffman code of its table", 2: "a run past coefficient 63", 4: "the scan ends before the last MCU",
+               8: "a DC coefficient out of range", 16: "bits left over behind the last MCU", 32: "a marker inside the scan",
+               64: "the scan lies outside the buffer"}
+
+
+def describe_status(word: int) -> str:
+    """The names of the bits set in one image's status word."""
+    return "; ".join(text for bit, text in STATUS_BITS.items() if int(word) & bit) or "ok"
+
+
+def parse_file(data: bytes) -> ParsedFile:
+    """Walks the marker segments of a JPEG file (ITU-T T.81 Annex B) up to its scan and returns what salve_bev_jpeg_decode needs.
+    Raises `Unsupported(reason)` for everything outside part 1 of what the device decodes: progressive and other non-baseline
+    frames, greyscale, other sampling factors, 12-bit samples, 16-bit quantisation entries, a restart interval, more than one scan,
+    a missing EOI, a truncated segment.  Pure host arithmetic."""
+    data = bytes(data)
+    if data[:2] != b"\xff\xd8":
+        raise Unsupported("no SOI marker")
+    qt: Dict[int, np.ndarray] = {}
+    huff: Dict[int, np.ndarray] = {}
+    frame = None
+    at = 2
+    while True:
+        if at + 4 > len(data):
+            raise Unsupported("truncated: the file ends in front of its scan")
+        if data[at] != 0xFF:
+            raise Unsupported(f"no marker at byte {at}")
+        marker = data[at + 1]
+        if marker == 0xFF:      # fill bytes in front of a marker
+            at += 1
+            continue
+        if marker in (0xD8, 0xD9, 0x01) or 0xD0 <= marker <= 0xD7:
+            raise Unsupported(f"marker FF{marker:02X} in front of the scan")
+        length = int.from_bytes(data[at + 2:at + 4], "big")
+        if length < 2 or at + 2 + length > len(data):
+            raise Unsupported(f"truncated: segment FF{marker:02X} at byte {at} runs past the end of the file")
+        body = data[at + 4:at + 2 + length]
+        at += 2 + length
+        if marker == 0xDB:
+            k = 0
+            while k < len(body):
+                pq, tq = body[k] >> 4, body[k] & 15
+                if pq != 0:
+                    raise Unsupported("16-bit quantisation entries")
+                if tq > 3 or k + 65 > len(body):
+                    raise Unsupported("a malformed DQT segment")
+                table = np.zeros(64, dtype=np.uint16)
+                table[ZIGZAG] = np.frombuffer(body, dtype=np.uint8, count=64, offset=k + 1)
+                if table.min() < 1:
+                    raise Unsupported("a quantisation entry of 0")
+                qt[tq] = table
+                k += 65
+        elif marker == 0xC4:
+            k = 0
+            while k < len(body):
+                if k + 17 > len(body):
+                    raise Unsupported("a malformed DHT segment")
+                tc, th = body[k] >> 4, body[k] & 15
+                bits = np.frombuffer(body, dtype=np.uint8, count=16, offset=k + 1)
+                count = int(bits.sum())
+                if tc > 1 or th > 3 or count > 256 or k + 17 + count > len(body):
+                    raise Unsupported("a malformed DHT segment")
+                code = 0
+                for length_bits in range(1, 17):
+                    code += int(bits[length_bits - 1])
+                    if code > (1 << length_bits):
+                        raise Unsupported("a Huffman table that over-subscribes its code space")
+                    code <<= 1
+                table = np.zeros(HUFFMAN_TABLE_BYTES, dtype=np.uint8)
+                table[:16] = bits
+                table[16:16 + count] = np.frombuffer(body, dtype=np.uint8, count=count, offset=k + 17)
+                huff[(tc << 4) | th] = table
+                k += 17 + count
+        elif marker == 0xC0:
+            if frame is not None:
+                raise Unsupported("more than one frame")
+            if len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise Unsupported("a malformed SOF0 segment")
+            if body[0] != 8:
+                raise Unsupported(f"{body[0]}-bit samples")
+            h, w, nc = int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big"), body[5]
+            if nc != 3:
+                raise Unsupported(f"{nc} component(s): greyscale or CMYK")
+            comps = [(body[6 + 3 * c], body[7 + 3 * c], body[8 + 3 * c]) for c in range(3)]   # id, sampling, table
+            if [c[1] for c in comps] != [0x22, 0x11, 0x11]:
+                raise Unsupported("sampling factors other than 4:2:0")
+            if comps[1][2] != comps[2][2]:
+                raise Unsupported("Cb and Cr use different quantisation tables")
+            if h < 1 or w < 1:
+                raise Unsupported("an empty frame (or DNL)")
+            frame = (h, w, comps)
+        elif 0xC1 <= marker <= 0xCF and marker not in (0xC4, 0xC8, 0xCC):
+            raise Unsupported({0xC2: "progressive (SOF2)", 0xC1: "extended sequential (SOF1)"}.get(marker, f"frame type FF{marker:02X}"))
+        elif marker == 0xCC:
+            raise Unsupported("arithmetic coding conditioning (DAC)")
+        elif marker == 0xDD:
+            if len(body) != 2:
+                raise Unsupported("a malformed DRI segment")
+            if int.from_bytes(body, "big") != 0:
+                raise Unsupported("a restart interval")
+        elif marker == 0xDA:
+            if frame is None:
+                raise Unsupported("a scan in front of its frame")
+            h, w, comps = frame
+            if len(body) != 10 or body[0] != 3:
+                raise Unsupported("a scan that does not interleave all three components")
+            sel = [(body[1 + 2 * c], body[2 + 2 * c]) for c in range(3)]
+            if [s[0] for s in sel] != [c[0] for c in comps]:
+                raise Unsupported("a scan whose components are not in the frame's order")
+            if sel[1][1] != sel[2][1]:
+                raise Unsupported("Cb and Cr use different Huffman tables")
+            if tuple(body[7:10]) != (0, 63, 0):
+                raise Unsupported("a spectral selection or successive approximation")
+            try:
+                qtab = np.stack([qt[comps[0][2]], qt[comps[1][2]]])
+                huffman = np.stack([huff[0x00 | (sel[0][1] >> 4)], huff[0x10 | (sel[0][1] & 15)],
+                                    huff[0x00 | (sel[1][1] >> 4)], huff[0x10 | (sel[1][1] & 15)]])
+            except KeyError:
+                raise Unsupported("a table the scan names is missing") from None
+            break
+        # every other segment (APPn, COM, ...) is skipped
+    if data[-2:] != b"\xff\xd9":
+        raise Unsupported("no EOI marker at the end of the file")
+    end = len(data) - 2
+    found = _MARKER_IN_SCAN.search(data, at, end)
+    if found is not None:
+        raise Unsupported(f"marker FF{data[found.start() + 1]:02X} inside the scan: restart markers or a further scan")
+    return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at])

@@ -117,6 +117,7 @@ class BevRasteriser:
         self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
         self._jpeg_ws = {}      # jpeg_roundtrip's workspaces by stream: callers on different streams never share one
         self._jpeg_encode_ws = {}   # jpeg_encode's, likewise
+        self._jpeg_decode_ws = {}   # jpeg_decode's, likewise
         self._jpeg_tables = {}  # quality -> uint16 [2, 64] (host)
 
     # ------------------------------------------------------------------ helpers
@@ -349,7 +350,7 @@ class BevRasteriser:
         _lib.check(st, "salve_bev_export_u8")
         return out
 
-    JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip: images per library call (bounds its workspace: 1.5 bytes per padded pixel)
+    JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip, jpeg_encode, jpeg_decode: images per library call (bounds its workspace: 1.5 bytes per padded pixel)
 
     def jpeg_roundtrip(self, bev: torch.Tensor, quality: int = 75, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """int32 [n, H, W] images (0x00BBGGRR: BEV renders, layout images) -> what the reference's file hop makes of them: Pillow's
@@ -435,6 +436,62 @@ class BevRasteriser:
                                                     ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
                 _lib.check(st, "salve_bev_jpeg_encode")
         return scan, nbytes
+
+    def jpeg_decode(self, scans: torch.Tensor, scan_offset, scan_bytes, h: int, w: int, qtab: np.ndarray, huffman: np.ndarray,
+                    out: Optional[torch.Tensor] = None, stages: int = _lib.JPEG_STAGES_ALL) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The entropy-coded scans of n baseline 4:2:0 JPEG files of ONE size that SHARE their tables (`salve_amd.jpeg.parse_file`: equal
+        `header_key`) -> (int32 [n, h, w] images holding 0x00BBGGRR, int32 [n] status), both on the device: the pixels Pillow decodes
+        from those files, bit for bit (include/salve_hip.h: salve_bev_jpeg_decode; zind_data.py:306-315).
+        scans: uint8 device tensor, 1-D; image i is scans[scan_offset[i] : scan_offset[i] + scan_bytes[i]] (HOST integer arrays), as it
+        stands in the file (stuffed, padded, no EOI), at any alignment; at least 16 bytes of the tensor lie behind the last scan.
+        qtab: uint16 [2, 64] natural order; huffman: uint8 [4, 272] -- `parse_file`'s.  status[i] != 0: image i's scan was malformed
+        (jpeg.STATUS_BITS names the bits); its pixels are what had been decoded, the other images are whole.  Nothing is read back here.
+        stages: _lib.JPEG_STAGES_ALL (default).  For timing, _lib.JPEG_STAGE_ENTROPY runs the Huffman stage alone (status written, images
+        not) and _lib.JPEG_STAGE_INVERSE the inverse stage alone, on the coefficients the entropy stage of the SAME arguments left in
+        this stream's workspace (status not written) -- so at most JPEG_IMAGES_PER_CALL images when the stages are called apart.
+        On the current stream; at most JPEG_IMAGES_PER_CALL images per library call, one workspace per stream."""
+        from salve_amd.jpeg import HUFFMAN_TABLE_BYTES, SCAN_PADDING
+
+        if scans.dim() != 1 or scans.dtype != torch.uint8 or not scans.is_contiguous() or scans.device != self.device:
+            raise _lib.SalveHipError(f"jpeg_decode takes the scans as a contiguous 1-D uint8 tensor on {self.device}, got {scans.dtype} {tuple(scans.shape)}")
+        off = np.ascontiguousarray(scan_offset, dtype=np.int64).reshape(-1)
+        nb = np.ascontiguousarray(scan_bytes, dtype=np.int64).reshape(-1)
+        n, h, w = int(off.shape[0]), int(h), int(w)
+        if nb.shape[0] != n:
+            raise _lib.SalveHipError(f"jpeg_decode: {n} offsets, {nb.shape[0]} lengths")
+        if n and (int(off.min()) < 0 or int(nb.min()) < 0 or int(nb.max()) >= 2 ** 31 or int((off + nb).max()) + SCAN_PADDING > scans.numel()):
+            raise _lib.SalveHipError(f"jpeg_decode: every scan must lie inside the {scans.numel()} bytes given, with {SCAN_PADDING} bytes of padding behind the last")
+        qtab = np.ascontiguousarray(qtab, dtype=np.uint16)
+        huffman = np.ascontiguousarray(huffman, dtype=np.uint8)
+        if qtab.shape != (2, 64) or huffman.shape != (4, HUFFMAN_TABLE_BYTES):
+            raise _lib.SalveHipError(f"jpeg_decode takes qtab [2, 64] and huffman [4, {HUFFMAN_TABLE_BYTES}], got {qtab.shape} and {huffman.shape}")
+        if out is None:
+            out = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
+        elif tuple(out.shape) != (n, h, w) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != self.device:
+            raise _lib.SalveHipError(f"jpeg_decode: out must be contiguous int32 {(n, h, w)} on {self.device}, got {out.dtype} {tuple(out.shape)}")
+        image_status = torch.empty(n, dtype=torch.int32, device=self.device)
+        if n == 0:
+            return out, image_status
+        if stages != _lib.JPEG_STAGES_ALL and n > self.JPEG_IMAGES_PER_CALL:
+            raise _lib.SalveHipError(f"jpeg_decode: the stages can be called apart for at most {self.JPEG_IMAGES_PER_CALL} images (one workspace), got {n}")
+        per = min(n, self.JPEG_IMAGES_PER_CALL)
+        need = self.lib.salve_bev_jpeg_decode_workspace_bytes(per, h, w)
+        if need == 0:
+            _lib.check(-1, "salve_bev_jpeg_decode_workspace_bytes")
+        table = torch.from_numpy(np.concatenate([off.view(np.uint8), nb.astype(np.int32).view(np.uint8)])).to(self.device)   # one upload
+        stream = torch.cuda.current_stream(self.device)
+        ws = self._jpeg_decode_ws.get(stream.cuda_stream)
+        if ws is None or ws.numel() < need:   # (allocated under the stream that uses it, as jpeg_roundtrip's)
+            ws = self._jpeg_decode_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            for lo in range(0, n, per):
+                m = min(per, n - lo)
+                st = self.lib.salve_bev_jpeg_decode(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
+                                                    ctypes.c_void_p(table.data_ptr() + 8 * n + 4 * lo), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
+                                                    huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
+                                                    ctypes.c_void_p(image_status[lo:].data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), int(stages), self._stream())
+                _lib.check(st, "salve_bev_jpeg_decode")
+        return out, image_status
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:
         """Tile jobs naming image `bev_index` of a BEV array -- or, with pretiled, of an array of TILE_U8X4 images."""
