@@ -240,9 +240,10 @@ template <class T>
 __device__ __forceinline__ void store_wb(T* p, T v) { *p = v; }
 
 // Hard-site list: two words per entry, the site (y << 16 | x) and the state its lean walk was in when it gave up
-// (sd_star_resume: a + 128 in two bytes, n0 + 1 in two bits each, bit 20 counter-clockwise, bit 21 half walk), or
-// HARD_FRESH if there is nothing to take over.  A list that overflows (every second pixel a hard site) is a failed render.
+// (sd_star_resume: a + 128 in two bytes, n0 + 1 in two bits each, bit 20 counter-clockwise, bit 21 half walk, bit 23 = HARD_SECOND: the walk was in its second
+// direction, sd_walk's rdir = +-2), or HARD_FRESH if there is nothing to take over.  A list that overflows (every second pixel a hard site) is a failed render.
 constexpr uint32_t HARD_FRESH = 1u << 22;
+constexpr uint32_t HARD_SECOND = 1u << 23;
 __device__ __forceinline__ void push_hard(uint32_t* list, int* counter, int cap, uint32_t site, uint32_t state, int32_t* status) {
     const int k = atomicAdd(counter, 1);
     if (k < cap) {
@@ -627,7 +628,7 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
                     if (r == SDL_LEAN_HARD)   // the general walk takes over at the edge this walk could not answer
                         push_hard(hardlist, &scal[7], hard_cap, ((uint32_t)st.sy << 16) | (uint32_t)st.sx,
                                   (uint32_t)((st.ax + 128) & 0xFF) | ((uint32_t)((st.ay + 128) & 0xFF) << 8) | ((uint32_t)(st.n0x + 1) << 16) |
-                                      ((uint32_t)(st.n0y + 1) << 18) | (st.dir > 0 ? 1u << 20 : 0u) | (st.half ? 1u << 21 : 0u), status);
+                                      ((uint32_t)(st.n0y + 1) << 18) | (st.dir > 0 ? 1u << 20 : 0u) | (st.half ? 1u << 21 : 0u) | (st.dir & 1 ? 0u : HARD_SECOND), status);
                 }
             }
         }
@@ -676,7 +677,7 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
                     const uint32_t s = (uint32_t)__shfl((int)run_words, gw.gbase + 2 * (i - i0));
                     const uint32_t w = (uint32_t)__shfl((int)run_words, gw.gbase + 2 * (i - i0) + 1);
                     const int hx = (int)(s & 0xFFFFu), hy = (int)(s >> 16);
-                    const int r = sd_walk(gw, hx, hy, (w & HARD_FRESH) != 0, (int)(w & 0xFF) - 128, (int)((w >> 8) & 0xFF) - 128, (w >> 20) & 1u ? 1 : -1,
+                    const int r = sd_walk(gw, hx, hy, (w & HARD_FRESH) != 0, (int)(w & 0xFF) - 128, (int)((w >> 8) & 0xFF) - 128, ((w >> 20) & 1u ? 1 : -1) * ((w & HARD_SECOND) ? 2 : 1),
                                           ((w >> 21) & 1u) != 0, (int)((w >> 16) & 3u) - 1, (int)((w >> 18) & 3u) - 1, rw);
                     if (r < 0) err = 1;
                 }

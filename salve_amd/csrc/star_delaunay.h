@@ -267,6 +267,9 @@ SD_FN bool sd_nearest(const SdGrid& g, int sx, int sy, int* nx, int* ny) {
 #ifndef SD_COUNT
 #define SD_COUNT(counter)
 #endif
+#ifndef SD_QUERY_DONE   // sd_walk, after every apex query: did it answer a triangle the site owns?  (tools/probe/host/walk_counters.cpp)
+#define SD_QUERY_DONE(owned)
+#endif
 #ifndef SD_NOW
 #define SD_NOW() 0
 #define SD_LAP(slot, t) (void)(t)
@@ -654,56 +657,81 @@ SD_FN bool sd_apex(const SdGrid& g, int sx, int sy, int ax, int ay, int dir, int
 // (so each triangle of the triangulation is emitted exactly once over all sites), counter-clockwise.
 // Returns the number of wrap steps, or -1 if the safety bound was hit.
 //
-// Only triangles whose other two vertices FOLLOW s in raster order are emitted, i.e. neighbours at angles [0, pi)
-// counter-clockwise from +x.  Three modes, ONE loop (and one inlined copy of sd_apex and of the emit functor):
-//   HALF  the pixel to the right is a site -- the first of those neighbours, adjacent pixels always being Delaunay
-//         neighbours: walk counter-clockwise from it and stop at the first neighbour that precedes s, or at the hull;
-//   CCW   otherwise: counter-clockwise from some neighbour n0 (the nearest site) until the star closes at n0; if the hull
-//         comes first, s is a hull vertex and the fan is finished  CW  (clockwise) from n0 to the hull on the other side.
+// Only triangles whose other two vertices FOLLOW s in raster order are emitted (up(v) := sd_before(s, v)), i.e. those between
+// consecutive neighbours at angles [0, pi) counter-clockwise from +x: the OWNED half of the star.  Consecutive neighbour pairs inside
+// [0, pi) are exactly the owned triangles, so a walk only has to visit that half, each pair once, and may stop where it leaves it.
+// A walk has a FIRST direction and at most one SECOND direction, which starts again at the first neighbour n0 and goes the other
+// way round.  ONE loop (and one inlined copy of sd_apex and of the emit functor) serves them all:
+//   HALF    the pixel to the right is a site -- the first of the owned neighbours, adjacent pixels always being Delaunay
+//           neighbours: walk counter-clockwise from it and stop at the first neighbour that precedes s, or at the hull.  It has
+//           no other direction to go: it is run as a second direction from the start.
+//   FIRST   otherwise, from some neighbour n0 (an 8-neighbour or the nearest site): clockwise if n0 precedes s and lies to its
+//           left (n0x < sx; from (-1, 0) the owned half is entered at once), counter-clockwise in every other case.  After an
+//           answered query on s -> a with apex p the triangle is emitted iff up(a) && up(p).  If up(a) && !up(p) the walk has left
+//           the owned half: with up(n0) the part of the half on the other side of n0 is still to do -- the second direction --,
+//           without it the walk entered the half at one end and has left it at the other: done.  On a hull edge: with up(a) &&
+//           !up(n0) the walk entered the owned half at one end and is inside it, and the hull gap, which is >= pi, covers the
+//           rest of it: done; in every other case the second direction.  (Closing at n0 would take a first direction through
+//           [pi, 2 pi) and so never happens before one of these; the test stays as a safety net.)
+//   SECOND  from n0 the other way round, until up(a) && !up(p), or the hull.
+// Until round 7 the non-HALF walks went round the whole star and threw away every triangle found in [pi, 2 pi) -- for a site on
+// the lower outline of the cloud the expensive half: large empty circles, sweeps and hull proofs.
 // `fresh` = false takes the walk up where a lean walk (star_local.h) gave up: at the edge s -> s + (rax, ray) it could not
-// answer, in its direction, with its first neighbour n0 = s + (rn0x, rn0y) or as a half walk; what that walk emitted before
-// is not emitted again.
-enum { SD_MODE_HALF = 0, SD_MODE_CCW = 1, SD_MODE_CW = 2 };
+// answer, with its first neighbour n0 = s + (rn0x, rn0y), as a half walk or in the direction rdir: +1 / -1 counter-clockwise /
+// clockwise in its first direction, +2 / -2 in its second; what that walk emitted before is not emitted again.
 template <class Emit>
 SD_FN int sd_walk(const SdGrid& g, int sx, int sy, bool fresh, int rax, int ray, int rdir, bool rhalf, int rn0x, int rn0y, Emit& emit) {
     int steps = 0;
-    int mode, ax, ay, n0x, n0y;
+    int dir = 1, ax, ay, n0x, n0y;
+    bool second = false;
     if (!fresh) {
-        mode = rhalf ? SD_MODE_HALF : (rdir > 0 ? SD_MODE_CCW : SD_MODE_CW);
+        dir = rdir > 0 ? 1 : -1;
+        second = rhalf || (rdir & 1) == 0;
         ax = sx + rax; ay = sy + ray; n0x = sx + rn0x; n0y = sy + rn0y;
     } else if (sx + 1 < g.W && ((g.occ[SD_MUL(sy, g.wpr) + ((sx + 1) >> 5)] >> ((sx + 1) & 31)) & 1u)) {
-        mode = SD_MODE_HALF;
+        second = true;
         ax = n0x = sx + 1; ay = n0y = sy;
     } else {
         long long lap_n = SD_NOW();
         if (!sd_nearest(g, sx, sy, &n0x, &n0y)) return 0;
         SD_LAP(nearest, lap_n);
-        mode = SD_MODE_CCW;
         ax = n0x; ay = n0y;
+        if (!sd_before(sx, sy, n0x, n0y) && n0x < sx) dir = -1;
     }
-    const bool half = mode == SD_MODE_HALF;
+    const bool n0up = sd_before(sx, sy, n0x, n0y);
+    bool aup = sd_before(sx, sy, ax, ay);
     for (;;) {
         int px, py;
-        if (!sd_apex(g, sx, sy, ax, ay, mode == SD_MODE_CW ? -1 : +1, &px, &py)) {
-            if (mode != SD_MODE_CCW) break;
-            mode = SD_MODE_CW;  // hull vertex: back to the first neighbour, the other way round
-            ax = n0x;
-            ay = n0y;
-            continue;
+        bool pup, sw;
+        if (!sd_apex(g, sx, sy, ax, ay, dir, &px, &py)) {
+            SD_QUERY_DONE(false);
+            if (second || (aup && !n0up)) break;
+            sw = true;
+        } else {
+            pup = sd_before(sx, sy, px, py);
+            SD_QUERY_DONE(aup && pup);
+            if (aup && pup) {
+                const bool cw = dir < 0;  // (counter-clockwise vertex order either way)
+                long long lap_e = SD_NOW();
+                emit(sx, sy, cw ? px : ax, cw ? py : ay, cw ? ax : px, cw ? ay : py);
+                SD_LAP(e1_total, lap_e);
+            }
+            if (++steps > SD_MAX_DEGREE) return -1;
+            sw = aup && !pup;  // left the owned half
+            if (sw ? (second || !n0up) : (!second && px == n0x && py == n0y)) break;
         }
-        if (half && !sd_before(sx, sy, px, py)) break;
-        if (half || (sd_before(sx, sy, ax, ay) && sd_before(sx, sy, px, py))) {
-            const bool cw = mode == SD_MODE_CW;  // (counter-clockwise vertex order either way)
-            long long lap_e = SD_NOW();
-            emit(sx, sy, cw ? px : ax, cw ? py : ay, cw ? ax : px, cw ? ay : py);
-            SD_LAP(e1_total, lap_e);
+        if (sw) {  // the second direction: back to the first neighbour, the other way round
+            second = true;
+            dir = -dir;
+            px = n0x;
+            py = n0y;
+            pup = n0up;
         }
-        if (++steps > SD_MAX_DEGREE) return -1;
         ax = px;
         ay = py;
-        if (mode == SD_MODE_CCW && ax == n0x && ay == n0y) break;  // closed
+        aup = pup;
     }
-    return half ? steps + 1 : steps;
+    return steps;
 }
 
 template <class Emit>

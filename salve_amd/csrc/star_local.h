@@ -75,9 +75,10 @@ enum { SDL_LEAN_CONTINUE = 0, SDL_LEAN_DONE = 1, SDL_LEAN_HARD = 2 };
 struct SdLean {
     int sx, sy;
     int n0x, n0y, ax, ay;  // first neighbour, current edge end (relative to s)
-    int dir, deg;
+    int dir, deg;          // dir: +1 / -1 counter-clockwise / clockwise in the walk's FIRST direction, +2 / -2 in its SECOND (sd_walk)
     int round;             // table probe round of the current query (4 candidates per round)
     bool half;             // the walk started at the neighbour (+1, 0): stop at the first neighbour that precedes s in raster order
+    bool aup;              // a follows s in raster order: the previous step's answer for its apex
 };
 
 SD_FN int sdl_lean_begin(SdLean& s, const SdGrid& g, int sx, int sy) {
@@ -87,6 +88,7 @@ SD_FN int sdl_lean_begin(SdLean& s, const SdGrid& g, int sx, int sy) {
     s.dir = 1;
     s.round = 0;
     s.half = false;
+    s.aup = false;
     s.n0x = s.n0y = s.ax = s.ay = 0;
     if (g.tab == nullptr) return SDL_LEAN_HARD;
     const uint32_t c = sdl_row32(g, sy, sx + SDL_XLO), u = sdl_row32(g, sy + 1, sx + SDL_XLO), d = sdl_row32(g, sy - 1, sx + SDL_XLO);
@@ -103,6 +105,12 @@ SD_FN int sdl_lean_begin(SdLean& s, const SdGrid& g, int sx, int sy) {
     s.half = ((c >> (o + 1)) & 1u) != 0;
     s.n0x = s.ax = nx;
     s.n0y = s.ay = ny;
+    // Only the neighbours at angles [0, pi) matter (sd_walk).  A half walk starts at angle 0 and has no other direction: it IS a
+    // second direction (+2).  From (-1, 0) or (-1, -1) the owned half is entered at once clockwise; from every other first
+    // neighbour counter-clockwise.
+    const bool n0up = ny > 0 || s.half;   // (ny == 0 && nx > 0 is the half walk)
+    s.aup = n0up;
+    s.dir = s.half ? 2 : ((!n0up && nx < 0) ? -1 : 1);
     return nx == SDL_NONE ? SDL_LEAN_HARD : SDL_LEAN_CONTINUE;  // no 8-neighbour: the general walk finds the nearest site
 }
 
@@ -133,25 +141,37 @@ SD_FN int sdl_lean_step(SdLean& s, const SdGrid& g, Emit& emit) {
         }
     }
     s.round = 0;
+    const bool second = (s.dir & 1) == 0, aup = s.aup;
+    const bool n0up = s.n0y > 0;             // where it matters: (1, 0) is the first neighbour of half walks only, which are second
+    const bool fin = second | (aup & !n0up);   // no second direction to come: this is it, or n0 precedes s and a does not
+    bool sw;
+    bool up = aup;
     if (px == SDL_NONE) {
         if (!sd_side_is_empty(g, s.sx, s.sy, s.sx + s.ax, s.sy + s.ay, s.dir)) {
             SD_HARD_REASON((vx >= -SDT_AMAX && vx <= SDT_AMAX && vy >= -SDT_AMAX && vy <= SDT_AMAX) ? 7 : 6);
             return SDL_LEAN_HARD;
         }
-        // Hull edge.  A half walk owns nothing beyond it; a full walk goes back to its first neighbour and fans out
-        // clockwise until it meets the hull on the other side.
-        if (s.half || s.dir < 0) return SDL_LEAN_DONE;
-        s.dir = -1;
-        s.ax = s.n0x;
-        s.ay = s.n0y;
-        return SDL_LEAN_CONTINUE;
+        // Hull edge.  A second direction (a half walk is one) owns nothing beyond it; nor does a first direction that entered the
+        // owned half from below and is inside it now: the hull gap is >= pi and covers the rest of the half.
+        if (fin) return SDL_LEAN_DONE;
+        sw = true;
+    } else {
+        const bool pup = sd_before(0, 0, px, py);
+        if (aup & pup) {
+            if (s.dir > 0) emit(s.sx, s.sy, s.sx + s.ax, s.sy + s.ay, s.sx + px, s.sy + py);
+            else emit(s.sx, s.sy, s.sx + px, s.sy + py, s.sx + s.ax, s.sy + s.ay);
+        }
+        sw = aup & !pup;                               // the walk has left the owned half
+        if (sw ? fin : (!second && px == s.n0x && py == s.n0y)) return SDL_LEAN_DONE;
+        up = pup;
     }
-    if (sd_before(0, 0, s.ax, s.ay) && sd_before(0, 0, px, py)) {
-        if (s.dir > 0) emit(s.sx, s.sy, s.sx + s.ax, s.sy + s.ay, s.sx + px, s.sy + py);
-        else emit(s.sx, s.sy, s.sx + px, s.sy + py, s.sx + s.ax, s.sy + s.ay);
+    if (sw) {   // the second direction: from the first neighbour, the other way round
+        s.dir = s.dir > 0 ? -2 : 2;
+        px = s.n0x;
+        py = s.n0y;
+        up = n0up;
     }
-    if (s.dir > 0 && px == s.n0x && py == s.n0y) return SDL_LEAN_DONE;
-    if (s.half && !sd_before(0, 0, px, py)) return SDL_LEAN_DONE;
+    s.aup = up;
     s.ax = px;
     s.ay = py;
     if (++s.deg > 64) return SDL_LEAN_HARD;

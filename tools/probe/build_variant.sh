@@ -7,9 +7,10 @@ ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 cd "$ROOT/salve_amd/csrc"
 mkdir -p "$ROOT/tools/probe/_abl" /tmp/variant_obj_$tag
 F="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC"
-for f in bev_render layout resnet abi; do
+for src in *.hip; do   # every translation unit of the product (salve_amd/_lib.py binds all their symbols), with build()'s per-file flags
+  f=${src%.hip}
   extra=""; [ "$f.hip" = "$unit" ] && extra="$*"
-  slp="-fno-slp-vectorize"; [ "$f" = resnet ] && slp=""; [ "$f" = abi ] && slp=""
+  slp="-fno-slp-vectorize"; [ "$f" = resnet ] && slp=""; [ "$f" = abi ] && slp=""; [ "$f" = optim_train ] && slp=""
   hipcc $F $slp $extra -c $f.hip -o /tmp/variant_obj_$tag/$f.o &
 done
 wait

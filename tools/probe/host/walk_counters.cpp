@@ -13,6 +13,10 @@
 #include <vector>
 static long long g_apex, g_apex_table, g_apex_cached, g_apex_far, g_apex_slow, g_rows, g_bits, g_exact;
 #define SD_COUNT(c) (g_##c++)
+// sd_walk reports every query it made: a SWEEPING query (one that neither the table nor the cache answered) that found a triangle
+// the site does not own, or the hull, is a lead-in or a terminating query -- work the walk needs only to know where it stands
+static long long g_sweep_seen, g_sweep_owned, g_sweep_not_owned;
+#define SD_QUERY_DONE(owned) do { const long long sw_ = g_apex - g_apex_table - g_apex_cached; ((owned) ? g_sweep_owned : g_sweep_not_owned) += sw_ - g_sweep_seen; g_sweep_seen = sw_; } while (0)
 #include "../../../salve_amd/csrc/star_delaunay.h"
 #include "../../../salve_amd/csrc/star_table.h"
 #include "../../../salve_amd/csrc/star_local.h"
@@ -56,11 +60,14 @@ int main(int argc, char** argv) {
         memset(cache, 0, sizeof(cache)); memset(pend, 0, sizeof(pend));
         SdGrid g = {H, W, wpr, occ.data(), rmin.data(), rmax.data(), 0, 1, &t.off[0][0][0], bx0, bx1, by0, by1, cache};
         g_apex = g_apex_table = g_apex_cached = g_apex_far = g_apex_slow = g_rows = g_bits = g_exact = 0;
+        g_sweep_seen = g_sweep_owned = g_sweep_not_owned = 0;
+        long long lean_steps = 0, walked = 0;   // of the sites the kernel walks at all (sdl_walk_word)
         std::vector<int> out; Collect c = {&out}; std::vector<HardEnt> hl;
         for (int i = 0; i < n; i++) {   // E1: the lean walks
             SdLean ls; long long it = 0;
             int r = sdl_lean_begin(ls, g, xy[2 * i], xy[2 * i + 1]);
             while (r == SDL_LEAN_CONTINUE && it < 100000) { r = sdl_lean_step(ls, g, c); it++; }
+            if ((sdl_walk_word(occ.data(), H, wpr, xy[2 * i + 1] * wpr + (xy[2 * i] >> 5)) >> (xy[2 * i] & 31)) & 1u) { lean_steps += it; walked++; }
             if (r != SDL_LEAN_DONE) { HardEnt h = {xy[2 * i], xy[2 * i + 1], ls.n0x == SDL_NONE, ls.ax, ls.ay, ls.dir, ls.half, ls.n0x, ls.n0y}; hl.push_back(h); }
         }
         if (ORDER == 1) std::stable_sort(hl.begin(), hl.end(), [](const HardEnt& a, const HardEnt& b) { return (a.y / BLK) * 64 + a.x / BLK < (b.y / BLK) * 64 + b.x / BLK; });
@@ -85,8 +92,8 @@ int main(int argc, char** argv) {
         std::vector<std::vector<int>> tris; for (size_t k = 0; k + 5 < out.size(); k += 6) tris.push_back(std::vector<int>(out.begin() + k, out.begin() + k + 6));
         std::sort(tris.begin(), tris.end());
         unsigned long long hsum = 0; for (auto& tr : tris) for (int q : tr) hsum = hsum * 1000003ull + (unsigned)q;
-        printf("%s: sites %d triangles %zu (hash %llx) hard sites %zu | apex queries %lld = table %lld + cache %lld + sweeping %lld | window growths %lld circle sweeps %lld | lane-rows %lld candidates %lld exact predicates %lld\n",
-               argv[f], n, tris.size(), hsum, hl.size(), g_apex, g_apex_table, g_apex_cached, g_apex - g_apex_table - g_apex_cached, g_apex_far, g_apex_slow, g_rows, g_bits, g_exact);
+        printf("%s: sites %d triangles %zu (hash %llx) hard sites %zu | walked sites %lld lean steps %lld | apex queries %lld = table %lld + cache %lld + sweeping %lld (%lld of them for a triangle the site does not own) | window growths %lld circle sweeps %lld | lane-rows %lld candidates %lld exact predicates %lld\n",
+               argv[f], n, tris.size(), hsum, hl.size(), walked, lean_steps, g_apex, g_apex_table, g_apex_cached, g_apex - g_apex_table - g_apex_cached, g_sweep_not_owned, g_apex_far, g_apex_slow, g_rows, g_bits, g_exact);
     }
     return 0;
 }
