@@ -789,7 +789,9 @@ int salve_bev_jpeg_encode(const uint32_t* bev, int32_t n, int32_t h, int32_t w, 
  *   stages:      SALVE_JPEG_STAGES_ALL for a decode.  SALVE_JPEG_STAGE_ENTROPY alone runs the first launch only (scans -> coefficients in
  *                the workspace, image_status written; bev_out untouched); SALVE_JPEG_STAGE_INVERSE alone runs the other two on the
  *                coefficients the last entropy stage left in the SAME workspace for the same n, h, w (image_status untouched): a caller
- *                can put events between the stages (tools/measure/bench_tile_files.py).  Any other value: SALVE_ERR_BAD_ARG.
+ *                can put events between the stages (tools/measure/bench_tile_files.py), and nothing else may write that workspace
+ *                between them -- with BevRasteriser, whose JPEG methods share one workspace per stream: no other JPEG call on that
+ *                stream.  Any other value: SALVE_ERR_BAD_ARG.
  *   Three launches, asynchronous on `stream`.  Integer arithmetic and plain stores only, one writer per output: the same input
  *   gives the same bits.  Offsets are 64-bit.
  * ------------------------------------------------------------------------------------------------ */

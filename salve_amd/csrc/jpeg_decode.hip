@@ -9,11 +9,11 @@
 //                         the scan into LDS in coalesced runs and expand the look-ahead tables there; the symbol loop runs on
 //                         wave-uniform values; every block leaves as one 128-byte store of int16 coefficients, natural order,
 //                         MCU-interleaved, into the workspace.  A batch's images are resident together: the grid is n workgroups of 64.
-//   jpeg_idct_kernel      eight threads per block, 32 blocks per workgroup: dequantise, the column pass, the row pass
-//                         (jpeg_inverse.h: idct_1d, the function salve_bev_jpeg_roundtrip uses), the range limit, one 8-byte store per
-//                         block row into the planes jpeg_roundtrip.hip's jpeg_blocks_kernel writes.  The luma blocks of an edge MCU that
-//                         lie outside the image land in the planes' margin, which nothing reads.
-//   jpeg_pixels_kernel    jpeg_inverse.h, unchanged: upsampling, colour conversion, the pixels.
+//   jpeg_idct_kernel      eight threads per block, 32 blocks per workgroup: dequantise, the column pass (jpeg_inverse.h: idct_1d), then
+//                         jpeg_store_decoded_row, the function salve_bev_jpeg_roundtrip ends with: the row pass, the range limit, one
+//                         8-byte store per block row into the planes.  The luma blocks of an edge MCU that lie outside the image land
+//                         in the planes' margin, which nothing reads.
+//   jpeg_pixels_kernel    jpeg_inverse.h (jpeg_launch_pixels): upsampling, colour conversion, the pixels.
 // `stages` selects the first launch alone, the other two alone (on the coefficients in the workspace) or, as every product path does,
 // all three: a measurement can put events between the entropy stage and the inverse stage.
 // A malformed scan sets bits in its image's status word (include/salve_hip.h: SALVE_JPEG_*), keeps what it had decoded, has zeros
@@ -81,29 +81,12 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_idct_kernel(const int16_t* 
         for (int j = 0; j < 8; j++) base[j * 8 + r] = d[j];
     }
     __syncthreads();
-    if (working) {   // inverse pass 2 on row r; the decoded row leaves as one 8-byte store
+    if (working) {   // inverse pass 2 on row r
 #pragma unroll
         for (int j = 0; j < 8; j++) d[j] = base[r * 8 + j];
-        idct_1d(d, CONST_BITS + PASS1_BITS + 3);
-        uint32_t lo = 0, hi = 0;
-#pragma unroll
-        for (int j = 0; j < 4; j++) {
-            lo |= idct_range_limit(d[j]) << (8 * j);
-            hi |= idct_range_limit(d[j + 4]) << (8 * j);
-        }
         const int my = mcu / mcus_w, mx = mcu - my * mcus_w;
-        const int64_t ysize = (int64_t)Hm * Wm;
-        uint8_t* planes = ws + (int64_t)blockIdx.z * (ysize + ysize / 2);
-        uint8_t* dst;
-        if (k < 4) dst = planes + (int64_t)(my * 16 + (k >> 1) * 8 + r) * Wm + mx * 16 + (k & 1) * 8;
-        else dst = planes + ysize + (k - 4) * (ysize / 4) + (int64_t)(my * 8 + r) * (Wm / 2) + mx * 8;
-        *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+        jpeg_store_decoded_row(d, ws, Hm, Wm, my, mx, k, r);
     }
-}
-
-size_t planes_bytes(int32_t n, int32_t h, int32_t w) {
-    const size_t Hm = ((size_t)h + 15) / 16 * 16, Wm = ((size_t)w + 15) / 16 * 16;
-    return (size_t)n * (Hm * Wm + Hm * Wm / 2);   // a multiple of 384
 }
 
 }  // namespace
@@ -111,49 +94,33 @@ size_t planes_bytes(int32_t n, int32_t h, int32_t w) {
 extern "C" {
 
 size_t salve_bev_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    if (!jpeg_good_shape(n, h, w)) {
-        salve_fail("salve_bev_jpeg_decode_workspace_bytes: n outside 1..65535 or h / w outside 1..4096");
-        return 0;
-    }
-    const size_t mcus = (((size_t)h + 15) / 16) * (((size_t)w + 15) / 16);
-    return planes_bytes(n, h, w) + (size_t)n * mcus * 6 * 64 * sizeof(int16_t);
+    if (!jpeg_shape_ok("salve_bev_jpeg_decode_workspace_bytes", n, h, w)) return 0;
+    const JpegGeometry g(h, w);
+    return jpeg_planes_bytes(n, g) + (size_t)n * g.mcus() * 6 * 64 * sizeof(int16_t);
 }
 
 int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes, int32_t n, int32_t h, int32_t w,
                           const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws, size_t ws_bytes,
                           uint32_t stages, void* stream) {
-    if (!scans || !scan_offset || !scan_bytes || !qtab || !huffman || !bev_out || !image_status || !ws) {
-        salve_fail("salve_bev_jpeg_decode: null pointer");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (stages < SALVE_JPEG_STAGE_ENTROPY || stages > SALVE_JPEG_STAGES_ALL) {
-        salve_fail("salve_bev_jpeg_decode: stages must be SALVE_JPEG_STAGE_ENTROPY, SALVE_JPEG_STAGE_INVERSE or both");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (!jpeg_good_shape(n, h, w)) { salve_fail("salve_bev_jpeg_decode: n outside 1..65535 or h / w outside 1..4096"); return SALVE_ERR_BAD_ARG; }
-    if (scans_size < SALVE_JPEG_SCAN_PADDING) { salve_fail("salve_bev_jpeg_decode: the scan buffer is smaller than its padding"); return SALVE_ERR_BAD_ARG; }
+    const char* me = "salve_bev_jpeg_decode";
+    const bool null = !scans || !scan_offset || !scan_bytes || !qtab || !huffman || !bev_out || !image_status || !ws;
+    if (null) { jpeg_refuse(me, "null pointer"); return SALVE_ERR_BAD_ARG; }
+    if (stages < SALVE_JPEG_STAGE_ENTROPY || stages > SALVE_JPEG_STAGES_ALL) { jpeg_refuse(me, "stages must be SALVE_JPEG_STAGE_ENTROPY, SALVE_JPEG_STAGE_INVERSE or both"); return SALVE_ERR_BAD_ARG; }
+    if (!jpeg_shape_ok(me, n, h, w)) return SALVE_ERR_BAD_ARG;
+    if (scans_size < SALVE_JPEG_SCAN_PADDING) { jpeg_refuse(me, "the scan buffer is smaller than its padding"); return SALVE_ERR_BAD_ARG; }
     if (((uintptr_t)scan_offset & 7) || (((uintptr_t)scan_bytes | (uintptr_t)bev_out | (uintptr_t)image_status) & 3)) {
-        salve_fail("salve_bev_jpeg_decode: scan_offset must be 8-byte, scan_bytes, bev_out and image_status 4-byte aligned");
+        jpeg_refuse(me, "scan_offset must be 8-byte, scan_bytes, bev_out and image_status 4-byte aligned");
         return SALVE_ERR_BAD_ARG;
     }
     QTables qt;
-    for (int i = 0; i < 128; i++) {
-        if (qtab[i] < 1 || qtab[i] > 255) { salve_fail("salve_bev_jpeg_decode: a quantisation table entry outside 1..255 (baseline)"); return SALVE_ERR_BAD_ARG; }
-        qt.q[i >> 6][i & 63] = qtab[i];
-    }
+    if (!jpeg_load_qtables(me, qtab, &qt)) return SALVE_ERR_BAD_ARG;
     JeTables tab;
-    if (!je_make_tables(huffman, &tab)) {
-        salve_fail("salve_bev_jpeg_decode: a Huffman table's BITS over-subscribe the code space or sum past 256");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (ws_bytes < salve_bev_jpeg_decode_workspace_bytes(n, h, w) || ((uintptr_t)ws & 15)) {
-        salve_fail("salve_bev_jpeg_decode: the workspace is smaller than salve_bev_jpeg_decode_workspace_bytes says or not 16-byte aligned");
-        return SALVE_ERR_BAD_ARG;
-    }
-    const int Hm = (h + 15) / 16 * 16, Wm = (w + 15) / 16 * 16;
-    const int mcus_w = Wm / 16, mcus = mcus_w * (Hm / 16), nblocks = 6 * mcus;
+    if (!je_make_tables(huffman, &tab)) { jpeg_refuse(me, "a Huffman table's BITS over-subscribe the code space or sum past 256"); return SALVE_ERR_BAD_ARG; }
+    if (!jpeg_workspace_ok(me, ws, ws_bytes, salve_bev_jpeg_decode_workspace_bytes(n, h, w))) return SALVE_ERR_BAD_ARG;
+    const JpegGeometry g(h, w);
+    const int mcus = (int)g.mcus(), nblocks = 6 * mcus;
     uint8_t* planes = (uint8_t*)ws;
-    int16_t* coef = (int16_t*)(planes + planes_bytes(n, h, w));
+    int16_t* coef = (int16_t*)(planes + jpeg_planes_bytes(n, g));
     if (stages & SALVE_JPEG_STAGE_ENTROPY) {
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, scans, scan_offset, scan_bytes, (uint64_t)scans_size, mcus, tab,
                            coef, image_status);
@@ -161,12 +128,9 @@ int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t
     }
     if (stages & SALVE_JPEG_STAGE_INVERSE) {   // from the coefficients the entropy stage left in this workspace
         hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((nblocks + IDCT_BLOCKS - 1) / IDCT_BLOCKS), 1, (unsigned)n), dim3(JPEG_THREADS), 0, (hipStream_t)stream,
-                           (const int16_t*)coef, planes, mcus_w, nblocks, Hm, Wm, qt);
+                           (const int16_t*)coef, planes, g.mcus_w, nblocks, g.Hm, g.Wm, qt);
         SALVE_HIP_CHECK(hipGetLastError());
-        const int cw = (w + 1) / 2;
-        hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), dim3(64, 4), 0, (hipStream_t)stream,
-                           (const uint8_t*)planes, bev_out, (int)h, (int)w, Hm, Wm);
-        SALVE_HIP_CHECK(hipGetLastError());
+        SALVE_HIP_CHECK(jpeg_launch_pixels(planes, bev_out, n, h, w, g, (hipStream_t)stream));
     }
     return SALVE_OK;
 }

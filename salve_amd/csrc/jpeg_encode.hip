@@ -2,7 +2,7 @@
 // defaults (opt-in: BevRasteriser.jpeg_encode, render_dataset.render_building_floor_pairs(jpeg="device")).
 //
 // The reference writes every BEV render as a JPEG (imageio -> Pillow -> libjpeg, quality 75; bev_rendering_utils.py:629-630).  The
-// quantised coefficients come from the forward chain of jpeg_forward.h, the same functions jpeg_roundtrip.hip decodes again; behind
+// quantised coefficients come from the forward tile of jpeg_forward.h (jpeg_forward_rows / _column), the one jpeg_roundtrip.hip decodes again; behind
 // them runs jchuff.c's encode_one_block with the standard tables of ITU-T T.81 Annex K (Pillow's optimize=False), one interleaved scan
 // without restart intervals, MCU = Y0 Y1 Y2 Y3 Cb Cr:
 //   DC      difference against the previous block of the same component in scan order (0 before the first), its category's code,
@@ -12,7 +12,7 @@
 //   bytes   most significant bit first, the last byte padded with 1-bits, a 0x00 stuffed behind every 0xFF (padding included)
 //
 // Launches, all per image in grid.y / grid.z and asynchronous on the caller's stream:
-//   jpeg_coef_kernel        the forward chain (the tile of jpeg_forward.h); a block's 64 levels leave in zigzag order as int16, 128
+//   jpeg_coef_kernel        the forward tile, then quantisation; a block's 64 levels leave in zigzag order as int16, 128
 //                           bytes per block in MCU-interleaved order, 16 bytes per thread.  Luma blocks of an edge MCU that lie
 //                           outside the image's blocks are libjpeg's dummy blocks (jccoefct.c): zero AC, the DC of a neighbour
 //   jpeg_code_kernel<false> eight threads per block, eight zigzag positions each: the block's coded length in bits.  The DC
@@ -111,10 +111,11 @@ struct Layout {   // of the workspace, per call; every section starts 16-byte al
 };
 
 Layout layout_of(int32_t n, int32_t h, int32_t w) {
+    const JpegGeometry g(h, w);
     Layout L;
-    L.mcus_w = (uint32_t)(w + 15) / 16;
-    L.mcus_h = (uint32_t)(h + 15) / 16;
-    const uint32_t mcus = L.mcus_w * L.mcus_h;
+    L.mcus_w = (uint32_t)g.mcus_w;
+    L.mcus_h = (uint32_t)g.mcus_h;
+    const uint32_t mcus = (uint32_t)g.mcus();
     L.nb = 6 * mcus;
     L.nbp = (L.nb + 3) & ~3u;
     L.wpi = ((MCU_MAX_BYTES * mcus + 3) / 4 + 2 + 3) & ~3u;
@@ -137,33 +138,14 @@ Layout layout_of(int32_t n, int32_t h, int32_t w) {
 // grid (MCU groups across, MCU rows, images)
 __global__ __launch_bounds__(JPEG_THREADS) void jpeg_coef_kernel(const uint32_t* __restrict__ in, int16_t* __restrict__ coef, int h, int w, int mcus_w,
                                                                  uint32_t nb, QTables qt) {
-    __shared__ int s_y[16 * SY];
-    __shared__ int s_c[2][8 * SC];
-    __shared__ int s_q[2][64];
-    const int tid = threadIdx.x;
-    const int gx0 = blockIdx.x * TW, gy0 = blockIdx.y * 16;   // the tile's first luma sample
-    const uint32_t* img = in + (int64_t)blockIdx.z * h * w;
-    if (tid < 128) s_q[tid >> 6][tid & 63] = qt.q[tid >> 6][tid & 63];
-    jpeg_stage_quad(img, h, w, gx0, gy0, tid, s_y, s_c);
-    __syncthreads();
-
-    const JpegBlockMap map(tid);
+    __shared__ JpegTile t;
+    const JpegBlockMap map = jpeg_forward_rows(in, h, w, qt, t);
     const int r = map.r, stride = map.stride;
-    int* base = map.base(s_y, s_c);
-    const int* q = s_q[map.luma ? 0 : 1];
-    int d[8];
-    if (map.working) {   // forward pass 1: rows
-#pragma unroll
-        for (int k = 0; k < 8; k++) d[k] = base[r * stride + k];
-        fdct_1d<false>(d);
-#pragma unroll
-        for (int k = 0; k < 8; k++) base[r * stride + k] = d[k];
-    }
-    __syncthreads();
+    int* base = map.base;
     if (map.working) {   // forward pass 2 on column r, quantise
-#pragma unroll
-        for (int k = 0; k < 8; k++) d[k] = base[k * stride + r];
-        fdct_1d<true>(d);
+        const int* q = t.q[map.luma ? 0 : 1];
+        int d[8];
+        jpeg_forward_column(map, d);
 #pragma unroll
         for (int k = 0; k < 8; k++) base[k * stride + r] = jpeg_quantise(d[k], q[k * 8 + r]);
     }
@@ -176,7 +158,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_coef_kernel(const uint32_t*
         const bool right = map.luma && mcu_x * 2 + map.bx >= wblocks, below = map.luma && (int)blockIdx.y * 2 + map.by >= hblocks;
         const bool y1_real = mcu_x * 2 + 1 < wblocks;
         const int sby = below ? 0 : map.by, sbx = below ? (y1_real ? 1 : 0) : 0;
-        const int dummy_dc = s_y[(sby * 8) * SY + map.m * 16 + sbx * 8];
+        const int dummy_dc = t.y[(sby * 8) * SY + map.m * 16 + sbx * 8];
         uint32_t v[4];
 #pragma unroll
         for (int k = 0; k < 4; k++) {
@@ -188,7 +170,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_coef_kernel(const uint32_t*
             }
             v[k] = ((uint32_t)va & 0xFFFFu) | ((uint32_t)vb << 16);
         }
-        const uint32_t block = ((uint32_t)blockIdx.y * mcus_w + mcu_x) * 6 + (map.luma ? map.by * 2 + map.bx : 3 + map.comp);
+        const uint32_t block = ((uint32_t)blockIdx.y * mcus_w + mcu_x) * 6 + map.k;
         int16_t* dst = coef + ((int64_t)blockIdx.z * nb + block) * 64 + 8 * r;
         *reinterpret_cast<uint4*>(dst) = make_uint4(v[0], v[1], v[2], v[3]);
     }
@@ -422,38 +404,26 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_ff_kernel(const uint32_t* _
 extern "C" {
 
 size_t salve_bev_jpeg_encode_workspace_bytes(int32_t n, int32_t h, int32_t w) {
-    if (!jpeg_good_shape(n, h, w)) {
-        salve_fail("salve_bev_jpeg_encode_workspace_bytes: n outside 1..65535 or h / w outside 1..4096");
-        return 0;
-    }
+    if (!jpeg_shape_ok("salve_bev_jpeg_encode_workspace_bytes", n, h, w)) return 0;
     return layout_of(n, h, w).bytes;
 }
 
 size_t salve_bev_jpeg_encode_max_bytes(int32_t h, int32_t w) {
-    if (!jpeg_good_shape(1, h, w)) {
-        salve_fail("salve_bev_jpeg_encode_max_bytes: h / w outside 1..4096");
-        return 0;
-    }
+    if (!jpeg_shape_ok("salve_bev_jpeg_encode_max_bytes", 1, h, w)) return 0;
     const Layout L = layout_of(1, h, w);
     return ((size_t)2 * MCU_MAX_BYTES * L.mcus_w * L.mcus_h + 3) & ~(size_t)3;   // every byte may be 0xFF and get a 0x00 behind it
 }
 
 int salve_bev_jpeg_encode(const uint32_t* bev, int32_t n, int32_t h, int32_t w, const uint16_t* qtab, uint8_t* scan, size_t scan_stride,
                           int32_t* scan_bytes, void* ws, size_t ws_bytes, void* stream) {
-    if (!bev || !qtab || !scan || !scan_bytes || !ws) { salve_fail("salve_bev_jpeg_encode: null pointer"); return SALVE_ERR_BAD_ARG; }
-    if (!jpeg_good_shape(n, h, w)) { salve_fail("salve_bev_jpeg_encode: n outside 1..65535 or h / w outside 1..4096"); return SALVE_ERR_BAD_ARG; }
-    if (((uintptr_t)bev | (uintptr_t)scan_bytes) & 3) { salve_fail("salve_bev_jpeg_encode: the images and scan_bytes must be 4-byte aligned"); return SALVE_ERR_BAD_ARG; }
-    if (scan_stride == 0 || (scan_stride & 3)) { salve_fail("salve_bev_jpeg_encode: scan_stride must be a positive multiple of 4"); return SALVE_ERR_BAD_ARG; }
+    const char* me = "salve_bev_jpeg_encode";
+    if (!bev || !qtab || !scan || !scan_bytes || !ws) { jpeg_refuse(me, "null pointer"); return SALVE_ERR_BAD_ARG; }
+    if (!jpeg_shape_ok(me, n, h, w)) return SALVE_ERR_BAD_ARG;
+    if (((uintptr_t)bev | (uintptr_t)scan_bytes) & 3) { jpeg_refuse(me, "the images and scan_bytes must be 4-byte aligned"); return SALVE_ERR_BAD_ARG; }
+    if (scan_stride == 0 || (scan_stride & 3)) { jpeg_refuse(me, "scan_stride must be a positive multiple of 4"); return SALVE_ERR_BAD_ARG; }
     QTables qt;
-    for (int i = 0; i < 128; i++) {
-        if (qtab[i] < 1 || qtab[i] > 255) { salve_fail("salve_bev_jpeg_encode: a quantisation table entry outside 1..255 (baseline)"); return SALVE_ERR_BAD_ARG; }
-        qt.q[i >> 6][i & 63] = qtab[i];
-    }
     const Layout L = layout_of(n, h, w);
-    if (ws_bytes < L.bytes || ((uintptr_t)ws & 15)) {
-        salve_fail("salve_bev_jpeg_encode: the workspace is smaller than salve_bev_jpeg_encode_workspace_bytes says or not 16-byte aligned");
-        return SALVE_ERR_BAD_ARG;
-    }
+    if (!jpeg_load_qtables(me, qtab, &qt) || !jpeg_workspace_ok(me, ws, ws_bytes, L.bytes)) return SALVE_ERR_BAD_ARG;
     uint8_t* base = (uint8_t*)ws;
     int16_t* coef = (int16_t*)(base + L.coef);
     uint32_t* lens = (uint32_t*)(base + L.lens);

@@ -3,14 +3,21 @@
 // downsampling, the slow-integer forward DCT and quantisation, in libjpeg's order and with its constants (jccolor.c, jcprepct.c,
 // jcsample.c, jfdctint.c, jcdctmgr.c).  32-bit integer arithmetic only; every offset is 64-bit.
 //
-// The tile both files work on: a workgroup of 256 threads owns four MCUs (16 x 16 pixels each) side by side.  Every thread converts one
-// 2 x 2 pixel quad into LDS (four luma samples, one Cb, one Cr: jpeg_stage_quad); then each of the 24 blocks (16 luma, 4 Cb, 4 Cr) gets
-// eight threads, one per row / column (JpegBlockMap), for the 1-D passes through LDS.
+// The tile both files work on (jpeg_forward_rows, jpeg_forward_column): a workgroup of 256 threads owns four MCUs (16 x 16 pixels each)
+// side by side.  Every thread converts one 2 x 2 pixel quad into LDS (four luma samples, one Cb, one Cr: jpeg_stage_quad); then each of
+// the 24 blocks (16 luma, 4 Cb, 4 Cr) gets eight threads, one per row / column (JpegBlockMap), for the 1-D passes through LDS (JpegTile).
+// The two end with the unquantised coefficients of a block's column in registers; what happens to them is the calling kernel's.
+//
+// At the end, the host side the three entries share: the geometry in whole MCUs and the refusals, each naming the entry that refused.
 #ifndef SALVE_JPEG_FORWARD_H
 #define SALVE_JPEG_FORWARD_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include <string>
+
+#include "salve_common.h"
 
 namespace {
 
@@ -74,6 +81,12 @@ __device__ __forceinline__ int jpeg_quantise(int d, int qk) {
     return d < 0 ? -(int)mag : (int)mag;
 }
 
+struct JpegTile {   // a workgroup's LDS, 6784 bytes: declare one __shared__ per kernel
+    int y[16 * SY];      // luma, level-shifted; the passes work in place
+    int c[2][8 * SC];    // Cb, Cr after downsampling
+    int q[2][64];        // the quantisation tables: luma, chroma; natural order
+};
+
 // Colour conversion, edge replication and chroma downsampling of the tile whose first luma sample is (gx0, gy0): one 2 x 2 quad per
 // thread, level-shifted samples into s_y [16 * SY] and s_c [2][8 * SC].
 __device__ __forceinline__ void jpeg_stage_quad(const uint32_t* __restrict__ img, int h, int w, int gx0, int gy0, int tid, int* s_y,
@@ -115,8 +128,10 @@ struct JpegBlockMap {
     bool working, luma;
     int m, comp;     // MCU of the workgroup; 0 Y, 1 Cb, 2 Cr
     int by, bx;      // luma: block row / column inside the MCU
+    int k;           // block inside the MCU, in the scan's order: 0 .. 3 luma (row-major), 4 Cb, 5 Cr
     int stride;      // LDS row stride of the block's plane
-    __device__ __forceinline__ explicit JpegBlockMap(int tid) {
+    int* base;       // the block's first sample in the tile
+    __device__ __forceinline__ JpegBlockMap(int tid, JpegTile& t) {
         blk = tid >> 3;
         r = tid & 7;
         working = blk < 6 * MCUS;
@@ -125,15 +140,73 @@ struct JpegBlockMap {
         comp = luma ? 0 : 1 + ((blk - 4 * MCUS) >> 2);
         by = luma ? (blk >> 1) & 1 : 0;
         bx = luma ? blk & 1 : 0;
+        k = luma ? by * 2 + bx : 3 + comp;
         stride = luma ? SY : SC;
-    }
-    __device__ __forceinline__ int* base(int* s_y, int (*s_c)[8 * SC]) const {
-        return luma ? s_y + (by * 8) * SY + m * 16 + bx * 8 : s_c[working ? comp - 1 : 0] + m * 8;
+        base = luma ? t.y + (by * 8) * SY + m * 16 + bx * 8 : t.c[working ? comp - 1 : 0] + m * 8;
     }
 };
 
-inline bool jpeg_good_shape(int32_t n, int32_t h, int32_t w) {
-    return n > 0 && n <= MAX_IMAGES && h >= 1 && h <= MAX_DIM && w >= 1 && w <= MAX_DIM;
+// The forward half of the workgroup's tile -- MCUs MCUS * blockIdx.x .. + MCUS - 1 of MCU row blockIdx.y of image blockIdx.z -- in two steps.
+// jpeg_forward_rows: the tables into LDS (t.q), the samples (jpeg_stage_quad), the row pass in place; returns the thread's place in the
+// tile.  EVERY thread of the workgroup calls it: it has two barriers, the second behind the row pass.
+__device__ __forceinline__ JpegBlockMap jpeg_forward_rows(const uint32_t* __restrict__ in, int h, int w, const QTables& qt, JpegTile& t) {
+    const int tid = threadIdx.x;
+    const int gx0 = blockIdx.x * TW, gy0 = blockIdx.y * 16;   // the tile's first luma sample
+    const uint32_t* img = in + (int64_t)blockIdx.z * h * w;
+    if (tid < 128) t.q[tid >> 6][tid & 63] = qt.q[tid >> 6][tid & 63];
+    jpeg_stage_quad(img, h, w, gx0, gy0, tid, t.y, t.c);   // colour conversion, edge replication and chroma downsampling
+    __syncthreads();
+    const JpegBlockMap map(tid, t);
+    if (map.working) {
+        int d[8];
+#pragma unroll
+        for (int k = 0; k < 8; k++) d[k] = map.base[map.r * map.stride + k];
+        fdct_1d<false>(d);
+#pragma unroll
+        for (int k = 0; k < 8; k++) map.base[map.r * map.stride + k] = d[k];
+    }
+    __syncthreads();
+    return map;
+}
+
+// jpeg_forward_column, for a WORKING thread behind jpeg_forward_rows: d[0 .. 7] = column map.r of its block through the second pass,
+// the coefficients scaled by 8 and not yet quantised.  (A step of its own so that the calling kernel goes on under the same
+// `if (map.working)`: two such regions in a row compile to more instructions than one.)
+__device__ __forceinline__ void jpeg_forward_column(const JpegBlockMap& map, int* d) {
+#pragma unroll
+    for (int k = 0; k < 8; k++) d[k] = map.base[k * map.stride + map.r];
+    fdct_1d<true>(d);
+}
+
+// ---------------------------------------------------------------- host side of the entries
+
+struct JpegGeometry {   // an image in whole 16 x 16 MCUs
+    int mcus_w, mcus_h, Wm, Hm;   // MCUs across and down; the padded size (the planes' of jpeg_inverse.h)
+    JpegGeometry(int32_t h, int32_t w) : mcus_w((w + 15) / 16), mcus_h((h + 15) / 16), Wm(mcus_w * 16), Hm(mcus_h * 16) {}
+    size_t mcus() const { return (size_t)mcus_w * mcus_h; }
+};
+
+// The refusals.  `entry` is the exported function that refuses; every helper returns false after recording "<entry>: <why>".
+inline bool jpeg_refuse(const char* entry, const std::string& why) { return salve_fail((std::string(entry) + ": " + why).c_str()); }
+
+inline bool jpeg_shape_ok(const char* entry, int32_t n, int32_t h, int32_t w) {
+    if (n > 0 && n <= MAX_IMAGES && h >= 1 && h <= MAX_DIM && w >= 1 && w <= MAX_DIM) return true;
+    return jpeg_refuse(entry, "n outside 1..65535 or h / w outside 1..4096");
+}
+
+// qtab: uint16 [2][64] on the host, natural order
+inline bool jpeg_load_qtables(const char* entry, const uint16_t* qtab, QTables* qt) {
+    for (int i = 0; i < 128; i++) {
+        if (qtab[i] < 1 || qtab[i] > 255) return jpeg_refuse(entry, "a quantisation table entry outside 1..255 (baseline)");
+        qt->q[i >> 6][i & 63] = qtab[i];
+    }
+    return true;
+}
+
+// need: what <entry>_workspace_bytes returns for the call's n, h, w
+inline bool jpeg_workspace_ok(const char* entry, const void* ws, size_t ws_bytes, size_t need) {
+    if (ws_bytes >= need && !((uintptr_t)ws & 15)) return true;
+    return jpeg_refuse(entry, std::string("the workspace is smaller than ") + entry + "_workspace_bytes says or not 16-byte aligned");
 }
 
 }  // namespace

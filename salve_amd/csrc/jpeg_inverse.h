@@ -1,16 +1,16 @@
 // jpeg_inverse.h -- the inverse half of libjpeg's baseline 4:2:0 chain as device code, shared by jpeg_roundtrip.hip (which takes the
 // quantised coefficients from the forward chain) and jpeg_decode.hip (which takes them from a file's entropy-coded scan): the 1-D pass of
-// the slow-integer inverse DCT with its range limit (jidctint.c), and the launch that upsamples the chroma planes, converts to RGB and
-// stores the pixels (jdsample.c, jdcolor.c).  Both files leave the decoded samples in the same planes: luma [Hm][Wm], Cb and Cr
-// [Hm / 2][Wm / 2] bytes per image, Hm and Wm the image rounded up to whole 16 x 16 MCUs.  32-bit integer arithmetic only; every offset
-// is 64-bit.
+// the slow-integer inverse DCT with its range limit (jidctint.c), the store of a block's decoded row into the planes
+// (jpeg_store_decoded_row: the planes' layout is written there, once), and the launch that upsamples the chroma planes, converts to RGB
+// and stores the pixels (jpeg_pixels_kernel behind jpeg_launch_pixels; jdsample.c, jdcolor.c).  32-bit integer arithmetic only; every
+// offset is 64-bit.
 #ifndef SALVE_JPEG_INVERSE_H
 #define SALVE_JPEG_INVERSE_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "jpeg_forward.h"   // the DCT's constants, descale, JPEG_THREADS
+#include "jpeg_forward.h"   // the DCT's constants, descale, JPEG_THREADS, JpegGeometry
 
 namespace {
 
@@ -58,6 +58,33 @@ __device__ __forceinline__ uint32_t idct_range_limit(int v) {
     return (uint32_t)(i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896);
 }
 
+// The planes, the layout contract between the kernels that decode blocks and jpeg_pixels_kernel: per image, luma [Hm][Wm] bytes, then Cb
+// [Hm / 2][Wm / 2], then Cr likewise, Hm and Wm the image rounded up to whole 16 x 16 MCUs; the images follow each other without a gap.
+__host__ __device__ __forceinline__ int64_t jpeg_image_planes_bytes(int Hm, int Wm) {
+    const int64_t ysize = (int64_t)Hm * Wm;
+    return ysize + ysize / 2;   // a multiple of 384
+}
+
+inline size_t jpeg_planes_bytes(int32_t n, const JpegGeometry& g) { return (size_t)n * (size_t)jpeg_image_planes_bytes(g.Hm, g.Wm); }
+
+// Inverse pass 2 on row r of block k (JpegBlockMap::k: 0 .. 3 luma, 4 Cb, 5 Cr) of MCU (my, mx): d[0 .. 7] is that row after pass 1.
+// Range limit, and the row leaves as ONE 8-byte store into the planes of image blockIdx.z of `ws`.
+__device__ __forceinline__ void jpeg_store_decoded_row(int* d, uint8_t* __restrict__ ws, int Hm, int Wm, int my, int mx, int k, int r) {
+    idct_1d(d, CONST_BITS + PASS1_BITS + 3);
+    uint32_t lo = 0, hi = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        lo |= idct_range_limit(d[j]) << (8 * j);
+        hi |= idct_range_limit(d[j + 4]) << (8 * j);
+    }
+    const int64_t ysize = (int64_t)Hm * Wm;
+    uint8_t* planes = ws + blockIdx.z * jpeg_image_planes_bytes(Hm, Wm);
+    uint8_t* dst;
+    if (k < 4) dst = planes + (int64_t)(my * 16 + (k >> 1) * 8 + r) * Wm + mx * 16 + (k & 1) * 8;
+    else dst = planes + ysize + (k - 4) * (ysize / 4) + (int64_t)(my * 8 + r) * (Wm / 2) + mx * 8;
+    *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
+}
+
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
 
 // 3 * nearer row + further row of one chroma column (jdsample.c: thiscolsum)
@@ -72,7 +99,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixels_kernel(const uint8_t
     const int cw = (w + 1) >> 1, ch = (h + 1) >> 1;
     if (cx >= cw || y >= h) return;
     const int64_t ysize = (int64_t)Hm * Wm;
-    const uint8_t* planes = ws + (int64_t)blockIdx.z * (ysize + ysize / 2);
+    const uint8_t* planes = ws + blockIdx.z * jpeg_image_planes_bytes(Hm, Wm);
     const uint8_t* yrow = planes + (int64_t)y * Wm;
     const int cy = y >> 1;
     int c_even[2], c_odd[2];
@@ -102,6 +129,14 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixels_kernel(const uint8_t
         const int G = clamp255(Y + ((-22554 * cbx + 32768 - 46802 * crx) >> 16));
         orow[x] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
     }
+}
+
+// The planes of n images -> their pixels (out: uint32 [n][h][w], 0x00BBGGRR)
+inline hipError_t jpeg_launch_pixels(const uint8_t* planes, uint32_t* out, int32_t n, int32_t h, int32_t w, const JpegGeometry& g, hipStream_t stream) {
+    const int cw = (w + 1) / 2;
+    hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), dim3(64, 4), 0, stream, planes, out,
+                       (int)h, (int)w, g.Hm, g.Wm);
+    return hipGetLastError();
 }
 
 }  // namespace

@@ -115,9 +115,7 @@ class BevRasteriser:
         self._ws_slots = {}   # workspaces by slot: a caller that keeps two batches in flight alternates `ws_slot`
         self.ws_slot = 0
         self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
-        self._jpeg_ws = {}      # jpeg_roundtrip's workspaces by stream: callers on different streams never share one
-        self._jpeg_encode_ws = {}   # jpeg_encode's, likewise
-        self._jpeg_decode_ws = {}   # jpeg_decode's, likewise
+        self._jpeg_ws = {}      # the JPEG methods' workspace by stream, the largest any of them needed: callers on different streams never share one
         self._jpeg_tables = {}  # quality -> uint16 [2, 64] (host)
 
     # ------------------------------------------------------------------ helpers
@@ -352,39 +350,54 @@ class BevRasteriser:
 
     JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip, jpeg_encode, jpeg_decode: images per library call (bounds its workspace: 1.5 bytes per padded pixel)
 
-    def jpeg_roundtrip(self, bev: torch.Tensor, quality: int = 75, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """int32 [n, H, W] images (0x00BBGGRR: BEV renders, layout images) -> what the reference's file hop makes of them: Pillow's
-        `save(quality=quality)` and decode (bev_rendering_utils.py:629-630 -> zind_data.py:306-315), bit for bit, on the current stream
-        (include/salve_hip.h: salve_bev_jpeg_roundtrip).  `out`: default a new tensor; `out=bev` works in place."""
-        if bev.dim() != 3 or bev.dtype != torch.int32 or not bev.is_contiguous() or bev.device != self.device:
-            raise _lib.SalveHipError(f"jpeg_roundtrip takes contiguous int32 [n, H, W] images on {self.device}, got {bev.dtype} {tuple(bev.shape)}")
-        if out is None:
-            out = torch.empty_like(bev)
-        elif out.shape != bev.shape or out.dtype != bev.dtype or not out.is_contiguous() or out.device != bev.device:
-            raise _lib.SalveHipError(f"jpeg_roundtrip: out must match the images ({bev.dtype} {tuple(bev.shape)}), got {out.dtype} {tuple(out.shape)}")
-        n, h, w = (int(v) for v in bev.shape)
-        if n == 0:
-            return out
+    def _jpeg_images(self, who: str, t: torch.Tensor, shape=None) -> None:
+        """Refuse `t` unless it is a contiguous int32 [n, H, W] tensor on this device (of `shape`, if one is given)."""
+        if t.dim() != 3 or t.dtype != torch.int32 or not t.is_contiguous() or t.device != self.device or (shape is not None and tuple(t.shape) != tuple(shape)):
+            raise _lib.SalveHipError(f"{who} must be contiguous int32 {'[n, H, W]' if shape is None else tuple(shape)} images on {self.device}, "
+                                     f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+
+    def _jpeg_qtab(self, quality: int):
+        """libjpeg's tables of `quality`, uint16 [2, 64] on the host, as the argument of a library call."""
         q = int(quality)
         if q not in self._jpeg_tables:
             from salve_amd.jpeg import quality_tables
 
             self._jpeg_tables[q] = np.ascontiguousarray(quality_tables(q), dtype=np.uint16)
-        qtab = self._jpeg_tables[q]
+        return self._jpeg_tables[q].ctypes.data_as(ctypes.c_void_p)
+
+    def _jpeg_calls(self, route: str, n: int, h: int, w: int):
+        """The library calls of one JPEG method on n images: yields (lo, m, workspace pointer, workspace bytes) for images lo .. lo + m - 1,
+        at most JPEG_IMAGES_PER_CALL at a time, with this device current.  The three methods share ONE workspace per stream (only one of
+        their calls runs on a stream at a time); it grows to the largest need seen."""
+        if n == 0:
+            return
         per = min(n, self.JPEG_IMAGES_PER_CALL)
-        need = self.lib.salve_bev_jpeg_roundtrip_workspace_bytes(per, h, w)
+        size_fn = f"salve_bev_jpeg_{route}_workspace_bytes"
+        need = getattr(self.lib, size_fn)(per, h, w)
         if need == 0:
-            _lib.check(-1, "salve_bev_jpeg_roundtrip_workspace_bytes")
-        stream = torch.cuda.current_stream(self.device)
-        ws = self._jpeg_ws.get(stream.cuda_stream)
+            _lib.check(-1, size_fn)
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._jpeg_ws.get(key)
         if ws is None or ws.numel() < need:   # (allocated under the stream that uses it: the caching allocator orders its reuse against that stream)
-            ws = self._jpeg_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._jpeg_ws[key] = torch.empty(need, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             for lo in range(0, n, per):
-                m = min(per, n - lo)
-                st = self.lib.salve_bev_jpeg_roundtrip(ctypes.c_void_p(bev[lo:].data_ptr()), ctypes.c_void_p(out[lo:].data_ptr()), m, h, w,
-                                                       qtab.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
-                _lib.check(st, "salve_bev_jpeg_roundtrip")
+                yield lo, min(per, n - lo), ctypes.c_void_p(ws.data_ptr()), ws.numel()
+
+    def jpeg_roundtrip(self, bev: torch.Tensor, quality: int = 75, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n, H, W] images (0x00BBGGRR: BEV renders, layout images) -> what the reference's file hop makes of them: Pillow's
+        `save(quality=quality)` and decode (bev_rendering_utils.py:629-630 -> zind_data.py:306-315), bit for bit, on the current stream
+        (include/salve_hip.h: salve_bev_jpeg_roundtrip).  `out`: default a new tensor; `out=bev` works in place."""
+        self._jpeg_images("jpeg_roundtrip: bev", bev)
+        if out is None:
+            out = torch.empty_like(bev)
+        else:
+            self._jpeg_images("jpeg_roundtrip: out", out, bev.shape)
+        n, h, w = (int(v) for v in bev.shape)
+        for lo, m, ws, ws_bytes in self._jpeg_calls("roundtrip", n, h, w):
+            st = self.lib.salve_bev_jpeg_roundtrip(ctypes.c_void_p(bev[lo:].data_ptr()), ctypes.c_void_p(out[lo:].data_ptr()), m, h, w,
+                                                   self._jpeg_qtab(quality), ws, ws_bytes, self._stream())
+            _lib.check(st, "salve_bev_jpeg_roundtrip")
         return out
 
     JPEG_STRIDE_FRACTION = 8   # jpeg_encode's default slot: 1 / 8 of salve_bev_jpeg_encode_max_bytes (see its docstring)
@@ -399,8 +412,7 @@ class BevRasteriser:
         is incomplete, and the caller encodes that image another way (or again with a larger stride); the other images are whole.
         The bytes of a slot beyond nbytes[i] are not written (the array is not initialised).  On the current stream; batches of at
         most 1024 images per library call, one workspace per stream."""
-        if bev.dim() != 3 or bev.dtype != torch.int32 or not bev.is_contiguous() or bev.device != self.device:
-            raise _lib.SalveHipError(f"jpeg_encode takes contiguous int32 [n, H, W] images on {self.device}, got {bev.dtype} {tuple(bev.shape)}")
+        self._jpeg_images("jpeg_encode: bev", bev)
         n, h, w = (int(v) for v in bev.shape)
         bound = self.lib.salve_bev_jpeg_encode_max_bytes(h, w)
         if bound == 0:
@@ -412,29 +424,10 @@ class BevRasteriser:
             raise _lib.SalveHipError(f"jpeg_encode: stride must be a positive multiple of 4, got {stride}")
         scan = torch.empty((n, stride), dtype=torch.uint8, device=self.device)
         nbytes = torch.empty(n, dtype=torch.int32, device=self.device)
-        if n == 0:
-            return scan, nbytes
-        q = int(quality)
-        if q not in self._jpeg_tables:
-            from salve_amd.jpeg import quality_tables
-
-            self._jpeg_tables[q] = np.ascontiguousarray(quality_tables(q), dtype=np.uint16)
-        qtab = self._jpeg_tables[q]
-        per = min(n, self.JPEG_IMAGES_PER_CALL)
-        need = self.lib.salve_bev_jpeg_encode_workspace_bytes(per, h, w)
-        if need == 0:
-            _lib.check(-1, "salve_bev_jpeg_encode_workspace_bytes")
-        stream = torch.cuda.current_stream(self.device)
-        ws = self._jpeg_encode_ws.get(stream.cuda_stream)
-        if ws is None or ws.numel() < need:   # (allocated under the stream that uses it, as jpeg_roundtrip's)
-            ws = self._jpeg_encode_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            for lo in range(0, n, per):
-                m = min(per, n - lo)
-                st = self.lib.salve_bev_jpeg_encode(ctypes.c_void_p(bev[lo:].data_ptr()), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
-                                                    ctypes.c_void_p(scan[lo:].data_ptr()), stride, ctypes.c_void_p(nbytes[lo:].data_ptr()),
-                                                    ctypes.c_void_p(ws.data_ptr()), ws.numel(), self._stream())
-                _lib.check(st, "salve_bev_jpeg_encode")
+        for lo, m, ws, ws_bytes in self._jpeg_calls("encode", n, h, w):
+            st = self.lib.salve_bev_jpeg_encode(ctypes.c_void_p(bev[lo:].data_ptr()), m, h, w, self._jpeg_qtab(quality), ctypes.c_void_p(scan[lo:].data_ptr()),
+                                                stride, ctypes.c_void_p(nbytes[lo:].data_ptr()), ws, ws_bytes, self._stream())
+            _lib.check(st, "salve_bev_jpeg_encode")
         return scan, nbytes
 
     def jpeg_decode(self, scans: torch.Tensor, scan_offset, scan_bytes, h: int, w: int, qtab: np.ndarray, huffman: np.ndarray,
@@ -448,7 +441,8 @@ class BevRasteriser:
         (jpeg.STATUS_BITS names the bits); its pixels are what had been decoded, the other images are whole.  Nothing is read back here.
         stages: _lib.JPEG_STAGES_ALL (default).  For timing, _lib.JPEG_STAGE_ENTROPY runs the Huffman stage alone (status written, images
         not) and _lib.JPEG_STAGE_INVERSE the inverse stage alone, on the coefficients the entropy stage of the SAME arguments left in
-        this stream's workspace (status not written) -- so at most JPEG_IMAGES_PER_CALL images when the stages are called apart.
+        this stream's workspace (status not written) -- so at most JPEG_IMAGES_PER_CALL images when the stages are called apart, and NO
+        other JPEG method (jpeg_roundtrip, jpeg_encode, another jpeg_decode) on this stream between the two: they share the workspace.
         On the current stream; at most JPEG_IMAGES_PER_CALL images per library call, one workspace per stream."""
         from salve_amd.jpeg import HUFFMAN_TABLE_BYTES, SCAN_PADDING
 
@@ -467,30 +461,18 @@ class BevRasteriser:
             raise _lib.SalveHipError(f"jpeg_decode takes qtab [2, 64] and huffman [4, {HUFFMAN_TABLE_BYTES}], got {qtab.shape} and {huffman.shape}")
         if out is None:
             out = torch.empty((n, h, w), dtype=torch.int32, device=self.device)
-        elif tuple(out.shape) != (n, h, w) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != self.device:
-            raise _lib.SalveHipError(f"jpeg_decode: out must be contiguous int32 {(n, h, w)} on {self.device}, got {out.dtype} {tuple(out.shape)}")
+        else:
+            self._jpeg_images("jpeg_decode: out", out, (n, h, w))
         image_status = torch.empty(n, dtype=torch.int32, device=self.device)
-        if n == 0:
-            return out, image_status
         if stages != _lib.JPEG_STAGES_ALL and n > self.JPEG_IMAGES_PER_CALL:
             raise _lib.SalveHipError(f"jpeg_decode: the stages can be called apart for at most {self.JPEG_IMAGES_PER_CALL} images (one workspace), got {n}")
-        per = min(n, self.JPEG_IMAGES_PER_CALL)
-        need = self.lib.salve_bev_jpeg_decode_workspace_bytes(per, h, w)
-        if need == 0:
-            _lib.check(-1, "salve_bev_jpeg_decode_workspace_bytes")
         table = torch.from_numpy(np.concatenate([off.view(np.uint8), nb.astype(np.int32).view(np.uint8)])).to(self.device)   # one upload
-        stream = torch.cuda.current_stream(self.device)
-        ws = self._jpeg_decode_ws.get(stream.cuda_stream)
-        if ws is None or ws.numel() < need:   # (allocated under the stream that uses it, as jpeg_roundtrip's)
-            ws = self._jpeg_decode_ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        with torch.cuda.device(self.device):
-            for lo in range(0, n, per):
-                m = min(per, n - lo)
-                st = self.lib.salve_bev_jpeg_decode(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
-                                                    ctypes.c_void_p(table.data_ptr() + 8 * n + 4 * lo), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
-                                                    huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
-                                                    ctypes.c_void_p(image_status[lo:].data_ptr()), ctypes.c_void_p(ws.data_ptr()), ws.numel(), int(stages), self._stream())
-                _lib.check(st, "salve_bev_jpeg_decode")
+        for lo, m, ws, ws_bytes in self._jpeg_calls("decode", n, h, w):
+            st = self.lib.salve_bev_jpeg_decode(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
+                                                ctypes.c_void_p(table.data_ptr() + 8 * n + 4 * lo), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
+                                                huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
+                                                ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, int(stages), self._stream())
+            _lib.check(st, "salve_bev_jpeg_decode")
         return out, image_status
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:

@@ -2,7 +2,8 @@
 
   * --encode: `BevRasteriser.jpeg_encode` of N 501 x 501 images per call, on real renders of the synthetic scene and on full-frame
     noise: HIP events around the call, per image; the scans' sizes; and against them the pixel download the host route makes
-    (`export_u8(bev).cpu()`) and the scan download the device route makes (one 2-D copy of [n, longest scan] bytes);
+    (`export_u8(bev).cpu()`) and the scan download the device route makes (one 2-D copy of [n, longest scan] bytes); and, on the same
+    images, `BevRasteriser.jpeg_roundtrip` (DESIGN.md 4.17), which has no tool of its own, by events likewise;
   * --floor FILES: `render_dataset.render_building_floor_pairs` on one synthetic floor on disk with at least FILES tile files (four
     panoramas, FILES / 4 hypotheses, two surfaces), every route of --routes into a fresh directory, alternating, --rounds times:
     files / s by the host clock (the call ends with the files written), and the device route's files compared byte for byte
@@ -99,7 +100,10 @@ def bench_encode(n: int, reps: int) -> None:
     noise = torch.randint(0, 1 << 24, (n, Hb, Wb), dtype=torch.int32, device=DEV, generator=torch.Generator(DEV).manual_seed(1))
     print(f"n = {n} images of {Hb} x {Wb}; bound {ras.lib.salve_bev_jpeg_encode_max_bytes(Hb, Wb)} bytes, default slot "
           f"{ras.jpeg_encode(renders[:1])[0].shape[1]} bytes, workspace {ras.lib.salve_bev_jpeg_encode_workspace_bytes(n, Hb, Wb) / 2**20:.0f} MiB")
+    rt_out = torch.empty_like(renders)
     for name, imgs in (("renders", renders), ("noise", noise)):
+        med, lo, hi = _timed(lambda: ras.jpeg_roundtrip(imgs, 75, out=rt_out), reps)
+        print(f"{name:8s} roundtrip {med:8.3f} ms per call (min {lo:.3f}, max {hi:.3f}) = {med / n * 1e3:7.2f} us per image")
         scan, nbytes = ras.jpeg_encode(imgs, 75)
         lens = nbytes.cpu().numpy()
         med, lo, hi = _timed(lambda: ras.jpeg_encode(imgs, 75), reps)

@@ -18,7 +18,9 @@ were written moments before they are read: the reads come from the page cache, n
 
 --decode-only times the whole call and, in the same run, its two stages apart.  (The inverse stage's two launches, jpeg_idct_kernel and
 jpeg_pixels_kernel, can be told apart by `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_tile_files.py --decode-only
---reps 2`, a run of its own.)  Medians (min .. max); run the command twice for the spread.
+--reps 2`, a run of its own.)  Calling the stages apart needs the coefficients to stay in the stream's JPEG workspace, which the
+rasteriser's three JPEG methods share: nothing here calls one of them between an entropy stage and its inverse stage.
+Medians (min .. max); run the command twice for the spread.
 """
 
 from __future__ import annotations
