@@ -1,11 +1,13 @@
-"""The seeded layout fixtures the host and the GPU tests of device-side layout posing share, the comparator of the integer tables,
-and an emulator of WRONG posing kernels the comparator must reject (not a test module)."""
+"""The seeded layout fixtures the host and the GPU tests of device-side layout posing share -- the seeded set, the half-pixel set and
+the strided set (rooms and W/D/O lists longer than the posing kernel's 64 threads, also in a non-square window) --, the comparator of
+the integer tables, and an emulator of WRONG posing kernels the comparator must reject (not a test module)."""
 
 import functools
 
 import numpy as np
 
 from salve_amd import layout, synthetic, synthetic_layouts
+from salve_amd.common.bevparams import BEVParams
 from salve_amd.common.sim2 import Sim2
 
 P, N = 64, 512   # panoramas, posed images (the P identity images follow them)
@@ -51,6 +53,61 @@ def half_pixel_set():
     pl = layout.PanoLayouts.from_specs([(room, [("doors", np.array([[-0.5, -0.5], [1.5, -0.5]])), ("windows", np.array([[1.5, 1.5], [-0.5, 1.5]]))]),
                                         (room[::-1].copy(), [("openings", np.array([[3.5, 0.5], [1.5, 1.5]]))])])
     return pl, np.array([0, 1]), None, None, None, np.array([False, False])
+
+
+STRIDE_ROOMS, STRIDE_WDOS = (1, 63, 64, 65, 130, 200), (0, 31, 32, 33, 70)   # salve_layout_pose strides by 64 threads: vertex 64, W/D/O 32
+STRIDE_PANOS = ((1, 0), (63, 31), (64, 32), (65, 33), (130, 70), (200, 31), (64, 70), (200, 0))   # (stored room vertices, W/D/Os) per panorama
+WINDOWS = {"default": None, "44x82 at 0.1": dict(img_h=44, img_w=82, meters_per_px=0.1)}
+
+
+def window_params(name):
+    """The BEVParams of a WINDOWS entry (None: the default 500 x 500 at 0.02 m per pixel)."""
+    kw = WINDOWS[name]
+    return None if kw is None else BEVParams(**kw)
+
+
+@functools.lru_cache(maxsize=None)
+def strided_set():
+    """(PanoLayouts, pano, R, t, s, posed) for the second pass of the posing kernel's loops: rooms of 1, 63, 64, 65, 130 and 200
+    stored vertices (closed rings on a wobbling circle; the single vertex is a point), 0, 31, 32, 33 and 70 W/D/Os per panorama
+    spread over all three types, every panorama under three poses like `seeded_set`'s -- rotations over the full circle,
+    translations that push geometry out of the window, scales 1 and not 1 --, then every panorama's own layout."""
+    rng = np.random.default_rng(5)
+    specs = []
+    for nv, nw in STRIDE_PANOS:
+        if nv == 1:
+            room = np.array([[0.3, -0.2]])
+        else:
+            a = 2 * np.pi * np.arange(nv - 1) / (nv - 1)
+            rad = 2.0 + 0.5 * np.sin(5 * a) + rng.uniform(-0.1, 0.1, nv - 1)
+            ring = np.stack([rad * np.cos(a), rad * np.sin(a)], 1)
+            room = np.vstack([ring, ring[:1]])
+        wdos = []
+        for j in range(nw):
+            a0 = 2 * np.pi * j / nw
+            c = np.array([2.1 * np.cos(a0), 2.1 * np.sin(a0)])
+            d = 0.3 * np.array([-np.sin(a0 + 0.2), np.cos(a0 + 0.2)])
+            wdos.append((layout.WDO_TYPES[j % 3], np.stack([c - d, c + d])))
+        specs.append((room, wdos))
+    pl = layout.PanoLayouts.from_specs(specs)
+    P_, per = len(STRIDE_PANOS), 3
+    n = P_ * per
+    ang = rng.uniform(0, 2 * np.pi, n) + 2 * np.pi * np.arange(n) / n
+    R = np.stack([np.stack([np.cos(ang), -np.sin(ang)], 1), np.stack([np.sin(ang), np.cos(ang)], 1)], 1).astype(np.float32)
+    t = rng.uniform(-1.5, 1.5, (n, 2)).astype(np.float32)
+    s = np.where(np.arange(n) % 3 == 0, 1.0, rng.uniform(0.8, 1.25, n))
+    pano = np.concatenate([np.repeat(np.arange(P_), per), np.arange(P_)])
+    return (pl, pano, np.concatenate([R, np.full((P_, 2, 2), 3.0, np.float32)]), np.concatenate([t, np.full((P_, 2), -7.0, np.float32)]),
+            np.concatenate([s, np.full(P_, 9.0)]), np.arange(n + P_) < n)
+
+
+@functools.lru_cache(maxsize=None)
+def strided_host_tables(window):
+    """`pack_layout_tables`' rec / poly / seg of the strided set in a WINDOWS entry (computed once, never changed)."""
+    tabs = layout.pack_layout_tables(host_specs(*strided_set()), window_params(window))
+    for a in tabs:
+        a.setflags(write=False)
+    return tabs
 
 
 def tables_equal(a, b) -> bool:

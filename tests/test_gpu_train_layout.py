@@ -65,6 +65,42 @@ def test_layout_pose_tables_and_images_equal_the_host_path():
     assert bool((out[0] == 0).all()) and bool((out[lc.N + 1] == 0).all()) and bool((out[1] == 0x00ffffff).any())   # the empty room, posed and own
 
 
+@pytest.mark.parametrize("window", list(lc.WINDOWS))
+def test_strided_pose_tables_equal_the_host_paths(window):
+    """Rooms of up to 200 vertices and 70 W/D/Os: the second and later passes of the kernel's 64-thread loops."""
+    case = lc.strided_set()
+    pl, n = case[0], len(case[1])
+    bp = lc.window_params(window)
+    dl = layout.DeviceLayouts(pl, DEV, n, bev_params=bp)
+    dl.pose(torch.from_numpy(layout.pose_records(*case).view(np.uint8)).to(DEV), n)
+    status.check(DEV, "strided layout pose")
+    got = _device_tables(dl, n)
+    for name, want in (("pose_layouts_numpy", layout.pose_layouts_numpy(*case, bev_params=bp)), ("pack_layout_tables", lc.strided_host_tables(window))):
+        for tab, a, b in zip(("records", "poly_xy", "segs"), want, got):
+            assert a.dtype == b.dtype and a.shape == b.shape, (name, tab)
+            if not np.array_equal(a, b):
+                at = np.argwhere(a.view(np.int32).reshape(len(a), -1) != b.view(np.int32).reshape(len(b), -1))[:5]
+                raise AssertionError(f"{tab} differ from {name} at {at.tolist()}")
+        assert lc.tables_equal(want, got), name
+
+
+@pytest.mark.parametrize("window", list(lc.WINDOWS))
+def test_strided_pose_images_equal_the_host_path(window):
+    """The same set drawn: 70 segments are ten chunks of the rasteriser, in a square and a non-square window."""
+    case = lc.strided_set()
+    pl, n = case[0], len(case[1])
+    bp = lc.window_params(window)
+    dl = layout.DeviceLayouts(pl, DEV, n, bev_params=bp)
+    out = torch.full((n, *dl.hw), -1, dtype=torch.int32, device=DEV)
+    dl.draw(layout.pose_records(*case), out)
+    status.check(DEV, "strided layout pose + rasterise")
+    images = layout.rasterise_layouts(lc.host_specs(*case), DEV, bev_params=bp)
+    status.check(DEV, "strided layouts through the host path")
+    assert tuple(images.shape) == (n, *dl.hw) == ((n, 501, 501) if bp is None else (n, 45, 83))
+    assert torch.equal(out, images)
+    assert all(bool((out[k] != 0).any()) for k in range(n) if int(pl.wdo_count[case[1][k]]) > 0)
+
+
 def test_layout_pose_half_pixel_ties_round_to_even():
     case = lc.half_pixel_set()
     dl = layout.DeviceLayouts(case[0], DEV, 2)

@@ -162,6 +162,31 @@ def test_pose_layouts_numpy_equals_pack_layouts_on_the_seeded_set():
     assert np.array_equal(recs["R"][posed], R[posed].reshape(-1, 4)) and np.array_equal(recs["s"][posed], s[posed])
 
 
+@pytest.mark.parametrize("window", list(lc.WINDOWS))
+def test_pose_layouts_numpy_equals_pack_layouts_on_the_strided_set(window):
+    """Rooms and W/D/O lists longer than the posing kernel's 64 threads (its loops' second pass), in the default window and a
+    non-square one at another resolution."""
+    pl, pano, R, t, s, posed = lc.strided_set()
+    assert sorted(set(pl.room_count.tolist())) == [1, 63, 64, 65, 130, 200] and sorted(set(pl.wdo_count.tolist())) == [0, 31, 32, 33, 70]
+    for p in range(pl.P):   # every panorama with W/D/Os holds all three types
+        kinds = set(pl.wdo_type[pl.wdo_off[p]:pl.wdo_off[p + 1]].tolist())
+        assert kinds == ({0, 1, 2} if pl.wdo_count[p] else set())
+    assert set(pano[posed].tolist()) == set(pano[~posed].tolist()) == set(range(pl.P)) and (s[posed] == 1.0).any() and (s[posed] != 1.0).any()
+    theta = np.degrees(np.arctan2(R[posed][:, 1, 0], R[posed][:, 0, 0])) % 360.0
+    assert np.histogram(theta, bins=4, range=(0, 360))[0].min() > 0
+    bp = lc.window_params(window)
+    want = lc.strided_host_tables(window)
+    got = layout.pose_layouts_numpy(pl, pano, R, t, s, posed, bev_params=bp)
+    assert lc.tables_equal(want, got)
+    rec, poly, seg = got
+    H, W = (501, 501) if bp is None else (bp.img_h + 1, bp.img_w + 1)
+    assert rec["n_poly"].max() == 200 and rec["n_seg"].max() == 70 and len(poly) == int(rec["n_poly"].sum()) and len(seg) == int(rec["n_seg"].sum())
+    assert (poly < 0).any() and (poly[:, 0] >= W).any() and (poly[:, 1] >= H).any()      # parts of rooms outside the window
+    assert set(seg[:, 4].tolist()) == {0x0000ff, 0x00ff00, 0xff0000} and set(seg[:, 5].tolist()) == {8}
+    if bp is not None:   # another window gives other tables
+        assert not lc.tables_equal(lc.strided_host_tables("default"), got)
+
+
 def test_empty_tables_follow_pack_layouts_conventions():
     pl = lc.seeded_set()[0]
     for pano in ([], [1], [1, 1], [2]):   # nothing; the empty room; a room without W/D/Os
