@@ -46,7 +46,9 @@ typedef enum {
                                         salve_bev_pano_index_update (with SALVE_STATUS_BAD_PANO_SLOT), salve_layout_pose (with SALVE_STATUS_BAD_LAYOUT),
                                         salve_adam_step, salve_head_* (the training classifier head), salve_bev_jpeg_roundtrip, salve_bev_jpeg_encode
                                         (with salve_bev_jpeg_encode_workspace_bytes / _max_bytes), salve_bev_jpeg_decode (with
-                                        salve_bev_jpeg_decode_workspace_bytes and the SALVE_JPEG_* bits of its per-image status) */
+                                        salve_bev_jpeg_decode_workspace_bytes and the SALVE_JPEG_* bits of its per-image status),
+                                        salve_bev_jpeg_decode_lanes (with salve_bev_jpeg_decode_lanes_workspace_bytes, salve_bev_jpeg_subseq_bytes
+                                        and salve_jpeg_segment_t) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -810,6 +812,51 @@ size_t salve_bev_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w);
 int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes, int32_t n, int32_t h,
                           int32_t w, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws,
                           size_t ws_bytes, uint32_t stages, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * salve_bev_jpeg_decode with a LANE-PARALLEL entropy stage, and with restart intervals (additive within ABI 7): opt-in.
+ * salve_bev_jpeg_decode runs one wavefront per image whose symbol loop is scalar: its time is the latency of ONE image whatever the
+ * batch, and a panorama's scan of several hundred KB takes far longer than on the host.  Here a workgroup of 256 lanes takes one
+ * SEGMENT -- a whole scan, or one restart interval of it -- and every lane decodes salve_bev_jpeg_subseq_bytes() bytes of the
+ * stuffed stream at once: self-synchronising Huffman decoding (Weissenberger and Schmidt; salve_amd/csrc/jpeg_entropy_lanes.h has
+ * the passes, their bounds and what a wrong guess may meet).  Everything else is salve_bev_jpeg_decode's: the arguments, the
+ * inverse stage (the same two launches on the same coefficients), image_status, `stages`, the workspace's layout.
+ *   segments     device salve_jpeg_segment_t [n_segments], 8-byte aligned, in place of scan_offset / scan_bytes: the segment's bytes
+ *                scans + offset .. + bytes (stuffed, no RSTn marker, any alignment; offset + bytes + 16 <= scans_size), the image it
+ *                belongs to, its first MCU in the image's scan order and its MCUs.  An image without restart markers is ONE segment
+ *                (first_mcu 0, mcu_count = the image's MCUs); the DC predictors start at 0 in every segment (T.81 E.1.4).  The
+ *                segments of an image must tile its MCUs; their order in the table is free.  The table is on the device, so the
+ *                library cannot read it: BevRasteriser.jpeg_decode checks the tiling on the host before the upload.  Whatever the
+ *                table says, the kernel reads no byte outside scans[0 .. scans_size) and writes no coefficient outside its image:
+ *                a segment outside the buffer, or whose MCU range is not inside the image, decodes nothing and reports
+ *                SALVE_JPEG_BAD_SLOT to its image; a segment whose image is outside [0, n) is ignored; an MCU no segment names
+ *                decodes as zeros (mid grey) WITHOUT a status bit.
+ *   image_status 0 for an image whose segments are all well-formed, non-zero exactly when salve_bev_jpeg_decode would report the
+ *                same bytes (one segment) -- the OR over the image's segments of: too few blocks SALVE_JPEG_TRUNCATED, blocks or
+ *                more than 7 bits left over (or pad bits that are not 1) SALVE_JPEG_LEFTOVER, a DC value outside +-2047 after the
+ *                scan SALVE_JPEG_DC_RANGE, and BAD_CODE / COEF_OVERRUN / MARKER for what the TRUE pass met.  The bits may differ from
+ *                salve_bev_jpeg_decode's, and so may a failing image's pixels (deterministic, otherwise unspecified: this decoder
+ *                does not stop at the first error).  The other images do not notice.
+ *   Checks:      salve_bev_jpeg_decode's, and SALVE_ERR_BAD_ARG (0 from the size query) for n_segments outside [n, 2^24], a null or
+ *                misaligned segment table.
+ *   Workspace:   salve_bev_jpeg_decode's bytes (the lanes keep their state in LDS); no initialisation by the caller -- the call
+ *                itself clears the coefficients (the lanes store the non-zero ones only) and image_status (the segments OR into it).
+ *   Two clears and three launches, asynchronous on `stream`.  Integer arithmetic; plain stores, and one vector atomic OR per failing
+ *   segment into the zeroed status word (no dependence on order): the same input gives the same bits.
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_JPEG_MAX_SEGMENTS (1 << 24)
+typedef struct salve_jpeg_segment_t {
+    int64_t offset;     /* first byte of the segment in `scans` */
+    int32_t bytes;
+    int32_t image;      /* 0 .. n - 1 */
+    int32_t first_mcu;  /* in the image's scan order */
+    int32_t mcu_count;
+} salve_jpeg_segment_t;
+size_t salve_bev_jpeg_decode_lanes_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t n_segments);
+int32_t salve_bev_jpeg_subseq_bytes(void);
+int salve_bev_jpeg_decode_lanes(const uint8_t* scans, size_t scans_size, const salve_jpeg_segment_t* segments, int32_t n_segments, int32_t n,
+                                int32_t h, int32_t w, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status,
+                                void* ws, size_t ws_bytes, uint32_t stages, void* stream);
 
 #ifdef __cplusplus
 }

@@ -83,6 +83,9 @@ EXPORTED_SYMBOLS = (
     "salve_bev_jpeg_encode",
     "salve_bev_jpeg_decode_workspace_bytes",
     "salve_bev_jpeg_decode",
+    "salve_bev_jpeg_decode_lanes_workspace_bytes",
+    "salve_bev_jpeg_subseq_bytes",
+    "salve_bev_jpeg_decode_lanes",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -122,6 +125,8 @@ TILE_JOB_DTYPE = np.dtype([("bev_offset", "<i8"), ("slot", "<i4"), ("chan", "<i4
 LAYOUT_DTYPE = np.dtype([("n_poly", "<i4"), ("poly_off", "<i4"), ("n_seg", "<i4"), ("seg_off", "<i4")])
 LAYOUT_POSE_DTYPE = np.dtype([("pano", "<i4"), ("poly_off", "<i4"), ("seg_off", "<i4"), ("reserved", "<i4"), ("R", "<f4", (4,)), ("t", "<f4", (2,)),
                               ("s", "<f8")])
+JPEG_SEGMENT_DTYPE = np.dtype([("offset", "<i8"), ("bytes", "<i4"), ("image", "<i4"), ("first_mcu", "<i4"), ("mcu_count", "<i4")])   # salve_jpeg_segment_t
+JPEG_MAX_SEGMENTS = 1 << 24
 TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 TILE_HFLIP, TILE_VFLIP = 1, 2
 assert LAYOUT_POSE_DTYPE.itemsize == 48 and HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
@@ -295,6 +300,12 @@ def load() -> ctypes.CDLL:
     # scans, scans_size, scan_offset, scan_bytes, n, h, w, HOST qtab, HOST huffman, bev_out, image_status, ws, ws_bytes, stages, stream
     lib.salve_bev_jpeg_decode.argtypes = [vp, sz, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
     lib.salve_bev_jpeg_decode.restype = ctypes.c_int
+    lib.salve_bev_jpeg_decode_lanes_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.salve_bev_jpeg_decode_lanes_workspace_bytes.restype = sz
+    lib.salve_bev_jpeg_subseq_bytes.argtypes = []
+    lib.salve_bev_jpeg_subseq_bytes.restype = i32
+    lib.salve_bev_jpeg_decode_lanes.argtypes = [vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
+    lib.salve_bev_jpeg_decode_lanes.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

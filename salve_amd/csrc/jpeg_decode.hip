@@ -24,6 +24,7 @@
 
 #include "../../include/salve_hip.h"
 #include "jpeg_entropy.h"
+#include "jpeg_entropy_lanes.h"
 #include "jpeg_inverse.h"
 #include "salve_common.h"
 
@@ -31,6 +32,8 @@ static_assert(JE_BAD_CODE == SALVE_JPEG_BAD_CODE && JE_COEF_OVERRUN == SALVE_JPE
                   JE_DC_RANGE == SALVE_JPEG_DC_RANGE && JE_LEFTOVER == SALVE_JPEG_LEFTOVER && JE_MARKER == SALVE_JPEG_MARKER &&
                   JE_BAD_SLOT == SALVE_JPEG_BAD_SLOT,
               "jpeg_entropy.h and salve_hip.h name the same status bits");
+static_assert(sizeof(JlSegment) == sizeof(salve_jpeg_segment_t) && sizeof(JlSegment) == 24 && JE_SUBSEQ % 4 == 0 && JE_SUBSEQ >= 4,
+              "jpeg_entropy_lanes.h and salve_hip.h name the same segment");
 
 namespace {
 
@@ -55,6 +58,23 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     }
     const uint32_t decoded = je_decode_image(sh, scans + off, nbytes, mcus, coef + i * mcus * 384, lane, 64);   // (a bad slot: all coefficients zero)
     if (lane == 0) image_status[i] = (int32_t)(status ? status : decoded);
+}
+
+// The lane-parallel entropy stage (jpeg_entropy_lanes.h): grid (segments), JL_LANES threads; one lane per JE_SUBSEQ bytes of the segment's
+// stuffed stream.  coef and image_status are ZERO on entry (salve_bev_jpeg_decode_lanes clears them on the stream).  A segment's status
+// bits are OR-ed into its image's word: bit-wise OR into a zeroed word does not depend on the order of the segments.
+__global__ __launch_bounds__(JL_LANES) void jpeg_entropy_lanes_kernel(const uint8_t* __restrict__ scans, const JlSegment* __restrict__ segments, uint64_t scans_size,
+                                                                      int n, int mcus, JeTables tab, int16_t* __restrict__ coef, int32_t* __restrict__ image_status) {
+    __shared__ JlShared sh;
+    const JlSegment seg = segments[blockIdx.x];
+    if (seg.image < 0 || seg.image >= n) return;   // (whole workgroup) no image to report to: the wrapper refuses such a table
+    if (!jl_segment_inside(seg, scans_size, mcus)) {   // not inside the buffer or the image: decode nothing
+        if (threadIdx.x == 0) atomicOr(&image_status[seg.image], (int)JE_BAD_SLOT);
+        return;
+    }
+    je_prepare_tables(sh, tab, (int)threadIdx.x, JL_LANES);
+    const uint32_t status = jl_decode_segment(sh, scans + seg.offset, seg.bytes, seg.mcu_count, coef + ((int64_t)seg.image * mcus + seg.first_mcu) * 384, nullptr);
+    if (threadIdx.x == 0 && status) atomicOr(&image_status[seg.image], (int)status);
 }
 
 // grid (blocks of an image / 32, 1, images)
@@ -91,6 +111,11 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_idct_kernel(const int16_t* 
 
 }  // namespace
 
+// The two entries differ in their entropy stage alone: segments == nullptr is salve_bev_jpeg_decode.
+static int jpeg_decode_any(const char* me, const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes,
+                           const salve_jpeg_segment_t* segments, int32_t n_segments, int32_t n, int32_t h, int32_t w, const uint16_t* qtab,
+                           const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws, size_t ws_bytes, uint32_t stages, void* stream);
+
 extern "C" {
 
 size_t salve_bev_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w) {
@@ -99,11 +124,39 @@ size_t salve_bev_jpeg_decode_workspace_bytes(int32_t n, int32_t h, int32_t w) {
     return jpeg_planes_bytes(n, g) + (size_t)n * g.mcus() * 6 * 64 * sizeof(int16_t);
 }
 
+size_t salve_bev_jpeg_decode_lanes_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t n_segments) {
+    const char* me = "salve_bev_jpeg_decode_lanes_workspace_bytes";
+    if (!jpeg_shape_ok(me, n, h, w)) return 0;
+    if (n_segments < n || n_segments > SALVE_JPEG_MAX_SEGMENTS) { jpeg_refuse(me, "n_segments must lie in [n, 2^24]"); return 0; }
+    return salve_bev_jpeg_decode_workspace_bytes(n, h, w);   // the planes and the coefficients; the lanes keep their state in LDS
+}
+
+int32_t salve_bev_jpeg_subseq_bytes(void) { return JE_SUBSEQ; }
+
+int salve_bev_jpeg_decode_lanes(const uint8_t* scans, size_t scans_size, const salve_jpeg_segment_t* segments, int32_t n_segments, int32_t n, int32_t h,
+                                int32_t w, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws,
+                                size_t ws_bytes, uint32_t stages, void* stream) {
+    const char* me = "salve_bev_jpeg_decode_lanes";
+    if (!segments) { jpeg_refuse(me, "null pointer"); return SALVE_ERR_BAD_ARG; }
+    if (((uintptr_t)segments & 7)) { jpeg_refuse(me, "segments must be 8-byte aligned"); return SALVE_ERR_BAD_ARG; }
+    if (n_segments < n || n_segments > SALVE_JPEG_MAX_SEGMENTS) { jpeg_refuse(me, "n_segments must lie in [n, 2^24]"); return SALVE_ERR_BAD_ARG; }
+    return jpeg_decode_any(me, scans, scans_size, nullptr, nullptr, segments, n_segments, n, h, w, qtab, huffman, bev_out, image_status, ws, ws_bytes, stages, stream);
+}
+
 int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes, int32_t n, int32_t h, int32_t w,
                           const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws, size_t ws_bytes,
                           uint32_t stages, void* stream) {
     const char* me = "salve_bev_jpeg_decode";
-    const bool null = !scans || !scan_offset || !scan_bytes || !qtab || !huffman || !bev_out || !image_status || !ws;
+    if (!scan_offset || !scan_bytes) { jpeg_refuse(me, "null pointer"); return SALVE_ERR_BAD_ARG; }
+    return jpeg_decode_any(me, scans, scans_size, scan_offset, scan_bytes, nullptr, 0, n, h, w, qtab, huffman, bev_out, image_status, ws, ws_bytes, stages, stream);
+}
+
+}  // extern "C"
+
+static int jpeg_decode_any(const char* me, const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes,
+                           const salve_jpeg_segment_t* segments, int32_t n_segments, int32_t n, int32_t h, int32_t w, const uint16_t* qtab,
+                           const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status, void* ws, size_t ws_bytes, uint32_t stages, void* stream) {
+    const bool null = !scans || !qtab || !huffman || !bev_out || !image_status || !ws;
     if (null) { jpeg_refuse(me, "null pointer"); return SALVE_ERR_BAD_ARG; }
     if (stages < SALVE_JPEG_STAGE_ENTROPY || stages > SALVE_JPEG_STAGES_ALL) { jpeg_refuse(me, "stages must be SALVE_JPEG_STAGE_ENTROPY, SALVE_JPEG_STAGE_INVERSE or both"); return SALVE_ERR_BAD_ARG; }
     if (!jpeg_shape_ok(me, n, h, w)) return SALVE_ERR_BAD_ARG;
@@ -121,7 +174,13 @@ int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t
     const int mcus = (int)g.mcus(), nblocks = 6 * mcus;
     uint8_t* planes = (uint8_t*)ws;
     int16_t* coef = (int16_t*)(planes + jpeg_planes_bytes(n, g));
-    if (stages & SALVE_JPEG_STAGE_ENTROPY) {
+    if ((stages & SALVE_JPEG_STAGE_ENTROPY) && segments) {   // the lanes write the non-zero coefficients and OR the status bits: both zero first
+        SALVE_HIP_CHECK(hipMemsetAsync(coef, 0, (size_t)n * mcus * 384 * sizeof(int16_t), (hipStream_t)stream));
+        SALVE_HIP_CHECK(hipMemsetAsync(image_status, 0, (size_t)n * sizeof(int32_t), (hipStream_t)stream));
+        hipLaunchKernelGGL(jpeg_entropy_lanes_kernel, dim3((unsigned)n_segments), dim3(JL_LANES), 0, (hipStream_t)stream, scans, (const JlSegment*)segments,
+                           (uint64_t)scans_size, n, mcus, tab, coef, image_status);
+        SALVE_HIP_CHECK(hipGetLastError());
+    } else if (stages & SALVE_JPEG_STAGE_ENTROPY) {
         hipLaunchKernelGGL(jpeg_entropy_kernel, dim3((unsigned)n), dim3(64), 0, (hipStream_t)stream, scans, scan_offset, scan_bytes, (uint64_t)scans_size, mcus, tab,
                            coef, image_status);
         SALVE_HIP_CHECK(hipGetLastError());
@@ -134,5 +193,3 @@ int salve_bev_jpeg_decode(const uint8_t* scans, size_t scans_size, const int64_t
     }
     return SALVE_OK;
 }
-
-}  // extern "C"

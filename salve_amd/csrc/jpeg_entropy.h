@@ -100,21 +100,19 @@ static inline bool je_make_tables(const uint8_t* huffman, JeTables* out) {
     return true;
 }
 
-// All lanes: the tables into shared memory, the look-ahead expanded from them.
-JE_FN void je_prepare(JeShared& sh, const JeTables& tab, int lane, int nlanes) {
+// All lanes: the tables into shared memory, the look-ahead expanded from them.  Sh: JeShared, or jpeg_entropy_lanes.h's JlShared
+// (the members look, maxcode, valoff, huffval and nat).
+template <class Sh>
+JE_FN void je_prepare_tables(Sh& sh, const JeTables& tab, int lane, int nlanes) {
     constexpr uint8_t zigzag[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                     41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                     30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-    for (int j = lane; j < 64; j += nlanes) {
-        sh.nat[j] = zigzag[j];
-        sh.blk[j] = 0;
-    }
+    for (int j = lane; j < 64; j += nlanes) sh.nat[j] = zigzag[j];
     for (int j = lane; j < 4 * 17; j += nlanes) {
         sh.maxcode[j / 17][j % 17] = tab.maxcode[j / 17][j % 17];
         sh.valoff[j / 17][j % 17] = tab.valoff[j / 17][j % 17];
     }
     for (int j = lane; j < 4 * 256; j += nlanes) sh.huffval[j >> 8][j & 255] = tab.huffval[j >> 8][j & 255];
-    for (int j = lane; j < JE_STAGE / 4 + 1; j += nlanes) sh.stage[j] = 0;
     JE_SYNC();
     for (int e = lane; e < 4 << JE_LOOK; e += nlanes) {
         const int t = e >> JE_LOOK, p = e & ((1 << JE_LOOK) - 1);
@@ -129,6 +127,12 @@ JE_FN void je_prepare(JeShared& sh, const JeTables& tab, int lane, int nlanes) {
         sh.look[t][e & ((1 << JE_LOOK) - 1)] = (uint16_t)entry;
     }
     JE_SYNC();
+}
+
+JE_FN void je_prepare(JeShared& sh, const JeTables& tab, int lane, int nlanes) {
+    for (int j = lane; j < 64; j += nlanes) sh.blk[j] = 0;
+    for (int j = lane; j < JE_STAGE / 4 + 1; j += nlanes) sh.stage[j] = 0;
+    je_prepare_tables(sh, tab, lane, nlanes);
 }
 
 // All lanes: stage[] <- src[pos ..), 64 consecutive bytes per step.  Called with pos < nbytes.

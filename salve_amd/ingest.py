@@ -1,7 +1,8 @@
 """The step BEFORE the hot path: panoramas and alignment hypotheses from disk to the device.
 
 * `PanoStore` -- the panoramas of one floor, resident on the GPU in the layout the rasteriser reads
-  (`u8 [P,512,1024,3]`, `u16 [P,512,1024]`): the RGB JPEG is decoded on the host (Pillow) and resized ON THE DEVICE with
+  (`u8 [P,512,1024,3]`, `u16 [P,512,1024]`): the RGB JPEG is decoded on the host (Pillow) -- or, with `decode="device"`, on the
+  device by the lane-parallel JPEG decoder, the same pixels -- and resized ON THE DEVICE with
   cv2's INTER_LINEAR arithmetic (bev_rendering_utils.py:370-375; `salve_resize_rgb_u8`); the `.depth.png` is the uint16
   millimetre map HoHoNet inference wrote (infer_depth.py:55-62, read at bev_rendering_utils.py:367).
 * `load_floor_hypotheses` -- the work list of one (building, floor): `{root}/{building}/{floor}/{label}/{i1}_{i2}__
@@ -61,6 +62,12 @@ def resize_rgb_on_device(rgb_dev: torch.Tensor, out_hw: Tuple[int, int]) -> torc
     return out
 
 
+def _read_rgb3(path: str) -> np.ndarray:
+    """uint8 [H, W, 3] by Pillow; a greyscale file repeated into three channels."""
+    rgb = image_io.read_rgb(path)
+    return np.repeat(rgb[:, :, None], 3, axis=2) if rgb.ndim == 2 else rgb
+
+
 class PanoStore:
     """Panoramas of one floor on the device, addressed by pano id."""
 
@@ -70,30 +77,112 @@ class PanoStore:
         self.index: Dict[int, int] = {}
         self.fpaths: List[str] = []
         self.rgb = self.depth = None
+        self.host_decoded = 0      # load(decode="device"): the files Pillow decoded
+        self._ras = None
 
-    def load(self, img_fpaths: Dict[int, str], depth_save_root: str, building_id: str, pano_ids: Sequence[int]) -> "PanoStore":
-        """Decode (host) -> upload -> resize (device).  Depth maps are `{depth_save_root}/{building}/{stem}.depth.png`
+    DECODES = ("host", "device")
+    READ_THREADS = 16          # decode="device": the pool that reads and parses the files (and inflates the depth PNGs)
+    PANOS_PER_CALL = 32        # decode="device": panoramas per jpeg_decode call (its workspace: 4.5 bytes per pixel and panorama)
+
+    def load(self, img_fpaths: Dict[int, str], depth_save_root: str, building_id: str, pano_ids: Sequence[int], decode: str = "host") -> "PanoStore":
+        """Decode -> resize (device).  Depth maps are `{depth_save_root}/{building}/{stem}.depth.png`
         (bev_rendering_utils.py:610-611); one that is missing or of the wrong size raises, as the reference's imread /
-        broadcast would."""
+        broadcast would.
+        decode: "host" (default) decodes every JPEG with Pillow, one after the other, and uploads its pixels.  "device": a thread pool
+        reads and parses the files (jpeg.parse_file(restart=True)) and inflates the depth PNGs; the panoramas that share size and
+        tables go through BevRasteriser.jpeg_decode(entropy="lanes") together -- only their entropy-coded scans are uploaded -- and a
+        file the device does not decode (greyscale, 4:4:4, 4:2:2, progressive ...) or reports as malformed takes Pillow into the same
+        slot.  The same `rgb`, bit for bit."""
+        if decode not in self.DECODES:
+            raise ValueError(f"decode must be one of {self.DECODES}, got {decode!r}")
         h, w = self.pano_hw
-        rgbs, depths = [], []
-        for k, pid in enumerate(sorted(set(int(p) for p in pano_ids))):
-            fp = img_fpaths[pid]
-            rgb = image_io.read_rgb(fp)
-            if rgb.ndim == 2:
-                rgb = np.repeat(rgb[:, :, None], 3, axis=2)
-            depth = image_io.read_depth_png(f"{depth_save_root}/{building_id}/{Path(fp).stem}.depth.png")
-            if depth.shape != (h, w):
-                raise ValueError(f"depth map must be {w}x{h}, got {depth.shape[::-1]}")
+        pids = sorted(set(int(p) for p in pano_ids))
+        fps = [img_fpaths[pid] for pid in pids]
+        depth_fps = [f"{depth_save_root}/{building_id}/{Path(fp).stem}.depth.png" for fp in fps]
+        if decode == "device":
+            rgb, depths = self._load_device(fps, depth_fps)
+        else:
+            rgbs, depths = [], []
+            for fp, dfp in zip(fps, depth_fps):
+                rgbs.append(torch.from_numpy(_read_rgb3(fp)).to(self.device)[None])
+                depths.append(image_io.read_depth_png(dfp))
+                self._check_depth(depths[-1])
+            # panoramas of one tour share a size; resize per distinct size so that mixed inputs still work
+            rgb = torch.cat([resize_rgb_on_device(t, (h, w)) for t in rgbs], 0).contiguous()
+        for k, (pid, fp) in enumerate(zip(pids, fps)):
             self.index[pid] = k
             self.fpaths.append(fp)
-            rgbs.append(torch.from_numpy(rgb).to(self.device)[None])
-            depths.append(depth)
-        # panoramas of one tour share a size; resize per distinct size so that mixed inputs still work
-        out = [resize_rgb_on_device(t, (h, w)) for t in rgbs]
-        self.rgb = torch.cat(out, 0).contiguous()
+        self.rgb = rgb
         self.depth = torch.from_numpy(np.stack(depths).view(np.int16)).to(self.device)
         return self
+
+    def _check_depth(self, depth: np.ndarray) -> None:
+        h, w = self.pano_hw
+        if depth.shape != (h, w):
+            raise ValueError(f"depth map must be {w}x{h}, got {depth.shape[::-1]}")
+
+    def _load_device(self, fps: List[str], depth_fps: List[str]) -> Tuple[torch.Tensor, List[np.ndarray]]:
+        """load(decode="device"): (uint8 [P, h, w, 3] on the device, the depth maps)."""
+        import concurrent.futures
+
+        from salve_amd import jpeg
+        from salve_amd.rasteriser import BevRasteriser
+
+        h, w = self.pano_hw
+
+        def read(k: int):
+            with open(fps[k], "rb") as f:
+                data = f.read()
+            try:
+                parsed = jpeg.parse_file(data, restart=True)
+                if max(parsed.h, parsed.w) > jpeg.DEVICE_MAX_SIDE or max(s[1] for s in parsed.segments) > jpeg.DEVICE_MAX_SEGMENT_BYTES:
+                    raise jpeg.Unsupported("larger than salve_bev_jpeg_decode_lanes takes")
+                return data, parsed, None
+            except jpeg.Unsupported:
+                return None, None, _read_rgb3(fps[k])
+
+        with concurrent.futures.ThreadPoolExecutor(max_workers=min(self.READ_THREADS, max(1, 2 * len(fps))), thread_name_prefix="salve-panos") as pool:
+            reads = [pool.submit(read, k) for k in range(len(fps))]                # both kinds of file are in the pool together
+            inflates = [pool.submit(image_io.read_depth_png, p) for p in depth_fps]
+            files = [f.result() for f in reads]
+            depths = [f.result() for f in inflates]
+        for d in depths:
+            self._check_depth(d)
+        out = torch.empty((len(fps), h, w, 3), dtype=torch.uint8, device=self.device)
+        groups: Dict[bytes, List[int]] = {}
+        for k, (_, parsed, _) in enumerate(files):
+            if parsed is not None:
+                groups.setdefault(parsed.header_key, []).append(k)
+        if groups and self._ras is None:
+            self._ras = BevRasteriser(self.device)
+        pending = []
+        for members in groups.values():
+            first = files[members[0]][1]
+            for lo in range(0, len(members), self.PANOS_PER_CALL):
+                part = members[lo:lo + self.PANOS_PER_CALL]
+                rows, off, nb, at = [], [], [], 0
+                for j, k in enumerate(part):
+                    parsed = files[k][1]
+                    rows += [(at + o - parsed.scan_offset, n, j, m0, mc) for o, n, m0, mc in parsed.segments]
+                    off.append(at)
+                    nb.append(parsed.scan_bytes)
+                    at += parsed.scan_bytes
+                blob = np.empty(at + jpeg.SCAN_PADDING, dtype=np.uint8)
+                blob[at:] = 0
+                for k, o, n in zip(part, off, nb):
+                    blob[o:o + n] = np.frombuffer(files[k][0], dtype=np.uint8, count=n, offset=files[k][1].scan_offset)
+                img, st = self._ras.jpeg_decode(torch.from_numpy(blob).to(self.device), off, nb, first.h, first.w, first.qtab, first.huffman,
+                                                entropy="lanes", segments=rows)
+                out[torch.as_tensor(part, device=self.device)] = resize_rgb_on_device(self._ras.export_u8(img), (h, w))
+                pending.append((part, st))
+        host_route = [k for k, (_, parsed, _) in enumerate(files) if parsed is None]
+        for part, st in pending:                       # (one wait, behind the last launch) a scan the device reports: Pillow's verdict counts
+            host_route += [k for k, word in zip(part, st.cpu().numpy()) if word]
+        for k in host_route:
+            rgb = files[k][2] if files[k][2] is not None else _read_rgb3(fps[k])
+            out[k] = resize_rgb_on_device(torch.from_numpy(rgb).to(self.device)[None], (h, w))[0]
+        self.host_decoded = len(host_route)
+        return out, depths
 
     def __len__(self) -> int:
         return len(self.index)
@@ -171,10 +260,12 @@ def load_floor_hypotheses(hypotheses_save_root: str, building_id: str, floor_id:
 
 
 def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypotheses_save_root: str, bev_save_root: str,
-                building_id: str, floor_id: str, serialization_save_dir: str, batch_size: int = 64, chunk: Optional[int] = None):
+                building_id: str, floor_id: str, serialization_save_dir: str, batch_size: int = 64, chunk: Optional[int] = None,
+                decode: str = "host"):
     """Disk -> predictions for one floor without writing a tile: the fused counterpart of running
     scripts/render_dataset_bev.py and then scripts/test.py on that floor.  chunk = hypotheses per launch; None: the pipeline picks the
-    largest launch that fits the free HBM (pipeline.pick_launch)."""
+    largest launch that fits the free HBM (pipeline.pick_launch).  decode: PanoStore.load's ("device": the panoramas' JPEG files are
+    decoded on the GPU; the same prediction files)."""
     from salve_amd import evaluate
     from salve_amd.pipeline import RenderVerifyPipeline
 
@@ -182,7 +273,7 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     if len(hyps) == 0:
         return None
     img_fpaths = floor_pano_fpaths(raw_dataset_dir, building_id)
-    store = PanoStore(device).load(img_fpaths, depth_save_root, building_id, np.concatenate([hyps.i1, hyps.i2]))
+    store = PanoStore(device).load(img_fpaths, depth_save_root, building_id, np.concatenate([hyps.i1, hyps.i2]), decode=decode)
     pipe = RenderVerifyPipeline(model, device, pano_hw=store.pano_hw, chunk=chunk, n_hypotheses=len(hyps))
     pipe.set_panos(store.rgb, store.depth)
     return evaluate.run_fused_epoch(pipe, hyps.table(store, img_fpaths), hyps.tile_names(bev_save_root, img_fpaths), hyps.label,

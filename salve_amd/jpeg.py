@@ -12,7 +12,7 @@ Pure host arithmetic, no device.
 from __future__ import annotations
 
 import re
-from typing import Dict, NamedTuple
+from typing import Dict, NamedTuple, Tuple
 
 import numpy as np
 
@@ -156,10 +156,14 @@ class ParsedFile(NamedTuple):
     scan_offset: int          # the entropy-coded scan is data[scan_offset : scan_offset + scan_bytes] (stuffed, padded; no EOI)
     scan_bytes: int
     header_key: bytes         # the bytes before the scan: files with equal keys share size and tables and may go into one call
+    segments: Tuple[Tuple[int, int, int, int], ...] = ()   # (file offset, bytes, first MCU, MCUs) of the scan's restart intervals, the RSTn
+    #                           markers excluded; a scan without restart markers is one segment.  For BevRasteriser.jpeg_decode(entropy="lanes")
 
 
 HUFFMAN_TABLE_BYTES = 272
 SCAN_PADDING = 16             # include/salve_hip.h: SALVE_JPEG_SCAN_PADDING
+DEVICE_MAX_SIDE = 4096        # salve_bev_jpeg_decode / _lanes refuse a taller or wider image (parse_file itself has no limit) ...
+DEVICE_MAX_SEGMENT_BYTES = 1 << 27   # ... and the lanes report a longer segment as SALVE_JPEG_BAD_SLOT: callers send such files to the host
 _MARKER_IN_SCAN = re.compile(rb"\xff[^\x00]")   # inside entropy-coded data every 0xFF is followed by a stuffed 0x00
 # include/salve_hip.h: SALVE_JPEG_*, the bits of salve_bev_jpeg_decode's per-image status
 STATUS_BITS = {1: "a bit pattern that is no Huffman code of its table", 2: "a run past coefficient 63", 4: "the scan ends before the last MCU",
@@ -172,12 +176,16 @@ def describe_status(word: int) -> str:
     return "; ".join(text for bit, text in STATUS_BITS.items() if int(word) & bit) or "ok"
 
 
-def parse_file(data: bytes) -> ParsedFile:
+def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
     """Walks the marker segments of a JPEG file (ITU-T T.81 Annex B) up to its scan and returns what salve_bev_jpeg_decode needs.
     Raises `Unsupported(reason)` for everything outside part 1 of what the device decodes: progressive and other non-baseline
     frames, greyscale, other sampling factors, 12-bit samples, 16-bit quantisation entries, a restart interval, more than one scan,
-    a missing EOI, a truncated segment.  Pure host arithmetic."""
+    a missing EOI, a truncated segment.  Pure host arithmetic.
+    restart=True (for salve_bev_jpeg_decode_lanes) also takes a DRI segment and the RSTn markers inside the scan: the markers must
+    count D0 .. D7 in order, and there must be exactly as many intervals as the image's MCUs need (interval i starts at MCU i * Ri:
+    every interval but the last holds Ri MCUs by position); `segments` then names the intervals, the marker bytes excluded."""
     data = bytes(data)
+    interval = 0
     if data[:2] != b"\xff\xd8":
         raise Unsupported("no SOI marker")
     qt: Dict[int, np.ndarray] = {}
@@ -260,7 +268,8 @@ def parse_file(data: bytes) -> ParsedFile:
         elif marker == 0xDD:
             if len(body) != 2:
                 raise Unsupported("a malformed DRI segment")
-            if int.from_bytes(body, "big") != 0:
+            interval = int.from_bytes(body, "big")
+            if interval != 0 and not restart:
                 raise Unsupported("a restart interval")
         elif marker == 0xDA:
             if frame is None:
@@ -286,7 +295,21 @@ def parse_file(data: bytes) -> ParsedFile:
     if data[-2:] != b"\xff\xd9":
         raise Unsupported("no EOI marker at the end of the file")
     end = len(data) - 2
-    found = _MARKER_IN_SCAN.search(data, at, end)
-    if found is not None:
-        raise Unsupported(f"marker FF{data[found.start() + 1]:02X} inside the scan: restart markers or a further scan")
-    return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at])
+    mcus = -(-h // 16) * -(-w // 16)
+    if interval == 0:
+        found = _MARKER_IN_SCAN.search(data, at, end)
+        if found is not None:
+            raise Unsupported(f"marker FF{data[found.start() + 1]:02X} inside the scan: restart markers or a further scan")
+        return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], ((at, end - at, 0, mcus),))
+    segments, lo = [], at
+    for k, found in enumerate(_MARKER_IN_SCAN.finditer(data, at, end)):
+        marker = data[found.start() + 1]
+        if marker != 0xD0 + (k & 7):
+            raise Unsupported(f"marker FF{marker:02X} inside the scan where restart marker FF{0xD0 + (k & 7):02X} is due")
+        segments.append((lo, found.start() - lo, k * interval, interval))
+        lo = found.start() + 2
+    first = len(segments) * interval
+    if first >= mcus or first + interval < mcus:
+        raise Unsupported(f"{len(segments) + 1} restart intervals of {interval} MCUs in a scan of {mcus} MCUs: wrong MCU count per interval")
+    segments.append((lo, end - lo, first, mcus - first))
+    return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], tuple(segments))

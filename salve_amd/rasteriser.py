@@ -431,7 +431,8 @@ class BevRasteriser:
         return scan, nbytes
 
     def jpeg_decode(self, scans: torch.Tensor, scan_offset, scan_bytes, h: int, w: int, qtab: np.ndarray, huffman: np.ndarray,
-                    out: Optional[torch.Tensor] = None, stages: int = _lib.JPEG_STAGES_ALL) -> Tuple[torch.Tensor, torch.Tensor]:
+                    out: Optional[torch.Tensor] = None, stages: int = _lib.JPEG_STAGES_ALL, entropy: str = "image",
+                    segments=None) -> Tuple[torch.Tensor, torch.Tensor]:
         """The entropy-coded scans of n baseline 4:2:0 JPEG files of ONE size that SHARE their tables (`salve_amd.jpeg.parse_file`: equal
         `header_key`) -> (int32 [n, h, w] images holding 0x00BBGGRR, int32 [n] status), both on the device: the pixels Pillow decodes
         from those files, bit for bit (include/salve_hip.h: salve_bev_jpeg_decode; zind_data.py:306-315).
@@ -443,8 +444,19 @@ class BevRasteriser:
         not) and _lib.JPEG_STAGE_INVERSE the inverse stage alone, on the coefficients the entropy stage of the SAME arguments left in
         this stream's workspace (status not written) -- so at most JPEG_IMAGES_PER_CALL images when the stages are called apart, and NO
         other JPEG method (jpeg_roundtrip, jpeg_encode, another jpeg_decode) on this stream between the two: they share the workspace.
-        On the current stream; at most JPEG_IMAGES_PER_CALL images per library call, one workspace per stream."""
+        On the current stream; at most JPEG_IMAGES_PER_CALL images per library call, one workspace per stream.
+        entropy: "image" (default) is salve_bev_jpeg_decode: one wavefront per image, no restart intervals.  "lanes" is
+        salve_bev_jpeg_decode_lanes: a workgroup per SEGMENT with a lane per salve_bev_jpeg_subseq_bytes() bytes, the same pixels and
+        the same zero / non-zero status (a failing image's bits and pixels may differ).  segments ("lanes" only): the restart
+        intervals, rows (offset in `scans`, bytes, image, first MCU, MCUs) or a _lib.JPEG_SEGMENT_DTYPE array -- `parse_file(data,
+        restart=True).segments` rebased to the buffer -- sorted by image, each image's rows tiling its MCUs in order (checked here:
+        the device cannot refuse a table it has not read); default one segment per image, scan_offset / scan_bytes."""
         from salve_amd.jpeg import HUFFMAN_TABLE_BYTES, SCAN_PADDING
+
+        if entropy not in ("image", "lanes"):
+            raise _lib.SalveHipError(f"jpeg_decode: entropy is 'image' or 'lanes', got {entropy!r}")
+        if segments is not None and entropy != "lanes":
+            raise _lib.SalveHipError("jpeg_decode: a segment table needs entropy='lanes' (salve_bev_jpeg_decode takes no restart intervals)")
 
         if scans.dim() != 1 or scans.dtype != torch.uint8 or not scans.is_contiguous() or scans.device != self.device:
             raise _lib.SalveHipError(f"jpeg_decode takes the scans as a contiguous 1-D uint8 tensor on {self.device}, got {scans.dtype} {tuple(scans.shape)}")
@@ -466,6 +478,8 @@ class BevRasteriser:
         image_status = torch.empty(n, dtype=torch.int32, device=self.device)
         if stages != _lib.JPEG_STAGES_ALL and n > self.JPEG_IMAGES_PER_CALL:
             raise _lib.SalveHipError(f"jpeg_decode: the stages can be called apart for at most {self.JPEG_IMAGES_PER_CALL} images (one workspace), got {n}")
+        if entropy == "lanes":
+            return self._jpeg_decode_lanes(scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, int(stages))
         table = torch.from_numpy(np.concatenate([off.view(np.uint8), nb.astype(np.int32).view(np.uint8)])).to(self.device)   # one upload
         for lo, m, ws, ws_bytes in self._jpeg_calls("decode", n, h, w):
             st = self.lib.salve_bev_jpeg_decode(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
@@ -473,6 +487,54 @@ class BevRasteriser:
                                                 huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
                                                 ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, int(stages), self._stream())
             _lib.check(st, "salve_bev_jpeg_decode")
+        return out, image_status
+
+    def _jpeg_decode_lanes(self, scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, stages):
+        """jpeg_decode(entropy="lanes") behind its argument checks: the segment table checked, rebased per library call, uploaded once."""
+        from salve_amd.jpeg import SCAN_PADDING
+
+        mcus = -(-h // 16) * -(-w // 16)
+        if segments is None:
+            seg = np.zeros(n, dtype=_lib.JPEG_SEGMENT_DTYPE)
+            seg["offset"], seg["bytes"], seg["image"], seg["mcu_count"] = off, nb, np.arange(n), mcus
+        else:
+            rows = np.asarray(segments)
+            if rows.dtype != _lib.JPEG_SEGMENT_DTYPE:
+                rows = np.asarray(segments, dtype=np.int64).reshape(-1, 5)
+                seg = np.zeros(rows.shape[0], dtype=_lib.JPEG_SEGMENT_DTYPE)
+                if rows.size and (np.abs(rows[:, 1:]).max() >= 2 ** 31):
+                    raise _lib.SalveHipError("jpeg_decode: a segment's bytes, image or MCUs do not fit 32 bits")
+                for k, name in enumerate(_lib.JPEG_SEGMENT_DTYPE.names):
+                    seg[name] = rows[:, k]
+            else:
+                seg = np.ascontiguousarray(rows).reshape(-1)
+        if not n <= seg.shape[0] <= _lib.JPEG_MAX_SEGMENTS:
+            raise _lib.SalveHipError(f"jpeg_decode: {seg.shape[0]} segments for {n} images: every image has at least one, a call at most {_lib.JPEG_MAX_SEGMENTS}")
+        if seg.shape[0]:
+            image = seg["image"].astype(np.int64)
+            if int(image.min()) < 0 or int(image.max()) >= n:
+                raise _lib.SalveHipError(f"jpeg_decode: a segment names an image outside [0, {n})")
+            first, count = seg["first_mcu"].astype(np.int64), seg["mcu_count"].astype(np.int64)
+            if int(first.min()) < 0 or int(count.min()) < 1 or int((first + count).max()) > mcus:
+                raise _lib.SalveHipError(f"jpeg_decode: a segment's MCU range lies outside its image's {mcus} MCUs")
+            if int(seg["offset"].min()) < 0 or int(seg["bytes"].min()) < 0 or int((seg["offset"] + seg["bytes"].astype(np.int64)).max()) + SCAN_PADDING > scans.numel():
+                raise _lib.SalveHipError(f"jpeg_decode: every segment must lie inside the {scans.numel()} bytes given, with {SCAN_PADDING} bytes of padding behind the last")
+            starts = np.flatnonzero(np.r_[True, image[1:] != image[:-1]])            # the first row of each image's run
+            expect = np.cumsum(count) - count - np.repeat((np.cumsum(count) - count)[starts], np.diff(np.r_[starts, seg.shape[0]]))
+            ends = np.r_[starts[1:], seg.shape[0]] - 1
+            tiled = (np.diff(image) >= 0).all() and starts.shape[0] == n and np.array_equal(first, expect) and np.array_equal((first + count)[ends], np.full(n, mcus))
+            if not tiled:
+                raise _lib.SalveHipError("jpeg_decode: the segments must be sorted by image, and each image's segments must tile its MCUs in order")
+        bounds = np.searchsorted(seg["image"], np.arange(0, n + self.JPEG_IMAGES_PER_CALL, self.JPEG_IMAGES_PER_CALL)) if n else np.zeros(1, dtype=np.int64)
+        seg = seg.copy()
+        seg["image"] %= self.JPEG_IMAGES_PER_CALL          # rebased to its library call's first image
+        table = torch.from_numpy(seg.view(np.uint8)).to(self.device) if seg.shape[0] else None   # one upload
+        for k, (lo, m, ws, ws_bytes) in enumerate(self._jpeg_calls("decode", n, h, w)):
+            s0, s1 = int(bounds[k]), int(bounds[k + 1])
+            st = self.lib.salve_bev_jpeg_decode_lanes(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + _lib.JPEG_SEGMENT_DTYPE.itemsize * s0),
+                                                      s1 - s0, m, h, w, qtab.ctypes.data_as(ctypes.c_void_p), huffman.ctypes.data_as(ctypes.c_void_p),
+                                                      ctypes.c_void_p(out[lo:].data_ptr()), ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, stages, self._stream())
+            _lib.check(st, "salve_bev_jpeg_decode_lanes")
         return out, image_status
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:

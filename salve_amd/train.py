@@ -3,6 +3,7 @@
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}] [--decode {host,device}]
+                              [--decode-entropy {image,lanes}]
                               [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]] [--jpeg-quality Q]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
@@ -15,7 +16,8 @@ classifier head (average pool, fc, softmax, cross-entropy, accuracy counts): los
 read once per pass, so the host never waits for the device between batches; the default is torch's head.  See salve_amd/training.py.
 --decode device (the rendered dataset on disk; not with --render-from) reads each batch's JPEG tiles with a thread pool, decodes them on
 the GPU in one call and makes the batch with one tile launch (salve_amd/train_files.py); the default, host, decodes every tile with
-Pillow in the DataLoader.  The batches are the same bits.
+Pillow in the DataLoader.  The batches are the same bits.  --decode-entropy lanes (with --decode device) takes the lane-parallel
+entropy stage, which also decodes tiles written with restart intervals on the GPU; the same bits again.
 --render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
 val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
 A configuration whose modalities include "layout" also needs DIR/layouts.npz: the layouts are posed and drawn on the GPU.
@@ -58,6 +60,8 @@ def main(argv=None) -> None:
                     help="torch (default: avgpool, fc, softmax, cross_entropy) or hip (one fused HIP forward and backward; loss and accuracy stay on the device)")
     ap.add_argument("--decode", choices=("host", "device"), default="host",
                     help="host (default: Pillow decodes each tile in the DataLoader) or device (whole batches of JPEG tiles decoded on the GPU)")
+    ap.add_argument("--decode-entropy", choices=("image", "lanes"), default="image",
+                    help="--decode device: image (default: one wavefront per tile) or lanes (a lane per 128 bytes of scan; also takes tiles with restart intervals)")
     ap.add_argument("--render-from", default=None, metavar="DIR",
                     help="render the training batches on the GPU from DIR/panos_rgb.npy, panos_depth.npy, train.json, val.json")
     ap.add_argument("--identity", choices=("kept", "batch"), default=None,
@@ -70,6 +74,8 @@ def main(argv=None) -> None:
                     help="--render-from: JPEG round trip of every rendered image on the GPU at quality Q (the reference writes its tiles at 75)")
     a = ap.parse_args(argv)
     training._check_head(a.head)
+    if a.decode_entropy != "image" and a.decode != "device":
+        raise SystemExit("--decode-entropy selects the entropy stage of --decode device")
     if a.decode == "device" and a.render_from is not None:
         raise SystemExit("--decode device reads the rendered dataset on disk: it cannot be combined with --render-from DIR (which reads no tile file)")
     if a.jpeg_quality is not None:
@@ -126,7 +132,7 @@ def main(argv=None) -> None:
                                           norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality)
     else:
         results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
-                                 head=a.head, decode=a.decode)
+                                 head=a.head, decode=a.decode, entropy=a.decode_entropy)
     logging.info(f"results in {out}: {results}")
 
 

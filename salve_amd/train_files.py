@@ -14,8 +14,10 @@ The grouping and ordering of the examples stay `ZindData`'s: both classes are bu
   TileFileLoader   the evaluation DataLoader's tuples `(x1, x2[, x3, x4[, x5, x6]], is_match, fp0, fp1)`: float32 NCHW tiles from
                    one salve_bev_tiles launch per batch, for `evaluate.run_test_epoch`.
 
-A file the device does not decode (`parse_file` raises Unsupported: progressive, restart markers, other subsamplings, greyscale ...)
-is decoded by Pillow and uploaded into its image slot with the same copy.  Every tile of a data set has one size (the first file's);
+`entropy="lanes"` (both classes) takes the lane-parallel entropy stage (salve_bev_jpeg_decode_lanes): the same
+batches bit for bit, and files with restart intervals stay on the device.
+A file the device does not decode (`parse_file` raises Unsupported: progressive, restart markers unless entropy="lanes", other
+subsamplings, greyscale ...) is decoded by Pillow and uploaded into its image slot with the same copy.  Every tile of a data set has one size (the first file's);
 a file of another size raises, naming it.  The decoder's per-image status is read ONCE per epoch, after the last batch; a non-zero
 entry raises, naming the file.  `close()` (or a `with` block) ends the reader threads; `training.train` and `evaluate_model` call it.
 """
@@ -38,15 +40,20 @@ from salve_amd.utils import image_io
 
 MAX_READ_THREADS = 16
 SPLITS = ("train", "val", "test")
+ENTROPY_STAGES = ("image", "lanes")   # BevRasteriser.jpeg_decode(entropy=)
 
 
-def _read_and_parse(path: str):
+def _read_and_parse(path: str, restart: bool = False):
     with open(path, "rb") as f:
         data = f.read()
     try:
-        return data, jpeg.parse_file(data)
+        return data, jpeg.parse_file(data, restart=restart)
     except jpeg.Unsupported:
         return data, None
+
+
+def _read_and_parse_restart(path: str):
+    return _read_and_parse(path, restart=True)
 
 
 @dataclass
@@ -56,7 +63,7 @@ class _Batch:
     position: np.ndarray                      # image slot of each path
     offsets: np.ndarray                       # [:decoded]: each decoded image's scan in the buffer
     lengths: np.ndarray
-    groups: list = field(default_factory=list)   # (images, qtab, huffman) per decode call, in slot order
+    groups: list = field(default_factory=list)   # (images, qtab, huffman, segment rows or None) per decode call, in slot order
     names: list = field(default_factory=list)    # path by image slot
     decoded: int = 0                          # images the device decodes; the host route's follow them
     host_route: int = 0
@@ -68,9 +75,13 @@ class _Batch:
 class _TileFiles:
     """What the two batch sources share: the files of a batch -> int32 [n, H, W] images on the device."""
 
-    def __init__(self, device, data_list: Sequence[tuple], resize_hw: Tuple[int, int], crop_hw: Tuple[int, int], read_threads: int) -> None:
+    def __init__(self, device, data_list: Sequence[tuple], resize_hw: Tuple[int, int], crop_hw: Tuple[int, int], read_threads: int,
+                 entropy: str = "image") -> None:
         if not 1 <= int(read_threads) <= MAX_READ_THREADS:
             raise ValueError(f"read_threads must be 1 .. {MAX_READ_THREADS}, got {read_threads}")
+        if entropy not in ENTROPY_STAGES:
+            raise ValueError(f"entropy must be one of {ENTROPY_STAGES}, got {entropy!r}")
+        self.entropy = entropy                          # "lanes": salve_bev_jpeg_decode_lanes, which also takes files with restart intervals
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise _lib.SalveHipError("decode=\"device\" needs a HIP device ('cuda:N'); there is no CPU path")
@@ -108,9 +119,10 @@ class _TileFiles:
         """[(file bytes, ParsedFile or None)] of the batch's files, by the thread pool."""
         if self._pool is None:
             self._pool = concurrent.futures.ThreadPoolExecutor(max_workers=self.read_threads, thread_name_prefix="salve-tile-files")
-        return list(self._pool.map(self._read_one, paths))
+        return list(self._pool.map(self._read_one if self.entropy == "image" else self._read_one_restart, paths))
 
     _read_one = staticmethod(_read_and_parse)
+    _read_one_restart = staticmethod(_read_and_parse_restart)
 
     def _pack(self, paths: List[str], read: list) -> "_Batch":
         """Groups the files by `header_key` and fills the pinned buffer: the groups' scans one behind the other, the padding, then
@@ -134,7 +146,14 @@ class _TileFiles:
         at = k = 0
         order: List[int] = []
         for members in groups.values():
-            b.groups.append((len(members), read[members[0]][1].qtab, read[members[0]][1].huffman))
+            rows = None
+            if self.entropy == "lanes":   # the restart intervals (one per file without markers), where `at` will put them
+                rows, to = [], at
+                for j, i in enumerate(members):
+                    parsed = read[i][1]
+                    rows += [(to + off - parsed.scan_offset, nbytes, j, first, count) for off, nbytes, first, count in parsed.segments]
+                    to += parsed.scan_bytes
+            b.groups.append((len(members), read[members[0]][1].qtab, read[members[0]][1].huffman, rows))
             for i in members:
                 b.position[i], b.offsets[k], b.lengths[k] = k, at, read[i][1].scan_bytes
                 at += read[i][1].scan_bytes
@@ -186,9 +205,10 @@ class _TileFiles:
         image_status = torch.zeros(b.n, dtype=torch.int32, device=self.device)
         with tracing.range("salve.jpeg_decode"):
             lo = 0
-            for m, qtab, huffman in b.groups:
+            for m, qtab, huffman, rows in b.groups:
+                kw = {} if self.entropy == "image" else dict(entropy=self.entropy, segments=rows)
                 image_status[lo:lo + m] = self._decode_group(dev[:b.scans_end], b.offsets[lo:lo + m], b.lengths[lo:lo + m], H, W, qtab, huffman,
-                                                             out=images[lo:lo + m])
+                                                             out=images[lo:lo + m], **kw)
                 lo += m
         if b.host_route:
             images[b.decoded:] = dev[b.pixels_at:].view(torch.int32).view(b.host_route, H, W)
@@ -223,14 +243,15 @@ class TileFileSource(_TileFiles):
     data_list: `ZindData(...).data_list`."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int = 256, precision: str = "fp32", split: str = "train", seed: int = 0,
-                 resize_hw: Tuple[int, int] = (234, 234), crop_hw: Tuple[int, int] = (224, 224), read_threads: int = MAX_READ_THREADS) -> None:
+                 resize_hw: Tuple[int, int] = (234, 234), crop_hw: Tuple[int, int] = (224, 224), read_threads: int = MAX_READ_THREADS,
+                 entropy: str = "image") -> None:
         if split not in SPLITS:
             raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
         if precision not in ("fp32", "bf16"):
             raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
         if int(batch_size) <= 0:
             raise ValueError(f"batch size must be positive, got {batch_size}")
-        super().__init__(device, data_list, resize_hw, crop_hw, read_threads)
+        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy)
         self.split, self.batch_size = split, int(batch_size)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
         self.per_sample = self.images_per_example // 2            # image PAIRS per example
@@ -291,10 +312,10 @@ class TileFileLoader(_TileFiles):
     nothing dropped.  data_list: `ZindData(...).data_list`, or a slice of it (a rank's block of whole batches)."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int, resize_hw: Tuple[int, int], crop_hw: Tuple[int, int],
-                 read_threads: int = MAX_READ_THREADS) -> None:
+                 read_threads: int = MAX_READ_THREADS, entropy: str = "image") -> None:
         if int(batch_size) <= 0:
             raise ValueError(f"batch size must be positive, got {batch_size}")
-        super().__init__(device, data_list, resize_hw, crop_hw, read_threads)
+        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy)
         self.batch_size = int(batch_size)
 
     def __len__(self) -> int:

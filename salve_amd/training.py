@@ -144,16 +144,16 @@ def _check_decode(decode: str) -> None:
         raise ValueError(f"decode must be one of {DECODES}, got {decode!r}")
 
 
-def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32"):
+def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32", entropy: str = "image"):
     """`get_dataloader`'s examples in its order as a train_files.TileFileSource: whole batches of the data set's JPEG tiles decoded
-    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's."""
+    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy: TileFileSource's."""
     from salve_amd.dataset.zind_data import ZindData
     from salve_amd.train_files import TileFileSource
 
     get_train_transform(args)   # (the refusals of the host path: photometric augmentation, crop-with-padding)
     data = ZindData(split=split, transform=None, args=args)
     return TileFileSource(torch.device("cuda", torch.cuda.current_device()), data.data_list, batch_size=args.batch_size, precision=precision,
-                          split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w))
+                          split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w), entropy=entropy)
 
 
 def get_dataloader(args: TrainingConfig, split: str, seed: int = 0) -> torch.utils.data.DataLoader:
@@ -260,7 +260,7 @@ def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_l
 
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
-          norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host") -> Dict[str, list]:
+          norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image") -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
@@ -269,17 +269,22 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     checkpoint.  optim: "torch" (default) or "hip", HipAdam -- the checkpoint's "optimizer" entry keeps torch.optim.Adam's format.
     head: "torch" (default) or "hip", the fused HIP classifier head with loss and accuracy on the device -- same results JSON.
     decode: "host" (default: Pillow decodes every tile in the DataLoader) or "device": the same examples in the same order with the
-    same draws, whole batches of JPEG tiles decoded on the device (train_files.TileFileSource) -- the same batches, bit for bit."""
+    same draws, whole batches of JPEG tiles decoded on the device (train_files.TileFileSource) -- the same batches, bit for bit.
+    entropy (decode="device" only): "image" (default) or "lanes", the lane-parallel entropy stage, which also keeps files with restart
+    intervals on the device -- the same batches again."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
     _check_head(head)
     _check_decode(decode)
+    if entropy != "image" and decode != "device":
+        raise ValueError(f'entropy={entropy!r} selects the device decoder\'s entropy stage: it needs decode="device"')
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
     if decode == "device":
-        with get_tile_file_source(args, "train", seed, precision) as train_source, get_tile_file_source(args, "val", seed, precision) as val_source:
+        with get_tile_file_source(args, "train", seed, precision, entropy) as train_source, \
+                get_tile_file_source(args, "val", seed, precision, entropy) as val_source:
             return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)   # (leaving ends their reader threads)
     return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim, head)
 

@@ -15,6 +15,14 @@ were written moments before they are read: the reads come from the page cache, n
 
     python tools/measure/bench_tile_files.py [--examples 768] [--batch 256] [--host-batches 2] [--device-batches 6] [--keep DIR]
     python tools/measure/bench_tile_files.py --decode-only [--n 1024] [--reps 5]      # jpeg_decode alone on n tiles, by events
+    python tools/measure/bench_tile_files.py --decode-only --entropy both --n 1024,256,64   # ... both entropy stages
+    python tools/measure/bench_tile_files.py --panos 32 [--reps 5]                    # 2048 x 1024 panoramas: the entropy stages, Pillow, PanoStore.load
+
+--entropy image (default) is salve_bev_jpeg_decode's one wavefront per tile, lanes the lane-parallel stage (salve_bev_jpeg_decode_lanes);
+the feed benchmark takes one of them, --decode-only and --panos also `both` (the same data through one, then the other).
+--panos N writes N synthetic panoramas (synthetic.make_pano doubled to 2048 x 1024, the ingest tests' files) and times, on the same
+files: the two entropy stages alone by events; Pillow decoding the files in the host route's loop by the host clock; and
+ingest.PanoStore.load end to end, decode="host" against decode="device", by the host clock around a call that ends in a synchronise.
 
 --decode-only times the whole call and, in the same run, its two stages apart.  (The inverse stage's two launches, jpeg_idct_kernel and
 jpeg_pixels_kernel, can be told apart by `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_tile_files.py --decode-only
@@ -83,11 +91,13 @@ class TimedSource(TileFileSource):
             data = f.read()
         t1 = time.perf_counter()
         try:
-            parsed = jpeg.parse_file(data)
+            parsed = jpeg.parse_file(data, restart=self.entropy == "lanes")
         except jpeg.Unsupported:
             parsed = None
         self._per_file.append((t1 - t0, time.perf_counter() - t1))
         return data, parsed
+
+    _read_one_restart = _read_one
 
     def _read(self, paths):
         self._per_file = []
@@ -171,7 +181,7 @@ def bench_feed(a) -> None:
         data = ZindData(split="train", transform=None, args=args)
         plan = [np.arange(lo, lo + a.batch) % len(data.data_list) for lo in range(0, a.batch * (a.device_batches + 1), a.batch)]
         for cls in (TileFileSource, TimedSource):
-            with cls(DEV, data.data_list, batch_size=a.batch, split="train", seed=0) as src:
+            with cls(DEV, data.data_list, batch_size=a.batch, split="train", seed=0, entropy=a.entropy) as src:
                 random.seed(0)
                 src.batch(plan[0], src.draws(a.batch))   # warm-up: the pinned buffer, the workspace, code objects
                 torch.cuda.synchronize()
@@ -186,7 +196,7 @@ def bench_feed(a) -> None:
                 src._check_epoch("bench_tile_files")
                 if cls is TileFileSource:
                     dev_ms = ms
-                    print(f"TileFileSource (device decode, one tile launch)      {_stat(dev_ms)}")
+                    print(f"TileFileSource (device decode, entropy={a.entropy}, one tile launch)      {_stat(dev_ms)}")
                     print(f"speed-up of the batch: {statistics.median(host_ms) / statistics.median(dev_ms):.1f} x;  files decoded by Pillow in the device route: {src.fallbacks}")
                 else:
                     print(f"its stages (TimedSource; the batch itself            {_stat(ms)}):")
@@ -196,7 +206,7 @@ def bench_feed(a) -> None:
         # ---- the same batch both ways: the feed must not change what the model sees
         random.seed(5)
         ref = next(iter(training.get_dataloader(args, "train", seed=0)))
-        src2 = TileFileSource(DEV, data.data_list, batch_size=a.batch, split="train", seed=0)
+        src2 = TileFileSource(DEV, data.data_list, batch_size=a.batch, split="train", seed=0, entropy=a.entropy)
         random.seed(5)
         x, y = next(iter(src2))
         src2.close()
@@ -207,12 +217,52 @@ def bench_feed(a) -> None:
             raise SystemExit(1)
 
 
+def _time_stages(ras, args, kw, reps):
+    """Medians by events of the whole jpeg_decode call and of its two stages called apart -> (whole, entropy, inverse) lists of ms."""
+    fn = lambda **more: ras.jpeg_decode(*args, **kw, **more)
+    for _ in range(2):
+        _, st = fn()
+    torch.cuda.synchronize()
+    assert not bool(st.any())
+    whole, ent, inv = [], [], []
+    for _ in range(reps):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        e.synchronize()
+        whole.append(s.elapsed_time(e))
+    for _ in range(reps):
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+        ev[0].record()
+        fn(stages=_lib.JPEG_STAGE_ENTROPY)
+        ev[1].record()
+        fn(stages=_lib.JPEG_STAGE_INVERSE)
+        ev[2].record()
+        ev[2].synchronize()
+        ent.append(ev[0].elapsed_time(ev[1]))
+        inv.append(ev[1].elapsed_time(ev[2]))
+    return whole, ent, inv
+
+
+def _entropies(a):
+    return ("image", "lanes") if a.entropy == "both" else (a.entropy,)
+
+
+def _report(tag, whole, ent, inv, n):
+    med = statistics.median
+    print(f"{tag}, entropy + inverse: {med(whole):.2f} ms ({min(whole):.2f} .. {max(whole):.2f}); {med(whole) * 1e3 / n:.1f} us per image")
+    print(f"    {'entropy stage':<34} {med(ent):.3f} ms ({min(ent):.3f} .. {max(ent):.3f})")
+    print(f"    {'inverse kernels (idct + pixels)':<34} {med(inv):.3f} ms ({min(inv):.3f} .. {max(inv):.3f})")
+
+
 def bench_decode(a) -> None:
     import io
 
     from PIL import Image
 
     ras = BevRasteriser(DEV)
+    print(f"subsequence: {ras.lib.salve_bev_jpeg_subseq_bytes()} bytes")
     files = []
     for i in range(16):
         buf = io.BytesIO()
@@ -220,41 +270,83 @@ def bench_decode(a) -> None:
         files.append(buf.getvalue())
     parsed = [jpeg.parse_file(f) for f in files]
     scans = [f[p.scan_offset:p.scan_offset + p.scan_bytes] for f, p in zip(files, parsed)]
-    pick = [i % 16 for i in range(a.n)]
-    off = np.cumsum([0] + [len(scans[i]) for i in pick])
-    blob = b"".join(scans[i] for i in pick) + bytes(jpeg.SCAN_PADDING)
-    dev = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(DEV)
-    nb = np.array([len(scans[i]) for i in pick])
-    out = torch.empty((a.n, H, W), dtype=torch.int32, device=DEV)
     p = parsed[0]
-    fn = lambda: ras.jpeg_decode(dev, off[:-1], nb, H, W, p.qtab, p.huffman, out=out)
-    for _ in range(2):
-        fn()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(a.reps):
-        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        s.record()
-        _, st = fn()
-        e.record()
-        e.synchronize()
-        ms.append(s.elapsed_time(e))
-    assert not bool(st.any())
-    parts = {}
-    for _ in range(a.reps):
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-        ev[0].record()
-        ras.jpeg_decode(dev, off[:-1], nb, H, W, p.qtab, p.huffman, out=out, stages=_lib.JPEG_STAGE_ENTROPY)
-        ev[1].record()
-        ras.jpeg_decode(dev, off[:-1], nb, H, W, p.qtab, p.huffman, out=out, stages=_lib.JPEG_STAGE_INVERSE)
-        ev[2].record()
-        ev[2].synchronize()
-        parts.setdefault("entropy kernel", []).append(ev[0].elapsed_time(ev[1]))
-        parts.setdefault("inverse kernels (idct + pixels)", []).append(ev[1].elapsed_time(ev[2]))
-    print(f"jpeg_decode of {a.n} tiles of 501 x 501 ({len(blob) / a.n / 1024:.1f} KB of scan each), entropy + inverse: "
-          f"{statistics.median(ms):.2f} ms ({min(ms):.2f} .. {max(ms):.2f}); {statistics.median(ms) * 1e3 / a.n:.1f} us per tile")
-    for tag, vals in parts.items():
-        print(f"    {tag:<34} {statistics.median(vals):.2f} ms ({min(vals):.2f} .. {max(vals):.2f})")
+    for n in a.n:
+        pick = [i % 16 for i in range(n)]
+        off = np.cumsum([0] + [len(scans[i]) for i in pick])
+        blob = b"".join(scans[i] for i in pick) + bytes(jpeg.SCAN_PADDING)
+        dev = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(DEV)
+        nb = np.array([len(scans[i]) for i in pick])
+        out = torch.empty((n, H, W), dtype=torch.int32, device=DEV)
+        results = {}
+        for entropy in _entropies(a):
+            kw = dict(out=out) if entropy == "image" else dict(out=out, entropy=entropy)
+            whole, ent, inv = _time_stages(ras, (dev, off[:-1], nb, H, W, p.qtab, p.huffman), kw, a.reps)
+            results[entropy] = out.clone()
+            _report(f"jpeg_decode(entropy={entropy!r}) of {n} tiles of 501 x 501 ({len(blob) / n / 1024:.1f} KB of scan each)", whole, ent, inv, n)
+        if len(results) == 2:
+            print(f"    the two routes' images: {'bit-identical' if torch.equal(results['image'], results['lanes']) else 'DIFFERENT'}")
+
+
+def bench_panos(a) -> None:
+    from PIL import Image
+
+    from salve_amd import ingest, synthetic
+    from salve_amd.utils import image_io
+
+    n = a.panos
+    with tempfile.TemporaryDirectory() as tmp:
+        root = Path(tmp)
+        (root / "zind" / "0003" / "panos").mkdir(parents=True)
+        fpaths = {}
+        for i in range(n):
+            rgb, depth = synthetic.make_pano(i)
+            fp = root / "zind" / "0003" / "panos" / f"floor_01_partial_room_{i:02d}_pano_{i}.jpg"
+            image_io.write_jpeg(str(fp), np.repeat(np.repeat(rgb, 2, axis=0), 2, axis=1))
+            image_io.write_depth_png(str(root / "depth" / "0003" / f"{fp.stem}.depth.png"), depth)
+            fpaths[i] = str(fp)
+        files = [Path(fpaths[i]).read_bytes() for i in range(n)]
+        parsed = [jpeg.parse_file(f) for f in files]
+        p = parsed[0]
+        assert len({q.header_key for q in parsed}) == 1 and (p.h, p.w) == (1024, 2048)
+        nb = np.array([q.scan_bytes for q in parsed])
+        off = np.cumsum(np.r_[0, nb])
+        blob = b"".join(f[q.scan_offset:q.scan_offset + q.scan_bytes] for f, q in zip(files, parsed)) + bytes(jpeg.SCAN_PADDING)
+        print(f"{n} panoramas of 2048 x 1024, {nb.mean() / 1024:.0f} KB of scan each ({nb.min() / 1024:.0f} .. {nb.max() / 1024:.0f}); subsequence: "
+              f"{_lib.load().salve_bev_jpeg_subseq_bytes()} bytes")
+        ras = BevRasteriser(DEV)
+        dev = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(DEV)
+        out = torch.empty((n, p.h, p.w), dtype=torch.int32, device=DEV)
+        results = {}
+        for entropy in _entropies(a):
+            kw = dict(out=out) if entropy == "image" else dict(out=out, entropy=entropy)
+            whole, ent, inv = _time_stages(ras, (dev, off[:-1], nb, p.h, p.w, p.qtab, p.huffman), kw, a.reps)
+            results[entropy] = out.clone()
+            _report(f"jpeg_decode(entropy={entropy!r}) of the {n} panoramas", whole, ent, inv, n)
+        if len(results) == 2:
+            print(f"    the two routes' images: {'bit-identical' if torch.equal(results['image'], results['lanes']) else 'DIFFERENT'}")
+        del out, results
+        ms = []
+        for _ in range(max(2, a.reps // 2)):
+            t = time.perf_counter()
+            for i in range(n):
+                image_io.read_rgb(fpaths[i])
+            ms.append((time.perf_counter() - t) * 1e3)
+        print(f"Pillow decoding the {n} files, one after the other (host clock): {statistics.median(ms):.1f} ms ({min(ms):.1f} .. {max(ms):.1f}); "
+              f"{statistics.median(ms) / n:.1f} ms per panorama")
+        stores = {}
+        for decode in ("host", "device"):
+            ms = []
+            for r in range(a.reps + 1):   # (the first call warms up: code objects, the workspace)
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                stores[decode] = ingest.PanoStore(DEV).load(fpaths, str(root / "depth"), "0003", list(range(n)), decode=decode)
+                torch.cuda.synchronize()
+                if r:
+                    ms.append((time.perf_counter() - t) * 1e3)
+            print(f"PanoStore.load(decode={decode!r}) of the {n} panoramas, end to end (host clock): {statistics.median(ms):.1f} ms ({min(ms):.1f} .. {max(ms):.1f})")
+        same = torch.equal(stores["host"].rgb, stores["device"].rgb) and torch.equal(stores["host"].depth, stores["device"].depth)
+        print(f"    the two stores: {'bit-identical' if same else 'DIFFERENT'}; files Pillow decoded in the device route: {stores['device'].host_decoded}")
 
 
 if __name__ == "__main__":
@@ -265,9 +357,13 @@ if __name__ == "__main__":
     ap.add_argument("--device-batches", type=int, default=6)
     ap.add_argument("--keep", default=None, help="write the data set here and keep it (reused if it exists)")
     ap.add_argument("--decode-only", action="store_true")
-    ap.add_argument("--n", type=int, default=1024)
+    ap.add_argument("--n", type=lambda v: [int(x) for x in v.split(",")], default=[1024], help="--decode-only: tiles per call; several sizes separated by commas")
+    ap.add_argument("--entropy", choices=("image", "lanes", "both"), default="image")
+    ap.add_argument("--panos", type=int, default=0, help="time this many 2048 x 1024 panoramas instead of tiles")
     ap.add_argument("--reps", type=int, default=5)
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_tile_files needs the MI355X: there is nothing to time without it")
-    bench_decode(a) if a.decode_only else bench_feed(a)
+    if a.entropy == "both" and not (a.decode_only or a.panos):
+        raise SystemExit("--entropy both compares the two stages on the same data: with --decode-only or --panos")
+    bench_panos(a) if a.panos else bench_decode(a) if a.decode_only else bench_feed(a)
