@@ -48,7 +48,8 @@ typedef enum {
                                         (with salve_bev_jpeg_encode_workspace_bytes / _max_bytes), salve_bev_jpeg_decode (with
                                         salve_bev_jpeg_decode_workspace_bytes and the SALVE_JPEG_* bits of its per-image status),
                                         salve_bev_jpeg_decode_lanes (with salve_bev_jpeg_decode_lanes_workspace_bytes, salve_bev_jpeg_subseq_bytes
-                                        and salve_jpeg_segment_t) */
+                                        and salve_jpeg_segment_t), salve_bev_jpeg_decode_sampled / _lanes_sampled (with their two
+                                        _workspace_bytes queries and SALVE_JPEG_SAMPLING_*) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -857,6 +858,47 @@ int32_t salve_bev_jpeg_subseq_bytes(void);
 int salve_bev_jpeg_decode_lanes(const uint8_t* scans, size_t scans_size, const salve_jpeg_segment_t* segments, int32_t n_segments, int32_t n,
                                 int32_t h, int32_t w, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out, int32_t* image_status,
                                 void* ws, size_t ws_bytes, uint32_t stages, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * salve_bev_jpeg_decode and salve_bev_jpeg_decode_lanes for 4:2:2, 4:4:4 and greyscale files as well (additive within ABI 7): opt-in.
+ * The tile data set is always 4:2:0; panoramas come from cameras (4:2:2), editors (4:4:4) and scanners (one component).  The two
+ * entries below are the two above with ONE more argument, `sampling`, behind w; with SALVE_JPEG_SAMPLING_420 they ARE the two above
+ * (the same launches, the same bits).  Everything not named here is as documented there.
+ *   sampling     the frame's sampling factors, and with them the MCU -- its blocks in scan order and its size in pixels:
+ *                  SALVE_JPEG_SAMPLING_420   Y 2x2, Cb 1x1, Cr 1x1   Y0 Y1 Y2 Y3 Cb Cr (6 blocks)   16 x 16
+ *                  SALVE_JPEG_SAMPLING_422   Y 2x1, Cb 1x1, Cr 1x1   Y0 Y1 Cb Cr (4)                16 wide x 8 high
+ *                  SALVE_JPEG_SAMPLING_444   Y 1x1, Cb 1x1, Cr 1x1   Y Cb Cr (3)                      8 x 8
+ *                  SALVE_JPEG_SAMPLING_GREY  one component           Y (1): the scan is not interleaved, its blocks count
+ *                                                                    ceil(w / 8) x ceil(h / 8) in raster order                8 x 8
+ *                An image's MCUs -- what a segment's first_mcu / mcu_count count, and a restart interval -- are
+ *                ceil(w / MCU width) * ceil(h / MCU height).  A DC predictor per component, restarted per segment.
+ *   qtab, huffman as above: [luma, chroma] and [DC luma, AC luma, DC chroma, AC chroma]; a greyscale call reads the luma ones only,
+ *                but all of them are checked: the caller repeats the luma tables in the chroma slots (salve_amd/jpeg.py: parse_file).
+ *   Pixels:      entropy decoding, dequantisation and the inverse DCT are the same; 4:2:2 chroma is upsampled as libjpeg's
+ *                h2v1_fancy_upsample does (along the row only: (3 near + far + 1) >> 2 to the left, + 2 to the right, the two end
+ *                pixels copied; a row of at most two chroma samples is replicated), 4:4:4 has none; the colour conversion is the
+ *                same; greyscale leaves Y | Y << 8 | Y << 16.  Bit for bit Pillow's pixels (mode L repeated into three channels).
+ *                The caller decides that a three-component file IS YCbCr (libjpeg reads some 1x1 1x1 1x1 files as RGB:
+ *                salve_amd/jpeg.py has the rule).
+ *   Workspace:   per image, the component planes back to back, each rounded up to whole MCUs -- 1.5 / 2 / 3 / 1 bytes per
+ *                MCU-rounded pixel for 4:2:0 / 4:2:2 / 4:4:4 / greyscale -- then 128 bytes of coefficients per block
+ *                (6 / 4 / 3 / 1 blocks per MCU); the `_workspace_bytes` queries say how much.
+ *   Checks:      those of the entries above, and SALVE_ERR_BAD_ARG (0 from the size queries) for a `sampling` that is none of the
+ *                four.  The bounds hold for every sampling: no byte read at or behind a scan's or segment's end, no coefficient
+ *                written outside the image's MCUs * blocks * 64.
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_JPEG_SAMPLING_420 0
+#define SALVE_JPEG_SAMPLING_422 1
+#define SALVE_JPEG_SAMPLING_444 2
+#define SALVE_JPEG_SAMPLING_GREY 3
+size_t salve_bev_jpeg_decode_sampled_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t sampling);
+size_t salve_bev_jpeg_decode_lanes_sampled_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t n_segments, int32_t sampling);
+int salve_bev_jpeg_decode_sampled(const uint8_t* scans, size_t scans_size, const int64_t* scan_offset, const int32_t* scan_bytes, int32_t n,
+                                  int32_t h, int32_t w, int32_t sampling, const uint16_t* qtab, const uint8_t* huffman, uint32_t* bev_out,
+                                  int32_t* image_status, void* ws, size_t ws_bytes, uint32_t stages, void* stream);
+int salve_bev_jpeg_decode_lanes_sampled(const uint8_t* scans, size_t scans_size, const salve_jpeg_segment_t* segments, int32_t n_segments,
+                                        int32_t n, int32_t h, int32_t w, int32_t sampling, const uint16_t* qtab, const uint8_t* huffman,
+                                        uint32_t* bev_out, int32_t* image_status, void* ws, size_t ws_bytes, uint32_t stages, void* stream);
 
 #ifdef __cplusplus
 }

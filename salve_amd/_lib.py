@@ -86,12 +86,17 @@ EXPORTED_SYMBOLS = (
     "salve_bev_jpeg_decode_lanes_workspace_bytes",
     "salve_bev_jpeg_subseq_bytes",
     "salve_bev_jpeg_decode_lanes",
+    "salve_bev_jpeg_decode_sampled_workspace_bytes",
+    "salve_bev_jpeg_decode_lanes_sampled_workspace_bytes",
+    "salve_bev_jpeg_decode_sampled",
+    "salve_bev_jpeg_decode_lanes_sampled",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
 RESNET_NO_PROJ_FUSE, RESNET_NO_CHAIN, RESNET_CHAIN_EXPAND_ONLY, RESNET_CHAIN_16_WAVES, RESNET_CHAIN_NO_SPLIT = 32, 64, 128, 256, 512
 RESNET_CHAIN_STORE_ALL, RESNET_NO_TRANSPOSED_TILES, RESNET_NO_NEXT_FUSE = 1024, 2048, 4096
 JPEG_STAGE_ENTROPY, JPEG_STAGE_INVERSE, JPEG_STAGES_ALL = 1, 2, 3   # salve_bev_jpeg_decode's `stages`
+JPEG_SAMPLINGS = {"4:2:0": 0, "4:2:2": 1, "4:4:4": 2, "grey": 3}     # include/salve_hip.h: SALVE_JPEG_SAMPLING_* by salve_amd.jpeg's names
 STATUS_WALK_FAILED = 1
 STATUS_FP16_RANGE = 2
 STATUS_BAD_HYPOTHESIS = 4
@@ -306,6 +311,15 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_jpeg_subseq_bytes.restype = i32
     lib.salve_bev_jpeg_decode_lanes.argtypes = [vp, sz, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
     lib.salve_bev_jpeg_decode_lanes.restype = ctypes.c_int
+    # the same four with `sampling`: last in the size queries, behind w in the calls
+    lib.salve_bev_jpeg_decode_sampled_workspace_bytes.argtypes = [i32, i32, i32, i32]
+    lib.salve_bev_jpeg_decode_sampled_workspace_bytes.restype = sz
+    lib.salve_bev_jpeg_decode_lanes_sampled_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
+    lib.salve_bev_jpeg_decode_lanes_sampled_workspace_bytes.restype = sz
+    lib.salve_bev_jpeg_decode_sampled.argtypes = [vp, sz, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
+    lib.salve_bev_jpeg_decode_sampled.restype = ctypes.c_int
+    lib.salve_bev_jpeg_decode_lanes_sampled.argtypes = [vp, sz, vp, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, ctypes.c_uint32, vp]
+    lib.salve_bev_jpeg_decode_lanes_sampled.restype = ctypes.c_int
     # The bindings above are written for ONE ABI: an older or newer library (a stale git-ignored .so, a SALVE_HIP_LIB override
     # built from another revision) would be called with shifted arguments -- device memory corruption instead of an error.
     got = int(lib.salve_hip_version())

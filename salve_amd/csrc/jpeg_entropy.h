@@ -4,7 +4,8 @@
 // it may make the decoder read outside scan[0 .. nbytes), write outside its outputs, or loop without end.
 //
 // What it decodes: 8-bit, three components, 4:2:0, one interleaved scan without restart intervals, MCU = Y0 Y1 Y2 Y3 Cb Cr; the scan
-// as it stands in the file (stuffed, padded, no header, no EOI), at any byte alignment.
+// as it stands in the file (stuffed, padded, no header, no EOI), at any byte alignment.  The MCU's block pattern is a template
+// argument (JeSampling: 4:2:0 by default, 4:2:2 = Y0 Y1 Cb Cr, 4:4:4 = Y Cb Cr, greyscale = Y); nothing else depends on it.
 //   DC      the category's Huffman code, then that many value bits with the EXTEND rule; a predictor per component that runs across
 //           the whole scan
 //   AC      (run << 4 | size) symbols in zigzag order; 0xF0 (ZRL) skips 16 positions, 0x00 (EOB) ends the block
@@ -51,6 +52,25 @@
 #define JE_LOOK 9            // look-ahead bits: 4 tables x 512 entries x 2 bytes = 4 KB (a full 16-bit table per Huffman table does not fit)
 #define JE_STAGE 4096        // staged scan bytes (a multiple of 4)
 #define JE_TABLE_BYTES 272   // 16 BITS + 256 HUFFVAL per table; the four tables: DC luma, AC luma, DC chroma, AC chroma
+
+// The samplings (include/salve_hip.h: SALVE_JPEG_SAMPLING_*) and what the entropy stage needs of one: the blocks of an MCU and the
+// component of block slot k (0 Y, 1 Cb, 2 Cr).  A compile-time argument everywhere: no lane branches on it.
+#define JE_SAMPLING_420 0    // Y0 Y1 Y2 Y3 Cb Cr
+#define JE_SAMPLING_422 1    // Y0 Y1 Cb Cr
+#define JE_SAMPLING_444 2    // Y Cb Cr
+#define JE_SAMPLING_GREY 3   // Y (one component: the "MCU" of its non-interleaved scan is one block)
+#define JE_MAX_BLOCKS 6      // blocks of the largest MCU
+
+template <int S>
+struct JeSampling {
+    static_assert(S >= JE_SAMPLING_420 && S <= JE_SAMPLING_GREY, "a sampling of JE_SAMPLING_*");
+    static constexpr int blocks = S == JE_SAMPLING_420 ? 6 : S == JE_SAMPLING_422 ? 4 : S == JE_SAMPLING_444 ? 3 : 1;
+    static constexpr int luma = S == JE_SAMPLING_GREY ? 1 : blocks - 2;   // the luma blocks lead the MCU
+    static constexpr int coefs = blocks * 64;                              // coefficients of an MCU
+};
+
+template <int S>
+JE_FN int je_comp(int slot) { return slot < JeSampling<S>::luma ? 0 : slot - JeSampling<S>::luma + 1; }
 
 struct JeTables {            // Annex F.2.2.3's decoder tables, by table and code length 1 .. 16
     int32_t maxcode[4][17];  // the largest code of that length, -1: none
@@ -219,7 +239,9 @@ JE_FN int32_t je_value(JeReader& r, int32_t s) {
     return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v;
 }
 
-// All lanes: the scan of one image -> coef [mcus][6][64] int16 in natural order; returns the status word (the same in every lane).
+// All lanes: the scan of one image -> coef [mcus][blocks of an MCU][64] int16 in natural order ([mcus][6][64] for the default, 4:2:0);
+// returns the status word (the same in every lane).
+template <int S = JE_SAMPLING_420>
 JE_FN uint32_t je_decode_image(JeShared& sh, const uint8_t* scan, int32_t nbytes, int32_t mcus, int16_t* coef, int lane, int nlanes) {
     JeReader r;
     r.src = scan;
@@ -232,8 +254,8 @@ JE_FN uint32_t je_decode_image(JeShared& sh, const uint8_t* scan, int32_t nbytes
     int32_t pred[3] = {0, 0, 0};
     bool dead = false;
     for (int32_t m = 0; m < mcus; m++) {
-        for (int b = 0; b < 6; b++) {
-            const int comp = b < 4 ? 0 : b - 3, t = comp ? 2 : 0;
+        for (int b = 0; b < JeSampling<S>::blocks; b++) {
+            const int comp = je_comp<S>(b), t = comp ? 2 : 0;
             if (!dead) {   // DC
                 je_fill(sh, r);
                 const int32_t s = r.status ? -2 : je_symbol(sh, r, t);
@@ -297,7 +319,7 @@ JE_FN uint32_t je_decode_image(JeShared& sh, const uint8_t* scan, int32_t nbytes
                 k++;
             }
             JE_SYNC();
-            int16_t* out = coef + ((int64_t)m * 6 + b) * 64;
+            int16_t* out = coef + ((int64_t)m * JeSampling<S>::blocks + b) * 64;
             for (int j = lane; j < 64; j += nlanes) {   // the block leaves as 128 contiguous bytes, and is zero again
                 out[j] = sh.blk[j];
                 sh.blk[j] = 0;

@@ -8,6 +8,8 @@
 //
 // Units: a SEGMENT is a whole scan or one restart interval of it (the marker excluded); it starts with the DC predictors at 0 and holds
 //   `mcus` MCUs = 6 * mcus blocks.  It is walked in CHUNKS of JL_LANES subsequences of JE_SUBSEQ bytes.
+//   (6 blocks, slots 0..5, coef [mcus][6][64] and mcus * 384 are 4:2:0's, the default of the template argument S; with another of
+//   jpeg_entropy.h's JeSampling they read 4 / 3 / 1 blocks, and the slot runs 0 .. blocks - 1.)
 // State at a symbol boundary: (bit position in the STUFFED stream, block slot 0..5 of the MCU, zigzag index 0..63, 0: a DC code is next).
 //   A boundary behind a 0xFF byte points behind its stuffed 0x00.
 // Per chunk:
@@ -199,7 +201,7 @@ JE_FN int32_t jl_value(JlReader& r, int32_t s) {   // je_value
 // blocks: + the blocks completed.  WRITE (pass C): coef is the segment's [mcus][6][64], gb the index of the block the lane starts in,
 // total = 6 * mcus; the lane stops in front of block `total`, and the one that completes block total - 1 judges what is left
 // (JE_LEFTOVER) and sets *done.
-template <bool WRITE>
+template <bool WRITE, int S = JE_SAMPLING_420>
 JE_FN uint32_t jl_run(const JlShared& sh, JlReader& r, int32_t endbit, uint32_t& sk, int32_t& blocks, int16_t* coef, int32_t gb, int32_t total, int32_t* done) {
     int32_t slot = (int32_t)(sk >> 8) & 7, k = (int32_t)(sk & 63u);
     uint32_t err = 0;
@@ -207,7 +209,7 @@ JE_FN uint32_t jl_run(const JlShared& sh, JlReader& r, int32_t endbit, uint32_t&
         jl_fill(r);
         if (jl_bitpos(r) >= endbit) break;
         if (WRITE && gb >= total) break;
-        const int t = slot < 4 ? 0 : 2;
+        const int t = je_comp<S>(slot) ? 2 : 0;
         bool complete = false;
         if (k == 0) {   // DC: the difference stays
             const int32_t s = jl_symbol(sh, r, t);
@@ -249,7 +251,7 @@ JE_FN uint32_t jl_run(const JlShared& sh, JlReader& r, int32_t endbit, uint32_t&
         if (r.cnt < r.fake) err |= JE_TRUNCATED;   // the symbol took bits from beyond the segment: the position is now behind every end
         if (complete) {
             k = 0;
-            slot = slot == 5 ? 0 : slot + 1;
+            slot = slot >= JeSampling<S>::blocks - 1 ? 0 : slot + 1;
             blocks++;
             gb++;
             if (WRITE && gb == total) {   // what is left must be the padding: at most 7 bits, all 1
@@ -282,10 +284,12 @@ JE_FN int jl_prefix(JlShared& sh, int ncomp) {
 
 // All lanes of the workgroup: one segment -> coef [mcus][6][64] int16 in natural order, which the caller has ZEROED; returns the status
 // word (the same in every lane).  sh holds je_prepare_tables' tables.  rounds (host): + the rounds of pass B.
+template <int S = JE_SAMPLING_420>
 JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbytes, int32_t mcus, int16_t* coef, int32_t* rounds) {
     if (nbytes < 0) nbytes = 0;
     if (mcus < 0) mcus = 0;
-    const int32_t total = 6 * mcus;
+    constexpr int BLK = JeSampling<S>::blocks;
+    const int32_t total = BLK * mcus;
     JE_SYNC();
     JL_FOR_LANES(lane) {
         if (lane == 0) {
@@ -333,7 +337,7 @@ JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbyt
             int32_t blocks = 0;
             if (lane < active) {
                 jl_start(r, p, lane != 0);
-                jl_run<false>(sh, r, endbit, sk, blocks, nullptr, 0, 0, nullptr);
+                jl_run<false, S>(sh, r, endbit, sk, blocks, nullptr, 0, 0, nullptr);
                 sh.exit_pos[0][lane] = jl_bitpos(r);
             } else {
                 sh.exit_pos[0][lane] = p;
@@ -366,7 +370,7 @@ JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbyt
                         jl_start(r, pp, false);
                         uint32_t sk = ps;
                         int32_t blocks = 0;
-                        jl_run<false>(sh, r, endbit, sk, blocks, nullptr, 0, 0, nullptr);
+                        jl_run<false, S>(sh, r, endbit, sk, blocks, nullptr, 0, 0, nullptr);
                         xp = jl_bitpos(r);
                         ns = sk;
                         sh.count[lane] = blocks;
@@ -398,7 +402,7 @@ JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbyt
                 jl_start(r, sh.start_pos[lane], false);
                 uint32_t sk = sh.start_sk[lane];
                 int32_t blocks = 0;
-                const uint32_t err = jl_run<true>(sh, r, endbit, sk, blocks, coef, (int32_t)gb, total, &sh.done);
+                const uint32_t err = jl_run<true, S>(sh, r, endbit, sk, blocks, coef, (int32_t)gb, total, &sh.done);
                 if (err) {
                     sh.lane_err[lane] = err;
                     sh.any_err = 1;   // (several lanes may: the same value)
@@ -426,7 +430,7 @@ JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbyt
         const int32_t lo = lane * per < mcus ? lane * per : mcus, hi = lo + per < mcus ? lo + per : mcus;
         int32_t s[3] = {0, 0, 0};
         for (int32_t m = lo; m < hi; m++)
-            for (int b = 0; b < 6; b++) s[b < 4 ? 0 : b - 3] += coef[((int64_t)m * 6 + b) * 64];
+            for (int b = 0; b < BLK; b++) s[je_comp<S>(b)] += coef[((int64_t)m * BLK + b) * 64];
         for (int cmp = 0; cmp < 3; cmp++) sh.scan[0][cmp][lane] = s[cmp];
     }
     const int at = jl_prefix(sh, 3);
@@ -436,9 +440,9 @@ JE_FN uint32_t jl_decode_segment(JlShared& sh, const uint8_t* scan, int32_t nbyt
         for (int cmp = 0; cmp < 3; cmp++) s[cmp] = lane ? sh.scan[at][cmp][lane - 1] : 0;
         bool bad = false;
         for (int32_t m = lo; m < hi; m++)
-            for (int b = 0; b < 6; b++) {
-                int16_t* dc = coef + ((int64_t)m * 6 + b) * 64;
-                int32_t& v = s[b < 4 ? 0 : b - 3];
+            for (int b = 0; b < BLK; b++) {
+                int16_t* dc = coef + ((int64_t)m * BLK + b) * 64;
+                int32_t& v = s[je_comp<S>(b)];
                 v += *dc;
                 bad |= v < -2047 || v > 2047;
                 *dc = (int16_t)(v < -32768 ? -32768 : v > 32767 ? 32767 : v);

@@ -180,9 +180,12 @@ __device__ __forceinline__ void jpeg_forward_column(const JpegBlockMap& map, int
 
 // ---------------------------------------------------------------- host side of the entries
 
-struct JpegGeometry {   // an image in whole 16 x 16 MCUs
+struct JpegGeometry {   // an image in whole MCUs: 16 x 16 (4:2:0, the default), or the MCU of another sampling of jpeg_entropy.h's JE_SAMPLING_*
+    int mcu_w, mcu_h;             // the MCU in luma samples: 16 x 16 (4:2:0), 16 wide x 8 high (4:2:2), 8 x 8 (4:4:4, greyscale)
     int mcus_w, mcus_h, Wm, Hm;   // MCUs across and down; the padded size (the planes' of jpeg_inverse.h)
-    JpegGeometry(int32_t h, int32_t w) : mcus_w((w + 15) / 16), mcus_h((h + 15) / 16), Wm(mcus_w * 16), Hm(mcus_h * 16) {}
+    JpegGeometry(int32_t h, int32_t w, int sampling = 0)
+        : mcu_w(sampling <= 1 ? 16 : 8), mcu_h(sampling == 0 ? 16 : 8), mcus_w((w + mcu_w - 1) / mcu_w), mcus_h((h + mcu_h - 1) / mcu_h),
+          Wm(mcus_w * mcu_w), Hm(mcus_h * mcu_h) {}
     size_t mcus() const { return (size_t)mcus_w * mcus_h; }
 };
 

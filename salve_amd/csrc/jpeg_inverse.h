@@ -1,4 +1,4 @@
-// jpeg_inverse.h -- the inverse half of libjpeg's baseline 4:2:0 chain as device code, shared by jpeg_roundtrip.hip (which takes the
+// jpeg_inverse.h -- the inverse half of libjpeg's baseline chain (4:2:0, and for jpeg_decode.hip 4:2:2, 4:4:4 and greyscale) as device code, shared by jpeg_roundtrip.hip (which takes the
 // quantised coefficients from the forward chain) and jpeg_decode.hip (which takes them from a file's entropy-coded scan): the 1-D pass of
 // the slow-integer inverse DCT with its range limit (jidctint.c), the store of a block's decoded row into the planes
 // (jpeg_store_decoded_row: the planes' layout is written there, once), and the launch that upsamples the chroma planes, converts to RGB
@@ -58,18 +58,30 @@ __device__ __forceinline__ uint32_t idct_range_limit(int v) {
     return (uint32_t)(i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896);
 }
 
-// The planes, the layout contract between the kernels that decode blocks and jpeg_pixels_kernel: per image, luma [Hm][Wm] bytes, then Cb
-// [Hm / 2][Wm / 2], then Cr likewise, Hm and Wm the image rounded up to whole 16 x 16 MCUs; the images follow each other without a gap.
-__host__ __device__ __forceinline__ int64_t jpeg_image_planes_bytes(int Hm, int Wm) {
-    const int64_t ysize = (int64_t)Hm * Wm;
-    return ysize + ysize / 2;   // a multiple of 384
-}
+// The planes, the layout contract between the kernels that decode blocks and the pixels kernels: per image, the component planes back to
+// back -- luma [Hm][Wm] bytes, then Cb, then Cr -- Hm and Wm the image rounded up to whole MCUs of its sampling (JpegGeometry); the images
+// follow each other without a gap.  A chroma plane is [Hm / 2][Wm / 2] for 4:2:0 (16 x 16 MCUs: the default, and all jpeg_roundtrip.hip
+// knows), [Hm][Wm / 2] for 4:2:2 (16 x 8), [Hm][Wm] for 4:4:4 (8 x 8); greyscale has the luma plane alone.  JpegPlanes is that contract
+// for sampling S (jpeg_entropy.h: JE_SAMPLING_*), a compile-time argument of every kernel that touches the planes.
+template <int S>
+struct JpegPlanes {
+    static constexpr int cshift_x = S <= 1 ? 1 : 0, cshift_y = S == 0 ? 1 : 0;   // luma samples per chroma sample, as shifts
+    static constexpr int chroma_planes = S == 3 ? 0 : 2;
+    static constexpr int luma_across = S <= 1 ? 2 : 1, luma_down = S == 0 ? 2 : 1;   // luma blocks of an MCU
+    static constexpr int luma_blocks = luma_across * luma_down;
+    __host__ __device__ static __forceinline__ int64_t chroma_bytes(int Hm, int Wm) { return ((int64_t)Hm * Wm) >> (cshift_x + cshift_y); }
+    __host__ __device__ static __forceinline__ int64_t image_bytes(int Hm, int Wm) { return (int64_t)Hm * Wm + chroma_planes * chroma_bytes(Hm, Wm); }   // a multiple of 64
+};
+
+__host__ __device__ __forceinline__ int64_t jpeg_image_planes_bytes(int Hm, int Wm) { return JpegPlanes<0>::image_bytes(Hm, Wm); }   // 4:2:0: a multiple of 384
 
 inline size_t jpeg_planes_bytes(int32_t n, const JpegGeometry& g) { return (size_t)n * (size_t)jpeg_image_planes_bytes(g.Hm, g.Wm); }
 
-// Inverse pass 2 on row r of block k (JpegBlockMap::k: 0 .. 3 luma, 4 Cb, 5 Cr) of MCU (my, mx): d[0 .. 7] is that row after pass 1.
-// Range limit, and the row leaves as ONE 8-byte store into the planes of image blockIdx.z of `ws`.
+// Inverse pass 2 on row r of block k of MCU (my, mx), k in the scan's order (for 4:2:0 JpegBlockMap::k: 0 .. 3 luma, 4 Cb, 5 Cr): d[0 .. 7]
+// is that row after pass 1.  Range limit, and the row leaves as ONE 8-byte store into the planes of image blockIdx.z of `ws`.
+template <int S = 0>
 __device__ __forceinline__ void jpeg_store_decoded_row(int* d, uint8_t* __restrict__ ws, int Hm, int Wm, int my, int mx, int k, int r) {
+    using P = JpegPlanes<S>;
     idct_1d(d, CONST_BITS + PASS1_BITS + 3);
     uint32_t lo = 0, hi = 0;
 #pragma unroll
@@ -78,14 +90,27 @@ __device__ __forceinline__ void jpeg_store_decoded_row(int* d, uint8_t* __restri
         hi |= idct_range_limit(d[j + 4]) << (8 * j);
     }
     const int64_t ysize = (int64_t)Hm * Wm;
-    uint8_t* planes = ws + blockIdx.z * jpeg_image_planes_bytes(Hm, Wm);
+    uint8_t* planes = ws + blockIdx.z * P::image_bytes(Hm, Wm);
     uint8_t* dst;
-    if (k < 4) dst = planes + (int64_t)(my * 16 + (k >> 1) * 8 + r) * Wm + mx * 16 + (k & 1) * 8;
-    else dst = planes + ysize + (k - 4) * (ysize / 4) + (int64_t)(my * 8 + r) * (Wm / 2) + mx * 8;
+    if (k < P::luma_blocks) {
+        const int by = P::luma_across == 2 ? k >> 1 : 0, bx = P::luma_across == 2 ? k & 1 : 0;
+        dst = planes + (int64_t)((my * P::luma_down + by) * 8 + r) * Wm + (mx * P::luma_across + bx) * 8;
+    } else {
+        dst = planes + ysize + (k - P::luma_blocks) * P::chroma_bytes(Hm, Wm) + (int64_t)(my * 8 + r) * (Wm >> P::cshift_x) + mx * 8;
+    }
     *reinterpret_cast<uint2*>(dst) = make_uint2(lo, hi);
 }
 
 __device__ __forceinline__ int clamp255(int v) { return v < 0 ? 0 : v > 255 ? 255 : v; }
+
+// jdcolor.c: the four tables of ycc_rgb_convert (arithmetic shifts of negative sums, as RIGHT_SHIFT) on one sample -> 0x00BBGGRR
+__device__ __forceinline__ uint32_t jpeg_ycc_pixel(int Y, int cb, int cr) {
+    const int cbx = cb - 128, crx = cr - 128;
+    const int R = clamp255(Y + ((91881 * crx + 32768) >> 16));
+    const int B = clamp255(Y + ((116130 * cbx + 32768) >> 16));
+    const int G = clamp255(Y + ((-22554 * cbx + 32768 - 46802 * crx) >> 16));
+    return (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
+}
 
 // 3 * nearer row + further row of one chroma column (jdsample.c: thiscolsum)
 __device__ __forceinline__ int colsum(const uint8_t* __restrict__ near_row, const uint8_t* __restrict__ far_row, int c) {
@@ -122,12 +147,52 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixels_kernel(const uint8_t
     for (int e = 0; e < 2; e++) {
         const int x = 2 * cx + e;
         if (x >= w) break;
-        const int Y = yrow[x], cbx = (e ? c_odd[0] : c_even[0]) - 128, crx = (e ? c_odd[1] : c_even[1]) - 128;
-        // jdcolor.c: the four tables of ycc_rgb_convert (arithmetic shifts of negative sums, as RIGHT_SHIFT)
-        const int R = clamp255(Y + ((91881 * crx + 32768) >> 16));
-        const int B = clamp255(Y + ((116130 * cbx + 32768) >> 16));
-        const int G = clamp255(Y + ((-22554 * cbx + 32768 - 46802 * crx) >> 16));
-        orow[x] = (uint32_t)R | ((uint32_t)G << 8) | ((uint32_t)B << 16);
+        orow[x] = jpeg_ycc_pixel(yrow[x], e ? c_odd[0] : c_even[0], e ? c_odd[1] : c_even[1]);
+    }
+}
+
+// The pixels of the samplings beyond 4:2:0 (S: JE_SAMPLING_422, _444 or _GREY), the same thread map and grid.  4:2:2 is jdsample.c's
+// h2v1_fancy_upsample, horizontally only: 3/4 of the nearer chroma sample and 1/4 of the further, rounded with + 1 to the left and + 2 to
+// the right, the row's two end pixels copied; 4:4:4 takes its chroma as it stands; greyscale is Y in all three bytes (Pillow's mode L
+// repeated into three channels).
+template <int S>
+__global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixels_sampled_kernel(const uint8_t* __restrict__ ws, uint32_t* __restrict__ out, int h, int w,
+                                                                           int Hm, int Wm) {
+    static_assert(S >= 1 && S <= 3, "4:2:0 is jpeg_pixels_kernel");
+    using P = JpegPlanes<S>;
+    const int cx = blockIdx.x * 64 + threadIdx.x, y = blockIdx.y * 4 + threadIdx.y;
+    const int cw = (w + 1) >> 1;
+    if (cx >= cw || y >= h) return;
+    const int64_t ysize = (int64_t)Hm * Wm;
+    const uint8_t* planes = ws + blockIdx.z * P::image_bytes(Hm, Wm);
+    const uint8_t* yrow = planes + (int64_t)y * Wm;
+    uint32_t* orow = out + ((int64_t)blockIdx.z * h + y) * w;
+    int c_even[2] = {0, 0}, c_odd[2] = {0, 0};
+    if (S == 1) {
+#pragma unroll
+        for (int k = 0; k < 2; k++) {
+            const uint8_t* row = planes + ysize + k * P::chroma_bytes(Hm, Wm) + (int64_t)y * (Wm >> 1);
+            const int here = row[cx];
+            if (cw <= 2) {   // libjpeg upsamples a component of at most two samples a row by replication
+                c_even[k] = c_odd[k] = here;
+                continue;
+            }
+            c_even[k] = cx == 0 ? here : (3 * here + (int)row[cx - 1] + 1) >> 2;
+            c_odd[k] = cx == cw - 1 ? here : (3 * here + (int)row[cx + 1] + 2) >> 2;
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 2; e++) {
+        const int x = 2 * cx + e;
+        if (x >= w) break;
+        const int Y = yrow[x];
+        if (S == 3) {
+            orow[x] = (uint32_t)Y | ((uint32_t)Y << 8) | ((uint32_t)Y << 16);
+        } else if (S == 2) {
+            orow[x] = jpeg_ycc_pixel(Y, planes[ysize + (int64_t)y * Wm + x], planes[2 * ysize + (int64_t)y * Wm + x]);
+        } else {
+            orow[x] = jpeg_ycc_pixel(Y, e ? c_odd[0] : c_even[0], e ? c_odd[1] : c_even[1]);
+        }
     }
 }
 
@@ -136,6 +201,14 @@ inline hipError_t jpeg_launch_pixels(const uint8_t* planes, uint32_t* out, int32
     const int cw = (w + 1) / 2;
     hipLaunchKernelGGL(jpeg_pixels_kernel, dim3((unsigned)((cw + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), dim3(64, 4), 0, stream, planes, out,
                        (int)h, (int)w, g.Hm, g.Wm);
+    return hipGetLastError();
+}
+
+template <int S>
+inline hipError_t jpeg_launch_pixels_sampled(const uint8_t* planes, uint32_t* out, int32_t n, int32_t h, int32_t w, const JpegGeometry& g, hipStream_t stream) {
+    const int cw = (w + 1) / 2;
+    hipLaunchKernelGGL(jpeg_pixels_sampled_kernel<S>, dim3((unsigned)((cw + 63) / 64), (unsigned)((h + 3) / 4), (unsigned)n), dim3(64, 4), 0, stream, planes,
+                       out, (int)h, (int)w, g.Hm, g.Wm);
     return hipGetLastError();
 }
 

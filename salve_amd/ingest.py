@@ -82,9 +82,11 @@ class PanoStore:
 
     DECODES = ("host", "device")
     READ_THREADS = 16          # decode="device": the pool that reads and parses the files (and inflates the depth PNGs)
-    PANOS_PER_CALL = 32        # decode="device": panoramas per jpeg_decode call (its workspace: 4.5 bytes per pixel and panorama)
+    PANOS_PER_CALL = 32        # decode="device": panoramas per jpeg_decode call (its workspace per pixel and panorama: 4.5 bytes for 4:2:0 --
+    #                            1.5 of planes, 3 of coefficients -- 6 for 4:2:2, 9 for 4:4:4, 3 for greyscale: 600 MB for 32 4:4:4 panoramas of 2048 x 1024)
 
-    def load(self, img_fpaths: Dict[int, str], depth_save_root: str, building_id: str, pano_ids: Sequence[int], decode: str = "host") -> "PanoStore":
+    def load(self, img_fpaths: Dict[int, str], depth_save_root: str, building_id: str, pano_ids: Sequence[int], decode: str = "host",
+             samplings: Sequence[str] = ("4:2:0",)) -> "PanoStore":
         """Decode -> resize (device).  Depth maps are `{depth_save_root}/{building}/{stem}.depth.png`
         (bev_rendering_utils.py:610-611); one that is missing or of the wrong size raises, as the reference's imread /
         broadcast would.
@@ -92,15 +94,22 @@ class PanoStore:
         reads and parses the files (jpeg.parse_file(restart=True)) and inflates the depth PNGs; the panoramas that share size and
         tables go through BevRasteriser.jpeg_decode(entropy="lanes") together -- only their entropy-coded scans are uploaded -- and a
         file the device does not decode (greyscale, 4:4:4, 4:2:2, progressive ...) or reports as malformed takes Pillow into the same
-        slot.  The same `rgb`, bit for bit."""
+        slot.  The same `rgb`, bit for bit.
+        samplings (decode="device"): the members of jpeg.SAMPLINGS the device decodes; the default is 4:2:0 alone, what Pillow's
+        `save()` writes.  With jpeg.DEVICE_SAMPLINGS, 4:2:2 (360-degree cameras) and greyscale files stay on the device as well -- the
+        samplings measured faster there; 4:4:4 (editors) is as fast in the reader threads and joins only when named,
+        as in jpeg.SAMPLINGS.  A three-component file that libjpeg reads as RGB still goes to Pillow; `host_decoded` counts the rest."""
         if decode not in self.DECODES:
             raise ValueError(f"decode must be one of {self.DECODES}, got {decode!r}")
+        samplings = tuple(samplings)
+        if not samplings or any(s not in _lib.JPEG_SAMPLINGS for s in samplings):
+            raise ValueError(f"samplings must name members of {tuple(_lib.JPEG_SAMPLINGS)}, got {samplings!r}")
         h, w = self.pano_hw
         pids = sorted(set(int(p) for p in pano_ids))
         fps = [img_fpaths[pid] for pid in pids]
         depth_fps = [f"{depth_save_root}/{building_id}/{Path(fp).stem}.depth.png" for fp in fps]
         if decode == "device":
-            rgb, depths = self._load_device(fps, depth_fps)
+            rgb, depths = self._load_device(fps, depth_fps, samplings)
         else:
             rgbs, depths = [], []
             for fp, dfp in zip(fps, depth_fps):
@@ -121,12 +130,11 @@ class PanoStore:
         if depth.shape != (h, w):
             raise ValueError(f"depth map must be {w}x{h}, got {depth.shape[::-1]}")
 
-    def _load_device(self, fps: List[str], depth_fps: List[str]) -> Tuple[torch.Tensor, List[np.ndarray]]:
+    def _load_device(self, fps: List[str], depth_fps: List[str], samplings: Tuple[str, ...] = ("4:2:0",)) -> Tuple[torch.Tensor, List[np.ndarray]]:
         """load(decode="device"): (uint8 [P, h, w, 3] on the device, the depth maps)."""
         import concurrent.futures
 
         from salve_amd import jpeg
-        from salve_amd.rasteriser import BevRasteriser
 
         h, w = self.pano_hw
 
@@ -134,7 +142,7 @@ class PanoStore:
             with open(fps[k], "rb") as f:
                 data = f.read()
             try:
-                parsed = jpeg.parse_file(data, restart=True)
+                parsed = jpeg.parse_file(data, restart=True, samplings=samplings)
                 if max(parsed.h, parsed.w) > jpeg.DEVICE_MAX_SIDE or max(s[1] for s in parsed.segments) > jpeg.DEVICE_MAX_SEGMENT_BYTES:
                     raise jpeg.Unsupported("larger than salve_bev_jpeg_decode_lanes takes")
                 return data, parsed, None
@@ -145,10 +153,27 @@ class PanoStore:
             reads = [pool.submit(read, k) for k in range(len(fps))]                # both kinds of file are in the pool together
             inflates = [pool.submit(image_io.read_depth_png, p) for p in depth_fps]
             files = [f.result() for f in reads]
+            out, pending = self._decode_groups(files)                              # (launched, not waited for: the device decodes while the pool inflates)
             depths = [f.result() for f in inflates]
         for d in depths:
             self._check_depth(d)
-        out = torch.empty((len(fps), h, w, 3), dtype=torch.uint8, device=self.device)
+        host_route = [k for k, (_, parsed, _) in enumerate(files) if parsed is None]
+        for part, st in pending:                       # (one wait, behind the last launch) a scan the device reports: Pillow's verdict counts
+            host_route += [k for k, word in zip(part, st.cpu().numpy()) if word]
+        for k in host_route:
+            rgb = files[k][2] if files[k][2] is not None else _read_rgb3(fps[k])
+            out[k] = resize_rgb_on_device(torch.from_numpy(rgb).to(self.device)[None], (h, w))[0]
+        self.host_decoded = len(host_route)
+        return out, depths
+
+    def _decode_groups(self, files):
+        """The parsed files of _load_device, grouped by header, through BevRasteriser.jpeg_decode and the resize -> (uint8 [P, h, w, 3] on
+        the device with those slots filled, [(the slots of a call, its status tensor)]).  Nothing is waited for."""
+        from salve_amd import jpeg
+        from salve_amd.rasteriser import BevRasteriser
+
+        h, w = self.pano_hw
+        out = torch.empty((len(files), h, w, 3), dtype=torch.uint8, device=self.device)
         groups: Dict[bytes, List[int]] = {}
         for k, (_, parsed, _) in enumerate(files):
             if parsed is not None:
@@ -172,17 +197,10 @@ class PanoStore:
                 for k, o, n in zip(part, off, nb):
                     blob[o:o + n] = np.frombuffer(files[k][0], dtype=np.uint8, count=n, offset=files[k][1].scan_offset)
                 img, st = self._ras.jpeg_decode(torch.from_numpy(blob).to(self.device), off, nb, first.h, first.w, first.qtab, first.huffman,
-                                                entropy="lanes", segments=rows)
+                                                entropy="lanes", segments=rows, sampling=first.sampling)
                 out[torch.as_tensor(part, device=self.device)] = resize_rgb_on_device(self._ras.export_u8(img), (h, w))
                 pending.append((part, st))
-        host_route = [k for k, (_, parsed, _) in enumerate(files) if parsed is None]
-        for part, st in pending:                       # (one wait, behind the last launch) a scan the device reports: Pillow's verdict counts
-            host_route += [k for k, word in zip(part, st.cpu().numpy()) if word]
-        for k in host_route:
-            rgb = files[k][2] if files[k][2] is not None else _read_rgb3(fps[k])
-            out[k] = resize_rgb_on_device(torch.from_numpy(rgb).to(self.device)[None], (h, w))[0]
-        self.host_decoded = len(host_route)
-        return out, depths
+        return out, pending
 
     def __len__(self) -> int:
         return len(self.index)
@@ -261,11 +279,11 @@ def load_floor_hypotheses(hypotheses_save_root: str, building_id: str, floor_id:
 
 def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypotheses_save_root: str, bev_save_root: str,
                 building_id: str, floor_id: str, serialization_save_dir: str, batch_size: int = 64, chunk: Optional[int] = None,
-                decode: str = "host"):
+                decode: str = "host", samplings: Sequence[str] = ("4:2:0",)):
     """Disk -> predictions for one floor without writing a tile: the fused counterpart of running
     scripts/render_dataset_bev.py and then scripts/test.py on that floor.  chunk = hypotheses per launch; None: the pipeline picks the
     largest launch that fits the free HBM (pipeline.pick_launch).  decode: PanoStore.load's ("device": the panoramas' JPEG files are
-    decoded on the GPU; the same prediction files)."""
+    decoded on the GPU; the same prediction files), and so is samplings (which JPEG samplings stay on the device)."""
     from salve_amd import evaluate
     from salve_amd.pipeline import RenderVerifyPipeline
 
@@ -273,7 +291,7 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     if len(hyps) == 0:
         return None
     img_fpaths = floor_pano_fpaths(raw_dataset_dir, building_id)
-    store = PanoStore(device).load(img_fpaths, depth_save_root, building_id, np.concatenate([hyps.i1, hyps.i2]), decode=decode)
+    store = PanoStore(device).load(img_fpaths, depth_save_root, building_id, np.concatenate([hyps.i1, hyps.i2]), decode=decode, samplings=samplings)
     pipe = RenderVerifyPipeline(model, device, pano_hw=store.pano_hw, chunk=chunk, n_hypotheses=len(hyps))
     pipe.set_panos(store.rgb, store.depth)
     return evaluate.run_fused_epoch(pipe, hyps.table(store, img_fpaths), hyps.tile_names(bev_save_root, img_fpaths), hyps.label,

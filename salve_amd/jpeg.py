@@ -145,7 +145,25 @@ def file_bytes(scan: bytes, h: int, w: int, quality: int) -> bytes:
 # ---------------------------------------------------------------------------------------------------- reading a file's header
 class Unsupported(ValueError):
     """A file outside what `BevRasteriser.jpeg_decode` takes (baseline, 8-bit, three components, 4:2:0, one interleaved scan, no
-    restart interval): the caller decodes it on the host."""
+    restart interval -- or, where the caller asks for them, another of SAMPLINGS): the caller decodes it on the host."""
+
+
+# The samplings salve_bev_jpeg_decode_sampled / _lanes_sampled decode (include/salve_hip.h: SALVE_JPEG_SAMPLING_*), by the frame's sampling
+# factors (Y, Cb, Cr as H << 4 | V; greyscale has one component); the MCU in pixels (rows, columns) and its blocks.
+# DEVICE_SAMPLINGS: those whose device route loads a floor of panoramas faster than Pillow in the reader threads by more than the spread
+# between repeats (profiles/r12_jpeg_samplings.txt; DESIGN.md 4.21) -- what callers pass as `samplings=` to take all that pays.  4:4:4 is
+# decoded bit for bit as well but measured level with the host (1.05 x, inside the spread): name it, or pass SAMPLINGS, to have it.
+SAMPLINGS = ("4:2:0", "4:2:2", "4:4:4", "grey")
+DEVICE_SAMPLINGS = ("4:2:0", "4:2:2", "grey")
+_SAMPLING_OF_FACTORS = {(0x22, 0x11, 0x11): "4:2:0", (0x21, 0x11, 0x11): "4:2:2", (0x11, 0x11, 0x11): "4:4:4"}
+MCU_SIZE = {"4:2:0": (16, 16), "4:2:2": (8, 16), "4:4:4": (8, 8), "grey": (8, 8)}
+MCU_BLOCKS = {"4:2:0": 6, "4:2:2": 4, "4:4:4": 3, "grey": 1}
+
+
+def mcu_grid(h: int, w: int, sampling: str = "4:2:0") -> Tuple[int, int]:
+    """(MCU rows, MCUs across) of an h x w image.  A greyscale scan is not interleaved: its "MCUs" are its 8 x 8 blocks."""
+    mh, mw = MCU_SIZE[sampling]
+    return -(-int(h) // mh), -(-int(w) // mw)
 
 
 class ParsedFile(NamedTuple):
@@ -158,6 +176,7 @@ class ParsedFile(NamedTuple):
     header_key: bytes         # the bytes before the scan: files with equal keys share size and tables and may go into one call
     segments: Tuple[Tuple[int, int, int, int], ...] = ()   # (file offset, bytes, first MCU, MCUs) of the scan's restart intervals, the RSTn
     #                           markers excluded; a scan without restart markers is one segment.  For BevRasteriser.jpeg_decode(entropy="lanes")
+    sampling: str = "4:2:0"   # one of SAMPLINGS: BevRasteriser.jpeg_decode(sampling=); MCUs count in MCU_SIZE[sampling]
 
 
 HUFFMAN_TABLE_BYTES = 272
@@ -176,14 +195,26 @@ def describe_status(word: int) -> str:
     return "; ".join(text for bit, text in STATUS_BITS.items() if int(word) & bit) or "ok"
 
 
-def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
+def parse_file(data: bytes, restart: bool = False, samplings: Tuple[str, ...] = ("4:2:0",)) -> ParsedFile:
     """Walks the marker segments of a JPEG file (ITU-T T.81 Annex B) up to its scan and returns what salve_bev_jpeg_decode needs.
     Raises `Unsupported(reason)` for everything outside part 1 of what the device decodes: progressive and other non-baseline
     frames, greyscale, other sampling factors, 12-bit samples, 16-bit quantisation entries, a restart interval, more than one scan,
     a missing EOI, a truncated segment.  Pure host arithmetic.
     restart=True (for salve_bev_jpeg_decode_lanes) also takes a DRI segment and the RSTn markers inside the scan: the markers must
     count D0 .. D7 in order, and there must be exactly as many intervals as the image's MCUs need (interval i starts at MCU i * Ri:
-    every interval but the last holds Ri MCUs by position); `segments` then names the intervals, the marker bytes excluded."""
+    every interval but the last holds Ri MCUs by position); `segments` then names the intervals, the marker bytes excluded.
+    samplings: the members of SAMPLINGS the caller takes (for salve_bev_jpeg_decode_sampled / _lanes_sampled); `sampling`
+    names the file's, and the MCUs of `segments` count in its MCU (16 x 8 for 4:2:2, 8 x 8 for 4:4:4; a greyscale scan's blocks).  A
+    greyscale file has the luma tables in the chroma slots of `qtab` and `huffman` as well.  With anything beyond the default, a
+    three-component file must also be YCbCr by libjpeg's rule (jdapimin.c: default_decompress_parms) -- a JFIF segment: yes; else an
+    Adobe segment: its transform byte, 0 is RGB; else the component ids 'R', 'G', 'B': RGB -- or it is refused ("colour space"):
+    Pillow's `save(keep_rgb=True)` writes a 1x1 1x1 1x1 frame that is RGB.  The default neither reads APP14 nor looks at the ids."""
+    samplings = tuple(samplings)
+    if not samplings or any(s not in SAMPLINGS for s in samplings):
+        raise ValueError(f"samplings must name members of {SAMPLINGS}, got {samplings!r}")
+    colour_rule = samplings != ("4:2:0",)
+    jfif, adobe = False, None
+    sampling = "4:2:0"
     data = bytes(data)
     interval = 0
     if data[:2] != b"\xff\xd8":
@@ -251,13 +282,20 @@ def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
             if body[0] != 8:
                 raise Unsupported(f"{body[0]}-bit samples")
             h, w, nc = int.from_bytes(body[1:3], "big"), int.from_bytes(body[3:5], "big"), body[5]
-            if nc != 3:
+            if nc == 1 and "grey" in samplings:
+                comps = [(body[6], body[7], body[8])]
+                if comps[0][1] != 0x11:
+                    raise Unsupported("sampling factors other than 1x1 in a greyscale frame")
+                sampling = "grey"
+            elif nc != 3:
                 raise Unsupported(f"{nc} component(s): greyscale or CMYK")
-            comps = [(body[6 + 3 * c], body[7 + 3 * c], body[8 + 3 * c]) for c in range(3)]   # id, sampling, table
-            if [c[1] for c in comps] != [0x22, 0x11, 0x11]:
-                raise Unsupported("sampling factors other than 4:2:0")
-            if comps[1][2] != comps[2][2]:
-                raise Unsupported("Cb and Cr use different quantisation tables")
+            else:
+                comps = [(body[6 + 3 * c], body[7 + 3 * c], body[8 + 3 * c]) for c in range(3)]   # id, sampling, table
+                sampling = _SAMPLING_OF_FACTORS.get(tuple(c[1] for c in comps))
+                if sampling not in samplings:
+                    raise Unsupported(f"sampling factors other than {', '.join(s for s in samplings if s != 'grey') or 'greyscale'}")
+                if comps[1][2] != comps[2][2]:
+                    raise Unsupported("Cb and Cr use different quantisation tables")
             if h < 1 or w < 1:
                 raise Unsupported("an empty frame (or DNL)")
             frame = (h, w, comps)
@@ -275,15 +313,28 @@ def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
             if frame is None:
                 raise Unsupported("a scan in front of its frame")
             h, w, comps = frame
-            if len(body) != 10 or body[0] != 3:
+            nc = len(comps)
+            if nc == 3 and (len(body) != 10 or body[0] != 3):
                 raise Unsupported("a scan that does not interleave all three components")
-            sel = [(body[1 + 2 * c], body[2 + 2 * c]) for c in range(3)]
+            if nc == 1 and (len(body) != 6 or body[0] != 1):
+                raise Unsupported("a scan that does not hold the frame's one component")
+            sel = [(body[1 + 2 * c], body[2 + 2 * c]) for c in range(nc)]
             if [s[0] for s in sel] != [c[0] for c in comps]:
                 raise Unsupported("a scan whose components are not in the frame's order")
-            if sel[1][1] != sel[2][1]:
+            if nc == 3 and sel[1][1] != sel[2][1]:
                 raise Unsupported("Cb and Cr use different Huffman tables")
-            if tuple(body[7:10]) != (0, 63, 0):
+            if tuple(body[-3:]) != (0, 63, 0):
                 raise Unsupported("a spectral selection or successive approximation")
+            if colour_rule and nc == 3:
+                if jfif:
+                    rgb = False
+                elif adobe is not None:
+                    rgb = adobe == 0
+                else:
+                    rgb = [c[0] for c in comps] == [0x52, 0x47, 0x42]
+                if rgb:
+                    raise Unsupported("colour space: libjpeg reads this three-component file as RGB, not YCbCr")
+            comps, sel = (comps * 2)[:2], (sel * 2)[:2]      # (greyscale: the luma tables in the chroma slots)
             try:
                 qtab = np.stack([qt[comps[0][2]], qt[comps[1][2]]])
                 huffman = np.stack([huff[0x00 | (sel[0][1] >> 4)], huff[0x10 | (sel[0][1] & 15)],
@@ -291,16 +342,20 @@ def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
             except KeyError:
                 raise Unsupported("a table the scan names is missing") from None
             break
+        elif colour_rule and marker == 0xE0 and len(body) >= 14 and body[:5] == b"JFIF\x00":      # (jdmarker.c: examine_app0)
+            jfif = True
+        elif colour_rule and marker == 0xEE and len(body) >= 12 and body[:5] == b"Adobe":         # (examine_app14: the transform byte)
+            adobe = body[11]
         # every other segment (APPn, COM, ...) is skipped
     if data[-2:] != b"\xff\xd9":
         raise Unsupported("no EOI marker at the end of the file")
     end = len(data) - 2
-    mcus = -(-h // 16) * -(-w // 16)
+    mcus = int(np.prod(mcu_grid(h, w, sampling)))
     if interval == 0:
         found = _MARKER_IN_SCAN.search(data, at, end)
         if found is not None:
             raise Unsupported(f"marker FF{data[found.start() + 1]:02X} inside the scan: restart markers or a further scan")
-        return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], ((at, end - at, 0, mcus),))
+        return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], ((at, end - at, 0, mcus),), sampling)
     segments, lo = [], at
     for k, found in enumerate(_MARKER_IN_SCAN.finditer(data, at, end)):
         marker = data[found.start() + 1]
@@ -312,4 +367,4 @@ def parse_file(data: bytes, restart: bool = False) -> ParsedFile:
     if first >= mcus or first + interval < mcus:
         raise Unsupported(f"{len(segments) + 1} restart intervals of {interval} MCUs in a scan of {mcus} MCUs: wrong MCU count per interval")
     segments.append((lo, end - lo, first, mcus - first))
-    return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], tuple(segments))
+    return ParsedFile(h, w, qtab, huffman, at, end - at, data[:at], tuple(segments), sampling)

@@ -348,7 +348,7 @@ class BevRasteriser:
         _lib.check(st, "salve_bev_export_u8")
         return out
 
-    JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip, jpeg_encode, jpeg_decode: images per library call (bounds its workspace: 1.5 bytes per padded pixel)
+    JPEG_IMAGES_PER_CALL = 1024   # jpeg_roundtrip, jpeg_encode, jpeg_decode: images per library call (bounds its workspace: 1.5 bytes per padded pixel; jpeg_decode's other samplings up to 3, plus the coefficients)
 
     def _jpeg_images(self, who: str, t: torch.Tensor, shape=None) -> None:
         """Refuse `t` unless it is a contiguous int32 [n, H, W] tensor on this device (of `shape`, if one is given)."""
@@ -365,7 +365,7 @@ class BevRasteriser:
             self._jpeg_tables[q] = np.ascontiguousarray(quality_tables(q), dtype=np.uint16)
         return self._jpeg_tables[q].ctypes.data_as(ctypes.c_void_p)
 
-    def _jpeg_calls(self, route: str, n: int, h: int, w: int):
+    def _jpeg_calls(self, route: str, n: int, h: int, w: int, *more: int):
         """The library calls of one JPEG method on n images: yields (lo, m, workspace pointer, workspace bytes) for images lo .. lo + m - 1,
         at most JPEG_IMAGES_PER_CALL at a time, with this device current.  The three methods share ONE workspace per stream (only one of
         their calls runs on a stream at a time); it grows to the largest need seen."""
@@ -373,7 +373,7 @@ class BevRasteriser:
             return
         per = min(n, self.JPEG_IMAGES_PER_CALL)
         size_fn = f"salve_bev_jpeg_{route}_workspace_bytes"
-        need = getattr(self.lib, size_fn)(per, h, w)
+        need = getattr(self.lib, size_fn)(per, h, w, *more)   # (more: what the route's size query takes behind w)
         if need == 0:
             _lib.check(-1, size_fn)
         key = torch.cuda.current_stream(self.device).cuda_stream
@@ -432,7 +432,7 @@ class BevRasteriser:
 
     def jpeg_decode(self, scans: torch.Tensor, scan_offset, scan_bytes, h: int, w: int, qtab: np.ndarray, huffman: np.ndarray,
                     out: Optional[torch.Tensor] = None, stages: int = _lib.JPEG_STAGES_ALL, entropy: str = "image",
-                    segments=None) -> Tuple[torch.Tensor, torch.Tensor]:
+                    segments=None, sampling: str = "4:2:0") -> Tuple[torch.Tensor, torch.Tensor]:
         """The entropy-coded scans of n baseline 4:2:0 JPEG files of ONE size that SHARE their tables (`salve_amd.jpeg.parse_file`: equal
         `header_key`) -> (int32 [n, h, w] images holding 0x00BBGGRR, int32 [n] status), both on the device: the pixels Pillow decodes
         from those files, bit for bit (include/salve_hip.h: salve_bev_jpeg_decode; zind_data.py:306-315).
@@ -450,8 +450,14 @@ class BevRasteriser:
         the same zero / non-zero status (a failing image's bits and pixels may differ).  segments ("lanes" only): the restart
         intervals, rows (offset in `scans`, bytes, image, first MCU, MCUs) or a _lib.JPEG_SEGMENT_DTYPE array -- `parse_file(data,
         restart=True).segments` rebased to the buffer -- sorted by image, each image's rows tiling its MCUs in order (checked here:
-        the device cannot refuse a table it has not read); default one segment per image, scan_offset / scan_bytes."""
+        the device cannot refuse a table it has not read); default one segment per image, scan_offset / scan_bytes.
+        sampling: one of jpeg.SAMPLINGS, `parse_file(..., samplings=)`'s `sampling` -- "4:2:2", "4:4:4" and "grey" go through
+        salve_bev_jpeg_decode_sampled / _lanes_sampled; MCUs then count in that sampling's MCU (jpeg.MCU_SIZE), and the workspace
+        grows to 2 / 3 / 1 bytes per padded pixel plus the coefficients."""
         from salve_amd.jpeg import HUFFMAN_TABLE_BYTES, SCAN_PADDING
+
+        if sampling not in _lib.JPEG_SAMPLINGS:
+            raise _lib.SalveHipError(f"jpeg_decode: sampling is one of {tuple(_lib.JPEG_SAMPLINGS)}, got {sampling!r}")
 
         if entropy not in ("image", "lanes"):
             raise _lib.SalveHipError(f"jpeg_decode: entropy is 'image' or 'lanes', got {entropy!r}")
@@ -479,21 +485,23 @@ class BevRasteriser:
         if stages != _lib.JPEG_STAGES_ALL and n > self.JPEG_IMAGES_PER_CALL:
             raise _lib.SalveHipError(f"jpeg_decode: the stages can be called apart for at most {self.JPEG_IMAGES_PER_CALL} images (one workspace), got {n}")
         if entropy == "lanes":
-            return self._jpeg_decode_lanes(scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, int(stages))
+            return self._jpeg_decode_lanes(scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, int(stages), sampling)
         table = torch.from_numpy(np.concatenate([off.view(np.uint8), nb.astype(np.int32).view(np.uint8)])).to(self.device)   # one upload
-        for lo, m, ws, ws_bytes in self._jpeg_calls("decode", n, h, w):
-            st = self.lib.salve_bev_jpeg_decode(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
-                                                ctypes.c_void_p(table.data_ptr() + 8 * n + 4 * lo), m, h, w, qtab.ctypes.data_as(ctypes.c_void_p),
-                                                huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
-                                                ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, int(stages), self._stream())
-            _lib.check(st, "salve_bev_jpeg_decode")
+        route, more = ("decode", ()) if sampling == "4:2:0" else ("decode_sampled", (_lib.JPEG_SAMPLINGS[sampling],))
+        entry = f"salve_bev_jpeg_{route}"
+        for lo, m, ws, ws_bytes in self._jpeg_calls(route, n, h, w, *more):
+            st = getattr(self.lib, entry)(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + 8 * lo),
+                                          ctypes.c_void_p(table.data_ptr() + 8 * n + 4 * lo), m, h, w, *more, qtab.ctypes.data_as(ctypes.c_void_p),
+                                          huffman.ctypes.data_as(ctypes.c_void_p), ctypes.c_void_p(out[lo:].data_ptr()),
+                                          ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, int(stages), self._stream())
+            _lib.check(st, entry)
         return out, image_status
 
-    def _jpeg_decode_lanes(self, scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, stages):
+    def _jpeg_decode_lanes(self, scans, off, nb, segments, n, h, w, qtab, huffman, out, image_status, stages, sampling="4:2:0"):
         """jpeg_decode(entropy="lanes") behind its argument checks: the segment table checked, rebased per library call, uploaded once."""
-        from salve_amd.jpeg import SCAN_PADDING
+        from salve_amd.jpeg import SCAN_PADDING, mcu_grid
 
-        mcus = -(-h // 16) * -(-w // 16)
+        mcus = int(np.prod(mcu_grid(h, w, sampling)))
         if segments is None:
             seg = np.zeros(n, dtype=_lib.JPEG_SEGMENT_DTYPE)
             seg["offset"], seg["bytes"], seg["image"], seg["mcu_count"] = off, nb, np.arange(n), mcus
@@ -529,12 +537,14 @@ class BevRasteriser:
         seg = seg.copy()
         seg["image"] %= self.JPEG_IMAGES_PER_CALL          # rebased to its library call's first image
         table = torch.from_numpy(seg.view(np.uint8)).to(self.device) if seg.shape[0] else None   # one upload
-        for k, (lo, m, ws, ws_bytes) in enumerate(self._jpeg_calls("decode", n, h, w)):
+        route, more = ("decode", ()) if sampling == "4:2:0" else ("decode_sampled", (_lib.JPEG_SAMPLINGS[sampling],))
+        entry = "salve_bev_jpeg_decode_lanes" + ("_sampled" if more else "")
+        for k, (lo, m, ws, ws_bytes) in enumerate(self._jpeg_calls(route, n, h, w, *more)):
             s0, s1 = int(bounds[k]), int(bounds[k + 1])
-            st = self.lib.salve_bev_jpeg_decode_lanes(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + _lib.JPEG_SEGMENT_DTYPE.itemsize * s0),
-                                                      s1 - s0, m, h, w, qtab.ctypes.data_as(ctypes.c_void_p), huffman.ctypes.data_as(ctypes.c_void_p),
-                                                      ctypes.c_void_p(out[lo:].data_ptr()), ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, stages, self._stream())
-            _lib.check(st, "salve_bev_jpeg_decode_lanes")
+            st = getattr(self.lib, entry)(ctypes.c_void_p(scans.data_ptr()), scans.numel(), ctypes.c_void_p(table.data_ptr() + _lib.JPEG_SEGMENT_DTYPE.itemsize * s0),
+                                          s1 - s0, m, h, w, *more, qtab.ctypes.data_as(ctypes.c_void_p), huffman.ctypes.data_as(ctypes.c_void_p),
+                                          ctypes.c_void_p(out[lo:].data_ptr()), ctypes.c_void_p(image_status[lo:].data_ptr()), ws, ws_bytes, stages, self._stream())
+            _lib.check(st, entry)
         return out, image_status
 
     def upload_tile_jobs(self, bev_index: Sequence[int], slot: Sequence[int], chan: Sequence[int], pretiled: bool = False) -> torch.Tensor:

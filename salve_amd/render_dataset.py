@@ -71,7 +71,8 @@ def available_floors(hypotheses_save_root: str, building_id: str) -> List[str]:
 def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypotheses_save_root: str, raw_dataset_dir: str,
                                 building_id: str, floor_id: str, layout_save_root: Optional[str], render_modalities: List[str],
                                 multiprocess_building_panos: bool = False, num_processes: int = 1, device=None, batch: int = 256,
-                                floor_pose_graph=None, jpeg: str = "host", jpeg_stride: Optional[int] = None, pano_decode: str = "host") -> int:
+                                floor_pose_graph=None, jpeg: str = "host", jpeg_stride: Optional[int] = None, pano_decode: str = "host",
+                                pano_samplings=("4:2:0",)) -> int:
     """All floor + ceiling texture maps of one floor (scripts/render_dataset_bev.py:34-117).  `multiprocess_building_panos`
     and `num_processes` are accepted for signature compatibility; the parallelism is the GPU's.  Returns the number of
     JPEG files written.
@@ -80,7 +81,8 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
     jpeg: "host" (default) downloads every image's pixels and encodes them with Pillow; "device" codes the files' entropy-coded scans
     on the GPU (BevRasteriser.jpeg_encode), downloads those and only writes bytes -- the same files, byte for byte.  `jpeg_stride`:
     the device route's bytes per image slot (default: jpeg_encode's); an image that needs more takes the host route.
-    pano_decode: ingest.PanoStore.load's `decode` ("device": the panoramas' JPEG files are decoded on the GPU; the same pixels)."""
+    pano_decode: ingest.PanoStore.load's `decode` ("device": the panoramas' JPEG files are decoded on the GPU; the same pixels);
+    pano_samplings: its `samplings` (salve_amd.jpeg.DEVICE_SAMPLINGS: 4:2:2 and greyscale panoramas stay on the GPU as well; jpeg.SAMPLINGS: 4:4:4 too)."""
     _check_jpeg_route(jpeg)
     if pano_decode not in ingest.PanoStore.DECODES:
         raise ValueError(f"pano_decode must be one of {ingest.PanoStore.DECODES}, got {pano_decode!r}")
@@ -102,7 +104,7 @@ def render_building_floor_pairs(depth_save_root: str, bev_save_root: str, hypoth
         return written
     dev = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
     needed = sorted({int(p) for j, _ in todo for p in (hyps.i1[j], hyps.i2[j])})
-    store = ingest.PanoStore(dev).load(img_fpaths, depth_save_root, building_id, needed, decode=pano_decode)
+    store = ingest.PanoStore(dev).load(img_fpaths, depth_save_root, building_id, needed, decode=pano_decode, samplings=pano_samplings)
     ras = BevRasteriser(dev, pano_hw=store.pano_hw)
     Hb, Wb = ras.bev_hw
 
@@ -177,13 +179,13 @@ def _render_floor_layouts(hyps, img_fpaths: Dict[int, str], layout_save_root: st
 def render_pairs(num_processes: int, depth_save_root: str, bev_save_root: str, raw_dataset_dir: str, hypotheses_save_root: str,
                  layout_save_root: Optional[str], render_modalities: List[str], split: Optional[str], building_id: Optional[str],
                  multiprocess_building_panos: bool = False, device=None, rank: int = 0, world: int = 1, jpeg: str = "host",
-                 pano_decode: str = "host") -> int:
+                 pano_decode: str = "host", pano_samplings=("4:2:0",)) -> int:
     """All floors of a split's buildings, or of one building (scripts/render_dataset_bev.py:120-191): exactly one of
     `split` / `building_id`; building 1348 is skipped (two panoramas share an id, :160-162).
     world > 1: one process per GPU.  The reference hands its (building, floor) work list to a multiprocessing.Pool
     (`p.starmap(render_building_floor_pairs, args)`, :186-188); here rank r takes items r, r + world, ... of the same list (round
     robin: buildings differ a lot in size, neighbours in the sorted list less so) and writes their files -- the items are
-    independent, nothing is exchanged.  Returns the number of JPEG files THIS rank wrote.  `jpeg`, `pano_decode`: as for
+    independent, nothing is exchanged.  Returns the number of JPEG files THIS rank wrote.  `jpeg`, `pano_decode`, `pano_samplings`: as for
     render_building_floor_pairs (the layout modality's pose graph is not loaded on this path)."""
     _check_jpeg_route(jpeg)
     if building_id is not None and split is not None:
@@ -194,7 +196,7 @@ def render_pairs(num_processes: int, depth_save_root: str, bev_save_root: str, r
     for bid, floor_id in floor_work_list(hypotheses_save_root, split, building_id)[rank::world]:
         written += render_building_floor_pairs(depth_save_root, bev_save_root, hypotheses_save_root, raw_dataset_dir, bid, floor_id,
                                                layout_save_root, render_modalities, multiprocess_building_panos, num_processes, device, jpeg=jpeg,
-                                               pano_decode=pano_decode)
+                                               pano_decode=pano_decode, pano_samplings=pano_samplings)
     return written
 
 
