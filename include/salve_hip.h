@@ -374,6 +374,9 @@ int salve_bev_tile_pairs(const uint32_t* bev_a, const uint32_t* bev_b, int32_t b
  *   jobs_b[r]   the pair's second image: .bev_offset = element offset of a SALVE_TILE_U8X4 image inside tiles_b, .chan its first channel
  *               (the two chans are the halves of one group of six, as for salve_bev_tile_pairs)
  * out_bev holds the complete images afterwards, exactly as after salve_bev_densify; `out` the same bits salve_bev_tile_pairs writes.
+ * SALVE_ERR_BAD_ARG on null pointers, crop <= 0, resize < crop, an odd out_c or one below 6; SALVE_ERR_UNSUPPORTED when the tile phase's
+ * tables (32 bytes per resized row + 3 KB) do not fit the densify kernel's LDS block -- two bits per pixel of the BEV image plus 12.5 KB:
+ * resize <= 290 fits every image, 234 at 501 x 501 uses a seventh of it.
  * (bev_rendering_utils.py:254-328 + train_utils.py:126-159 / transform.py:256-272, 386-420, 105-123, 177-202.) */
 int salve_bev_densify_tiles(const salve_bev_config_t* cfg, int32_t n, uint32_t* out_bev, const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b,
                             const uint32_t* tiles_b, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,

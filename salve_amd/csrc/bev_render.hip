@@ -1402,7 +1402,10 @@ static int bev_stage(const salve_bev_config_t* cfg, int stages, const uint8_t* p
         }
         if (tiles) {   // salve_bev_densify_tiles: the tile phase's arguments go into the key image behind order[] (TileFuse)
             if ((tile_fuse_word((size_t)n) * sizeof(int32_t) + sizeof(TileFuse)) > npx * sizeof(uint32_t)) { salve_fail("too many renders for the fused tile phase"); return SALVE_ERR_BAD_ARG; }
-            if ((size_t)tiles->resize * 2 * sizeof(int4) + 3 * 256 * sizeof(float) > (size_t)d.H * d.wpr * sizeof(uint32_t)) { salve_fail("resize too large for the fused tile phase"); return SALVE_ERR_UNSUPPORTED; }
+            // phase H keeps its taps and table at the front of the launch's dynamic LDS block, whose other tenants (bitmaps, row extents, scalars, the
+            // triangle cache) are all dead by then: this entry passes no development output, the only readers behind phase H.  (Until the contract tests
+            // of tests/tile_cases.py the bound was ONE bitmap, H * wpr words, which refused every image below some 300 x 300 pixels.)
+            if ((size_t)tiles->resize * 2 * sizeof(int4) + 3 * 256 * sizeof(float) > lds) { salve_fail("resize too large for the fused tile phase"); return SALVE_ERR_UNSUPPORTED; }
             hipLaunchKernelGGL(bev_tile_fuse_kernel, dim3(1), dim3(1), 0, s, *tiles, reinterpret_cast<TileFuse*>(reinterpret_cast<int32_t*>(ws.keys) + tile_fuse_word((size_t)n)));
             SALVE_HIP_CHECK(hipGetLastError());
             dc.out_flags |= DENSIFY_TILES;
