@@ -183,19 +183,22 @@ def run_test_epoch(args, serialization_save_dir: str, ckpt_fpath: str, model, da
 
 
 def evaluate_model(serialization_save_dir: str, ckpt_fpath: str, args, split: str, save_viz: bool = False, world: int = 1,
-                   rank: int = 0, decode: str = "host", entropy: str = "image") -> Dict[str, Any]:
+                   rank: int = 0, decode: str = "host", entropy: str = "image", read_ahead: bool = False) -> Dict[str, Any]:
     """scripts/test.py:280-303: data loader -> model -> checkpoint -> run_test_epoch -> `{ckpt stem}.json` summary.
     world > 1: one process per GPU (torch.distributed initialised by the caller), every rank scores its block of whole batches
     (`sharded_loader`), rank 0 writes the summary.  decode="device" (one process): the tiles' JPEG files are decoded on the device
     in whole batches (train_utils.get_dataloader) -- the same tuples, the same `batch_{i}.json` files; entropy="lanes" takes the
-    lane-parallel entropy stage there (at the reference's test batch of 64 the serial stage leaves most of the device idle)."""
+    lane-parallel entropy stage there (DESIGN.md 4.20: at the reference's test batch of 64 the serial stage leaves most of the device idle);
+    read_ahead=True (decode="device" only) reads and decodes the next batches beside the current one: the same files again."""
     from salve_amd import train_utils
 
+    if read_ahead and decode != "device":
+        raise ValueError('read_ahead=True reads the device decoder\'s next batch ahead: it needs decode="device"')
     if decode == "device" and world != 1:
         raise RuntimeError('decode="device" serves one process (world == 1)')
     model = train_utils.load_model_checkpoint(ckpt_fpath, train_utils.get_model(args), args)
     if world == 1:
-        loader = train_utils.get_dataloader(args, split=split, decode=decode, entropy=entropy)
+        loader = train_utils.get_dataloader(args, split=split, decode=decode, entropy=entropy, read_ahead=read_ahead)
         try:
             metrics = run_test_epoch(args, serialization_save_dir, ckpt_fpath, model.eval(), loader, split, save_viz)
         finally:

@@ -12,6 +12,7 @@ Pure host arithmetic, no device.
 from __future__ import annotations
 
 import re
+import threading
 from typing import Dict, NamedTuple, Tuple
 
 import numpy as np
@@ -209,13 +210,57 @@ def parse_file(data: bytes, restart: bool = False, samplings: Tuple[str, ...] = 
     three-component file must also be YCbCr by libjpeg's rule (jdapimin.c: default_decompress_parms) -- a JFIF segment: yes; else an
     Adobe segment: its transform byte, 0 is RGB; else the component ids 'R', 'G', 'B': RGB -- or it is refused ("colour space"):
     Pillow's `save(keep_rgb=True)` writes a 1x1 1x1 1x1 frame that is RGB.  The default neither reads APP14 nor looks at the ids."""
+    samplings = _check_samplings(samplings)
+    data = bytes(data)
+    return _parse_scan(data, *_walk_header(data, restart, samplings))
+
+
+class HeaderCache:
+    """`parse_file` for the files of a data set written by one program, whose headers are the same bytes: `parse(data)` is
+    `parse_file(data, restart=restart, samplings=samplings)` for every input -- the same ParsedFile field for field, or the same
+    Unsupported with the same message -- but the marker walk runs once per distinct `header_key`.  A file that starts with a key the
+    cache has met takes size, tables, sampling and the scan's offset from that key's entry (the walk reads nothing behind the key, so it
+    would find the same) and runs only the per-file half: the EOI check, the marker-in-scan search, the restart intervals.  A file
+    whose header the walk refuses leaves no entry and is walked in full every time.
+    The options belong to the cache, not to the call: an entry made under one `restart` / `samplings` cannot answer for another.
+    The ParsedFiles of one header share their `qtab` and `huffman` arrays: read them, do not write them.
+    `parse` may be called from several threads at once (entries are only ever added, under a lock; two threads that meet a new
+    header together both walk it and keep one entry)."""
+
+    def __init__(self, restart: bool = False, samplings: Tuple[str, ...] = ("4:2:0",)) -> None:
+        self.restart, self.samplings = bool(restart), _check_samplings(samplings)
+        self._lock = threading.Lock()
+        self._by_length: Dict[int, Dict[bytes, tuple]] = {}   # len(header_key) -> header_key -> `_walk_header`'s tuple
+
+    def __len__(self) -> int:
+        return sum(len(d) for d in self._by_length.values())
+
+    def parse(self, data: bytes) -> ParsedFile:
+        data = bytes(data)
+        for length, entries in list(self._by_length.items()):   # (a data set has one length, or a few)
+            header = entries.get(data[:length])
+            if header is not None:
+                return _parse_scan(data, *header)
+        header = _walk_header(data, self.restart, self.samplings)
+        with self._lock:
+            self._by_length.setdefault(header[4], {}).setdefault(data[:header[4]], header)
+        return _parse_scan(data, *header)
+
+
+def _check_samplings(samplings) -> Tuple[str, ...]:
     samplings = tuple(samplings)
     if not samplings or any(s not in SAMPLINGS for s in samplings):
         raise ValueError(f"samplings must name members of {SAMPLINGS}, got {samplings!r}")
+    return samplings
+
+
+def _walk_header(data: bytes, restart: bool, samplings: Tuple[str, ...]):
+    """The first half of `parse_file`: the marker segments up to and including SOS -> (h, w, qtab, huffman, the scan's offset, the
+    restart interval in MCUs or 0, sampling).  Depends on nothing behind the scan's offset: a file that starts with the same bytes
+    gives the same answer (what `HeaderCache` rests on)."""
     colour_rule = samplings != ("4:2:0",)
     jfif, adobe = False, None
     sampling = "4:2:0"
-    data = bytes(data)
     interval = 0
     if data[:2] != b"\xff\xd8":
         raise Unsupported("no SOI marker")
@@ -347,6 +392,12 @@ def parse_file(data: bytes, restart: bool = False, samplings: Tuple[str, ...] = 
         elif colour_rule and marker == 0xEE and len(body) >= 12 and body[:5] == b"Adobe":         # (examine_app14: the transform byte)
             adobe = body[11]
         # every other segment (APPn, COM, ...) is skipped
+    return h, w, qtab, huffman, at, interval, sampling
+
+
+def _parse_scan(data: bytes, h: int, w: int, qtab: np.ndarray, huffman: np.ndarray, at: int, interval: int, sampling: str) -> ParsedFile:
+    """The second half of `parse_file`, on the file itself: the EOI check, the marker-in-scan search and, with a restart interval, the
+    RSTn walk and the MCU count check."""
     if data[-2:] != b"\xff\xd9":
         raise Unsupported("no EOI marker at the end of the file")
     end = len(data) - 2

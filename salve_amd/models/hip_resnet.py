@@ -209,6 +209,8 @@ def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: T
 class HipResNet:
     """A compiled verifier on one GPU: immutable device weights inside a library handle + a workspace."""
 
+    IN_HW = (224, 224)   # build_program's default: the only input size the fp16 program is compiled for
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], num_layers: int, device: torch.device, flags: int = 0) -> None:
         """flags: _lib.RESNET_* kernel selection (0 = the product's; the bit-identity tests pass the others)."""
         self.lib = _lib.load()
@@ -241,6 +243,8 @@ class HipResNet:
     def forward_nhwc(self, x: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
         """x: fp16 [B, 224, 224, in_channels] on the device -> fp32 logits [B, num_classes]."""
         assert x.dtype == torch.float16 and x.is_contiguous() and x.shape[-1] == self.in_channels, (x.dtype, x.shape)
+        if x.dim() != 4 or tuple(x.shape[1:3]) != self.IN_HW:   # (the program is compiled for this size: the kernels would read past a smaller x)
+            raise _lib.SalveHipError(f"HipResNet.forward_nhwc takes [B, {self.IN_HW[0]}, {self.IN_HW[1]}, {self.in_channels}] tiles, got {tuple(x.shape)}")
         B = int(x.shape[0])
         need = self.lib.salve_resnet_workspace_bytes(self.handle, B)
         if self._ws is None or self._ws.numel() < need:

@@ -3,7 +3,7 @@
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}] [--decode {host,device}]
-                              [--decode-entropy {image,lanes}]
+                              [--decode-entropy {image,lanes}] [--decode-read-ahead]
                               [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]] [--jpeg-quality Q]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
@@ -18,6 +18,8 @@ read once per pass, so the host never waits for the device between batches; the 
 the GPU in one call and makes the batch with one tile launch (salve_amd/train_files.py); the default, host, decodes every tile with
 Pillow in the DataLoader.  The batches are the same bits.  --decode-entropy lanes (with --decode device) takes the lane-parallel
 entropy stage, which also decodes tiles written with restart intervals on the GPU; the same bits again.
+--decode-read-ahead (with --decode device) reads the next two batches' files and decodes the next batch on a second stream while the
+current batch trains: the same bits once more, one more batch of decoded tiles and one more decode workspace on the device.
 --render-from DIR trains from panoramas instead of a rendered dataset: DIR holds panos_rgb.npy, panos_depth.npy, train.json and
 val.json, the batches are rendered and augmented on the GPU (salve_amd/train_render.py); data_root is not read.
 A configuration whose modalities include "layout" also needs DIR/layouts.npz: the layouts are posed and drawn on the GPU.
@@ -62,6 +64,8 @@ def main(argv=None) -> None:
                     help="host (default: Pillow decodes each tile in the DataLoader) or device (whole batches of JPEG tiles decoded on the GPU)")
     ap.add_argument("--decode-entropy", choices=("image", "lanes"), default="image",
                     help="--decode device: image (default: one wavefront per tile) or lanes (a lane per 128 bytes of scan; also takes tiles with restart intervals)")
+    ap.add_argument("--decode-read-ahead", action="store_true",
+                    help="--decode device: read the next batches' tiles and decode the next batch beside the training step (the same batches)")
     ap.add_argument("--render-from", default=None, metavar="DIR",
                     help="render the training batches on the GPU from DIR/panos_rgb.npy, panos_depth.npy, train.json, val.json")
     ap.add_argument("--identity", choices=("kept", "batch"), default=None,
@@ -76,6 +80,8 @@ def main(argv=None) -> None:
     training._check_head(a.head)
     if a.decode_entropy != "image" and a.decode != "device":
         raise SystemExit("--decode-entropy selects the entropy stage of --decode device")
+    if a.decode_read_ahead and a.decode != "device":
+        raise SystemExit("--decode-read-ahead reads ahead for --decode device")
     if a.decode == "device" and a.render_from is not None:
         raise SystemExit("--decode device reads the rendered dataset on disk: it cannot be combined with --render-from DIR (which reads no tile file)")
     if a.jpeg_quality is not None:
@@ -132,7 +138,7 @@ def main(argv=None) -> None:
                                           norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality)
     else:
         results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
-                                 head=a.head, decode=a.decode, entropy=a.decode_entropy)
+                                 head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead)
     logging.info(f"results in {out}: {results}")
 
 

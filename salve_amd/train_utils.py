@@ -68,24 +68,27 @@ def get_img_transform_list(args: TrainingConfig, split: str):
     return get_val_test_transform(args)
 
 
-def get_dataloader(args: TrainingConfig, split: str, decode: str = "host", entropy: str = "image"):
+def get_dataloader(args: TrainingConfig, split: str, decode: str = "host", entropy: str = "image", read_ahead: bool = False):
     """DataLoader over the rendered tiles of a split (salve/train_utils.py:183-203): no shuffling, no dropped batch for
     val / test.  The transform launches GPU kernels, so tiles are decoded in the calling process (num_workers = 0)
     instead of in `args.workers` forked workers.  decode="device": a train_files.TileFileLoader over the same examples -- the same
-    tuples, whole batches of JPEG tiles decoded on the device and tiled in one launch; entropy: "image" (default) or "lanes", TileFileLoader's."""
+    tuples, whole batches of JPEG tiles decoded on the device and tiled in one launch; entropy: "image" (default) or "lanes", TileFileLoader's;
+    read_ahead: TileFileLoader's (the next batches read and decoded beside the current one)."""
     from salve_amd.dataset.zind_data import ZindData
 
     if decode not in ("host", "device"):
         raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
     if entropy != "image" and decode != "device":
         raise ValueError(f'entropy={entropy!r} selects the device decoder\'s entropy stage: it needs decode="device"')
+    if read_ahead and decode != "device":
+        raise ValueError('read_ahead=True reads the device decoder\'s next batch ahead: it needs decode="device"')
     if decode == "device":
         from salve_amd.train_files import TileFileLoader
 
         get_img_transform_list(args, split)   # (the host path's refusals)
         data = ZindData(split=split, transform=None, args=args)
         return TileFileLoader(torch.device("cuda", torch.cuda.current_device()), data.data_list, args.batch_size,
-                              (args.resize_h, args.resize_w), (args.train_h, args.train_w), entropy=entropy)
+                              (args.resize_h, args.resize_w), (args.train_h, args.train_w), entropy=entropy, read_ahead=read_ahead)
 
     data = ZindData(split=split, transform=get_img_transform_list(args, split), args=args)
     return torch.utils.data.DataLoader(data, batch_size=args.batch_size, shuffle=False, num_workers=0, drop_last=False)

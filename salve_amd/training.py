@@ -144,16 +144,18 @@ def _check_decode(decode: str) -> None:
         raise ValueError(f"decode must be one of {DECODES}, got {decode!r}")
 
 
-def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32", entropy: str = "image"):
+def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32", entropy: str = "image",
+                         read_ahead: bool = False):
     """`get_dataloader`'s examples in its order as a train_files.TileFileSource: whole batches of the data set's JPEG tiles decoded
-    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy: TileFileSource's."""
+    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy, read_ahead: TileFileSource's."""
     from salve_amd.dataset.zind_data import ZindData
     from salve_amd.train_files import TileFileSource
 
     get_train_transform(args)   # (the refusals of the host path: photometric augmentation, crop-with-padding)
     data = ZindData(split=split, transform=None, args=args)
     return TileFileSource(torch.device("cuda", torch.cuda.current_device()), data.data_list, batch_size=args.batch_size, precision=precision,
-                          split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w), entropy=entropy)
+                          split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w), entropy=entropy,
+                          read_ahead=read_ahead)
 
 
 def get_dataloader(args: TrainingConfig, split: str, seed: int = 0) -> torch.utils.data.DataLoader:
@@ -260,7 +262,8 @@ def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_l
 
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
-          norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image") -> Dict[str, list]:
+          norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image",
+          read_ahead: bool = False) -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
@@ -271,7 +274,9 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     decode: "host" (default: Pillow decodes every tile in the DataLoader) or "device": the same examples in the same order with the
     same draws, whole batches of JPEG tiles decoded on the device (train_files.TileFileSource) -- the same batches, bit for bit.
     entropy (decode="device" only): "image" (default) or "lanes", the lane-parallel entropy stage, which also keeps files with restart
-    intervals on the device -- the same batches again."""
+    intervals on the device -- the same batches again.
+    read_ahead (decode="device" only; default False): the next batches' files are read, and the next batch decoded on a side stream,
+    while the current batch trains (TileFileSource(read_ahead=True)) -- the same batches once more."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
@@ -279,12 +284,14 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     _check_decode(decode)
     if entropy != "image" and decode != "device":
         raise ValueError(f'entropy={entropy!r} selects the device decoder\'s entropy stage: it needs decode="device"')
+    if read_ahead and decode != "device":
+        raise ValueError('read_ahead=True reads the device decoder\'s next batch ahead: it needs decode="device"')
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
     if decode == "device":
-        with get_tile_file_source(args, "train", seed, precision, entropy) as train_source, \
-                get_tile_file_source(args, "val", seed, precision, entropy) as val_source:
+        with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead) as train_source, \
+                get_tile_file_source(args, "val", seed, precision, entropy, read_ahead) as val_source:
             return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)   # (leaving ends their reader threads)
     return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim, head)
 

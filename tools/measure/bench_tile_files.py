@@ -17,6 +17,7 @@ were written moments before they are read: the reads come from the page cache, n
     python tools/measure/bench_tile_files.py --decode-only [--n 1024] [--reps 5]      # jpeg_decode alone on n tiles, by events
     python tools/measure/bench_tile_files.py --decode-only --entropy both --n 1024,256,64   # ... both entropy stages
     python tools/measure/bench_tile_files.py --panos 32 [--reps 5]                    # 2048 x 1024 panoramas: the entropy stages, Pillow, PanoStore.load
+    python tools/measure/bench_tile_files.py --read-ahead [--examples 2048] [--reps 3] [--write-workers 16]   # the pipelined feed
 
 --entropy image (default) is salve_bev_jpeg_decode's one wavefront per tile, lanes the lane-parallel stage (salve_bev_jpeg_decode_lanes);
 the feed benchmark takes one of them, --decode-only and --panos also `both` (the same data through one, then the other).
@@ -28,12 +29,22 @@ ingest.PanoStore.load end to end, decode="host" against decode="device", by the 
 jpeg_pixels_kernel, can be told apart by `rocprofv3 --kernel-trace --stats -- python tools/measure/bench_tile_files.py --decode-only
 --reps 2`, a run of its own.)  Calling the stages apart needs the coefficients to stay in the stream's JPEG workspace, which the
 rasteriser's three JPEG methods share: nothing here calls one of them between an entropy stage and its inverse stage.
+--read-ahead times the feed THROUGH a training step that consumes it (ResNet-152, ceiling + floor, batch 256, bf16, HIP norm, optimiser
+and head): the host clock per batch from one device synchronise behind a step to the next, over epochs of at least eight batches, the
+median of an epoch's batches after its first two.  Four feeds, both entropy stages, alternating within each repeat: the serial feed with
+the full marker walk per file (what a checkout from before HeaderCache and read_ahead does: the baseline), the serial feed, the
+pipelined feed (read_ahead=True), and the same step on one resident batch (no feed: the floor).  Beside them the epoch's wall time with
+no synchronise between batches (the way `training.run_epoch` drives a HIP head), and the parse thread-seconds per batch with and without
+HeaderCache.  The pipelined feed counts as faster only if its median lies below the baseline's by more than the spread of the baseline's
+repeats; the verdict line says which.  The first epoch of every feed warms up (pinned buffers, workspaces, code objects) and carries the
+check that the pipelined batches are the serial ones.
 Medians (min .. max); run the command twice for the spread.
 """
 
 from __future__ import annotations
 
 import argparse
+import concurrent.futures
 import random
 import statistics
 import sys
@@ -97,8 +108,6 @@ class TimedSource(TileFileSource):
         self._per_file.append((t1 - t0, time.perf_counter() - t1))
         return data, parsed
 
-    _read_one_restart = _read_one
-
     def _read(self, paths):
         self._per_file = []
         out = self._clock("file read + parse: wall time of the thread pool (host)", lambda: super(TimedSource, self)._read(paths))
@@ -126,20 +135,34 @@ def _tile(kind: str, seed: int) -> np.ndarray:
     return np.roll(img, (7 * seed) % 97, axis=1) if kind == "layout" else img   # (layout has no seed of its own)
 
 
-def write_dataset(root: Path, examples: int) -> None:
-    """`examples` pairs of building 1208 (train split), alternating positive / negative; ceiling tiles are discs, floor tiles
-    alternate disc / layout."""
+def _write_example(root: Path, i: int) -> None:
     from PIL import Image
 
-    for i in range(examples):
-        label = "gt_alignment_approx" if i % 2 == 0 else "incorrect_alignment"
-        d = root / label / "1208"
-        d.mkdir(parents=True, exist_ok=True)
-        for s, surface in enumerate(("ceiling", "floor")):
-            for k, (room, pano) in enumerate(((4, 5), (7, 8))):
-                kind = "layout" if (surface == "floor" and i % 2) else "disc"
-                name = f"pair_{i}___door_0_0_rotated_{surface}_rgb_floor_01_partial_room_{room:02d}_pano_{pano}.jpg"
-                Image.fromarray(_tile(kind, 4 * i + 2 * s + k)).save(d / name, quality=75)
+    label = "gt_alignment_approx" if i % 2 == 0 else "incorrect_alignment"
+    d = root / label / "1208"
+    d.mkdir(parents=True, exist_ok=True)
+    for s, surface in enumerate(("ceiling", "floor")):
+        for k, (room, pano) in enumerate(((4, 5), (7, 8))):
+            kind = "layout" if (surface == "floor" and i % 2) else "disc"
+            name = f"pair_{i}___door_0_0_rotated_{surface}_rgb_floor_01_partial_room_{room:02d}_pano_{pano}.jpg"
+            Image.fromarray(_tile(kind, 4 * i + 2 * s + k)).save(d / name, quality=75)
+
+
+def _write_examples(root: Path, lo: int, hi: int) -> None:
+    for i in range(lo, hi):
+        _write_example(root, i)
+
+
+def write_dataset(root: Path, examples: int, workers: int = 1) -> None:
+    """`examples` pairs of building 1208 (train split), alternating positive / negative; ceiling tiles are discs, floor tiles
+    alternate disc / layout.  workers > 1: that many processes write a share each (they never touch the device)."""
+    if workers <= 1:
+        return _write_examples(root, 0, examples)
+    import multiprocessing
+
+    share = -(-examples // (4 * workers))
+    with concurrent.futures.ProcessPoolExecutor(max_workers=workers, mp_context=multiprocessing.get_context("spawn")) as pool:
+        list(pool.map(_write_examples, *zip(*[(root, lo, min(lo + share, examples)) for lo in range(0, examples, share)])))
 
 
 def config(root: Path, batch: int) -> TrainingConfig:
@@ -156,7 +179,7 @@ def bench_feed(a) -> None:
         root = keep or Path(tmp) / "bev"
         if not (root / "gt_alignment_approx").exists():
             t = time.perf_counter()
-            write_dataset(root, a.examples)
+            write_dataset(root, a.examples, a.write_workers)
             print(f"wrote {4 * a.examples} tiles in {time.perf_counter() - t:.1f} s")
         args = config(root, a.batch)
         sizes = [p.stat().st_size for p in root.rglob("*.jpg")]
@@ -215,6 +238,125 @@ def bench_feed(a) -> None:
         print(f"first batch of the epoch, DataLoader against TileFileSource (seed 0): {'bit-identical' if same else 'DIFFERENT'}")
         if not same:
             raise SystemExit(1)
+
+
+class FeedSource(TileFileSource):
+    """TileFileSource whose reader threads clock their two halves per file; `parse_s` / `read_s`: thread-seconds summed per batch.
+    cache=False parses every file with the full marker walk (jpeg.parse_file), as the source did before HeaderCache."""
+
+    def __init__(self, *a, cache=True, **kw):
+        super().__init__(*a, **kw)
+        self.cache, self.parse_s, self.read_s = cache, [], []
+
+    def _read_one(self, path):
+        t0 = time.perf_counter()
+        with open(path, "rb") as f:
+            data = f.read()
+        t1 = time.perf_counter()
+        try:
+            parsed = self.headers.parse(data) if self.cache else jpeg.parse_file(data, restart=self.entropy == "lanes")
+        except jpeg.Unsupported:
+            parsed = None
+        return data, parsed, t1 - t0, time.perf_counter() - t1
+
+    def _read(self, paths):   # (one batch at a time, in the iterating thread or in the one thread that packs)
+        out = super()._read(paths)
+        self.read_s.append(sum(r[2] for r in out))
+        self.parse_s.append(sum(r[3] for r in out))
+        return [r[:2] for r in out]
+
+
+def bench_read_ahead(a) -> None:
+    from salve_amd.evaluate import DeviceClassMeter
+
+    keep = Path(a.keep) if a.keep else None
+    with tempfile.TemporaryDirectory() as tmp:
+        root = keep or Path(tmp) / "bev"
+        if not (root / "gt_alignment_approx").exists():
+            t = time.perf_counter()
+            write_dataset(root, a.examples, a.write_workers)
+            print(f"wrote {4 * a.examples} tiles in {time.perf_counter() - t:.1f} s ({a.write_workers} process(es))")
+        args = config(root, a.batch)
+        sizes = [p.stat().st_size for p in root.rglob("*.jpg")]
+        data = ZindData(split="train", transform=None, args=args)
+        per_epoch = len(data.data_list) // a.batch
+        print(f"{len(sizes)} files, {np.mean(sizes) / 1024:.1f} KB on average ({min(sizes) / 1024:.1f} .. {max(sizes) / 1024:.1f}); batch {a.batch} = "
+              f"{4 * a.batch} tiles, {per_epoch} batches per epoch")
+        if per_epoch < 8:
+            raise SystemExit(f"--read-ahead wants at least eight batches per epoch for a steady state: --examples {8 * a.batch} or more")
+        torch.manual_seed(0)
+        model = training.get_model(args, "bf16", "hip", "hip").train()
+        optimizer = training.get_optimizer(args, model, "hip")
+        meter = DeviceClassMeter(args.num_ce_classes, DEV)
+
+        def step(x, y):
+            _, loss = training.cross_entropy_forward_packed(model, "train", x, y, meters=meter, accumulate_loss=True)
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+
+        def epoch(batches, synchronise=True):
+            """Host ms per batch, from the synchronise behind one step to the one behind the next -- or, free-running, the epoch's ms
+            per batch with one synchronise at its end -- and a checksum of the batches' bits."""
+            ms, sums = [], []
+            torch.cuda.synchronize()
+            start = t = time.perf_counter()
+            for x, y in batches:
+                sums.append(x.view(torch.int16 if x.dtype == torch.bfloat16 else torch.int32).sum(dtype=torch.int64))
+                step(x, y)
+                if synchronise:
+                    torch.cuda.synchronize()
+                    now = time.perf_counter()
+                    ms.append((now - t) * 1e3)
+                    t = now
+            torch.cuda.synchronize()
+            if not synchronise:
+                ms = [(time.perf_counter() - start) * 1e3 / max(1, len(sums))]
+            return ms, [int(s) for s in sums]
+
+        steady = lambda ms: ms[2:]
+        for entropy in ("image", "lanes"):
+            kw = dict(batch_size=a.batch, precision="bf16", split="train", seed=0, entropy=entropy)
+            feeds = {"serial, full marker walk (baseline)": FeedSource(DEV, data.data_list, cache=False, **kw),
+                     "serial": FeedSource(DEV, data.data_list, **kw),
+                     "read_ahead": FeedSource(DEV, data.data_list, read_ahead=True, **kw)}
+            print(f"---- entropy={entropy}")
+            first = {}
+            for name, src in feeds.items():   # warm-up epoch: pinned buffers, workspaces, code objects; the same seeds, so the same batches
+                random.seed(0)
+                _, first[name] = epoch(src)
+                src.parse_s, src.read_s = [], []
+            same = first["read_ahead"] == first["serial"] == first["serial, full marker walk (baseline)"]
+            print(f"first epoch, the three feeds' batches by checksum: {'bit-identical' if same else 'DIFFERENT'}")
+            if not same:
+                raise SystemExit(1)
+            resident = feeds["serial"].batch(np.arange(a.batch), feeds["serial"].draws(a.batch))
+            feeds["serial"]._check_epoch("bench_tile_files")
+            feeds["serial"].parse_s, feeds["serial"].read_s = [], []
+            medians = {name: [] for name in list(feeds) + ["resident batch (no feed)"]}
+            free = {name: [] for name in feeds}
+            for r in range(a.reps):
+                for name, src in feeds.items():   # alternating: one epoch of each feed per repeat
+                    ms, _ = epoch(src)
+                    medians[name].append(statistics.median(steady(ms)))
+                    print(f"  repeat {r}  {name:<38} {_stat(steady(ms))}")
+                ms, _ = epoch([resident] * per_epoch)
+                medians["resident batch (no feed)"].append(statistics.median(steady(ms)))
+                print(f"  repeat {r}  {'resident batch (no feed)':<38} {_stat(steady(ms))}")
+                for name, src in feeds.items():
+                    free[name].append(epoch(src, synchronise=False)[0][0])
+            for name, m in medians.items():
+                print(f"{name:<40} median of {len(m)} repeats' medians {statistics.median(m):8.2f} ms per batch  ({min(m):.2f} .. {max(m):.2f})")
+            for name, m in free.items():
+                print(f"{name:<40} free-running epoch {statistics.median(m):8.2f} ms per batch  ({min(m):.2f} .. {max(m):.2f})")
+            for name, src in feeds.items():
+                print(f"{name:<40} parse, thread-seconds per batch {_stat([v * 1e3 for v in src.parse_s])};  read {_stat([v * 1e3 for v in src.read_s])}")
+            base = medians["serial, full marker walk (baseline)"]
+            gain, spread = statistics.median(base) - statistics.median(medians["read_ahead"]), max(base) - min(base)
+            print(f"verdict, entropy={entropy}: read_ahead is {gain:.2f} ms per batch below the baseline, whose repeats spread over {spread:.2f} ms: "
+                  f"{'FASTER' if gain > spread else 'NOT FASTER'}")
+            for src in feeds.values():
+                src.close()
 
 
 def _time_stages(ras, args, kw, reps):
@@ -361,9 +503,13 @@ if __name__ == "__main__":
     ap.add_argument("--entropy", choices=("image", "lanes", "both"), default="image")
     ap.add_argument("--panos", type=int, default=0, help="time this many 2048 x 1024 panoramas instead of tiles")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--read-ahead", action="store_true", help="time the serial and the pipelined feed through a ResNet-152 training step")
+    ap.add_argument("--write-workers", type=int, default=1, help="processes that write the data set")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_tile_files needs the MI355X: there is nothing to time without it")
     if a.entropy == "both" and not (a.decode_only or a.panos):
         raise SystemExit("--entropy both compares the two stages on the same data: with --decode-only or --panos")
-    bench_panos(a) if a.panos else bench_decode(a) if a.decode_only else bench_feed(a)
+    if a.read_ahead and a.examples < 8 * a.batch:
+        a.examples = 8 * a.batch   # r10's workload, enlarged to eight batches per epoch
+    bench_read_ahead(a) if a.read_ahead else bench_panos(a) if a.panos else bench_decode(a) if a.decode_only else bench_feed(a)
