@@ -1,0 +1,72 @@
+"""What the two training feeds share (salve_amd.train_render.RenderedTrainSource, salve_amd.train_files.TileFileSource): the epoch's
+order, the augmentation draws and their table, the one upload of a batch's host tables, and the refusals of the arguments both take.
+Shuffle order and draws are those of `training.get_dataloader` + `transforms.TrainTransform`: the order of a
+`DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random`.
+Nothing here needs a device."""
+
+from __future__ import annotations
+
+from typing import List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from salve_amd import _lib
+
+SPLITS = ("train", "val")   # the orders `plan_epoch` knows; a source may name more splits and map them onto these
+
+Draw = Tuple[int, int, bool, bool]   # (crop_y, crop_x, hflip, vflip)
+
+
+def check_arguments(batch_size: int, split: Optional[str] = None, splits: Sequence[str] = SPLITS, precision: Optional[str] = None) -> None:
+    """The refusals the sources share; `splits`: the caller's own tuple.  None: the caller takes no such argument."""
+    if split is not None and split not in splits:
+        raise ValueError(f"split must be one of {tuple(splits)}, got {split!r}")
+    if precision is not None and precision not in ("fp32", "bf16"):
+        raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+    if int(batch_size) <= 0:
+        raise ValueError(f"batch size must be positive, got {batch_size}")
+
+
+def plan_epoch(n: int, batch: int, split: str, gen: Optional[torch.Generator] = None) -> List[np.ndarray]:
+    """Example indices of every batch of one epoch.  "train": the order `training.get_dataloader` gives its examples -- a
+    DataLoader(shuffle=True, generator=gen, drop_last=True) over the indices themselves, so that every draw the loader and its
+    sampler take from `gen` is taken here too -- the last partial batch dropped.  "val": table order, nothing dropped."""
+    check_arguments(batch, split)
+    if split == "val":
+        return [np.arange(lo, min(lo + batch, n), dtype=np.int64) for lo in range(0, n, batch)]
+    if gen is None:
+        raise ValueError('plan_epoch(split="train") needs the seeded torch.Generator')
+    if n == 0:
+        return []
+    loader = torch.utils.data.DataLoader(range(n), batch_size=batch, shuffle=True, generator=gen, num_workers=0, drop_last=True)
+    return [b.numpy().astype(np.int64) for b in loader]
+
+
+def batches_per_epoch(n: int, batch: int, split: str) -> int:
+    return n // batch if split == "train" else (n + batch - 1) // batch
+
+
+def draws(tf, split: str, n: int) -> List[Draw]:
+    """train: `TrainTransform.draw()` per example, from Python's `random`; every other split: the centre crop, no flips
+    (ValTestTransform)."""
+    if split == "train":
+        return [tf.draw() for _ in range(n)]
+    off = (tf.resize - tf.crop) // 2
+    return [(off, off, False, False)] * n
+
+
+def aug_table(draws: Sequence[Draw]) -> np.ndarray:
+    """salve_tile_aug_t rows of a batch's draws: TILE_AUG_DTYPE [B]."""
+    aug = np.zeros(len(draws), dtype=_lib.TILE_AUG_DTYPE)
+    for k, (cy, cx, hflip, vflip) in enumerate(draws):
+        aug[k] = (cy, cx, (_lib.TILE_HFLIP if hflip else 0) | (_lib.TILE_VFLIP if vflip else 0), 0)
+    return aug
+
+
+def upload_tables(parts: Sequence[np.ndarray], device) -> Tuple[torch.Tensor, np.ndarray]:
+    """A batch's host tables in ONE upload: (uint8 buffer on `device` holding them one behind the other, byte offsets [len(parts) + 1]);
+    table k is buf[offsets[k]:offsets[k + 1]].  Nothing is padded: the caller orders the tables so that each starts where its rows
+    may start."""
+    raw = [np.ascontiguousarray(p).reshape(-1).view(np.uint8) for p in parts]
+    return torch.from_numpy(np.concatenate(raw)).to(device), np.cumsum([0] + [r.nbytes for r in raw])

@@ -48,10 +48,10 @@ from typing import Callable, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from salve_amd import _lib, jpeg, status, tracing
+from salve_amd import _lib, jpeg, status, tracing, train_feed
 from salve_amd.common.bevparams import BEVParams
 from salve_amd.rasteriser import BevRasteriser
-from salve_amd.train_render import batches_per_epoch, plan_epoch
+from salve_amd.train_feed import batches_per_epoch, plan_epoch
 from salve_amd.transforms import TrainTransform
 from salve_amd.utils import image_io
 
@@ -428,12 +428,7 @@ class TileFileSource(_TileFiles):
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int = 256, precision: str = "fp32", split: str = "train", seed: int = 0,
                  resize_hw: Tuple[int, int] = (234, 234), crop_hw: Tuple[int, int] = (224, 224), read_threads: int = MAX_READ_THREADS,
                  entropy: str = "image", read_ahead: bool = False) -> None:
-        if split not in SPLITS:
-            raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
-        if int(batch_size) <= 0:
-            raise ValueError(f"batch size must be positive, got {batch_size}")
+        train_feed.check_arguments(batch_size, split, SPLITS, precision)
         super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead)
         self.split, self.batch_size = split, int(batch_size)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
@@ -447,11 +442,8 @@ class TileFileSource(_TileFiles):
         return batches_per_epoch(len(self.data_list), self.batch_size, "train" if self.split == "train" else "val")
 
     def draws(self, n: int) -> List[Tuple[int, int, bool, bool]]:
-        """train: `TrainTransform.draw()` per example, from Python's `random`; val / test: the centre crop, no flips."""
-        if self.split == "train":
-            return [self.tf.draw() for _ in range(n)]
-        off = (self.tf.resize - self.tf.crop) // 2
-        return [(off, off, False, False)] * n
+        """One draw per example of a batch (`train_feed.draws`)."""
+        return train_feed.draws(self.tf, self.split, n)
 
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]]) -> Tuple[torch.Tensor, torch.Tensor]:
         """Examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  Serial, whatever `read_ahead`."""
@@ -460,22 +452,26 @@ class TileFileSource(_TileFiles):
             raise ValueError(f"{len(idx)} examples, {len(draws)} draws")
         return self._tile(idx, draws, *self._load(self._paths(idx)))
 
-    def _tile(self, idx: np.ndarray, draws, images: torch.Tensor, position: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The batch from its decoded images: the job tables in ONE upload, ONE tile launch, on the current stream."""
+    def tile_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], position: np.ndarray):
+        """The host tables of one batch whose example b's images lie at `position[E b : E (b + 1)]` of the decoded array, in the order of
+        its tuple: (tile jobs [2][B][K], draws [B]).  Host arithmetic only."""
         B, K = len(idx), self.per_sample
+        if len(draws) != B:
+            raise ValueError(f"{B} examples, {len(draws)} draws")
         H, W = self.ras.bev_hw
-        pos = position.reshape(B, K, 2)
+        pos = np.asarray(position).reshape(B, K, 2)
         jobs = np.zeros((2, B, K), dtype=_lib.TILE_JOB_DTYPE)   # [first | second image of a pair][sample][pair]
         jobs["bev_offset"][0], jobs["bev_offset"][1] = pos[:, :, 0] * (H * W), pos[:, :, 1] * (H * W)
         jobs["slot"][:] = np.arange(B, dtype=np.int64)[None, :, None]
         jobs["chan"][0] = 6 * np.arange(K)[None, :]
         jobs["chan"][1] = 6 * np.arange(K)[None, :] + 3
-        aug = np.zeros(B, dtype=_lib.TILE_AUG_DTYPE)
-        for k, (cy, cx, hflip, vflip) in enumerate(draws):
-            aug[k] = (cy, cx, (_lib.TILE_HFLIP if hflip else 0) | (_lib.TILE_VFLIP if vflip else 0), 0)
-        parts = [jobs.view(np.uint8).reshape(-1), aug.view(np.uint8), self.labels[idx].view(np.uint8)]   # ONE upload of the tables
-        buf = torch.from_numpy(np.concatenate(parts)).to(self.device)
-        o = np.cumsum([0] + [p.nbytes for p in parts])
+        return jobs, train_feed.aug_table(draws)
+
+    def _tile(self, idx: np.ndarray, draws, images: torch.Tensor, position: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The batch from its decoded images: the tables in ONE upload, ONE tile launch, on the current stream."""
+        B, K = len(idx), self.per_sample
+        jobs, aug = self.tile_tables(idx, draws, position)
+        buf, o = train_feed.upload_tables([jobs, aug, self.labels[idx]], self.device)
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
         self._tile_launch(images, buf[:o[1] // 2], buf[o[1] // 2:o[1]], K, buf[o[1]:o[2]], B, out)
         return out, buf[o[2]:o[3]].view(torch.int64).view(B, 1)
@@ -506,8 +502,7 @@ class TileFileLoader(_TileFiles):
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int, resize_hw: Tuple[int, int], crop_hw: Tuple[int, int],
                  read_threads: int = MAX_READ_THREADS, entropy: str = "image", read_ahead: bool = False) -> None:
-        if int(batch_size) <= 0:
-            raise ValueError(f"batch size must be positive, got {batch_size}")
+        train_feed.check_arguments(batch_size)
         super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead)
         self.batch_size = int(batch_size)
 

@@ -15,59 +15,37 @@ sample.  Layout alone renders no texture map and uploads no panorama.
 
 Two opt-in arguments take the feed beyond panorama sets that fit the device.  `identity="batch"` keeps no identity image per
 panorama: the identity renders of the batch's distinct second panoramas ride in the batch's own scatter / densify launch pair, behind
-the posed renders.  `resident_panos=N` keeps a pool of N panorama slots on the device: `PanoCache` plans, batch by batch, which
+the posed renders.  `resident_panos=N` keeps a pool of N panorama slots on the device (salve_amd.pano_pool.PanoPool): `PanoCache` plans, batch by batch, which
 panoramas of the host arrays (np.memmap included) are uploaded into which slots -- the victim is the panorama whose next use in the
 epoch lies furthest ahead -- and `BevRasteriser.update_panos` rebuilds the panorama index of the written slots only.  `prefetch=True`
 (with a pool) does that one batch ahead, off the training step's path: worker threads gather the next batch's missed rows and the
 copies, slot writes and index update run on a copy stream of the pool's own while the current batch trains.
 
-Shuffle order and augmentation draws are those of `training.get_dataloader` + `transforms.TrainTransform`: the order of a
-`DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random`.
-The planning functions (`plan_epoch`, `plan_examples`, `check_launch`, `PanoCache`, `epoch_next_use`) are pure and need no device.
+Shuffle order and augmentation draws are those of `training.get_dataloader` + `transforms.TrainTransform` (salve_amd.train_feed, shared
+with the tile-file feed).  The planning functions are pure and need no device: `plan_examples` and `check_launch` here, `plan_epoch`
+(train_feed), `PanoCache` and `epoch_next_use` (pano_pool) -- the moved names still resolve in this module.
 """
 
 from __future__ import annotations
 
+import contextlib
 import json
-import time
-from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from salve_amd import _lib, status, tracing
+from salve_amd import _lib, status, tracing, train_feed
+from salve_amd.pano_pool import MAX_GATHER_THREADS, NEVER, PanoCache, PanoPool, epoch_next_use  # noqa: F401  (NEVER: re-exported)
 from salve_amd.pipeline import surfaces_for
 from salve_amd.rasteriser import SURFACES, BevRasteriser, pack_hypotheses
 from salve_amd.synthetic import HypothesisTable
+from salve_amd.train_feed import SPLITS, batches_per_epoch, plan_epoch
 from salve_amd.transforms import TrainTransform
 
 MAX_RENDERS_PER_CALL = 65535   # include/salve_hip.h: renders per scatter / densify call
 MAX_LAYOUTS_PER_LAUNCH = 65535  # include/salve_hip.h: images per salve_layout_pose / salve_layout_rasterise call
-SPLITS = ("train", "val")
-
-
-def plan_epoch(n: int, batch: int, split: str, gen: Optional[torch.Generator] = None) -> List[np.ndarray]:
-    """Example indices of every batch of one epoch.  "train": the order `training.get_dataloader` gives its examples -- a
-    DataLoader(shuffle=True, generator=gen, drop_last=True) over the indices themselves, so that every draw the loader and its
-    sampler take from `gen` is taken here too -- the last partial batch dropped.  "val": table order, nothing dropped."""
-    if split not in SPLITS:
-        raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
-    if batch <= 0:
-        raise ValueError(f"batch size must be positive, got {batch}")
-    if split == "val":
-        return [np.arange(lo, min(lo + batch, n), dtype=np.int64) for lo in range(0, n, batch)]
-    if gen is None:
-        raise ValueError('plan_epoch(split="train") needs the seeded torch.Generator')
-    if n == 0:
-        return []
-    loader = torch.utils.data.DataLoader(range(n), batch_size=batch, shuffle=True, generator=gen, num_workers=0, drop_last=True)
-    return [b.numpy().astype(np.int64) for b in loader]
-
-
-def batches_per_epoch(n: int, batch: int, split: str) -> int:
-    return n // batch if split == "train" else (n + batch - 1) // batch
 
 
 def check_launch(batch_size: int, n_surfaces: int, identity_rows: int = 0, layout: bool = False) -> None:
@@ -114,125 +92,6 @@ def plan_examples(hyp: HypothesisTable, is_match, n_panos: int) -> Dict[str, np.
 
 
 IDENTITIES = ("kept", "batch")
-MAX_GATHER_THREADS = 8   # prefetch: host threads that gather a batch's missed rows (a fixed small number, never the machine's CPU count)
-NEVER = np.iinfo(np.int64).max   # next use of a panorama the rest of the epoch does not name
-
-
-def epoch_next_use(batch_panos: Sequence[np.ndarray], n_panos: int) -> Tuple[np.ndarray, List[np.ndarray]]:
-    """The next-use bookkeeping of one epoch whose batches name the DISTINCT panoramas `batch_panos[b]`: (`first`, `after`).
-    first[p] is the first batch that names panorama p (NEVER if none does), after[b][k] the next batch behind b that names
-    batch_panos[b][k] again.  A caller that walks the epoch keeps `next_use = first.copy()` and sets
-    `next_use[batch_panos[b]] = after[b]` once batch b is planned: next_use[p] is then, for every panorama batch b + 1 does not
-    name, the batch of its next use -- what `PanoCache.plan` ranks its victims by."""
-    nxt = np.full(n_panos, NEVER, dtype=np.int64)
-    after: List[np.ndarray] = [np.empty(0, dtype=np.int64)] * len(batch_panos)
-    for b in range(len(batch_panos) - 1, -1, -1):
-        after[b] = nxt[batch_panos[b]].copy()
-        nxt[batch_panos[b]] = b
-    return nxt, after
-
-
-class PanoCache:
-    """Which panorama lives in which slot of a resident pool of `capacity` slots (pure host code).  `plan` makes one batch's
-    panoramas resident: no two panoramas share a slot, a panorama of the current batch is never the victim, the uploads are exactly
-    the misses.  policy "furthest" (the product's): the victim is the resident panorama whose next use lies furthest ahead (one
-    without further use counts as never), ties broken by the lower panorama id -- the epoch's order is known before its first batch.
-    policy "lru" (kept for the test that compares the two): the least recently planned panorama.  Counters: hits, misses,
-    uploaded_bytes (misses x bytes_per_pano)."""
-
-    def __init__(self, n_panos: int, capacity: int, batch_size: int, bytes_per_pano: int = 0, policy: str = "furthest", prefetch: bool = False) -> None:
-        if policy not in ("furthest", "lru"):
-            raise ValueError(f"policy must be 'furthest' or 'lru', got {policy!r}")
-        if n_panos <= 0 or batch_size <= 0:
-            raise ValueError(f"n_panos and batch_size must be positive, got {n_panos} and {batch_size}")
-        need = min(2 * batch_size, n_panos)
-        if prefetch and capacity < min(4 * batch_size, n_panos):
-            # the batch in flight and the batch being uploaded are pinned at once, up to 2 x batch_size panoramas each
-            raise ValueError(f"a pool of {capacity} panorama slots cannot hold two batches: with prefetch the batch in flight and the next one are "
-                             f"pinned at once, batch size {batch_size} names up to {min(4 * batch_size, n_panos)} of the {n_panos} panoramas in two "
-                             f"batches (resident_panos must be at least {min(4 * batch_size, n_panos)})")
-        if capacity < need:
-            raise ValueError(f"a pool of {capacity} panorama slots cannot hold one batch: batch size {batch_size} names up to {need} of the "
-                             f"{n_panos} panoramas at once (resident_panos must be at least {need})")
-        self.n_panos, self.capacity, self.policy, self.bytes_per_pano = int(n_panos), int(min(capacity, n_panos)), policy, int(bytes_per_pano)
-        self.slot_of = np.full(self.n_panos, -1, dtype=np.int64)
-        self.pano_in = np.full(self.capacity, -1, dtype=np.int64)
-        self.last_used = np.zeros(self.n_panos, dtype=np.int64)
-        self.clock = 0
-        self.hits = self.misses = self.uploaded_bytes = 0
-        self._last = None
-
-    def plan(self, batch_pano_ids, next_use: Optional[np.ndarray] = None, keep=None) -> Tuple[np.ndarray, List[Tuple[int, int]]]:
-        """(slot of every entry of `batch_pano_ids`, [(panorama, slot) to upload]) -- the uploads in panorama order.  `next_use`:
-        int64 [n_panos], the batch of every panorama's next use (`epoch_next_use`; None: nothing is known, every panorama counts as
-        never used again).  Entries of the current batch's own panoramas are not read.  `keep`: panorama ids that must not be chosen as
-        victims either (the batch in flight, when this one is planned ahead of it); the ranking of the others is unchanged, and too few
-        victims outside `keep` and the batch is a ValueError, raised before anything is changed."""
-        ids = np.asarray(batch_pano_ids, dtype=np.int64)
-        need = np.unique(ids)
-        if need.size and (int(need[0]) < 0 or int(need[-1]) >= self.n_panos):
-            raise ValueError(f"a batch names panorama {int(need[0]) if int(need[0]) < 0 else int(need[-1])}; the cache covers {self.n_panos}")
-        if need.size > self.capacity:
-            raise ValueError(f"a batch names {need.size} panoramas, the pool has {self.capacity} slots")
-        miss = need[self.slot_of[need] < 0]
-        if keep is not None:
-            kept = np.unique(np.asarray(keep, dtype=np.int64))
-            if kept.size and (int(kept[0]) < 0 or int(kept[-1]) >= self.n_panos):
-                raise ValueError(f"keep names panorama {int(kept[0]) if int(kept[0]) < 0 else int(kept[-1])}; the cache covers {self.n_panos}")
-            pinned = np.union1d(need, kept)
-            room = self.capacity - int((self.slot_of[pinned] >= 0).sum())   # free slots + residents that may be evicted
-            if miss.size > room:
-                raise ValueError(f"a batch misses {miss.size} panoramas, but only {room} of the pool's {self.capacity} slots are free or hold a "
-                                 f"panorama outside this batch and the {kept.size} kept ones: no kept panorama is evicted (a larger pool is needed)")
-        self.clock += 1
-        self.hits += int(need.size - miss.size)
-        self.misses += int(miss.size)
-        self.uploaded_bytes += int(miss.size) * self.bytes_per_pano
-        slots = np.flatnonzero(self.pano_in < 0)[:miss.size]   # free slots first, the lowest first
-        if slots.size < miss.size:
-            mine = np.zeros(self.n_panos, dtype=bool)
-            mine[need] = True
-            if keep is not None:
-                mine[kept] = True
-            cand = self.pano_in[(self.pano_in >= 0) & ~mine[np.maximum(self.pano_in, 0)]]   # resident, not of this batch
-            if self.policy == "lru":
-                order = np.lexsort((cand, self.last_used[cand]))
-            else:
-                far = np.full(cand.size, NEVER, dtype=np.int64) if next_use is None else np.asarray(next_use, dtype=np.int64)[cand]
-                order = np.lexsort((cand, -np.minimum(far, np.int64(2 ** 62))))   # furthest first (never = 2**62), then the lower id
-            victims = cand[order[:miss.size - slots.size]]
-            freed = np.sort(self.slot_of[victims])
-            self.slot_of[victims] = -1
-            slots = np.concatenate([slots, freed])
-        self.slot_of[miss] = slots
-        self.pano_in[slots] = miss
-        self._last = (need, self.last_used[need].copy())   # what `forget` needs to take this plan back
-        self.last_used[need] = self.clock
-        return self.slot_of[ids], [(int(p), int(sl)) for p, sl in zip(miss, slots)]
-
-    def lookup(self, pano_ids) -> np.ndarray:
-        """Slot of every entry of `pano_ids`, all of them resident (planned earlier): no counter moves."""
-        slots = self.slot_of[np.asarray(pano_ids, dtype=np.int64)]
-        if slots.size and int(slots.min()) < 0:
-            raise ValueError("lookup of a panorama that is not resident: plan the batch first")
-        return slots
-
-    def forget(self, uploads: Sequence[Tuple[int, int]]) -> None:
-        """Take back the MOST RECENT `plan` call, whose `uploads` [(panorama, slot)] did not happen: their slots are free again (the
-        victims stay evicted), and hits, misses, uploaded_bytes, the clock and the batch's last-use stamps are what they were before
-        it, so that the state matches what was uploaded and hits + misses still counts the panoramas of the plans that stand."""
-        if self._last is None or any(self.slot_of[p] != sl or self.pano_in[sl] != p for p, sl in uploads) \
-                or not np.isin([p for p, _ in uploads], self._last[0]).all():
-            raise ValueError("forget takes back the most recent plan only, with the uploads that plan returned")
-        need, stamps = self._last
-        for p, sl in uploads:
-            self.slot_of[p], self.pano_in[sl] = -1, -1
-        self.hits -= int(need.size) - len(uploads)
-        self.misses -= len(uploads)
-        self.uploaded_bytes -= len(uploads) * self.bytes_per_pano
-        self.last_used[need] = stamps
-        self.clock -= 1
-        self._last = None
 
 
 class RenderedTrainSource:
@@ -257,10 +116,7 @@ class RenderedTrainSource:
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
                  crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None,
                  prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None) -> None:
-        if split not in SPLITS:
-            raise ValueError(f"split must be one of {SPLITS}, got {split!r}")
-        if precision not in ("fp32", "bf16"):
-            raise ValueError(f"precision must be 'fp32' or 'bf16', got {precision!r}")
+        train_feed.check_arguments(batch_size, split, SPLITS, precision)
         if identity not in IDENTITIES:
             raise ValueError(f"identity must be one of {IDENTITIES}, got {identity!r}")
         if resident_panos is not None:
@@ -295,7 +151,7 @@ class RenderedTrainSource:
         self.lay_base = (0, 0)    # first layout image inside self.bev / self.ref_bev: they lie behind the texture renders
         self.n_panos: Optional[int] = None
         self.examples: Optional[Dict[str, np.ndarray]] = None
-        self.pool: Optional[Dict] = None   # resident_panos: host arrays, PanoCache, pinned staging buffers -- shared by share_panos
+        self.pool: Optional[PanoPool] = None   # resident_panos: host arrays, PanoCache, slots, staging buffers -- shared by share_panos
         self.timers = None   # a list: every launch appends (tag, start event, end event) -- tools/measure/bench_train_feed.py
 
     # ------------------------------------------------------------------ panoramas
@@ -370,21 +226,8 @@ class RenderedTrainSource:
         self._refuse_if_too_large((n_slots + n_rows) * H * W * 5 + n_rows * 12 + index_bytes
                                   + (self._batch_images(n_slots) + self._layout_images(n_slots)) * Hb * Wb * 4,
                                   f"a pool of {n_slots} panorama slots, its index, {'two batches' if self.prefetch else 'one batch'}'s uploads and one batch's BEV images")
-        # zero depth passes neither surface's z filter: an unfilled slot's index entries are empty boxes
-        self.pano_rgb = torch.zeros((n_slots, H, W, 3), dtype=torch.uint8, device=self.device)
-        self.pano_depth = torch.zeros((n_slots, H, W), dtype=torch.int16, device=self.device)
-        index = self.ras.pano_index(self.pano_depth)
-        # the host writes a staging buffer while an earlier copy may still read it: two buffers, an event each, waited on before the overwrite
-        stage = [{"rgb": torch.empty((n_stage, H, W, 3), dtype=torch.uint8).pin_memory(), "depth": torch.empty((n_stage, H, W), dtype=torch.int16).pin_memory(),
-                  "event": None} for _ in range(2)]
-        self.pool = {"rgb": rgb, "depth": depth, "cache": cache, "stage": stage, "turn": 0, "uploads": 0}
-        if self.prefetch and self.surfaces:
-            # the pool owns its index buffer and its copy stream: the uploads of the batch ahead run there, beside the step.
-            # "done": the event behind the last batch's last launch; "pending": the upload job in flight, if any; "iteration": the token of
-            # the iteration that plans the pool; "wait_s": host seconds the loop has waited for upload jobs so far
-            for st in stage:
-                st["slots"] = torch.empty(n_stage, dtype=torch.int32).pin_memory()
-            self.pool.update(index=index, stream=torch.cuda.Stream(self.device), done=None, pending=None, iteration=None, wait_s=0.0)
+        self.pool = PanoPool(self.ras, rgb, depth, cache, n_stage, prefetch=self.prefetch)
+        self.pano_rgb, self.pano_depth = self.pool.pano_rgb, self.pool.pano_depth
         self.n_panos, self.examples = P, None
         self._alloc_images(P, n_slots)
         self.ras._workspace(self._batch_images(n_slots))
@@ -451,12 +294,12 @@ class RenderedTrainSource:
 
     @property
     def cache(self) -> Optional[PanoCache]:
-        return None if self.pool is None else self.pool["cache"]
+        return None if self.pool is None else self.pool.cache
 
     @property
     def uploads(self) -> int:
         """Panoramas uploaded into the pool so far (0 without one)."""
-        return 0 if self.pool is None else self.pool["uploads"]
+        return 0 if self.pool is None else self.pool.uploads
 
     # ------------------------------------------------------------------ examples
     def set_examples(self, hyp: HypothesisTable, is_match) -> None:
@@ -475,162 +318,47 @@ class RenderedTrainSource:
         """The reference's JPEG round trip of `images`, in place, if this source was asked for it."""
         if self.jpeg_quality is None or images.shape[0] == 0:
             return
-        e1 = self._timed("jpeg")
-        with tracing.range("salve.jpeg"):
+        with self._launch("jpeg", "salve.jpeg"):
             self.ras.jpeg_roundtrip(images, self.jpeg_quality, out=images)
-        if e1 is not None:
-            e1.record()
 
-    def _timed(self, tag: str):
-        if self.timers is None:
-            return None
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        self.timers.append((tag, e0, e1))
-        e0.record()
-        return e1
-
-    def _make_resident(self, panos: np.ndarray, next_use: Optional[np.ndarray]) -> np.ndarray:
-        """Pool slot of every entry of `panos`; the misses are gathered into a pinned staging buffer, copied with one host-to-device
-        copy per array and written into their slots (BevRasteriser.update_panos), all on the current stream."""
-        pool = self.pool
-        slots, uploads = pool["cache"].plan(panos, next_use)
-        m = len(uploads)
-        if m == 0:
-            return slots
-        st = pool["stage"][pool["turn"]]
-        pool["turn"] ^= 1
-        if st["event"] is not None:
-            st["event"].synchronize()   # the copy that last read this buffer
-        rgb_np, depth_np = st["rgb"].numpy(), st["depth"].numpy().view(np.uint16)
-        for k, (p, _) in enumerate(uploads):
-            rgb_np[k] = pool["rgb"][p]
-            depth_np[k] = pool["depth"][p]
-        e1 = self._timed("upload")
-        with tracing.range("salve.pano_upload"):
-            rgb_rows = st["rgb"][:m].to(self.device, non_blocking=True)
-            depth_rows = st["depth"][:m].to(self.device, non_blocking=True)
-            slots_dev = torch.from_numpy(np.asarray([sl for _, sl in uploads], dtype=np.int32)).to(self.device)
-        st["event"] = torch.cuda.Event()
-        st["event"].record()
-        if e1 is not None:
+    @contextlib.contextmanager
+    def _launch(self, tag: str, name: str):
+        """Around one launch: the trace range `name`, and -- while `timers` is a list -- two HIP events around it, filed under `tag`."""
+        timed = self.timers is not None
+        if timed:
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            self.timers.append((tag, e0, e1))
+            e0.record()
+        with tracing.range(name):
+            yield
+        if timed:
             e1.record()
-        e1 = self._timed("index update")
-        with tracing.range("salve.pano_update"):
-            self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows, index=pool.get("index"))
-        if e1 is not None:
-            e1.record()
-        pool["uploads"] += m
-        return slots
 
     # ------------------------------------------------------------------ prefetch (DESIGN.md 4.14)
-    def _gather_rows(self, st: Dict, uploads: Sequence[Tuple[int, int]], lo: int, hi: int) -> None:
-        """Rows lo .. hi - 1 of a job's missed panoramas from the host arrays into the pinned staging buffer (one gather thread's share;
-        numpy copies rows of this size with the GIL released)."""
-        pool = self.pool
-        rgb_np, depth_np = st["rgb"].numpy(), st["depth"].numpy().view(np.uint16)
-        for k in range(lo, hi):
-            p = uploads[k][0]
-            rgb_np[k] = pool["rgb"][p]
-            depth_np[k] = pool["depth"][p]
-
-    def _upload_job(self, st: Dict, uploads: Sequence[Tuple[int, int]], after: Optional[torch.cuda.Event], gatherers: ThreadPoolExecutor):
-        """Worker thread: gather the missed rows (split over the gather threads), then enqueue the two copies, the slot writes and the
-        index update on the pool's copy stream -- behind `after`, the event of the last batch that may still read a victim's slot.
-        Returns the event behind the index update: what the compute stream waits on before it reads the slots."""
-        pool, m, T = self.pool, len(uploads), self.gather_threads
-        if st["event"] is not None:
-            st["event"].synchronize()   # the copy that last read this buffer
-        cuts = [m * t // T for t in range(T + 1)]
-        shares = [gatherers.submit(self._gather_rows, st, uploads, cuts[t], cuts[t + 1]) for t in range(T) if cuts[t + 1] > cuts[t]]
-        errors = [f.exception() for f in shares]   # (every thread has left the buffer before the first failure is raised)
-        for e in errors:
-            if e is not None:
-                raise e
-        st["slots"].numpy()[:m] = [sl for _, sl in uploads]
-        with torch.cuda.stream(pool["stream"]):
-            if after is not None:
-                pool["stream"].wait_event(after)
-            with tracing.range("salve.pano_upload"):   # (no `timers` entry: the caller that reads them does not know when this thread records)
-                rgb_rows = st["rgb"][:m].to(self.device, non_blocking=True)
-                depth_rows = st["depth"][:m].to(self.device, non_blocking=True)
-                slots_dev = st["slots"][:m].to(self.device, non_blocking=True)
-            st["event"] = torch.cuda.Event()
-            st["event"].record()
-            with tracing.range("salve.pano_update"):
-                self.ras.update_panos(self.pano_rgb, self.pano_depth, slots_dev, rgb_rows, depth_rows, index=pool["index"])
-            ready = torch.cuda.Event()
-            ready.record()
-        return ready
-
-    def _prefetch(self, panos: np.ndarray, next_use: np.ndarray, keep: np.ndarray, after: Optional[torch.cuda.Event], worker: ThreadPoolExecutor,
-                  gatherers: ThreadPoolExecutor) -> Dict:
-        """Plan the batch ahead (its victims spare `keep`, the batch in flight) and start its upload; the job is the pool's `pending`."""
-        pool = self.pool
-        _, uploads = pool["cache"].plan(panos, next_use, keep=keep)
-        job = {"uploads": uploads, "future": None}
-        if uploads:
-            st = pool["stage"][pool["turn"]]
-            pool["turn"] ^= 1
-            job["future"] = worker.submit(self._upload_job, st, uploads, after, gatherers)
-        pool["pending"] = job
-        return job
-
-    def _drain(self, raise_errors: bool = False) -> Optional[torch.cuda.Event]:
-        """Complete the pool's outstanding upload job, if any: join its worker and count its uploads; returns the event behind its index
-        update.  A job that failed is taken back from the `PanoCache` (its slots are free again: the state matches what was uploaded) and
-        the copy stream is synchronised; its exception is raised here only with `raise_errors` (the loop that needs the batch)."""
-        pool = self.pool
-        job = pool["pending"]
-        if job is None or job["future"] is None:
-            pool["pending"] = None
-            return None
-        t0 = time.perf_counter()
-        error = job["future"].exception()   # joins the worker; an interrupt of THIS thread leaves the job pending, to be completed later
-        pool["wait_s"] += time.perf_counter() - t0
-        pool["pending"] = None
-        if error is not None:   # the worker's own exception: nothing of the job's upload counts
-            pool["cache"].forget(job["uploads"])
-            pool["stream"].synchronize()
-            if raise_errors:
-                raise error
-            return None
-        pool["uploads"] += len(job["uploads"])
-        return job["future"].result()
-
     def _iter_prefetch(self, plan: List[np.ndarray]):
         """The epoch with the uploads one batch ahead: batch 0 is made resident on the compute stream as without prefetch; right behind
         batch b's launches batch b + 1 is planned and its upload started.  The copy stream writes only slots that neither batch b nor
         batch b + 1 names, behind the event of batch b - 1's last launch (the last batch of the epoch before, for b = 0)."""
         pool = self.pool
-        self._drain()   # another iteration on this pool (the other source's, or one of this source's left suspended) may have a job out
-        pool["stream"].synchronize()
-        mine = pool["iteration"] = object()   # one iteration at a time plans this pool: one that was suspended meanwhile refuses to go on
         panos = [self.batch_panos(idx) for idx in plan]
         next_use, after = epoch_next_use(panos, self.n_panos)
-        worker, gatherers = ThreadPoolExecutor(1, "salve-upload"), ThreadPoolExecutor(self.gather_threads, "salve-gather")
-        job = None
+        mine, planned = pool.begin(self.gather_threads), False
         try:
             for b, idx in enumerate(plan):
-                if pool["iteration"] is not mine:
-                    raise RuntimeError("another iteration over this resident pool was started while this one was suspended: with prefetch the "
-                                       "pool serves one iteration at a time (finish or close an epoch before the next begins)")
-                if job is not None:
-                    ready = self._drain(raise_errors=True)
+                pool.check(mine)   # one iteration at a time plans this pool: one that was suspended meanwhile refuses to go on
+                if planned:
+                    ready = pool.drain(raise_errors=True)
                     if ready is not None:
                         torch.cuda.current_stream(self.device).wait_event(ready)
-                out = self.batch(idx, self.draws(len(idx)), next_use, planned=job is not None)
+                out = self.batch(idx, self.draws(len(idx)), next_use, planned=planned)
                 next_use[panos[b]] = after[b]
-                before, pool["done"] = pool["done"], torch.cuda.Event()
-                pool["done"].record()
-                job = self._prefetch(panos[b + 1], next_use, panos[b], before, worker, gatherers) if b + 1 < len(plan) else None
+                before = pool.mark_done()
+                planned = b + 1 < len(plan)
+                if planned:
+                    pool.plan_ahead(panos[b + 1], next_use, panos[b], before, mine)
                 yield out
-        finally:   # closed or dropped mid-epoch, or an exception: nothing stays in flight, the cache matches the slots
-            if pool["iteration"] is mine:
-                self._drain()
-            worker.shutdown(wait=True)
-            gatherers.shutdown(wait=True)
-            if pool["iteration"] is mine:
-                pool["stream"].synchronize()
+        finally:
+            pool.end(mine)
 
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None,
               planned: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -642,49 +370,32 @@ class RenderedTrainSource:
         bev_b = self.ref_bev if self.identity == "kept" else self.bev
         # ONE upload per batch; every table starts on a multiple of 16 bytes (the 40-byte render rows come last)
         # (the 48-byte layout records hold a double: every table in front of them is a multiple of 8 bytes long)
-        parts = [jobs.view(np.uint8).reshape(-1), aug.view(np.uint8), self.examples["is_match"][idx].view(np.uint8), rows.view(np.uint8),
-                 lay_recs.view(np.uint8)]
-        buf = torch.from_numpy(np.concatenate(parts)).to(self.device)
-        o = np.cumsum([0] + [p.nbytes for p in parts])
+        buf, o = train_feed.upload_tables([jobs, aug, self.examples["is_match"][idx], rows, lay_recs], self.device)
         jobs_a, jobs_b = buf[:o[1] // 2], buf[o[1] // 2:o[1]]
         labels = buf[o[2]:o[3]].view(torch.int64).view(B, 1)
         if S:   # (layout alone: no texture map, as RenderVerifyPipeline)
-            e1 = self._timed("scatter")
-            with tracing.range("salve.scatter"):
-                self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:o[4]], n, self.bev,
-                                 index=None if self.pool is None else self.pool.get("index"))
-            if e1 is not None:
-                e1.record()
-            e1 = self._timed("densify")
-            with tracing.range("salve.densify"):
+            with self._launch("scatter", "salve.scatter"):
+                self.ras.scatter(self.pano_rgb, self.pano_depth, buf[o[3]:o[4]], n, self.bev, index=None if self.pool is None else self.pool.index)
+            with self._launch("densify", "salve.densify"):
                 self.ras.densify(n, self.bev)
-            if e1 is not None:
-                e1.record()
             self._jpeg(self.bev[:n])
         if self.has_layout:
-            e1 = self._timed("layout pose")
-            with tracing.range("salve.layout_pose"):
+            with self._launch("layout pose", "salve.layout_pose"):
                 self.lay.pose(buf[o[4]:], len(lay_recs))
-            if e1 is not None:
-                e1.record()
-            e1 = self._timed("layout rasterise")
-            with tracing.range("salve.layout_rasterise"):
+            with self._launch("layout rasterise", "salve.layout_rasterise"):
                 self.lay.rasterise(len(lay_recs), self.bev[self.lay_base[0]:])
-            if e1 is not None:
-                e1.record()
             self._jpeg(self.bev[self.lay_base[0]:self.lay_base[0] + len(lay_recs)])
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
-        e1 = self._timed("tiles")
-        with tracing.range("salve.train_tiles"):
+        with self._launch("tiles", "salve.train_tiles"):
             self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, K, buf[o[1]:o[2]], B, out)   # (identity="batch": one buffer, only read)
-        if e1 is not None:
-            e1.record()
         return out, labels
 
     def batch_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None, planned: bool = False):
         """The host tables of one batch: (tile jobs [2][B][K], draws [B], render rows, layout pose records, renders).  Host arithmetic,
-        except that a resident pool uploads its misses here (`_make_resident`)."""
+        except that a resident pool uploads its misses here (`PanoPool.make_resident`)."""
         ex, S, B, K = self.examples, len(self.surfaces), len(idx), self.per_sample
+        if len(draws) != B:
+            raise ValueError(f"{B} examples, {len(draws)} draws")
         Hb, Wb = self.ras.bev_hw
         i1 = ex["i1"][idx]
         surf = [SURFACES[s] for s in self.surfaces]
@@ -715,7 +426,7 @@ class RenderedTrainSource:
             uniq, inv = np.unique(ex["i2"][idx], return_inverse=True)
             U = len(uniq)
             pano = np.concatenate([i1, uniq])
-            where = pano if self.pool is None else self.pool["cache"].lookup(pano) if planned else self._make_resident(pano, next_use)
+            where = pano if self.pool is None else self.pool.lookup(pano) if planned else self.pool.make_resident(pano, next_use, self._launch)
             order = np.argsort(where, kind="stable")
             rank = np.empty(B + U, dtype=np.int64)
             rank[order] = np.arange(B + U)
@@ -735,10 +446,7 @@ class RenderedTrainSource:
         jobs["slot"][:] = np.arange(B, dtype=np.int64)[None, :, None]
         jobs["chan"][0] = 6 * np.arange(K)[None, :] + 3 * swap[:, None]   # the layout pair follows the texture maps (zind_data.py:26)
         jobs["chan"][1] = 6 * np.arange(K)[None, :] + 3 * (1 - swap)[:, None]
-        aug = np.zeros(B, dtype=_lib.TILE_AUG_DTYPE)
-        for k, (cy, cx, hflip, vflip) in enumerate(draws):
-            aug[k] = (cy, cx, (_lib.TILE_HFLIP if hflip else 0) | (_lib.TILE_VFLIP if vflip else 0), 0)
-        return jobs, aug, rows, lay_recs, n
+        return jobs, train_feed.aug_table(draws), rows, lay_recs, n
 
     def _layout_records(self, pano: np.ndarray, R: np.ndarray, t: np.ndarray, n_identity: int) -> np.ndarray:
         """salve_layout_pose_t rows of a batch: its posed layouts under (R, t) (alignment hypotheses are SE(2): scale 1), then
@@ -749,11 +457,8 @@ class RenderedTrainSource:
                                        np.concatenate([t, np.zeros((n_identity, 2), np.float32)]), None, np.arange(len(pano)) < len(R))
 
     def draws(self, n: int) -> List[Tuple[int, int, bool, bool]]:
-        """train: `TrainTransform.draw()` per example, from Python's `random`; val: the centre crop, no flips (ValTestTransform)."""
-        if self.split == "train":
-            return [self.tf.draw() for _ in range(n)]
-        off = (self.tf.resize - self.tf.crop) // 2
-        return [(off, off, False, False)] * n
+        """One draw per example of a batch (`train_feed.draws`)."""
+        return train_feed.draws(self.tf, self.split, n)
 
     def batch_panos(self, idx: np.ndarray) -> np.ndarray:
         """The distinct panoramas examples `idx` name."""
@@ -766,7 +471,7 @@ class RenderedTrainSource:
         if self.pool is None:
             for idx in plan:
                 yield self.batch(idx, self.draws(len(idx)))
-        elif "stream" in self.pool:
+        elif self.pool.prefetch:
             yield from self._iter_prefetch(plan)
         else:   # the epoch's order is known here, before its first batch: every panorama's next use, for the planner
             panos = [self.batch_panos(idx) for idx in plan]

@@ -97,7 +97,7 @@ def _check_counts(tr, va, schedule, builds, every_batch=True):
     assert tr.uploads == va.uploads == tr.cache.misses == sum(per)
     assert tr.cache.uploaded_bytes == tr.uploads * 512 * 1024 * 5
     assert (tr.ras.index_builds, va.ras.index_builds) == builds              # no full rebuild of the pool's index behind load_panos
-    assert tr.pool["pending"] is None and tr.pool["stream"].query()        # nothing left in flight
+    assert tr.pool.pending is None and tr.pool.stream.query()        # nothing left in flight
     status.check(DEV, "the prefetched epochs")
 
 
@@ -110,7 +110,7 @@ def test_prefetched_pool_equals_the_default_source(mods, precision):
     """Two train epochs with a val epoch between them on the shared pool: every batch -- rendered while the copy stream writes the NEXT
     batch's slots -- and its labels equal the default all-resident source's; the uploads are the look-ahead planner's misses."""
     tr, va = _pair(mods, precision, identity="batch", resident_panos=POOL, prefetch=True)
-    assert tr.uploads == 0 and tuple(tr.pano_rgb.shape) == (POOL, 512, 1024, 3) and va.pool is tr.pool and va.pool["stream"] is tr.pool["stream"]
+    assert tr.uploads == 0 and tuple(tr.pano_rgb.shape) == (POOL, 512, 1024, 3) and va.pool is tr.pool and va.pool.stream is tr.pool.stream
     builds = (tr.ras.index_builds, va.ras.index_builds)
     assert builds == (1, 0)
     ref, vref = _pair(mods, precision)
@@ -129,7 +129,7 @@ def test_iterator_closed_or_dropped_mid_epoch_leaves_the_pool_usable():
     builds = (tr.ras.index_builds, va.ras.index_builds)
     ref, vref = _pair(BOTH, "bf16")
     _same(_epoch(tr, 21, stop=2), _epoch(ref, 21, stop=2))
-    assert tr.pool["pending"] is None and tr.pool["stream"].query()
+    assert tr.pool.pending is None and tr.pool.stream.query()
     held = tr.cache.slot_of[tr.cache.slot_of >= 0]
     assert len(set(held.tolist())) == len(held) and tr.uploads == tr.cache.misses
     _same(_epoch(va, 22), _epoch(vref, 22))
@@ -141,7 +141,7 @@ def test_iterator_closed_or_dropped_mid_epoch_leaves_the_pool_usable():
     it = iter(tr)
     got = [tuple(t.clone() for t in next(it))]
     del it
-    assert tr.pool["pending"] is None and tr.pool["stream"].query()
+    assert tr.pool.pending is None and tr.pool.stream.query()
     _same(got, _epoch(ref, 24, stop=1))
     _same(_epoch(va, 25), _epoch(vref, 25))
     _check_counts(tr, va, schedule + [("train", 1), ("val", None)], builds, every_batch=False)
@@ -156,13 +156,13 @@ def test_a_suspended_iterator_refuses_to_go_on_after_another_iteration_on_the_po
     random.seed(41)
     it = iter(tr)
     got = [tuple(t.clone() for t in next(it))]
-    assert tr.pool["pending"] is not None
+    assert tr.pool.pending is not None
     _same(got, _epoch(ref, 41, stop=1))
     _same(_epoch(va, 42), _epoch(vref, 42))
-    assert tr.pool["pending"] is None and tr.uploads == tr.cache.misses
+    assert tr.pool.pending is None and tr.uploads == tr.cache.misses
     with pytest.raises(RuntimeError, match="one iteration at a time"):
         next(it)
-    assert tr.pool["pending"] is None and tr.pool["stream"].query() and tr.uploads == tr.cache.misses
+    assert tr.pool.pending is None and tr.pool.stream.query() and tr.uploads == tr.cache.misses
     _same(_epoch(tr, 43), _epoch(ref, 43))
     _check_counts(tr, va, [("train", 1), ("val", None), ("train", None)], (1, 0), every_batch=False)
 
@@ -203,7 +203,7 @@ def test_a_worker_exception_reaches_the_loop_and_the_source_stays_usable():
         next(it)
     _same(got, _epoch(ref, 31, stop=1))
     cache = tr.cache
-    assert tr.pool["pending"] is None and tr.pool["stream"].query()
+    assert tr.pool.pending is None and tr.pool.stream.query()
     assert cache.slot_of[bad] == -1 and tr.uploads == cache.misses == int((cache.slot_of >= 0).sum()) == len(first)   # batch 0's uploads alone
     assert all(cache.pano_in[cache.slot_of[p]] == p for p in np.flatnonzero(cache.slot_of >= 0))
     assert cache.hits == 0 and cache.hits + cache.misses == len(first)   # the failed plan's hits are taken back with its misses

@@ -153,7 +153,7 @@ def sustained(a, tag, model, opt, x_packed, y, src_c, src_e, n_it) -> None:
     for r in range(1 + a.rounds):
         for k, src in kinds.items():
             it = None if src is None else iter(src)
-            w0 = 0.0 if src is None or "wait_s" not in src.pool else src.pool["wait_s"]
+            w0 = 0.0 if src is None else src.pool.wait_s
             torch.cuda.synchronize()
             t0 = t_prev = time.perf_counter()
             per = []
@@ -176,14 +176,14 @@ def sustained(a, tag, model, opt, x_packed, y, src_c, src_e, n_it) -> None:
                 steps[k] += per[1:]
                 firsts[k].append(per[0])
                 epochs[k].append(total / n_it)
-                waits[k].append(0.0 if src is None or "wait_s" not in src.pool else (src.pool["wait_s"] - w0) / (n_it - 1))
+                waits[k].append(0.0 if src is None else (src.pool.wait_s - w0) / (n_it - 1))
     res = med(steps["resident"]) * 1e3
     for k in kinds:
         m = med(steps[k]) * 1e3
         line = (f"{tag}: consecutive steps, {a.rounds} epochs of {n_it}: {k}: median step behind the first {m:.1f} ms ({100 * (m / res - 1):+.1f} % over the "
                 f"resident step; min {min(steps[k]) * 1e3:.1f}, max {max(steps[k]) * 1e3:.1f}), first step of an epoch {med(firsts[k]) * 1e3:.1f} ms, epoch per batch "
                 + " / ".join(f"{v * 1e3:.1f}" for v in epochs[k]) + " ms")
-        if kinds[k] is not None and "wait_s" in kinds[k].pool:
+        if kinds[k] is not None and kinds[k].pool.prefetch:
             line += "; host wait for the upload job per prefetched batch " + " / ".join(f"{v * 1e3:.2f}" for v in waits[k]) + " ms"
         if kinds[k] is not None:
             line += f"; uploads so far {kinds[k].uploads}"
