@@ -13,8 +13,8 @@
 //                        star_delaunay.h) and the owned triangles are rasterised with exact rational barycentric
 //                        weights into the output image.  Reference: interpolation_utils.py:21-54 (griddata linear), :74-122 (mask),
 //                        bev_rendering_utils.py:318-319 (mask multiply, flipud).
-//   bev_tile_kernel      BEV -> verifier input tile (resize 234, crop 224, normalise).  Reference:
-//                        train_utils.py:126-159, transform.py:256-272, 386-420, 105-123, 177-202.
+//                        Phase H (salve_bev_densify_tiles) turns the finished image into the verifier's input tile while it is in the
+//                        L2, with the arithmetic of bev_tile_math.h; the tile kernels proper are in bev_tiles.hip.
 //
 // Exactness: pixel indices follow the reference's float64 op order bit for bit (float32 depth product, float64
 // table products, the FMA order of numpy's BLAS matmul, half-to-even rounding); everything after the pixel index
@@ -49,6 +49,7 @@ __shared__ int sd_phase[8];
 #include "star_local.h"
 #include "star_table.h"
 #include <mutex>
+#include "bev_tile_math.h"
 #include "salve_common.h"
 
 namespace {
@@ -293,24 +294,6 @@ __device__ __forceinline__ void wg_barrier_after_global_stores() {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 }
-
-// ---- the verifier's input tile (salve_hip.h: salve_bev_tiles) -- shared by the tile kernels below and by the densify kernel's phase H
-__device__ __forceinline__ uint16_t f32_to_f16(float f) { return __builtin_bit_cast(uint16_t, (_Float16)f); }  // |values| < 3: no saturation needed
-__device__ __forceinline__ void tile_pixel(const uint32_t* __restrict__ img, int W, const int4 cy, const int4 cx, const float* __restrict__ lut, float v[3]) {
-    const uint32_t p00 = img[(size_t)cy.x * W + cx.x], p01 = img[(size_t)cy.x * W + cx.y];
-    const uint32_t p10 = img[(size_t)cy.y * W + cx.x], p11 = img[(size_t)cy.y * W + cx.y];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const int a = (p00 >> (8 * ch)) & 255, b = (p01 >> (8 * ch)) & 255;
-        const int cc = (p10 >> (8 * ch)) & 255, d = (p11 >> (8 * ch)) & 255;
-        const int S0 = a * cx.z + b * cx.w;  // horizontal pass, x2048
-        const int S1 = cc * cx.z + d * cx.w;
-        int r = (((cy.z * (S0 >> 4)) >> 16) + ((cy.w * (S1 >> 4)) >> 16) + 2) >> 2;
-        r = min(max(r, 0), 255);
-        v[ch] = lut[ch * 256 + r];
-    }
-}
-
 
 // (r6) salve_bev_densify_tiles: the arguments of the tile phase, read by bev_densify_kernel from the workspace (behind order[] in the key
 // image) instead of as kernel arguments -- the kernel runs at the limit of the scalar register file, and every live scalar pair moves
@@ -789,8 +772,7 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
             uint16_t* osample = tf.out + (size_t)ja.slot * crop * crop * out_c;
             // A thread keeps ONE tile column (its two source columns and their weights stay in registers) and walks the rows: no division per
             // pixel, the row's taps are a broadcast LDS read.  Columns in groups of 256 lanes (crop = 224: 32 idle lanes per group), the
-            // DENSIFY_THREADS / 256 groups take the rows in turn.  24-bit multiplies (full rate; the tile kernels' v_mul_lo_u32 are quarter
-            // rate): every product here is < 2^28 of operands < 2^16 -- the same integers.
+            // DENSIFY_THREADS / 256 groups take the rows in turn.  24-bit multiplies throughout (bev_tile_math.h: bilinear_u8_mul24).
             constexpr int COLS = 256, RGROUPS = DENSIFY_THREADS / COLS;
             for (int j0 = 0; j0 < crop; j0 += COLS) {
                 const int j = j0 + (tid & (COLS - 1));
@@ -824,11 +806,7 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
                         for (int ch = 0; ch < 3; ch++) {
                             const uint32_t a = (p00[u] >> (8 * ch)) & 255u, b = (p01[u] >> (8 * ch)) & 255u;
                             const uint32_t cc = (p10[u] >> (8 * ch)) & 255u, d = (p11[u] >> (8 * ch)) & 255u;
-                            const int S0 = (int)(__umul24(a, cx.z) + __umul24(b, cx.w));   // horizontal pass, x2048 (tile_pixel, op for op)
-                            const int S1 = (int)(__umul24(cc, cx.z) + __umul24(d, cx.w));
-                            int r = (int)(((__umul24(cy[u].z, S0 >> 4) >> 16) + (__umul24(cy[u].w, S1 >> 4) >> 16) + 2u) >> 2);
-                            r = min(max(r, 0), 255);
-                            va[ch] = lut_l[ch * 256 + r];
+                            va[ch] = lut_l[ch * 256 + bilinear_u8_mul24(a, b, cc, d, cy[u], cx)];
                             vb[ch] = lut_l[ch * 256 + ((q[u] >> (8 * ch)) & 255u)];
                         }
                         const float* lo = a_first ? va : vb;
@@ -838,15 +816,7 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
                         const uint32_t w0 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){lo[0], lo[1]}, h2));   // (round to nearest even, as (_Float16)f)
                         const uint32_t w1 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){lo[2], hi[0]}, h2));
                         const uint32_t w2 = __builtin_bit_cast(uint32_t, __builtin_convertvector((f2){hi[1], hi[2]}, h2));
-                        uint16_t* px = osample + (size_t)idx * out_c;
-                        if (out_c == 8) {
-                            *reinterpret_cast<uint4*>(px) = make_uint4(w0, w1, w2, 0u);
-                        } else {
-                            uint32_t* o = reinterpret_cast<uint32_t*>(px + c0);
-                            o[0] = w0; o[1] = w1; o[2] = w2;
-                            if (c0 + 12 > out_c)
-                                for (int k = c0 + 6; k < out_c; k += 2) *reinterpret_cast<uint32_t*>(px + k) = 0u;
-                        }
+                        store_pair_pixel(osample + (size_t)idx * out_c, w0, w1, w2, c0, out_c);
                     }
                 }
             }
@@ -867,257 +837,6 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
 #else
         if (tid < 8) dbg_stats[rid * 8 + tid] = tid == 1 ? scal[9] : (tid == 2 ? scal[10] : (tid < 6 ? scal[tid] : scal[tid + 1]));  // [1] sites begun [2] checksum [6] hard sites [7] queued triangles
 #endif
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ tiles
-
-__global__ __launch_bounds__(256) void bev_tile_kernel(const uint32_t* __restrict__ bev, int W,
-                                                       const salve_tile_job_t* __restrict__ jobs,
-                                                       const int32_t* __restrict__ coef_y,
-                                                       const int32_t* __restrict__ coef_x, int resize, int crop,
-                                                       const float* __restrict__ lut, void* __restrict__ out, int fmt,
-                                                       int out_c) {
-    const salve_tile_job_t job = jobs[blockIdx.y];
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= crop * crop) return;
-    const int i = idx / crop, j = idx % crop;
-    const int off = (resize - crop) / 2;
-    const int4 cy = reinterpret_cast<const int4*>(coef_y)[i + off];
-    const int4 cx = reinterpret_cast<const int4*>(coef_x)[j + off];
-    const uint32_t* img = bev + job.bev_offset;
-    const uint32_t p00 = img[(size_t)cy.x * W + cx.x], p01 = img[(size_t)cy.x * W + cx.y];
-    const uint32_t p10 = img[(size_t)cy.y * W + cx.x], p11 = img[(size_t)cy.y * W + cx.y];
-    float v[3];
-    int rq[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const int a = (p00 >> (8 * ch)) & 255, b = (p01 >> (8 * ch)) & 255;
-        const int cc = (p10 >> (8 * ch)) & 255, d = (p11 >> (8 * ch)) & 255;
-        const int S0 = a * cx.z + b * cx.w;  // horizontal pass, x2048
-        const int S1 = cc * cx.z + d * cx.w;
-        int r = (((cy.z * (S0 >> 4)) >> 16) + ((cy.w * (S1 >> 4)) >> 16) + 2) >> 2;
-        r = min(max(r, 0), 255);
-        rq[ch] = r;
-        v[ch] = lut[ch * 256 + r];
-    }
-    if (fmt == SALVE_TILE_U8X4) {   // the resized + cropped image itself (before ToTensor / Normalize): 0x00BBGGRR, one image per slot
-        reinterpret_cast<uint32_t*>(out)[(size_t)job.slot * crop * crop + idx] = (uint32_t)rq[0] | ((uint32_t)rq[1] << 8) | ((uint32_t)rq[2] << 16);
-    } else if (fmt == SALVE_TILE_F32_NCHW) {
-        float* o = reinterpret_cast<float*>(out) + ((size_t)job.slot * out_c + job.chan) * crop * crop + idx;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) o[(size_t)ch * crop * crop] = v[ch];
-    } else {
-        uint16_t* o = reinterpret_cast<uint16_t*>(out) + ((size_t)job.slot * crop * crop + idx) * out_c + job.chan;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) o[ch] = f32_to_f16(v[ch]);
-    }
-}
-
-// salve_bev_tiles_aug: the train transform's tile -- bev_tile_kernel's F32_NCHW arithmetic (tile_pixel: the same taps, the same LUT) at
-// the job's crop offset, with the output pixel (i, j) taken from the crop's (crop-1-i if VFLIP, crop-1-j if HFLIP): the flips come after
-// the crop, as in the reference's Compose.  Offsets are clamped into [0, resize - crop] so that no tap outside the tables is read.
-__global__ __launch_bounds__(256) void bev_tile_aug_kernel(const uint32_t* __restrict__ bev, int W, const salve_tile_job_t* __restrict__ jobs,
-                                                           const salve_tile_aug_t* __restrict__ aug, const int32_t* __restrict__ coef_y,
-                                                           const int32_t* __restrict__ coef_x, int resize, int crop, const float* __restrict__ lut,
-                                                           float* __restrict__ out, int out_c) {
-    const salve_tile_job_t job = jobs[blockIdx.y];
-    const salve_tile_aug_t a = aug[blockIdx.y];
-    const int idx = blockIdx.x * 256 + threadIdx.x;
-    if (idx >= crop * crop) return;
-    const int i = idx / crop, j = idx % crop;
-    const int oy = min(max(a.crop_y, 0), resize - crop), ox = min(max(a.crop_x, 0), resize - crop);
-    const int si = (a.flags & SALVE_TILE_VFLIP) ? crop - 1 - i : i, sj = (a.flags & SALVE_TILE_HFLIP) ? crop - 1 - j : j;
-    const int4 cy = reinterpret_cast<const int4*>(coef_y)[si + oy];
-    const int4 cx = reinterpret_cast<const int4*>(coef_x)[sj + ox];
-    float v[3];
-    tile_pixel(bev + job.bev_offset, W, cy, cx, lut, v);
-    float* o = out + ((size_t)job.slot * out_c + job.chan) * crop * crop + idx;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) o[(size_t)ch * crop * crop] = v[ch];
-}
-
-// One tile pixel of image `img`: cv2 INTER_LINEAR on uint8 with 11-bit taps, then the normalisation LUT (bev_tile_kernel's arithmetic).
-// Both tiles of an early-fusion pair per thread, six channels (plus the sample's zero padding behind its last group) in
-// whole-pixel stores: see salve_bev_tile_pairs in salve_hip.h.
-__global__ __launch_bounds__(256) void bev_tile_pair_kernel(const uint32_t* __restrict__ bev_a, const uint32_t* __restrict__ bev_b, int W,
-                                                            const salve_tile_job_t* __restrict__ jobs_a, const salve_tile_job_t* __restrict__ jobs_b,
-                                                            const int32_t* __restrict__ coef_y, const int32_t* __restrict__ coef_x, int resize,
-                                                            int crop, const float* __restrict__ lut, uint16_t* __restrict__ out, int out_c,
-                                                            int n_pairs, int n_blocks, int xcd_group, int b_pretiled) {
-    // (the workgroups of one pair read the same two BEV images: same id % 8 = same XCD = one L2 -- as in bev_splat_kernel)
-    int job, blk;
-    if (xcd_group) {
-        const int id = blockIdx.x, s_ = id >> 3;
-        job = (s_ / n_blocks) * 8 + (id & 7);
-        blk = s_ % n_blocks;
-        if (job >= n_pairs) return;
-    } else {
-        job = blockIdx.x / n_blocks;
-        blk = blockIdx.x % n_blocks;
-    }
-    const salve_tile_job_t ja = jobs_a[job], jb = jobs_b[job];
-    const int idx = blk * 256 + threadIdx.x;
-    if (idx >= crop * crop) return;
-    const int i = idx / crop, j = idx % crop;
-    const int off = (resize - crop) / 2;
-    const int4 cy = reinterpret_cast<const int4*>(coef_y)[i + off];
-    const int4 cx = reinterpret_cast<const int4*>(coef_x)[j + off];
-    float va[3], vb[3];
-    tile_pixel(bev_a + ja.bev_offset, W, cy, cx, lut, va);
-    if (b_pretiled) {   // image b was resized and cropped before (SALVE_TILE_U8X4, once per panorama): ToTensor + Normalize only
-        const uint32_t q = bev_b[jb.bev_offset + idx];
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) vb[ch] = lut[ch * 256 + ((q >> (8 * ch)) & 255u)];
-    } else {
-        tile_pixel(bev_b + jb.bev_offset, W, cy, cx, lut, vb);
-    }
-    const bool a_first = ja.chan < jb.chan;
-    const int c0 = a_first ? ja.chan : jb.chan;   // first of the group's six channels (a multiple of 6)
-    uint32_t w[3];                                // the six halves, two per word
-    {
-        const float* lo = a_first ? va : vb;
-        const float* hi = a_first ? vb : va;
-        w[0] = (uint32_t)f32_to_f16(lo[0]) | ((uint32_t)f32_to_f16(lo[1]) << 16);
-        w[1] = (uint32_t)f32_to_f16(lo[2]) | ((uint32_t)f32_to_f16(hi[0]) << 16);
-        w[2] = (uint32_t)f32_to_f16(hi[1]) | ((uint32_t)f32_to_f16(hi[2]) << 16);
-    }
-    uint16_t* px = out + ((size_t)ja.slot * crop * crop + idx) * out_c;
-    if (out_c == 8) {   // one surface: the whole 16-byte pixel, padding channels 6 and 7 included
-        *reinterpret_cast<uint4*>(px) = make_uint4(w[0], w[1], w[2], 0u);
-    } else {
-        uint32_t* o = reinterpret_cast<uint32_t*>(px + c0);   // c0 is even: 4-byte aligned
-        o[0] = w[0]; o[1] = w[1]; o[2] = w[2];
-        if (c0 + 12 > out_c)   // the sample's last group: zero the padding channels behind it
-            for (int c = c0 + 6; c < out_c; c += 2) *reinterpret_cast<uint32_t*>(px + c) = 0u;
-    }
-}
-
-// salve_bev_train_tiles: the TRAIN transform of a whole batch in the training model's input layout -- NHWC [batch, crop, crop, CP],
-// fp32 or bf16, the channels behind the last image written as zero.  The workgroups of sample `smp` read its 2 * per_sample images (posed
-// renders from bev_a, identity renders from bev_b) with tile_pixel -- bev_tile_aug_kernel's arithmetic at the sample's ONE draw -- and a
-// thread stores all CP channels of its pixel with 16-byte stores.  The job tables live in device memory, so their ranges are checked HERE,
-// before any address is formed: a job outside its sample, its channels or its image array raises SALVE_STATUS_BAD_TILE_JOB and the
-// sample is left unwritten.
-struct TrainTiles {
-    const uint32_t* bev_a;
-    const uint32_t* bev_b;
-    const salve_tile_job_t* jobs_a;   // [batch][per_sample]
-    const salve_tile_job_t* jobs_b;   // [batch][per_sample]
-    const salve_tile_aug_t* aug;      // [batch]
-    const int32_t* coef_y;
-    const int32_t* coef_x;
-    const float* lut;
-    void* out;
-    int32_t* status;
-    long long px_a, px_b;             // uint32 elements of bev_a / bev_b
-    int W, HW, resize, crop, batch, per_sample, n_blocks;
-};
-
-template <int CP, bool BF16>
-__global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t) {
-    typedef __attribute__((__ext_vector_type__(8))) float f32x8;
-    typedef __attribute__((__ext_vector_type__(8))) __bf16 bf16x8;
-    constexpr int MAX_S = CP / 6, GROUPS = CP / 3;
-    // (the workgroups of one sample read the same images: same id % 8 = same XCD = one L2 -- as in bev_tile_pair_kernel)
-    const int id = blockIdx.x, s_ = id >> 3;
-    const int smp = (s_ / t.n_blocks) * 8 + (id & 7), blk = s_ % t.n_blocks;
-    if (smp >= t.batch) return;
-    const salve_tile_aug_t a = t.aug[smp];
-    salve_tile_job_t ja[MAX_S], jb[MAX_S];
-    bool bad = (a.flags & ~(SALVE_TILE_HFLIP | SALVE_TILE_VFLIP)) != 0;
-#pragma unroll
-    for (int k = 0; k < MAX_S; k++) {
-        if (k < t.per_sample) {
-            ja[k] = t.jobs_a[(size_t)smp * t.per_sample + k];
-            jb[k] = t.jobs_b[(size_t)smp * t.per_sample + k];
-            bad |= ja[k].slot != smp || ja[k].chan < 0 || ja[k].chan % 3 != 0 || ja[k].chan + 3 > CP || ja[k].bev_offset < 0 || ja[k].bev_offset + t.HW > t.px_a;
-            bad |= jb[k].slot != smp || jb[k].chan < 0 || jb[k].chan % 3 != 0 || jb[k].chan + 3 > CP || jb[k].bev_offset < 0 || jb[k].bev_offset + t.HW > t.px_b;
-        } else {
-            ja[k].chan = jb[k].chan = -1;   // names no channel group
-            ja[k].bev_offset = jb[k].bev_offset = 0;
-        }
-    }
-    if (bad) {
-        if (t.status && blk == 0 && threadIdx.x == 0) atomicOr(t.status, SALVE_STATUS_BAD_TILE_JOB);
-        return;
-    }
-    const int idx = blk * 256 + threadIdx.x;
-    if (idx >= t.crop * t.crop) return;
-    const int i = idx / t.crop, j = idx % t.crop;
-    const int oy = min(max(a.crop_y, 0), t.resize - t.crop), ox = min(max(a.crop_x, 0), t.resize - t.crop);
-    const int si = (a.flags & SALVE_TILE_VFLIP) ? t.crop - 1 - i : i, sj = (a.flags & SALVE_TILE_HFLIP) ? t.crop - 1 - j : j;
-    const int4 cy = reinterpret_cast<const int4*>(t.coef_y)[si + oy];
-    const int4 cx = reinterpret_cast<const int4*>(t.coef_x)[sj + ox];
-    float v[CP];
-#pragma unroll
-    for (int c = 0; c < CP; c++) v[c] = 0.0f;
-#pragma unroll
-    for (int g = 0; g < GROUPS; g++) {   // channel group g = channels 3 g .. 3 g + 2: the image whose job names it (workgroup-uniform)
-        const uint32_t* img = nullptr;
-#pragma unroll
-        for (int k = 0; k < MAX_S; k++) {
-            if (ja[k].chan == 3 * g) img = t.bev_a + ja[k].bev_offset;
-            if (jb[k].chan == 3 * g) img = t.bev_b + jb[k].bev_offset;
-        }
-        if (img) tile_pixel(img, t.W, cy, cx, t.lut, &v[3 * g]);
-    }
-    const size_t px = ((size_t)smp * t.crop * t.crop + idx) * CP;
-    if (BF16) {
-        uint4* o = reinterpret_cast<uint4*>(reinterpret_cast<uint16_t*>(t.out) + px);
-#pragma unroll
-        for (int c = 0; c < CP / 8; c++) {   // one rounding to nearest even (v_cvt_pk_bf16_f32), as conv_train_bf16.hip's epilogue
-            const f32x8 f = {v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6], v[8 * c + 7]};
-            o[c] = __builtin_bit_cast(uint4, __builtin_convertvector(f, bf16x8));
-        }
-    } else {
-        float4* o = reinterpret_cast<float4*>(reinterpret_cast<float*>(t.out) + px);
-#pragma unroll
-        for (int c = 0; c < CP / 4; c++) o[c] = make_float4(v[4 * c], v[4 * c + 1], v[4 * c + 2], v[4 * c + 3]);
-    }
-}
-
-__global__ __launch_bounds__(256) void bev_export_kernel(const uint32_t* __restrict__ bev, size_t npx,
-                                                         uint8_t* __restrict__ out) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= npx) return;
-    const uint32_t v = bev[i];
-    out[3 * i] = (uint8_t)v;
-    out[3 * i + 1] = (uint8_t)(v >> 8);
-    out[3 * i + 2] = (uint8_t)(v >> 16);
-}
-
-// Panorama ingest: cv2.resize(rgb, (w, h), INTER_LINEAR) on uint8 RGB (bev_rendering_utils.py:370-375).  OpenCV turns an
-// exact 2x down-scale into its INTER_AREA fast path ((a + b + c + d + 2) >> 2); everything else is the 11-bit fixed-point
-// bilinear of the tile kernel above.  One thread per destination pixel.
-__global__ __launch_bounds__(256) void resize_rgb_kernel(const uint8_t* __restrict__ src, int n, int Hs, int Ws,
-                                                         uint8_t* __restrict__ dst, int Hd, int Wd,
-                                                         const int32_t* __restrict__ coef_y, const int32_t* __restrict__ coef_x,
-                                                         int area2) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (size_t)n * Hd * Wd) return;
-    const int x = (int)(i % Wd), y = (int)((i / Wd) % Hd);
-    const uint8_t* img = src + (i / ((size_t)Hd * Wd)) * (size_t)Hs * Ws * 3;
-    uint8_t* o = dst + i * 3;
-    if (area2) {
-        const uint8_t* r0 = img + ((size_t)(2 * y) * Ws + 2 * x) * 3;
-        const uint8_t* r1 = r0 + (size_t)Ws * 3;
-#pragma unroll
-        for (int ch = 0; ch < 3; ch++) o[ch] = (uint8_t)((r0[ch] + r0[3 + ch] + r1[ch] + r1[3 + ch] + 2) >> 2);
-        return;
-    }
-    const int4 cy = reinterpret_cast<const int4*>(coef_y)[y];
-    const int4 cx = reinterpret_cast<const int4*>(coef_x)[x];
-    const uint8_t* p00 = img + ((size_t)cy.x * Ws + cx.x) * 3;
-    const uint8_t* p01 = img + ((size_t)cy.x * Ws + cx.y) * 3;
-    const uint8_t* p10 = img + ((size_t)cy.y * Ws + cx.x) * 3;
-    const uint8_t* p11 = img + ((size_t)cy.y * Ws + cx.y) * 3;
-#pragma unroll
-    for (int ch = 0; ch < 3; ch++) {
-        const int S0 = p00[ch] * cx.z + p01[ch] * cx.w;  // horizontal pass, x2048
-        const int S1 = p10[ch] * cx.z + p11[ch] * cx.w;
-        const int r = (((cy.z * (S0 >> 4)) >> 16) + ((cy.w * (S1 >> 4)) >> 16) + 2) >> 2;
-        o[ch] = (uint8_t)min(max(r, 0), 255);
     }
 }
 
@@ -1540,124 +1259,6 @@ int salve_bev_keys_from_pixels(const salve_bev_config_t* cfg, const int32_t* xy,
         SALVE_HIP_CHECK(hipGetLastError());
     }
     return emit_keys(d, ws, rgb, out_bev, nullptr, s);
-}
-
-int salve_bev_export_u8(const uint32_t* bev, int32_t n, int32_t bev_h, int32_t bev_w, uint8_t* out, void* stream) {
-    if (n == 0) return SALVE_OK;
-    if (!bev || !out || n < 0 || bev_h <= 0 || bev_w <= 0) { salve_fail("salve_bev_export_u8: bad argument"); return SALVE_ERR_BAD_ARG; }
-    const size_t npx = (size_t)n * bev_h * bev_w;
-    hipLaunchKernelGGL(bev_export_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, (hipStream_t)stream, bev, npx, out);
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
-}
-
-int salve_resize_rgb_u8(const uint8_t* src, int32_t n, int32_t src_h, int32_t src_w, uint8_t* dst, int32_t dst_h, int32_t dst_w,
-                        const int32_t* coef_y, const int32_t* coef_x, void* stream) {
-    if (n == 0) return SALVE_OK;
-    if (!src || !dst || n < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) {
-        salve_fail("salve_resize_rgb_u8: null pointer or bad size");
-        return SALVE_ERR_BAD_ARG;
-    }
-    const int area2 = (src_h == 2 * dst_h && src_w == 2 * dst_w) ? 1 : 0;
-    if (!area2 && (!coef_y || !coef_x)) { salve_fail("salve_resize_rgb_u8: tap tables are required unless the scale is exactly 2"); return SALVE_ERR_BAD_ARG; }
-    const size_t total = (size_t)n * dst_h * dst_w;
-    hipLaunchKernelGGL(resize_rgb_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src, n, src_h, src_w, dst,
-                       dst_h, dst_w, coef_y, coef_x, area2);
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
-}
-
-int salve_bev_tiles(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs, int32_t n_jobs,
-                    const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
-                    void* out, int32_t out_format, int32_t out_c, void* stream) {
-    if (n_jobs == 0) return SALVE_OK;
-    if (!bev || !jobs || !coef_y || !coef_x || !lut || !out || n_jobs < 0 || bev_h <= 0 || bev_w <= 0) {
-        salve_fail("salve_bev_tiles: null pointer or bad size");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (crop <= 0 || resize < crop || out_c < 3) { salve_fail("salve_bev_tiles: need 0 < crop <= resize, out_c >= 3"); return SALVE_ERR_BAD_ARG; }
-    if (out_format != SALVE_TILE_F32_NCHW && out_format != SALVE_TILE_F16_NHWC && out_format != SALVE_TILE_U8X4) { salve_fail("unknown tile format"); return SALVE_ERR_UNSUPPORTED; }
-    if (n_jobs > 65535) { salve_fail("at most 65535 tile jobs per call"); return SALVE_ERR_BAD_ARG; }
-    dim3 g((crop * crop + 255) / 256, n_jobs);
-    hipLaunchKernelGGL(bev_tile_kernel, g, dim3(256), 0, (hipStream_t)stream, bev, bev_w, jobs, coef_y, coef_x, resize, crop,
-                       lut, out, out_format, out_c);
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
-}
-
-int salve_bev_tiles_aug(const uint32_t* bev, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs, const salve_tile_aug_t* aug,
-                        int32_t n_jobs, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
-                        float* out, int32_t out_c, void* stream) {
-    if (n_jobs == 0) return SALVE_OK;
-    if (!bev || !jobs || !aug || !coef_y || !coef_x || !lut || !out || n_jobs < 0 || bev_h <= 0 || bev_w <= 0) {
-        salve_fail("salve_bev_tiles_aug: null pointer or bad size");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (crop <= 0 || resize < crop || out_c < 3) { salve_fail("salve_bev_tiles_aug: need 0 < crop <= resize, out_c >= 3"); return SALVE_ERR_BAD_ARG; }
-    if (n_jobs > 65535) { salve_fail("at most 65535 tile jobs per call"); return SALVE_ERR_BAD_ARG; }
-    dim3 g((crop * crop + 255) / 256, n_jobs);
-    hipLaunchKernelGGL(bev_tile_aug_kernel, g, dim3(256), 0, (hipStream_t)stream, bev, bev_w, jobs, aug, coef_y, coef_x, resize, crop, lut, out,
-                       out_c);
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
-}
-
-int salve_bev_tile_pairs(const uint32_t* bev_a, const uint32_t* bev_b, int32_t bev_h, int32_t bev_w, const salve_tile_job_t* jobs_a,
-                         const salve_tile_job_t* jobs_b, int32_t n_pairs, const int32_t* coef_y, const int32_t* coef_x, int32_t resize,
-                         int32_t crop, const float* lut, void* out, int32_t out_c, int32_t b_pretiled, void* stream) {
-    if (n_pairs == 0) return SALVE_OK;
-    if (!bev_a || !bev_b || !jobs_a || !jobs_b || !coef_y || !coef_x || !lut || !out || n_pairs < 0 || bev_h <= 0 || bev_w <= 0) {
-        salve_fail("salve_bev_tile_pairs: null pointer or bad size");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (crop <= 0 || resize < crop || out_c < 6 || out_c % 2 != 0) { salve_fail("salve_bev_tile_pairs: need 0 < crop <= resize, even out_c >= 6"); return SALVE_ERR_BAD_ARG; }
-    if (n_pairs > 65535) { salve_fail("at most 65535 tile pairs per call"); return SALVE_ERR_BAD_ARG; }
-    const int n_blocks = (crop * crop + 255) / 256;
-    const int xcd_group = 1;   // the workgroups of a pair on one XCD: its two BEV images are read through one L2 (round 3: -0.3 ms per 4096)
-    dim3 g((unsigned)((xcd_group ? (n_pairs + 7) / 8 * 8 : n_pairs) * n_blocks));
-    hipLaunchKernelGGL(bev_tile_pair_kernel, g, dim3(256), 0, (hipStream_t)stream, bev_a, bev_b, bev_w, jobs_a, jobs_b, coef_y, coef_x,
-                       resize, crop, lut, reinterpret_cast<uint16_t*>(out), out_c, n_pairs, n_blocks, xcd_group, b_pretiled ? 1 : 0);
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
-}
-
-int salve_bev_train_tiles(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
-                          const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
-                          int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
-                          void* out, int32_t out_format, int32_t out_c, int32_t* status, void* stream) {
-    if (batch == 0) return SALVE_OK;
-    if (!bev_a || !bev_b || !jobs_a || !jobs_b || !aug || !coef_y || !coef_x || !lut || !out || batch < 0 || n_bev_a <= 0 || n_bev_b <= 0 ||
-        bev_h <= 0 || bev_w <= 0) {
-        salve_fail("salve_bev_train_tiles: null pointer or bad size");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (crop <= 0 || resize < crop) { salve_fail("salve_bev_train_tiles: need 0 < crop <= resize"); return SALVE_ERR_BAD_ARG; }
-    if (per_sample < 1 || per_sample > 3) { salve_fail("salve_bev_train_tiles: 1 to 3 images per sample and table"); return SALVE_ERR_BAD_ARG; }
-    if (out_c <= 0 || out_c % 8 != 0 || out_c < 6 * per_sample || out_c > 24) {
-        salve_fail("salve_bev_train_tiles: out_c must be a multiple of 8 that holds the sample's 6 * per_sample channels (8, 16 or 24)");
-        return SALVE_ERR_BAD_ARG;
-    }
-    if (out_format != SALVE_TILE_F32_NHWC && out_format != SALVE_TILE_BF16_NHWC) { salve_fail("salve_bev_train_tiles: unknown tile format"); return SALVE_ERR_BAD_ARG; }
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) { salve_fail("salve_bev_train_tiles: out must be 16-byte aligned"); return SALVE_ERR_BAD_ARG; }
-    if (batch > 65535) { salve_fail("at most 65535 samples per call"); return SALVE_ERR_BAD_ARG; }
-    const int n_blocks = (crop * crop + 255) / 256;
-    const TrainTiles t = {bev_a, bev_b, jobs_a, jobs_b, aug, coef_y, coef_x, lut, out, status, (long long)n_bev_a * bev_h * bev_w,
-                          (long long)n_bev_b * bev_h * bev_w, bev_w, bev_h * bev_w, resize, crop, batch, per_sample, n_blocks};
-    const dim3 g((unsigned)((batch + 7) / 8 * 8 * n_blocks));
-    const bool bf16 = out_format == SALVE_TILE_BF16_NHWC;
-    hipStream_t s = (hipStream_t)stream;
-    if (out_c == 8) {
-        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<8, true>), g, dim3(256), 0, s, t);
-        else hipLaunchKernelGGL((bev_train_tile_kernel<8, false>), g, dim3(256), 0, s, t);
-    } else if (out_c == 16) {
-        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<16, true>), g, dim3(256), 0, s, t);
-        else hipLaunchKernelGGL((bev_train_tile_kernel<16, false>), g, dim3(256), 0, s, t);
-    } else {
-        if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<24, true>), g, dim3(256), 0, s, t);
-        else hipLaunchKernelGGL((bev_train_tile_kernel<24, false>), g, dim3(256), 0, s, t);
-    }
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
 }
 
 }  // extern "C"
