@@ -49,7 +49,8 @@ typedef enum {
                                         salve_bev_jpeg_decode_workspace_bytes and the SALVE_JPEG_* bits of its per-image status),
                                         salve_bev_jpeg_decode_lanes (with salve_bev_jpeg_decode_lanes_workspace_bytes, salve_bev_jpeg_subseq_bytes
                                         and salve_jpeg_segment_t), salve_bev_jpeg_decode_sampled / _lanes_sampled (with their two
-                                        _workspace_bytes queries and SALVE_JPEG_SAMPLING_*) */
+                                        _workspace_bytes queries and SALVE_JPEG_SAMPLING_*), salve_bev_train_tiles_jitter (with
+                                        salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -63,7 +64,8 @@ typedef enum {
 #define SALVE_STATUS_LAYOUT_THICKNESS 8 /* layout_rasterise: a segment of thickness >= 19 pixels (OpenCV draws its end caps as 20- / 72-gons,
                                           which are not implemented) -- that segment is not drawn */
 #define SALVE_STATUS_BAD_TILE_JOB 16 /* bev_train_tiles: a job names another sample, channels outside the sample, an image outside its array, or
-                                        a draw carries unknown flag bits -- that sample is not written */
+                                        a draw carries unknown flag bits (bev_train_tiles_jitter: or a jitter record is malformed) -- that
+                                        sample is not written */
 #define SALVE_STATUS_BAD_PANO_SLOT 32 /* bev_pano_index_update: the slot list names a slot outside [0, n_panos) -- that entry is skipped, the
                                          other listed slots are updated */
 #define SALVE_STATUS_BAD_LAYOUT 64 /* layout_pose: an image record names a panorama outside [0, n_panos), offsets outside the output capacities,
@@ -349,6 +351,46 @@ int salve_bev_train_tiles(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t
                           const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
                           int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
                           void* out, int32_t out_format, int32_t out_c, int32_t* status, void* stream);
+
+/* salve_bev_train_tiles with the reference's photometric augmentation between Resize and Crop: torchvision's tensor
+ * ColorJitter(brightness=0.5, contrast=0.5, saturation=0.5, hue=0.05) on the uint8 resized image (salve/utils/transform.py:619-686; the
+ * functional_tensor.py form of torchvision 0.11 / 0.12), every image of a sample with its OWN record.  The arithmetic is DESIGN.md 4.23's,
+ * float32 with one rounding per operation; trunc8(v) = v clamped to [0, 255], truncated to a byte:
+ *   grey        trunc8((0.2989f r + 0.587f g) + 0.114f b)
+ *   brightness  trunc8(b x + b_c 0);  saturation  trunc8(s x + s_c grey(pixel));  contrast  trunc8(c x + c_c m) with
+ *               m = (float)S / (float)(resize * resize), S the integer sum of grey over the WHOLE resized image as the operations in front
+ *               of contrast in this image's order left it (not the crop), one correctly rounded division
+ *   hue         x / 255 -> _rgb2hsv -> h = remainder(h + hue, 1) -> _hsv2rgb -> (byte)(c * 255): not the identity at hue = 0
+ * The record's operations run in `order`, the ones whose mask bit is clear skipped.  With every factor 1 and hue disabled the output is
+ * salve_bev_train_tiles', bit for bit.  Two launches on `stream` behind a memset of the workspace: the grey sums by integer atomic adds
+ * (order-independent: the same input gives the same bytes on every run), then salve_bev_train_tiles' kernel with the chain in front of
+ * the table lookup.
+ *   jitter      device salve_tile_jitter_t [batch][2 * per_sample]: record [s][g] belongs to the image whose job names channels 3 g ..
+ *               3 g + 2 of sample s (x1 .. x6 of the early-fusion concatenation).  Here every job's .chan + 3 <= 6 * per_sample.
+ *   workspace   device memory, 4-byte aligned, at least salve_bev_train_tiles_jitter_workspace_bytes(batch, per_sample) bytes (0 for a
+ *               batch or per_sample the entry refuses); only this call's launches use it
+ *   status      as salve_bev_train_tiles, and: a record whose order is no permutation of 0..3, with mask bits above 15 or with a
+ *               non-finite factor or complement raises SALVE_STATUS_BAD_TILE_JOB and leaves sample s unwritten.
+ * Refusals: salve_bev_train_tiles', and SALVE_ERR_UNSUPPORTED for resize * resize * 255 >= 2^24 (resize > 256: the grey sum would no
+ * longer be an exact float32), SALVE_ERR_BAD_ARG for a null table or workspace, SALVE_ERR_WORKSPACE for a short workspace. */
+#define SALVE_JITTER_BRIGHTNESS 0 /* operation codes of salve_tile_jitter_t.order (torchvision's fn_id) and bit numbers of .mask */
+#define SALVE_JITTER_CONTRAST 1
+#define SALVE_JITTER_SATURATION 2
+#define SALVE_JITTER_HUE 3
+typedef struct {
+    uint8_t order[4];   /* a permutation of the four operation codes, first applied first */
+    int32_t mask;       /* bit (1 << code) set: the operation is applied */
+    float brightness, contrast, saturation; /* blend factors f */
+    float hue;                              /* added to h, in turns */
+    float brightness_c, contrast_c, saturation_c; /* (float)(1.0 - (double)f), formed on the host */
+    int32_t reserved;
+} salve_tile_jitter_t;
+size_t salve_bev_train_tiles_jitter_workspace_bytes(int32_t batch, int32_t per_sample);
+int salve_bev_train_tiles_jitter(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                                 const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
+                                 int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                                 void* out, int32_t out_format, int32_t out_c, const salve_tile_jitter_t* jitter, void* workspace,
+                                 size_t workspace_bytes, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

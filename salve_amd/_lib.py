@@ -90,6 +90,8 @@ EXPORTED_SYMBOLS = (
     "salve_bev_jpeg_decode_lanes_sampled_workspace_bytes",
     "salve_bev_jpeg_decode_sampled",
     "salve_bev_jpeg_decode_lanes_sampled",
+    "salve_bev_train_tiles_jitter_workspace_bytes",
+    "salve_bev_train_tiles_jitter",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -135,6 +137,11 @@ JPEG_MAX_SEGMENTS = 1 << 24
 TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 TILE_HFLIP, TILE_VFLIP = 1, 2
 assert LAYOUT_POSE_DTYPE.itemsize == 48 and HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
+# salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
+TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
+                              ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
+JITTER_BRIGHTNESS, JITTER_CONTRAST, JITTER_SATURATION, JITTER_HUE = 0, 1, 2, 3
+assert TILE_JITTER_DTYPE.itemsize == 40
 
 # salve_conv_f32_* / salve_conv_bf16_* passes (include/salve_hip.h: SALVE_CONV_*)
 CONV_FWD, CONV_DGRAD, CONV_WGRAD = 0, 1, 2
@@ -264,6 +271,10 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_tiles_aug.restype = ctypes.c_int
     lib.salve_bev_train_tiles.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp]
     lib.salve_bev_train_tiles.restype = ctypes.c_int
+    lib.salve_bev_train_tiles_jitter_workspace_bytes.argtypes = [i32, i32]
+    lib.salve_bev_train_tiles_jitter_workspace_bytes.restype = sz
+    lib.salve_bev_train_tiles_jitter.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, sz, vp, vp]
+    lib.salve_bev_train_tiles_jitter.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -343,7 +354,7 @@ def check_status_word(word: int, what: str) -> None:
         raise SalveHipError(f"{what}: a layout segment of 19 pixels or more was left out (its OpenCV end caps are not implemented)")
     if word & STATUS_BAD_TILE_JOB:
         raise SalveHipError(f"{what}: a train-tile job names another sample, channels or an image outside its arrays (or a draw has unknown "
-                            "flag bits); that sample was not written")
+                            "flag bits, or a jitter record is malformed); that sample was not written")
     if word & STATUS_BAD_PANO_SLOT:
         raise SalveHipError(f"{what}: a panorama-index update names a slot outside the resident pool; that slot's index was not rebuilt")
     if word & STATUS_BAD_LAYOUT:

@@ -13,6 +13,8 @@
 //   bev_tile_aug_kernel     salve_bev_tiles_aug: the train transform (crop at the job's offset, then the flips), fp32 NCHW
 //   bev_tile_pair_kernel    salve_bev_tile_pairs: both tiles of an early-fusion pair, six fp16 channels in whole-pixel stores
 //   bev_train_tile_kernel   salve_bev_train_tiles: the train transform of a whole batch as NHWC [batch, crop, crop, CP], fp32 or bf16
+//   bev_jitter_grey_sum_kernel   salve_bev_train_tiles_jitter: ColorJitter's contrast needs the mean grey level of the whole resized image;
+//                           this launch sums it, bev_train_tile_kernel<.., JITTER> then runs the colour chain in front of the table lookup
 //   bev_export_kernel       salve_bev_export_u8: uint32 -> uint8 [.., 3], the array render_bev_image returns
 //   resize_rgb_kernel       salve_resize_rgb_u8: the panorama ingest's cv2.resize on uint8 RGB
 //
@@ -151,9 +153,107 @@ struct TrainTiles {
     int32_t* status;
     long long px_a, px_b;             // uint32 elements of bev_a / bev_b
     int W, HW, resize, crop, batch, per_sample, n_blocks;
+    const salve_tile_jitter_t* jitter;   // [batch][2 * per_sample], and the grey sums beside it: salve_bev_train_tiles_jitter only
+    uint32_t* grey_sum;
 };
 
-template <int CP, bool BF16>
+// The jobs of sample smp into ja / jb (k >= per_sample: naming no channel group); true if one of them is outside its sample, the channels
+// [0, chan_end) or its image array.
+template <int MAX_S>
+__device__ __forceinline__ bool train_jobs_bad(const TrainTiles& t, int smp, int chan_end, salve_tile_job_t ja[MAX_S], salve_tile_job_t jb[MAX_S]) {
+    bool bad = false;
+#pragma unroll
+    for (int k = 0; k < MAX_S; k++) {
+        if (k < t.per_sample) {
+            ja[k] = t.jobs_a[(size_t)smp * t.per_sample + k];
+            jb[k] = t.jobs_b[(size_t)smp * t.per_sample + k];
+            bad |= ja[k].slot != smp || ja[k].chan < 0 || ja[k].chan % 3 != 0 || ja[k].chan + 3 > chan_end || ja[k].bev_offset < 0 || ja[k].bev_offset + t.HW > t.px_a;
+            bad |= jb[k].slot != smp || jb[k].chan < 0 || jb[k].chan % 3 != 0 || jb[k].chan + 3 > chan_end || jb[k].bev_offset < 0 || jb[k].bev_offset + t.HW > t.px_b;
+        } else {
+            ja[k].chan = jb[k].chan = -1;   // names no channel group
+            ja[k].bev_offset = jb[k].bev_offset = 0;
+        }
+    }
+    return bad;
+}
+
+// The image whose job names channel group g of the sample, or null.
+template <int MAX_S>
+__device__ __forceinline__ const uint32_t* train_group_image(const TrainTiles& t, const salve_tile_job_t ja[MAX_S], const salve_tile_job_t jb[MAX_S], int g) {
+    const uint32_t* img = nullptr;
+#pragma unroll
+    for (int k = 0; k < MAX_S; k++) {
+        if (ja[k].chan == 3 * g) img = t.bev_a + ja[k].bev_offset;
+        if (jb[k].chan == 3 * g) img = t.bev_b + jb[k].bev_offset;
+    }
+    return img;
+}
+
+// ---- salve_bev_train_tiles_jitter: ColorJitter on the resized bytes (bev_tile_math.h), per image by its record.
+__device__ __forceinline__ bool jitter_record_bad(const salve_tile_jitter_t& r) {
+    int seen = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) seen |= r.order[k] < 4 ? 1 << r.order[k] : 16;
+    const float f[7] = {r.brightness, r.contrast, r.saturation, r.hue, r.brightness_c, r.contrast_c, r.saturation_c};
+    bool bad = seen != 15 || (r.mask & ~15) != 0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) bad |= !(fabsf(f[k]) <= 3.402823466e38f);   // NaN and the infinities
+    return bad;
+}
+
+// The record's enabled operations on one pixel, in its order.  UNTIL_CONTRAST: only the ones in front of contrast (what the grey sum is
+// taken over; `mean` is unused).
+template <bool UNTIL_CONTRAST>
+__device__ __forceinline__ void jitter_pixel(const salve_tile_jitter_t& r, int q[3], float mean) {
+    for (int k = 0; k < 4; k++) {
+        const int op = r.order[k];
+        if (UNTIL_CONTRAST && op == SALVE_JITTER_CONTRAST) return;
+        if (!((r.mask >> op) & 1)) continue;
+        if (op == SALVE_JITTER_BRIGHTNESS) jitter_blend(q, 0.0f, r.brightness, r.brightness_c);
+        else if (op == SALVE_JITTER_CONTRAST) jitter_blend(q, mean, r.contrast, r.contrast_c);
+        else if (op == SALVE_JITTER_SATURATION) jitter_blend(q, (float)jitter_grey(q), r.saturation, r.saturation_c);
+        else jitter_hue(q, r.hue);
+    }
+}
+
+// First launch: grey_sum[smp][g] += grey of every pixel of the WHOLE resized image of channel group g of sample smp, as the operations in
+// front of contrast leave it -- GREY_PIXELS resized pixels per thread, summed over the workgroup, one integer atomic add per workgroup
+// (integer adds commute: the sum does not depend on their order).  The workgroups of one image on one XCD, as the second launch's: image
+// (id >> 3) / n_blocks * 8 + (id & 7).  A sample with a bad job or record is skipped here and reported by the second launch; so is an
+// image whose contrast is disabled.
+constexpr int GREY_PIXELS = 8;
+
+__global__ __launch_bounds__(256) void bev_jitter_grey_sum_kernel(const TrainTiles t, int n_blocks) {
+    const int G = 2 * t.per_sample, id = blockIdx.x, s_ = id >> 3;
+    const int image = (s_ / n_blocks) * 8 + (id & 7), blk = s_ % n_blocks;
+    if (image >= t.batch * G) return;
+    const int smp = image / G, g = image % G;
+    salve_tile_job_t ja[3], jb[3];
+    bool bad = train_jobs_bad<3>(t, smp, 3 * G, ja, jb);
+    for (int k = 0; k < G; k++) bad |= jitter_record_bad(t.jitter[(size_t)smp * G + k]);
+    const uint32_t* img = train_group_image<3>(t, ja, jb, g);
+    const salve_tile_jitter_t r = t.jitter[(size_t)image];
+    if (bad || !img || !((r.mask >> SALVE_JITTER_CONTRAST) & 1)) return;   // (workgroup-uniform)
+    uint32_t grey = 0;
+    for (int p = 0; p < GREY_PIXELS; p++) {
+        const int idx = (blk * GREY_PIXELS + p) * 256 + threadIdx.x;
+        if (idx >= t.resize * t.resize) break;
+        const int4 cy = reinterpret_cast<const int4*>(t.coef_y)[idx / t.resize];
+        const int4 cx = reinterpret_cast<const int4*>(t.coef_x)[idx % t.resize];
+        int q[3];
+        tile_bytes(img, t.W, cy, cx, q);
+        jitter_pixel<true>(r, q, 0.0f);
+        grey += (uint32_t)jitter_grey(q);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) grey += __shfl_down(grey, o, 64);
+    __shared__ uint32_t part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = grey;
+    __syncthreads();
+    if (threadIdx.x == 0) atomicAdd(&t.grey_sum[(size_t)image], part[0] + part[1] + part[2] + part[3]);
+}
+
+template <int CP, bool BF16, bool JITTER>
 __global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t) {
     typedef __attribute__((__ext_vector_type__(8))) float f32x8;
     typedef __attribute__((__ext_vector_type__(8))) __bf16 bf16x8;
@@ -165,18 +265,9 @@ __global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t)
     const salve_tile_aug_t a = t.aug[smp];
     salve_tile_job_t ja[MAX_S], jb[MAX_S];
     bool bad = (a.flags & ~(SALVE_TILE_HFLIP | SALVE_TILE_VFLIP)) != 0;
-#pragma unroll
-    for (int k = 0; k < MAX_S; k++) {
-        if (k < t.per_sample) {
-            ja[k] = t.jobs_a[(size_t)smp * t.per_sample + k];
-            jb[k] = t.jobs_b[(size_t)smp * t.per_sample + k];
-            bad |= ja[k].slot != smp || ja[k].chan < 0 || ja[k].chan % 3 != 0 || ja[k].chan + 3 > CP || ja[k].bev_offset < 0 || ja[k].bev_offset + t.HW > t.px_a;
-            bad |= jb[k].slot != smp || jb[k].chan < 0 || jb[k].chan % 3 != 0 || jb[k].chan + 3 > CP || jb[k].bev_offset < 0 || jb[k].bev_offset + t.HW > t.px_b;
-        } else {
-            ja[k].chan = jb[k].chan = -1;   // names no channel group
-            ja[k].bev_offset = jb[k].bev_offset = 0;
-        }
-    }
+    bad |= train_jobs_bad<MAX_S>(t, smp, JITTER ? 6 * t.per_sample : CP, ja, jb);
+    if (JITTER)
+        for (int k = 0; k < 2 * t.per_sample; k++) bad |= jitter_record_bad(t.jitter[(size_t)smp * 2 * t.per_sample + k]);
     if (bad) {
         if (t.status && blk == 0 && threadIdx.x == 0) atomicOr(t.status, SALVE_STATUS_BAD_TILE_JOB);
         return;
@@ -193,13 +284,19 @@ __global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t)
     for (int c = 0; c < CP; c++) v[c] = 0.0f;
 #pragma unroll
     for (int g = 0; g < GROUPS; g++) {   // channel group g = channels 3 g .. 3 g + 2: the image whose job names it (workgroup-uniform)
-        const uint32_t* img = nullptr;
+        const uint32_t* img = train_group_image<MAX_S>(t, ja, jb, g);
+        if (!img) continue;
+        if (JITTER) {   // (a group with an image lies below 2 * per_sample: its jobs were checked against 6 * per_sample channels)
+            const salve_tile_jitter_t r = t.jitter[(size_t)smp * 2 * t.per_sample + g];
+            const float mean = (float)t.grey_sum[(size_t)smp * 2 * t.per_sample + g] / (float)(t.resize * t.resize);   // torch.mean: ONE division
+            int q[3];
+            tile_bytes(img, t.W, cy, cx, q);
+            jitter_pixel<false>(r, q, mean);
 #pragma unroll
-        for (int k = 0; k < MAX_S; k++) {
-            if (ja[k].chan == 3 * g) img = t.bev_a + ja[k].bev_offset;
-            if (jb[k].chan == 3 * g) img = t.bev_b + jb[k].bev_offset;
+            for (int ch = 0; ch < 3; ch++) v[3 * g + ch] = t.lut[ch * 256 + q[ch]];
+        } else {
+            tile_pixel(img, t.W, cy, cx, t.lut, &v[3 * g]);
         }
-        if (img) tile_pixel(img, t.W, cy, cx, t.lut, &v[3 * g]);
     }
     const size_t px = ((size_t)smp * t.crop * t.crop + idx) * CP;
     if (BF16) {
@@ -216,10 +313,19 @@ __global__ __launch_bounds__(256) void bev_train_tile_kernel(const TrainTiles t)
     }
 }
 
-template <int CP>
+template <int CP, bool JITTER>
 void launch_train_tiles(bool bf16, dim3 grid, hipStream_t s, const TrainTiles& t) {
-    if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<CP, true>), grid, dim3(256), 0, s, t);
-    else hipLaunchKernelGGL((bev_train_tile_kernel<CP, false>), grid, dim3(256), 0, s, t);
+    if (bf16) hipLaunchKernelGGL((bev_train_tile_kernel<CP, true, JITTER>), grid, dim3(256), 0, s, t);
+    else hipLaunchKernelGGL((bev_train_tile_kernel<CP, false, JITTER>), grid, dim3(256), 0, s, t);
+}
+
+template <bool JITTER>
+void launch_train_tiles(int out_c, bool bf16, dim3 grid, hipStream_t s, const TrainTiles& t) {
+    switch (out_c) {
+        case 8: launch_train_tiles<8, JITTER>(bf16, grid, s, t); break;
+        case 16: launch_train_tiles<16, JITTER>(bf16, grid, s, t); break;
+        default: launch_train_tiles<24, JITTER>(bf16, grid, s, t);
+    }
 }
 
 __global__ __launch_bounds__(256) void bev_export_kernel(const uint32_t* __restrict__ bev, size_t npx,
@@ -274,6 +380,55 @@ int refuse_tiles(const char* entry, bool args_ok, int32_t resize, int32_t crop, 
     else return SALVE_OK;
     salve_fail(msg);
     return code;
+}
+
+// salve_bev_train_tiles and salve_bev_train_tiles_jitter: one set of refusals, one launch geometry; with_jitter adds the entry's own
+// refusals, the zeroed grey sums and the launch that fills them.
+int train_tiles(const char* entry, const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug, int32_t batch,
+                const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut, void* out, int32_t out_format,
+                int32_t out_c, bool with_jitter, const salve_tile_jitter_t* jitter, void* workspace, size_t workspace_bytes, int32_t* status,
+                void* stream) {
+    char msg[200];
+    if (batch == 0) return SALVE_OK;
+    if (per_sample < 1 || per_sample > 3) { snprintf(msg, sizeof(msg), "%s: 1 to 3 images per sample and table", entry); salve_fail(msg); return SALVE_ERR_BAD_ARG; }
+    const int st = refuse_tiles(entry,
+                                bev_a && bev_b && jobs_a && jobs_b && aug && coef_y && coef_x && lut && out && batch > 0 && n_bev_a > 0 && n_bev_b > 0 && bev_h > 0 && bev_w > 0,
+                                resize, crop, out_c % 8 == 0 && out_c >= 6 * per_sample && out_c <= 24,
+                                "out_c a multiple of 8 that holds the sample's 6 * per_sample channels (8, 16 or 24)", batch,
+                                out_format == SALVE_TILE_F32_NHWC || out_format == SALVE_TILE_BF16_NHWC);
+    if (st != SALVE_OK) return st;
+    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) { snprintf(msg, sizeof(msg), "%s: out must be 16-byte aligned", entry); salve_fail(msg); return SALVE_ERR_BAD_ARG; }
+    const int n_blocks = (crop * crop + 255) / 256;
+    const TrainTiles t = {bev_a, bev_b, jobs_a, jobs_b, aug, coef_y, coef_x, lut, out, status, (long long)n_bev_a * bev_h * bev_w,
+                          (long long)n_bev_b * bev_h * bev_w, bev_w, bev_h * bev_w, resize, crop, batch, per_sample, n_blocks,
+                          jitter, reinterpret_cast<uint32_t*>(workspace)};
+    const dim3 g((unsigned)((batch + 7) / 8 * 8 * n_blocks));
+    const bool bf16 = out_format == SALVE_TILE_BF16_NHWC;
+    if (!with_jitter) {
+        launch_train_tiles<false>(out_c, bf16, g, (hipStream_t)stream, t);
+        SALVE_HIP_CHECK(hipGetLastError());
+        return SALVE_OK;
+    }
+    if ((long long)resize * resize * 255 >= (1LL << 24)) {
+        snprintf(msg, sizeof(msg), "%s: resize * resize * 255 must stay below 2^24 (resize <= 256): the grey sum is an exact float32", entry);
+        salve_fail(msg);
+        return SALVE_ERR_UNSUPPORTED;
+    }
+    if (!jitter || !workspace || reinterpret_cast<uintptr_t>(workspace) % 4 != 0) {
+        snprintf(msg, sizeof(msg), "%s: null jitter table or workspace, or a misaligned workspace", entry);
+        salve_fail(msg);
+        return SALVE_ERR_BAD_ARG;
+    }
+    const size_t need = salve_bev_train_tiles_jitter_workspace_bytes(batch, per_sample);
+    if (workspace_bytes < need) { snprintf(msg, sizeof(msg), "%s: workspace too small", entry); salve_fail(msg); return SALVE_ERR_WORKSPACE; }
+    SALVE_HIP_CHECK(hipMemsetAsync(workspace, 0, need, (hipStream_t)stream));
+    const int sum_blocks = (resize * resize + 256 * GREY_PIXELS - 1) / (256 * GREY_PIXELS), images = batch * 2 * per_sample;
+    hipLaunchKernelGGL(bev_jitter_grey_sum_kernel, dim3((unsigned)((images + 7) / 8 * 8 * sum_blocks)), dim3(256), 0, (hipStream_t)stream, t, sum_blocks);
+    SALVE_HIP_CHECK(hipGetLastError());
+    launch_train_tiles<true>(out_c, bf16, g, (hipStream_t)stream, t);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
 }
 
 }  // namespace
@@ -354,27 +509,22 @@ int salve_bev_train_tiles(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t
                           const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
                           int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
                           void* out, int32_t out_format, int32_t out_c, int32_t* status, void* stream) {
-    if (batch == 0) return SALVE_OK;
-    if (per_sample < 1 || per_sample > 3) { salve_fail("salve_bev_train_tiles: 1 to 3 images per sample and table"); return SALVE_ERR_BAD_ARG; }
-    const int st = refuse_tiles("salve_bev_train_tiles",
-                                bev_a && bev_b && jobs_a && jobs_b && aug && coef_y && coef_x && lut && out && batch > 0 && n_bev_a > 0 && n_bev_b > 0 && bev_h > 0 && bev_w > 0,
-                                resize, crop, out_c % 8 == 0 && out_c >= 6 * per_sample && out_c <= 24,
-                                "out_c a multiple of 8 that holds the sample's 6 * per_sample channels (8, 16 or 24)", batch,
-                                out_format == SALVE_TILE_F32_NHWC || out_format == SALVE_TILE_BF16_NHWC);
-    if (st != SALVE_OK) return st;
-    if (reinterpret_cast<uintptr_t>(out) % 16 != 0) { salve_fail("salve_bev_train_tiles: out must be 16-byte aligned"); return SALVE_ERR_BAD_ARG; }
-    const int n_blocks = (crop * crop + 255) / 256;
-    const TrainTiles t = {bev_a, bev_b, jobs_a, jobs_b, aug, coef_y, coef_x, lut, out, status, (long long)n_bev_a * bev_h * bev_w,
-                          (long long)n_bev_b * bev_h * bev_w, bev_w, bev_h * bev_w, resize, crop, batch, per_sample, n_blocks};
-    const dim3 g((unsigned)((batch + 7) / 8 * 8 * n_blocks));
-    const bool bf16 = out_format == SALVE_TILE_BF16_NHWC;
-    switch (out_c) {
-        case 8: launch_train_tiles<8>(bf16, g, (hipStream_t)stream, t); break;
-        case 16: launch_train_tiles<16>(bf16, g, (hipStream_t)stream, t); break;
-        default: launch_train_tiles<24>(bf16, g, (hipStream_t)stream, t);
-    }
-    SALVE_HIP_CHECK(hipGetLastError());
-    return SALVE_OK;
+    return train_tiles("salve_bev_train_tiles", bev_a, n_bev_a, bev_b, n_bev_b, bev_h, bev_w, jobs_a, jobs_b, per_sample, aug, batch, coef_y, coef_x, resize, crop,
+                       lut, out, out_format, out_c, false, nullptr, nullptr, 0, status, stream);
+}
+
+size_t salve_bev_train_tiles_jitter_workspace_bytes(int32_t batch, int32_t per_sample) {
+    if (batch <= 0 || batch > 65535 || per_sample < 1 || per_sample > 3) return 0;
+    return (size_t)batch * 2 * per_sample * sizeof(uint32_t);   // the grey sums
+}
+
+int salve_bev_train_tiles_jitter(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                                 const salve_tile_job_t* jobs_a, const salve_tile_job_t* jobs_b, int32_t per_sample, const salve_tile_aug_t* aug,
+                                 int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
+                                 void* out, int32_t out_format, int32_t out_c, const salve_tile_jitter_t* jitter, void* workspace,
+                                 size_t workspace_bytes, int32_t* status, void* stream) {
+    return train_tiles("salve_bev_train_tiles_jitter", bev_a, n_bev_a, bev_b, n_bev_b, bev_h, bev_w, jobs_a, jobs_b, per_sample, aug, batch, coef_y, coef_x, resize,
+                       crop, lut, out, out_format, out_c, true, jitter, workspace, workspace_bytes, status, stream);
 }
 
 }  // extern "C"

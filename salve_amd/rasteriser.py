@@ -117,6 +117,7 @@ class BevRasteriser:
         self.index_builds = 0   # full salve_bev_pano_index_build launches of `pano_index` so far (update_panos makes none)
         self._jpeg_ws = {}      # the JPEG methods' workspace by stream, the largest any of them needed: callers on different streams never share one
         self._jpeg_tables = {}  # quality -> uint16 [2, 64] (host)
+        self._jitter_ws = {}    # train_tiles(jitter=)'s grey sums by stream
 
     # ------------------------------------------------------------------ helpers
     def _stream(self) -> ctypes.c_void_p:
@@ -590,21 +591,34 @@ class BevRasteriser:
         return out
 
     def train_tiles(self, bev_a: torch.Tensor, bev_b: torch.Tensor, jobs_a: torch.Tensor, jobs_b: torch.Tensor, per_sample: int,
-                    aug: torch.Tensor, batch: int, out: torch.Tensor) -> torch.Tensor:
+                    aug: torch.Tensor, batch: int, out: torch.Tensor, jitter: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The train transform of a whole batch in one launch (include/salve_hip.h: salve_bev_train_tiles): `out` is the trainable
         model's packed input [batch, crop, crop, Cp], float32 or bfloat16, every channel written (padding channels zero).  bev_a / bev_b:
         int32 [*, H, W] images; jobs_a / jobs_b: `upload_tile_jobs` tables, sample-major [batch][per_sample]; aug: TILE_AUG_DTYPE
-        bytes, one draw per sample.  Bad jobs are reported through the device status word (`check`)."""
+        bytes, one draw per sample.  Bad jobs are reported through the device status word (`check`).
+        jitter: TILE_JITTER_DTYPE bytes [batch][2 * per_sample] (`train_feed.jitter_table`), one ColorJitter draw per image by channel
+        group -- salve_bev_train_tiles_jitter, the photometric augmentation between Resize and Crop (two launches; its workspace is
+        kept per stream)."""
         Hb, Wb = self.bev_hw
         if out.dtype not in (torch.float32, torch.bfloat16):
             raise _lib.SalveHipError(f"train_tiles writes float32 or bfloat16, got {out.dtype}")
         if not out.is_contiguous() or tuple(out.shape[:3]) != (batch, self.crop, self.crop):
             raise _lib.SalveHipError(f"train_tiles: out must be contiguous [{batch}, {self.crop}, {self.crop}, Cp], got {tuple(out.shape)}")
         p = lambda t: ctypes.c_void_p(t.data_ptr())
-        with torch.cuda.device(self.device):
-            st = self.lib.salve_bev_train_tiles(
-                p(bev_a), int(bev_a.numel() // (Hb * Wb)), p(bev_b), int(bev_b.numel() // (Hb * Wb)), Hb, Wb, p(jobs_a), p(jobs_b), per_sample,
+        args = (p(bev_a), int(bev_a.numel() // (Hb * Wb)), p(bev_b), int(bev_b.numel() // (Hb * Wb)), Hb, Wb, p(jobs_a), p(jobs_b), per_sample,
                 p(aug), batch, p(self.coef_y), p(self.coef_x), self.resize, self.crop, p(self.lut), p(out),
-                _lib.TILE_F32_NHWC if out.dtype == torch.float32 else _lib.TILE_BF16_NHWC, int(out.shape[3]), status.ptr(self.device), self._stream())
-        _lib.check(st, "salve_bev_train_tiles")
+                _lib.TILE_F32_NHWC if out.dtype == torch.float32 else _lib.TILE_BF16_NHWC, int(out.shape[3]))
+        with torch.cuda.device(self.device):
+            if jitter is None:
+                st, entry = self.lib.salve_bev_train_tiles(*args, status.ptr(self.device), self._stream()), "salve_bev_train_tiles"
+            else:
+                entry = "salve_bev_train_tiles_jitter"
+                need = self.lib.salve_bev_train_tiles_jitter_workspace_bytes(batch, per_sample)
+                key = torch.cuda.current_stream(self.device).cuda_stream
+                ws = self._jitter_ws.get(key)
+                if batch > 0 and (ws is None or ws.numel() < need):   # (allocated under the stream that uses it, as the JPEG workspace)
+                    ws = self._jitter_ws[key] = torch.empty(max(need, 4), dtype=torch.uint8, device=self.device)
+                st = self.lib.salve_bev_train_tiles_jitter(*args, p(jitter), None if ws is None else p(ws), 0 if ws is None else ws.numel(),
+                                                           status.ptr(self.device), self._stream())
+        _lib.check(st, entry)
         return out

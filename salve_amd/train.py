@@ -3,7 +3,7 @@
     python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}] [--decode {host,device}]
-                              [--decode-entropy {image,lanes}] [--decode-read-ahead]
+                              [--decode-entropy {image,lanes}] [--decode-read-ahead] [--photometric device]
                               [--render-from DIR [--identity {kept,batch}] [--resident-panos N [--prefetch]] [--jpeg-quality Q]]
 
 Writes `train_ckpt.pth` (the reference's keys) and `results-{cfg_stem}.json` into --out (default: the config's
@@ -30,6 +30,9 @@ uploaded as the batches need them: for panorama sets that do not fit in device m
 current batch trains: the same batches, the uploads hidden under the step.
 --jpeg-quality Q (with --render-from; the reference's files: 75) puts every rendered image through the reference's JPEG round trip on
 the GPU before it is tiled: the batches of the rendered dataset on disk, without the files.
+--photometric device permits a config with apply_photometric_augmentation: True (refused without it): the reference's PhotometricShift --
+ColorJitter(brightness 0.5, contrast 0.5, saturation 0.5, hue 0.05) on every resized train image, each with draws of its own -- runs on
+the GPU inside the train-tile call of whichever feed is selected.  With the field False the flag changes nothing.
 """
 
 from __future__ import annotations
@@ -76,6 +79,8 @@ def main(argv=None) -> None:
                     help="--resident-panos: upload the next batch's missing panoramas beside the training step (N at least 4 x batch size)")
     ap.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
                     help="--render-from: JPEG round trip of every rendered image on the GPU at quality Q (the reference writes its tiles at 75)")
+    ap.add_argument("--photometric", choices=("device",), default=None,
+                    help="accept apply_photometric_augmentation: True and run the photometric augmentation on the GPU (without it such a config is refused)")
     a = ap.parse_args(argv)
     training._check_head(a.head)
     if a.decode_entropy != "image" and a.decode != "device":
@@ -127,7 +132,8 @@ def main(argv=None) -> None:
                                                    batch_size=args.batch_size, precision=a.precision, split=split, seed=a.seed,
                                                    resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
                                                    identity=identity, resident_panos=a.resident_panos, layouts=layouts, prefetch=a.prefetch,
-                                                   jpeg_quality=a.jpeg_quality)
+                                                   jpeg_quality=a.jpeg_quality,
+                                                   photometric=a.photometric if args.apply_photometric_augmentation else None)
             if split == "train":
                 src.load_panos(rgb, depth)
             else:   # the panoramas (or their pool) and their identity renders are on the device once
@@ -135,10 +141,11 @@ def main(argv=None) -> None:
             src.set_examples(*examples[split])
             sources[split] = src
         results = training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
-                                          norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality)
+                                          norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality, photometric=a.photometric)
     else:
         results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
-                                 head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead)
+                                 head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead,
+                                 photometric=a.photometric)
     logging.info(f"results in {out}: {results}")
 
 

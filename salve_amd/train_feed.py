@@ -1,8 +1,9 @@
 """What the two training feeds share (salve_amd.train_render.RenderedTrainSource, salve_amd.train_files.TileFileSource): the epoch's
 order, the augmentation draws and their table, the one upload of a batch's host tables, and the refusals of the arguments both take.
 Shuffle order and draws are those of `training.get_dataloader` + `transforms.TrainTransform`: the order of a
-`DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random`.
-Nothing here needs a device."""
+`DataLoader(shuffle=True, generator=<seeded>)`, one `TrainTransform.draw()` per example in batch order from Python's `random` -- and,
+where the photometric augmentation is on (`photometric="device"`), one `TrainTransform.draw_jitter()` per image from
+torch's global generator, with the record table that carries them.  Nothing here needs a device."""
 
 from __future__ import annotations
 
@@ -16,6 +17,7 @@ from salve_amd import _lib
 SPLITS = ("train", "val")   # the orders `plan_epoch` knows; a source may name more splits and map them onto these
 
 Draw = Tuple[int, int, bool, bool]   # (crop_y, crop_x, hflip, vflip)
+JitterDraw = Tuple[Tuple[int, int, int, int], int, float, float, float, float]   # (order, mask, brightness, contrast, saturation, hue) of ONE image
 
 
 def check_arguments(batch_size: int, split: Optional[str] = None, splits: Sequence[str] = SPLITS, precision: Optional[str] = None) -> None:
@@ -62,6 +64,30 @@ def aug_table(draws: Sequence[Draw]) -> np.ndarray:
     for k, (cy, cx, hflip, vflip) in enumerate(draws):
         aug[k] = (cy, cx, (_lib.TILE_HFLIP if hflip else 0) | (_lib.TILE_VFLIP if vflip else 0), 0)
     return aug
+
+
+PHOTOMETRICS = (None, "device")   # the `photometric=` keyword of the feeds and of `training`: it permits, the config's field decides
+JITTER_TYPES = ("brightness", "contrast", "saturation", "hue")   # what the reference's train transform names (salve/train_utils.py:110-111)
+
+
+def check_photometric(photometric: Optional[str]) -> None:
+    if photometric not in PHOTOMETRICS:
+        raise ValueError(f"photometric must be one of {PHOTOMETRICS}, got {photometric!r}")
+
+
+def jitter_draws(tf, n_examples: int, images_per_example: int, generator=None) -> List[JitterDraw]:
+    """`TrainTransform.draw_jitter()` per image, example by example in batch order, an example's images in x1 .. x6 order: the draws
+    the DataLoader path takes from torch's generator, flattened [n_examples * images_per_example]."""
+    return [tf.draw_jitter(generator) for _ in range(n_examples * images_per_example)]
+
+
+def jitter_table(draws: Sequence[JitterDraw]) -> np.ndarray:
+    """salve_tile_jitter_t rows of the images' draws: TILE_JITTER_DTYPE [len(draws)].  The complements 1 - f are formed in double and
+    rounded once, as torchvision's _blend forms them."""
+    t = np.zeros(len(draws), dtype=_lib.TILE_JITTER_DTYPE)
+    for k, (order, mask, b, c, s, h) in enumerate(draws):
+        t[k] = (order, mask, b, c, s, h, *(np.float32(1.0 - float(f)) for f in (b, c, s)), 0)
+    return t
 
 
 def upload_tables(parts: Sequence[np.ndarray], device) -> Tuple[torch.Tensor, np.ndarray]:

@@ -113,7 +113,8 @@ class _TileFiles:
     """What the two batch sources share: the files of a batch -> int32 [n, H, W] images on the device."""
 
     def __init__(self, device, data_list: Sequence[tuple], resize_hw: Tuple[int, int], crop_hw: Tuple[int, int], read_threads: int,
-                 entropy: str = "image", read_ahead: bool = False) -> None:
+                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
+        train_feed.check_photometric(photometric)
         if not 1 <= int(read_threads) <= MAX_READ_THREADS:
             raise ValueError(f"read_threads must be 1 .. {MAX_READ_THREADS}, got {read_threads}")
         if entropy not in ENTROPY_STAGES:
@@ -128,7 +129,9 @@ class _TileFiles:
         if len(widths) > 1 or (widths and next(iter(widths)) not in (3, 5, 7)):
             raise RuntimeError(f"examples are (2, 4 or 6 tile paths, is_match) tuples of one length, got lengths {sorted(widths)}")
         self.images_per_example = (next(iter(widths)) - 1) if widths else 2
-        self.tf = TrainTransform(resize_hw, crop_hw)   # the draws (and the square / no-padding refusals); its kernels are not used
+        self.photometric = photometric   # (a source that yields train batches jitters them; the others only accept the keyword)
+        # the draws (and the square / no-padding refusals); its kernels are not used
+        self.tf = TrainTransform(resize_hw, crop_hw, jitter_types=train_feed.JITTER_TYPES if photometric else None)
         self.read_threads = int(read_threads)
         self.ras: Optional[BevRasteriser] = None       # made with the first batch: its image size is the first file's
         self.fallbacks = 0                              # files decoded by Pillow so far
@@ -423,13 +426,15 @@ class TileFileSource(_TileFiles):
     data_list: `ZindData(...).data_list`.
     read_ahead=True: the next two batches' files are read, and the next batch decoded on a side stream, while the current batch trains
     (the module's docstring): the same batches, one more batch of decoded images and one more decode workspace on the
-    device (about 1 GB + 1.2 GB at 1024 tiles of 501 x 501).  The yielded tensors belong to the current stream as always."""
+    device (about 1 GB + 1.2 GB at 1024 tiles of 501 x 501).  The yielded tensors belong to the current stream as always.
+    photometric: None (default), or "device": the train split's batches take the reference's PhotometricShift inside the train-tile call
+    (RenderedTrainSource's keyword), read_ahead or not; every other split never jitters."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int = 256, precision: str = "fp32", split: str = "train", seed: int = 0,
                  resize_hw: Tuple[int, int] = (234, 234), crop_hw: Tuple[int, int] = (224, 224), read_threads: int = MAX_READ_THREADS,
-                 entropy: str = "image", read_ahead: bool = False) -> None:
+                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
         train_feed.check_arguments(batch_size, split, SPLITS, precision)
-        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead)
+        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead, photometric if split == "train" else None)
         self.split, self.batch_size = split, int(batch_size)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
         self.per_sample = self.images_per_example // 2            # image PAIRS per example
@@ -445,12 +450,18 @@ class TileFileSource(_TileFiles):
         """One draw per example of a batch (`train_feed.draws`)."""
         return train_feed.draws(self.tf, self.split, n)
 
-    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]]) -> Tuple[torch.Tensor, torch.Tensor]:
-        """Examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  Serial, whatever `read_ahead`."""
+    def jitter_draws(self, n: int) -> Optional[List[train_feed.JitterDraw]]:
+        """The jitter draws of a batch of n examples (`train_feed.jitter_draws`), or None where the source does not jitter."""
+        return train_feed.jitter_draws(self.tf, n, self.images_per_example) if self.photometric else None
+
+    def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]],
+              jitter: Optional[Sequence[train_feed.JitterDraw]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  Serial, whatever `read_ahead`.
+        jitter (photometric="device"): one `TrainTransform.draw_jitter()` per image, example by example in the order of its tuple."""
         idx = np.asarray(idx, dtype=np.int64)
         if len(draws) != len(idx):
             raise ValueError(f"{len(idx)} examples, {len(draws)} draws")
-        return self._tile(idx, draws, *self._load(self._paths(idx)))
+        return self._tile(idx, draws, *self._load(self._paths(idx)), jitter=jitter)
 
     def tile_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], position: np.ndarray):
         """The host tables of one batch whose example b's images lie at `position[E b : E (b + 1)]` of the decoded array, in the order of
@@ -467,29 +478,32 @@ class TileFileSource(_TileFiles):
         jobs["chan"][1] = 6 * np.arange(K)[None, :] + 3
         return jobs, train_feed.aug_table(draws)
 
-    def _tile(self, idx: np.ndarray, draws, images: torch.Tensor, position: np.ndarray) -> Tuple[torch.Tensor, torch.Tensor]:
-        """The batch from its decoded images: the tables in ONE upload, ONE tile launch, on the current stream."""
+    def _tile(self, idx: np.ndarray, draws, images: torch.Tensor, position: np.ndarray, jitter=None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """The batch from its decoded images: the tables in ONE upload, ONE train-tile call, on the current stream."""
         B, K = len(idx), self.per_sample
+        if jitter is not None and len(jitter) != 2 * K * B:
+            raise ValueError(f"{B} examples of {2 * K} images, {len(jitter)} jitter draws")
         jobs, aug = self.tile_tables(idx, draws, position)
-        buf, o = train_feed.upload_tables([jobs, aug, self.labels[idx]], self.device)
+        buf, o = train_feed.upload_tables([jobs, aug, self.labels[idx], train_feed.jitter_table(jitter or [])], self.device)
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
-        self._tile_launch(images, buf[:o[1] // 2], buf[o[1] // 2:o[1]], K, buf[o[1]:o[2]], B, out)
+        self._tile_launch(images, buf[:o[1] // 2], buf[o[1] // 2:o[1]], K, buf[o[1]:o[2]], B, out, None if jitter is None else buf[o[3]:o[4]])
         return out, buf[o[2]:o[3]].view(torch.int64).view(B, 1)
 
-    def _tile_launch(self, images, jobs_a, jobs_b, per_sample, aug, batch, out) -> None:
-        """ONE salve_bev_train_tiles launch: both arrays of image pairs are the decoded images."""
+    def _tile_launch(self, images, jobs_a, jobs_b, per_sample, aug, batch, out, jitter=None) -> None:
+        """ONE salve_bev_train_tiles (or, with jitter records, salve_bev_train_tiles_jitter) call: both arrays of image pairs are the
+        decoded images."""
         with tracing.range("salve.train_tiles"):
-            self.ras.train_tiles(images, images, jobs_a, jobs_b, per_sample, aug, batch, out)
+            self.ras.train_tiles(images, images, jobs_a, jobs_b, per_sample, aug, batch, out, jitter=jitter)
 
     def __iter__(self):
         plan = plan_epoch(len(self.data_list), self.batch_size, "train" if self.split == "train" else "val", self.gen)
         if not self.read_ahead:
             for idx in plan:
-                yield self.batch(idx, self.draws(len(idx)))
+                yield self.batch(idx, self.draws(len(idx)), self.jitter_draws(len(idx)))
         else:
             with contextlib.closing(self._batches(plan)) as batches:
                 for idx, images, position in batches:   # (the draws now: Python's `random` is consumed batch by batch, as above)
-                    yield self._tile(np.asarray(idx, dtype=np.int64), self.draws(len(idx)), images, position)
+                    yield self._tile(np.asarray(idx, dtype=np.int64), self.draws(len(idx)), images, position, self.jitter_draws(len(idx)))
         self._check_epoch(f"tile files, {self.split} batches")
 
 
@@ -498,11 +512,13 @@ class TileFileLoader(_TileFiles):
     float32 [B, 3, crop, crop] tiles on the device (Resize -> centre Crop -> ToTensor -> Normalize, ONE salve_bev_tiles launch per
     batch), is_match int64 [B], and the two lists of tile paths that name the hypothesis (the floor pair where there is one).  In order,
     nothing dropped.  data_list: `ZindData(...).data_list`, or a slice of it (a rank's block of whole batches).
-    read_ahead=True: TileFileSource's, with the same cost in device memory."""
+    read_ahead=True: TileFileSource's, with the same cost in device memory.  photometric: TileFileSource's keyword, checked and without
+    effect: evaluation never jitters."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int, resize_hw: Tuple[int, int], crop_hw: Tuple[int, int],
-                 read_threads: int = MAX_READ_THREADS, entropy: str = "image", read_ahead: bool = False) -> None:
+                 read_threads: int = MAX_READ_THREADS, entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
         train_feed.check_arguments(batch_size)
+        train_feed.check_photometric(photometric)   # (accepted so that one set of keywords builds every loader; evaluation batches never jitter)
         super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead)
         self.batch_size = int(batch_size)
 

@@ -110,13 +110,17 @@ class RenderedTrainSource:
     jpeg_quality: None (default): the tiles come from the lossless images.  An integer (the reference's files: 75): every render and
     layout image takes the reference's JPEG round trip on the device (BevRasteriser.jpeg_roundtrip) between densify / rasterise and the
     train-tile launch -- kept identity images once, everything else with its batch -- so the batches equal the on-disk DataLoader's
-    (DESIGN.md 4.17).  It runs on the compute stream: prefetch and the resident pool are unaffected."""
+    (DESIGN.md 4.17).  It runs on the compute stream: prefetch and the resident pool are unaffected.
+    photometric: None (default), or "device": train batches take the reference's PhotometricShift -- ColorJitter on every resized image,
+    with draws of its own, in front of the crop -- inside the train-tile call (salve_bev_train_tiles_jitter), the draws
+    those of `TrainTransform.draw_jitter` per image in x1 .. x6 order from torch's global generator.  Val batches never jitter."""
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
                  crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None,
-                 prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None) -> None:
+                 prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None, photometric: Optional[str] = None) -> None:
         train_feed.check_arguments(batch_size, split, SPLITS, precision)
+        train_feed.check_photometric(photometric)
         if identity not in IDENTITIES:
             raise ValueError(f"identity must be one of {IDENTITIES}, got {identity!r}")
         if resident_panos is not None:
@@ -135,7 +139,9 @@ class RenderedTrainSource:
         self.layouts = layouts if self.has_layout else None   # salve_amd.layout.PanoLayouts, indexed by panorama
         self.per_sample = len(self.surfaces) + (1 if self.has_layout else 0)   # images per sample and array: texture maps, then the layout
         check_launch(batch_size, len(self.surfaces), batch_size if identity == "batch" else 0, layout=self.has_layout)
-        self.tf = TrainTransform(resize_hw, crop_hw)   # the draws (and the square / no-padding refusals); its kernels are not used
+        self.photometric = photometric if split == "train" else None   # (val batches never jitter)
+        # the draws (and the square / no-padding refusals); its kernels are not used
+        self.tf = TrainTransform(resize_hw, crop_hw, jitter_types=train_feed.JITTER_TYPES if self.photometric else None)
         self.split, self.batch_size = split, int(batch_size)
         self.identity, self.resident_panos = identity, None if resident_panos is None else int(resident_panos)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
@@ -350,7 +356,7 @@ class RenderedTrainSource:
                     ready = pool.drain(raise_errors=True)
                     if ready is not None:
                         torch.cuda.current_stream(self.device).wait_event(ready)
-                out = self.batch(idx, self.draws(len(idx)), next_use, planned=planned)
+                out = self.batch(idx, self.draws(len(idx)), next_use, planned=planned, jitter=self.jitter_draws(len(idx)))
                 next_use[panos[b]] = after[b]
                 before = pool.mark_done()
                 planned = b + 1 < len(plan)
@@ -361,16 +367,20 @@ class RenderedTrainSource:
             pool.end(mine)
 
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None,
-              planned: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+              planned: bool = False, jitter: Optional[Sequence[train_feed.JitterDraw]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Render examples `idx` with one draw (crop_y, crop_x, hflip, vflip) each: (x_packed, is_match).  `next_use` (resident pool
         only): the batch of every panorama's next use, for the planner (`epoch_next_use`).  `planned`: the batch's panoramas were made
-        resident ahead (prefetch): their slots are looked up, nothing is planned or uploaded here."""
+        resident ahead (prefetch): their slots are looked up, nothing is planned or uploaded here.  `jitter` (photometric="device"): one
+        `TrainTransform.draw_jitter()` per image, [B * 2 K] in example order, an example's images by channel group (`jitter_draws`)."""
         B, S, K = len(idx), len(self.surfaces), self.per_sample
+        if jitter is not None and len(jitter) != 2 * K * B:
+            raise ValueError(f"{B} examples of {2 * K} images, {len(jitter)} jitter draws")
         jobs, aug, rows, lay_recs, n = self.batch_tables(idx, draws, next_use, planned)
         bev_b = self.ref_bev if self.identity == "kept" else self.bev
         # ONE upload per batch; every table starts on a multiple of 16 bytes (the 40-byte render rows come last)
         # (the 48-byte layout records hold a double: every table in front of them is a multiple of 8 bytes long)
-        buf, o = train_feed.upload_tables([jobs, aug, self.examples["is_match"][idx], rows, lay_recs], self.device)
+        # (the 40-byte jitter records hold 4-byte fields only: they come behind everything else)
+        buf, o = train_feed.upload_tables([jobs, aug, self.examples["is_match"][idx], rows, lay_recs, train_feed.jitter_table(jitter or [])], self.device)
         jobs_a, jobs_b = buf[:o[1] // 2], buf[o[1] // 2:o[1]]
         labels = buf[o[2]:o[3]].view(torch.int64).view(B, 1)
         if S:   # (layout alone: no texture map, as RenderVerifyPipeline)
@@ -381,13 +391,14 @@ class RenderedTrainSource:
             self._jpeg(self.bev[:n])
         if self.has_layout:
             with self._launch("layout pose", "salve.layout_pose"):
-                self.lay.pose(buf[o[4]:], len(lay_recs))
+                self.lay.pose(buf[o[4]:o[5]], len(lay_recs))
             with self._launch("layout rasterise", "salve.layout_rasterise"):
                 self.lay.rasterise(len(lay_recs), self.bev[self.lay_base[0]:])
             self._jpeg(self.bev[self.lay_base[0]:self.lay_base[0] + len(lay_recs)])
         out = torch.empty((B, self.ras.crop, self.ras.crop, self.out_c), dtype=self.dtype, device=self.device)
         with self._launch("tiles", "salve.train_tiles"):
-            self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, K, buf[o[1]:o[2]], B, out)   # (identity="batch": one buffer, only read)
+            self.ras.train_tiles(self.bev, bev_b, jobs_a, jobs_b, K, buf[o[1]:o[2]], B, out,   # (identity="batch": one buffer, only read)
+                                 jitter=None if jitter is None else buf[o[5]:o[6]])
         return out, labels
 
     def batch_tables(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None, planned: bool = False):
@@ -460,6 +471,10 @@ class RenderedTrainSource:
         """One draw per example of a batch (`train_feed.draws`)."""
         return train_feed.draws(self.tf, self.split, n)
 
+    def jitter_draws(self, n: int) -> Optional[List[train_feed.JitterDraw]]:
+        """The jitter draws of a batch of n examples (`train_feed.jitter_draws`), or None where the source does not jitter."""
+        return train_feed.jitter_draws(self.tf, n, 2 * self.per_sample) if self.photometric else None
+
     def batch_panos(self, idx: np.ndarray) -> np.ndarray:
         """The distinct panoramas examples `idx` name."""
         return np.unique(np.concatenate([self.examples["i1"][idx], self.examples["i2"][idx]]))
@@ -470,14 +485,14 @@ class RenderedTrainSource:
         plan = plan_epoch(len(self.examples["i1"]), self.batch_size, self.split, self.gen)
         if self.pool is None:
             for idx in plan:
-                yield self.batch(idx, self.draws(len(idx)))
+                yield self.batch(idx, self.draws(len(idx)), jitter=self.jitter_draws(len(idx)))
         elif self.pool.prefetch:
             yield from self._iter_prefetch(plan)
         else:   # the epoch's order is known here, before its first batch: every panorama's next use, for the planner
             panos = [self.batch_panos(idx) for idx in plan]
             next_use, after = epoch_next_use(panos, self.n_panos)
             for b, idx in enumerate(plan):
-                out = self.batch(idx, self.draws(len(idx)), next_use)
+                out = self.batch(idx, self.draws(len(idx)), next_use, jitter=self.jitter_draws(len(idx)))
                 next_use[panos[b]] = after[b]
                 yield out
         status.check(self.device, f"rendered {self.split} batches")

@@ -9,7 +9,7 @@ strict=True).  salve_amd.train_utils stays inference-only and keeps refusing the
 module (and `python -m salve_amd.train`) only.
 
 Differences from the reference, all deliberate: one GPU (`dataparallel` is accepted and ignored, the state dict carries no
-`module.` prefix), num_workers = 0 (the transforms launch GPU kernels), photometric augmentation (False in every released config)
+`module.` prefix), num_workers = 0 (the transforms launch GPU kernels), photometric augmentation (False in every released config; opt-in: photometric="device")
 and crop-with-padding are refused, the shuffle order comes from a seeded torch.Generator.
 """
 
@@ -122,18 +122,29 @@ def cross_entropy_forward_packed(model: nn.Module, split: str, x_packed: Tensor,
     return probs, loss
 
 
-def get_train_transform(args: TrainingConfig):
-    """Resize -> random Crop -> random horizontal flip -> random vertical flip -> ToTensor -> Normalize for 2 / 4 / 6 images
-    (salve/train_utils.py:63-124), on the GPU (transforms.TrainTransform)."""
+def _jitter(args: TrainingConfig, photometric: Optional[str]) -> Optional[str]:
+    """What a feed is built with: `photometric` only permits, the config's field decides."""
+    return photometric if args.apply_photometric_augmentation else None
+
+
+def get_train_transform(args: TrainingConfig, photometric: Optional[str] = None):
+    """Resize -> [PhotometricShift ->] random Crop -> random horizontal flip -> random vertical flip -> ToTensor -> Normalize for
+    2 / 4 / 6 images (salve/train_utils.py:63-124), on the GPU (transforms.TrainTransform).  photometric: None (default) refuses a config
+    with apply_photometric_augmentation=True, as before the augmentation existed; "device" accepts it -- ColorJitter on the device, every
+    image with draws of its own.  With the field False the keyword changes nothing."""
+    from salve_amd.train_feed import JITTER_TYPES, check_photometric
     from salve_amd.transforms import TrainTransform
 
+    check_photometric(photometric)
     if len(args.modalities) not in (1, 2, 3):
         raise RuntimeError(f"Unsupported modalities. {str(args.modalities)}")
-    if args.apply_photometric_augmentation:
-        raise RuntimeError("apply_photometric_augmentation=True (PhotometricShift) is not implemented; every released config has False")
+    if args.apply_photometric_augmentation and photometric is None:
+        raise RuntimeError("apply_photometric_augmentation=True (PhotometricShift) is opt-in: pass photometric=\"device\" (--photometric device) "
+                           "to run the photometric augmentation on the device; every released config has False")
     if args.train_h > args.resize_h or args.train_w > args.resize_w:
         raise RuntimeError("crop larger than the resized image: the reference pads with the mean there, which is not implemented")
-    return TrainTransform((args.resize_h, args.resize_w), (args.train_h, args.train_w))
+    return TrainTransform((args.resize_h, args.resize_w), (args.train_h, args.train_w),
+                          jitter_types=JITTER_TYPES if _jitter(args, photometric) else None)
 
 
 DECODES = ("host", "device")
@@ -145,27 +156,29 @@ def _check_decode(decode: str) -> None:
 
 
 def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32", entropy: str = "image",
-                         read_ahead: bool = False):
+                         read_ahead: bool = False, photometric: Optional[str] = None):
     """`get_dataloader`'s examples in its order as a train_files.TileFileSource: whole batches of the data set's JPEG tiles decoded
-    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy, read_ahead: TileFileSource's."""
+    on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy, read_ahead: TileFileSource's.
+    photometric: `get_train_transform`'s keyword (the train split jitters iff the config's field is True)."""
     from salve_amd.dataset.zind_data import ZindData
     from salve_amd.train_files import TileFileSource
 
-    get_train_transform(args)   # (the refusals of the host path: photometric augmentation, crop-with-padding)
+    get_train_transform(args, photometric)   # (the refusals of the host path: photometric augmentation without the keyword, crop-with-padding)
     data = ZindData(split=split, transform=None, args=args)
     return TileFileSource(torch.device("cuda", torch.cuda.current_device()), data.data_list, batch_size=args.batch_size, precision=precision,
                           split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w), entropy=entropy,
-                          read_ahead=read_ahead)
+                          read_ahead=read_ahead, photometric=_jitter(args, photometric))
 
 
-def get_dataloader(args: TrainingConfig, split: str, seed: int = 0) -> torch.utils.data.DataLoader:
+def get_dataloader(args: TrainingConfig, split: str, seed: int = 0, photometric: Optional[str] = None) -> torch.utils.data.DataLoader:
     """salve/train_utils.py:183-203.  train: the train transform, shuffled (a torch.Generator seeded with `seed`), last partial
-    batch dropped; val / test: the centre-crop transform, in order, nothing dropped.  num_workers = 0."""
+    batch dropped; val / test: the centre-crop transform, in order, nothing dropped.  num_workers = 0.  photometric:
+    `get_train_transform`'s keyword; val / test never jitter."""
     from salve_amd import train_utils
     from salve_amd.dataset.zind_data import ZindData
 
     if split == "train":
-        data = ZindData(split=split, transform=get_train_transform(args), args=args)
+        data = ZindData(split=split, transform=get_train_transform(args, photometric), args=args)
         gen = torch.Generator()
         gen.manual_seed(seed)
         return torch.utils.data.DataLoader(data, batch_size=args.batch_size, shuffle=True, generator=gen, num_workers=0, drop_last=True)
@@ -263,7 +276,7 @@ def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_l
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
           norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image",
-          read_ahead: bool = False) -> Dict[str, list]:
+          read_ahead: bool = False, photometric: Optional[str] = None) -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
@@ -276,7 +289,9 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     entropy (decode="device" only): "image" (default) or "lanes", the lane-parallel entropy stage, which also keeps files with restart
     intervals on the device -- the same batches again.
     read_ahead (decode="device" only; default False): the next batches' files are read, and the next batch decoded on a side stream,
-    while the current batch trains (TileFileSource(read_ahead=True)) -- the same batches once more."""
+    while the current batch trains (TileFileSource(read_ahead=True)) -- the same batches once more.
+    photometric: None (default) or "device" -- a config with apply_photometric_augmentation=True trains only with "device": the
+    reference's PhotometricShift on the device in every train batch of either decode; val batches never jitter."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
@@ -290,24 +305,30 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     random.seed(seed)
     torch.manual_seed(seed)
     if decode == "device":
-        with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead) as train_source, \
-                get_tile_file_source(args, "val", seed, precision, entropy, read_ahead) as val_source:
+        with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead, photometric) as train_source, \
+                get_tile_file_source(args, "val", seed, precision, entropy, read_ahead, photometric) as val_source:
             return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)   # (leaving ends their reader threads)
-    return _fit(args, get_dataloader(args, "train", seed=seed), get_dataloader(args, "val"), results_dir, init_ckpt, precision, norm, optim, head)
+    return _fit(args, get_dataloader(args, "train", seed=seed, photometric=photometric), get_dataloader(args, "val"), results_dir, init_ckpt,
+                precision, norm, optim, head)
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
                    precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch",
-                   jpeg_quality: Optional[int] = None) -> Dict[str, list]:
+                   jpeg_quality: Optional[int] = None, photometric: Optional[str] = None) -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
     split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON.  jpeg_quality: the
     sources' own argument (the reference's JPEG round trip of every rendered image, on the device); the two sources must agree, and
-    an integer given here must be what they were built with."""
+    an integer given here must be what they were built with.  photometric: `train`'s keyword; the train source must have been built
+    with what the config and the keyword amount to (RenderedTrainSource(photometric=))."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
     _check_head(head)
-    get_train_transform(args)   # (the refusals of the on-disk path: photometric augmentation, crop-with-padding)
+    get_train_transform(args, photometric)   # (the refusals of the on-disk path: photometric augmentation without the keyword, crop-with-padding)
+    if getattr(train_source, "photometric", None) != _jitter(args, photometric):
+        raise RuntimeError(f"the train source was built with photometric={getattr(train_source, 'photometric', None)!r}; the config's "
+                           f"apply_photometric_augmentation={args.apply_photometric_augmentation} and photometric={photometric!r} ask for "
+                           f"{_jitter(args, photometric)!r}")
     want = torch.bfloat16 if precision == "bf16" else torch.float32
     for src in (train_source, val_source):
         if src.dtype != want:
