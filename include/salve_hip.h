@@ -676,6 +676,42 @@ int salve_adam_step(const salve_adam_segment_t* table, int32_t n_segments, const
                     const salve_adam_segment_t* host_table, const salve_adam_chunk_t* host_chunk_map, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * A flat bucket over any number of fp32 tensors, packed or unpacked in one launch (additive within ABI 7): the buffer that
+ * data-parallel training all-reduces once per step (salve_amd/dist_train.py: FlatBucket; the reference wraps its model in
+ * nn.DataParallel, salve/train_utils.py:214-215).
+ *     salve_flat_pack:    flat[offset_s + i] = tensor_s[i] * scale        salve_flat_unpack:  tensor_s[i] = flat[offset_s + i] * scale
+ *   Table:   device salve_flat_segment_t [n_segments], 8-byte aligned, one record per tensor:
+ *              tensor   address of device float [n], 4-byte aligned (a 16-byte aligned tensor takes the 16-byte path)
+ *              n        elements (64-bit), 0 allowed
+ *              offset   the segment's first element in `flat`: a multiple of 4, so that the flat side of every segment is 16-byte
+ *                       aligned.  Offsets ascend and segments do not overlap; the elements between offset + n and the next
+ *                       segment's offset are padding that neither entry reads or writes.
+ *   Chunks:  device salve_adam_chunk_t [n_chunks], one per workgroup of SALVE_ADAM_CHUNK elements, as salve_adam_step takes it: the
+ *            segments' chunks in table order, ceil(n / SALVE_ADAM_CHUNK) each, offsets ascending; an empty segment has none.
+ *   flat:    device float [flat_elems], 16-byte aligned.
+ *   scale:   1.0f copies 32-bit words and multiplies nothing: NaN payloads, infinities, -0 and denormals arrive unchanged.  Any
+ *            other value: one fp32 multiply per element.
+ *   Checks:  all on the host, before the launch, from host_table / host_chunk_map -- host copies of the same bytes, REQUIRED here
+ *            (a segment past flat_elems would write outside the buffer).  SALVE_ERR_BAD_ARG: negative counts; a null or misaligned
+ *            table, map or flat buffer; n < 0; an offset that is negative or not a multiple of 4; descending offsets or overlapping
+ *            segments; offset + n > flat_elems; a chunk map that is not exactly the table's; a null tensor (or flat) with n > 0; a
+ *            tensor address that is not 4-byte aligned.  Nothing is written then.  n_segments == 0: SALVE_OK, nothing is launched.
+ *   No atomics; every element is moved by exactly one thread.  The caller owns every buffer.  The launch is asynchronous on
+ *   `stream`: the device tables must stay unchanged until it has run.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct {
+    uint64_t tensor;
+    int64_t n;
+    int64_t offset;
+} salve_flat_segment_t; /* 24 bytes */
+int salve_flat_pack(const salve_flat_segment_t* table, int32_t n_segments, const salve_adam_chunk_t* chunk_map, int32_t n_chunks,
+                    const salve_flat_segment_t* host_table, const salve_adam_chunk_t* host_chunk_map, float* flat, int64_t flat_elems, float scale,
+                    void* stream);
+int salve_flat_unpack(const salve_flat_segment_t* table, int32_t n_segments, const salve_adam_chunk_t* chunk_map, int32_t n_chunks,
+                      const salve_flat_segment_t* host_table, const salve_adam_chunk_t* host_chunk_map, float* flat, int64_t flat_elems, float scale,
+                      void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * The classifier head of a training step with its loss and accuracy counts on the device (additive within ABI 7): opt-in, fp32
  * and bf16.  The reference ends its network in resnet.avgpool, flatten and fc (salve/models/early_fusion.py:78-83), forms
  * softmax probabilities on a clone of the logits and the cross-entropy loss (salve/train_utils.py:18-41), and feeds the arg-max

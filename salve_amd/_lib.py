@@ -92,6 +92,8 @@ EXPORTED_SYMBOLS = (
     "salve_bev_jpeg_decode_lanes_sampled",
     "salve_bev_train_tiles_jitter_workspace_bytes",
     "salve_bev_train_tiles_jitter",
+    "salve_flat_pack",
+    "salve_flat_unpack",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -173,6 +175,9 @@ ADAM_SEGMENT_DTYPE = np.dtype([("param", "<u8"), ("grad", "<u8"), ("exp_avg", "<
                                ("weight_decay", "<f4"), ("one_minus_beta1", "<f4"), ("one_minus_beta2", "<f4")])
 ADAM_CHUNK_DTYPE = np.dtype([("segment", "<i4"), ("reserved", "<i4"), ("offset", "<i8")])
 assert ADAM_SEGMENT_DTYPE.itemsize == 80 and ADAM_CHUNK_DTYPE.itemsize == 16
+# salve_flat_pack / salve_flat_unpack (include/salve_hip.h: salve_flat_segment_t); the chunk map is salve_adam_step's
+FLAT_SEGMENT_DTYPE = np.dtype([("tensor", "<u8"), ("n", "<i8"), ("offset", "<i8")])
+assert FLAT_SEGMENT_DTYPE.itemsize == 24
 
 # salve_head_* (include/salve_hip.h: SALVE_HEAD_*, salve_head_desc_t, salve_head_meter_t): the training classifier head.  It stands
 # behind the reference's avgpool + flatten + fc (salve/models/early_fusion.py:78-83), its softmax and cross-entropy
@@ -293,6 +298,9 @@ def load() -> ctypes.CDLL:
         getattr(lib, name).restype = ctypes.c_int
     lib.salve_adam_step.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     lib.salve_adam_step.restype = ctypes.c_int
+    for name in ("salve_flat_pack", "salve_flat_unpack"):   # table, n_segments, chunk_map, n_chunks, HOST table, HOST chunk_map, flat, flat_elems, scale, stream
+        getattr(lib, name).argtypes = [vp, i32, vp, i32, vp, vp, vp, ctypes.c_int64, ctypes.c_float, vp]
+        getattr(lib, name).restype = ctypes.c_int
     lib.salve_head_workspace_bytes.argtypes = [ctypes.POINTER(HeadDesc), i32]
     lib.salve_head_workspace_bytes.restype = sz
     for name in ("salve_head_f32_forward", "salve_head_bf16_forward"):   # d, x, weight, bias, target, pooled, logits, probs, loss, meter

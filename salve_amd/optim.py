@@ -81,6 +81,18 @@ def chunk_count(n: int) -> int:
     return (n + CHUNK - 1) // CHUNK
 
 
+def build_chunk_map(lengths) -> np.ndarray:
+    """The chunk map of segments of `lengths` elements, in their order: per segment ceil(n / CHUNK) ADAM_CHUNK_DTYPE records (segment
+    index, element offset), offsets ascending; an empty segment gets no chunk.  (Shared with dist_train.FlatBucket.)"""
+    n = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    counts = (n + (CHUNK - 1)) // CHUNK
+    chunk_map = np.zeros(int(counts.sum()), dtype=_lib.ADAM_CHUNK_DTYPE)
+    chunk_map["segment"] = np.repeat(np.arange(len(n), dtype=np.int32), counts)
+    first = np.repeat(np.cumsum(counts) - counts, counts)   # index of each chunk's segment's first chunk
+    chunk_map["offset"] = (np.arange(len(chunk_map), dtype=np.int64) - first) * CHUNK
+    return chunk_map
+
+
 def build_tables(segments: List[Segment]) -> Tuple[np.ndarray, np.ndarray]:
     """(table, chunk_map) of salve_adam_step for `segments`, in their order: one ADAM_SEGMENT_DTYPE record each, and per segment
     ceil(n / CHUNK) ADAM_CHUNK_DTYPE records (segment index, element offset), offsets ascending.  An empty segment gets a record
@@ -101,12 +113,7 @@ def build_tables(segments: List[Segment]) -> Tuple[np.ndarray, np.ndarray]:
         table[name] = [s[k] for s in segments]
     for k, name in enumerate(_lib.ADAM_SEGMENT_DTYPE.names[6:]):   # (adam_scalars returns them in the record's order)
         table[name] = [r[k] for r in rows]
-    counts = (table["n"] + (CHUNK - 1)) // CHUNK
-    chunk_map = np.zeros(int(counts.sum()), dtype=_lib.ADAM_CHUNK_DTYPE)
-    chunk_map["segment"] = np.repeat(np.arange(len(segments), dtype=np.int32), counts)
-    first = np.repeat(np.cumsum(counts) - counts, counts)   # index of each chunk's segment's first chunk
-    chunk_map["offset"] = (np.arange(len(chunk_map), dtype=np.int64) - first) * CHUNK
-    return table, chunk_map
+    return table, build_chunk_map(table["n"])
 
 
 def current_shadow(p: Tensor) -> Optional[Tensor]:

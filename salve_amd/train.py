@@ -1,6 +1,6 @@
-"""Train the verifier (scripts/train.py's command line, one GPU):
+"""Train the verifier (scripts/train.py's command line; one GPU, or --gpus N of one node data-parallel):
 
-    python -m salve_amd.train --config <reference yaml> [--epochs N] [--batch-size B] [--data-root DIR]
+    python -m salve_amd.train --config <reference yaml> [--gpus N [--dist-backend {nccl,gloo}] [--dist-timeout S]] [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}] [--decode {host,device}]
                               [--decode-entropy {image,lanes}] [--decode-read-ahead] [--photometric device]
@@ -33,16 +33,39 @@ the GPU before it is tiled: the batches of the rendered dataset on disk, without
 --photometric device permits a config with apply_photometric_augmentation: True (refused without it): the reference's PhotometricShift --
 ColorJitter(brightness 0.5, contrast 0.5, saturation 0.5, hue 0.05) on every resized train image, each with draws of its own -- runs on
 the GPU inside the train-tile call of whichever feed is selected.  With the field False the flag changes nothing.
+--gpus N (default 1; at most 16) trains data-parallel on N GPUs of this node (salve_amd/dist_train.py): started without
+a launcher, the program starts `python -m torch.distributed.run --nnodes=1 --nproc-per-node=N -m salve_amd.train ...` as a child
+process -- before anything touches a GPU -- and relays its exit code; a node that shows fewer than N GPUs is refused in one line.
+Every rank trains its rows of each batch (the batch size must be a multiple of N), the gradients are averaged by one all-reduce per
+step, rank 0 logs and writes the checkpoint and the results JSON.  Needs --render-from or --decode device.  --dist-backend: nccl
+(default: RCCL, a GPU per rank) or gloo (the buffer is reduced on the host).
 """
 
 from __future__ import annotations
 
 import argparse
 import logging
+import os
+import socket
+import subprocess
+import sys
 import time
 
 from salve_amd import training
 from salve_amd.training_config import load_training_config
+
+
+def _self_launch(gpus: int, argv) -> int:
+    """`python -m salve_amd.train --gpus N` without a launcher: the N ranks run under torch.distributed.run as a CHILD process (this
+    process has not touched the GPU and never will; nothing is exec'ed in place).  Returns the child's exit code."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        port = s.getsockname()[1]
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={gpus}", "--master-addr", "127.0.0.1",
+           "--master-port", str(port), "-m", "salve_amd.train"] + list(argv)
+    env = dict(os.environ)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    return subprocess.run(cmd, env=env).returncode
 
 
 def main(argv=None) -> None:
@@ -81,8 +104,32 @@ def main(argv=None) -> None:
                     help="--render-from: JPEG round trip of every rendered image on the GPU at quality Q (the reference writes its tiles at 75)")
     ap.add_argument("--photometric", choices=("device",), default=None,
                     help="accept apply_photometric_augmentation: True and run the photometric augmentation on the GPU (without it such a config is refused)")
+    ap.add_argument("--gpus", type=int, default=1, metavar="N", help="train data-parallel on N GPUs of this node, one process each (default 1)")
+    ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
+                    help="--gpus: nccl (default: RCCL reduces the gradients on the devices) or gloo (they are reduced on the host)")
+    ap.add_argument("--dist-timeout", type=float, default=600, metavar="S", help="--gpus: seconds a collective may wait for the other ranks (default 600)")
+    ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)   # under a launcher: run the collectives in a world of one too
+    argv = sys.argv[1:] if argv is None else list(argv)
     a = ap.parse_args(argv)
     training._check_head(a.head)
+    from salve_amd.dist_train import MAX_GPUS
+
+    if not 1 <= a.gpus <= MAX_GPUS:
+        raise SystemExit(f"salve_amd.train: --gpus must be 1 .. {MAX_GPUS}, got {a.gpus}; nothing was launched")
+    launched = "WORLD_SIZE" in os.environ
+    if not launched and a.gpus > 1:
+        import torch
+
+        have = torch.cuda.device_count()   # (does not initialise the GPU)
+        if a.gpus > have:
+            raise SystemExit(f"salve_amd.train: --gpus {a.gpus} but this node shows {have} GPU(s); nothing was launched")
+        if a.render_from is None and a.decode != "device":
+            raise SystemExit("--gpus N trains from --render-from DIR or with --decode device: the host DataLoader feed (--decode host) is not sharded")
+        raise SystemExit(_self_launch(a.gpus, argv))
+    if launched and int(os.environ["WORLD_SIZE"]) != a.gpus:
+        raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={os.environ['WORLD_SIZE']}")
+    if a.gpus > 1 and a.render_from is None and a.decode != "device":
+        raise SystemExit("--gpus N trains from --render-from DIR or with --decode device: the host DataLoader feed (--decode host) is not sharded")
     if a.decode_entropy != "image" and a.decode != "device":
         raise SystemExit("--decode-entropy selects the entropy stage of --decode device")
     if a.decode_read_ahead and a.decode != "device":
@@ -118,7 +165,24 @@ def main(argv=None) -> None:
     if a.layout_data_root is not None:
         args.layout_data_root = a.layout_data_root
     out = a.out or f"{args.model_save_dirpath}/{time.strftime('%Y_%m_%d_%H_%M_%S')}"
-    logging.info(str(args))
+    dist = None
+    if launched:
+        from salve_amd.dist_train import DataParallel
+
+        dist = DataParallel.from_env(a.dist_backend, timeout_s=a.dist_timeout, force=a.force_dist)
+    rank, world = (dist.rank, dist.world) if dist is not None else (0, 1)
+    if rank == 0:
+        logging.info(str(args))
+    try:
+        results = _train(a, args, out, identity, dist, rank, world)
+    finally:
+        if dist is not None:
+            dist.close()
+    if rank == 0:
+        logging.info(f"results in {out}: {results}")
+
+
+def _train(a, args, out: str, identity: str, dist, rank: int, world: int):
     if a.render_from is not None:
         import torch
 
@@ -133,20 +197,19 @@ def main(argv=None) -> None:
                                                    resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w),
                                                    identity=identity, resident_panos=a.resident_panos, layouts=layouts, prefetch=a.prefetch,
                                                    jpeg_quality=a.jpeg_quality,
-                                                   photometric=a.photometric if args.apply_photometric_augmentation else None)
+                                                   photometric=a.photometric if args.apply_photometric_augmentation else None,
+                                                   rank=rank, world=world)
             if split == "train":
                 src.load_panos(rgb, depth)
             else:   # the panoramas (or their pool) and their identity renders are on the device once
                 src.share_panos(sources["train"])
             src.set_examples(*examples[split])
             sources[split] = src
-        results = training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
-                                          norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality, photometric=a.photometric)
-    else:
-        results = training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
-                                 head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead,
-                                 photometric=a.photometric)
-    logging.info(f"results in {out}: {results}")
+        return training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
+                                       norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality, photometric=a.photometric, dist=dist)
+    return training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
+                          head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead,
+                          photometric=a.photometric, dist=dist)
 
 
 if __name__ == "__main__":

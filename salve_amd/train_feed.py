@@ -45,6 +45,46 @@ def plan_epoch(n: int, batch: int, split: str, gen: Optional[torch.Generator] = 
     return [b.numpy().astype(np.int64) for b in loader]
 
 
+def shard_bounds(n: int, rank: int, world: int) -> Tuple[int, int]:
+    """Rows [lo, hi) of an n-row batch that rank `rank` of `world` data-parallel ranks trains: the contiguous block split of
+    `HypothesisTable.shard_bounds` (sizes differ by at most one; a short batch may leave a rank nothing)."""
+    from salve_amd.synthetic import HypothesisTable
+
+    if world < 1 or not 0 <= rank < world:
+        raise ValueError(f"rank {rank} of a world of {world}")
+    return HypothesisTable.shard_bounds(int(n), int(rank), int(world))
+
+
+def check_shard(batch_size: int, split: str, rank: int, world: int) -> None:
+    """The refusals of the feeds' `rank` / `world` keywords: a train batch must split into equal blocks (every rank steps on the
+    same number of rows, and the mean of the ranks' gradients is the batch's); val batches split as they come."""
+    shard_bounds(0, rank, world)
+    if split == "train" and int(batch_size) % int(world) != 0:
+        raise ValueError(f"batch size {batch_size} is not a multiple of the {world} data-parallel ranks: the train batch is split into equal blocks")
+
+
+def shard_plan(plan: Sequence[np.ndarray], rank: int, world: int) -> Tuple[List[np.ndarray], List[Tuple[int, int, int]]]:
+    """An epoch's plan as rank `rank` sees it, sliced directly behind `plan_epoch`: (the rank's rows of every batch that leaves it
+    any, (rows of the whole batch, lo, hi) of each such batch).  Whoever plans ahead -- the resident pool, the file reader -- then
+    plans for this rank's rows only.  A batch that leaves the rank no row (a short last val batch) is left out: val takes no draw
+    from a generator, so no stream falls out of step."""
+    if world == 1:
+        return list(plan), [(len(idx), 0, len(idx)) for idx in plan]
+    mine, rows = [], []
+    for idx in plan:
+        lo, hi = shard_bounds(len(idx), rank, world)
+        if hi > lo:
+            mine.append(idx[lo:hi])
+            rows.append((len(idx), lo, hi))
+    return mine, rows
+
+
+def shard_draws(draws: Sequence[Draw], jitter: Optional[Sequence[JitterDraw]], images_per_example: int, lo: int, hi: int):
+    """Rows [lo, hi) of a whole batch's draws and of its jitter draws (per image: `images_per_example` consecutive ones per row).
+    The whole batch's draws were taken, so the generators stand where the single process's stand."""
+    return list(draws[lo:hi]), None if jitter is None else list(jitter[lo * images_per_example:hi * images_per_example])
+
+
 def batches_per_epoch(n: int, batch: int, split: str) -> int:
     return n // batch if split == "train" else (n + batch - 1) // batch
 

@@ -113,8 +113,10 @@ class _TileFiles:
     """What the two batch sources share: the files of a batch -> int32 [n, H, W] images on the device."""
 
     def __init__(self, device, data_list: Sequence[tuple], resize_hw: Tuple[int, int], crop_hw: Tuple[int, int], read_threads: int,
-                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
+                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None, rank: int = 0, world: int = 1) -> None:
         train_feed.check_photometric(photometric)
+        train_feed.shard_bounds(0, rank, world)   # (refuses a rank outside its world)
+        self.rank, self.world = int(rank), int(world)
         if not 1 <= int(read_threads) <= MAX_READ_THREADS:
             raise ValueError(f"read_threads must be 1 .. {MAX_READ_THREADS}, got {read_threads}")
         if entropy not in ENTROPY_STAGES:
@@ -428,13 +430,18 @@ class TileFileSource(_TileFiles):
     (the module's docstring): the same batches, one more batch of decoded images and one more decode workspace on the
     device (about 1 GB + 1.2 GB at 1024 tiles of 501 x 501).  The yielded tensors belong to the current stream as always.
     photometric: None (default), or "device": the train split's batches take the reference's PhotometricShift inside the train-tile call
-    (RenderedTrainSource's keyword), read_ahead or not; every other split never jitters."""
+    (RenderedTrainSource's keyword), read_ahead or not; every other split never jitters.
+    rank, world (data-parallel training): RenderedTrainSource's keywords -- the whole epoch is planned and the whole
+    batch's draws are taken, rows [lo, hi) of every batch are read, decoded and yielded; read_ahead reads this rank's files only."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int = 256, precision: str = "fp32", split: str = "train", seed: int = 0,
                  resize_hw: Tuple[int, int] = (234, 234), crop_hw: Tuple[int, int] = (224, 224), read_threads: int = MAX_READ_THREADS,
-                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
+                 entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None, rank: int = 0, world: int = 1) -> None:
         train_feed.check_arguments(batch_size, split, SPLITS, precision)
-        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead, photometric if split == "train" else None)
+        train_feed.check_shard(batch_size, split, rank, world)
+        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead, photometric if split == "train" else None,
+                         rank, world)
+        self._rows: List[Tuple[int, int, int]] = []   # the running epoch: (rows of the whole batch, lo, hi) per batch of this rank
         self.split, self.batch_size = split, int(batch_size)
         self.dtype = torch.bfloat16 if precision == "bf16" else torch.float32
         self.per_sample = self.images_per_example // 2            # image PAIRS per example
@@ -453,6 +460,11 @@ class TileFileSource(_TileFiles):
     def jitter_draws(self, n: int) -> Optional[List[train_feed.JitterDraw]]:
         """The jitter draws of a batch of n examples (`train_feed.jitter_draws`), or None where the source does not jitter."""
         return train_feed.jitter_draws(self.tf, n, self.images_per_example) if self.photometric else None
+
+    def _shard_draws(self, b: int):
+        """(draws, jitter draws) of batch `b` of this rank's plan: the whole batch's are taken, this rank's rows are kept."""
+        n, lo, hi = self._rows[b]
+        return train_feed.shard_draws(self.draws(n), self.jitter_draws(n), self.images_per_example, lo, hi)
 
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]],
               jitter: Optional[Sequence[train_feed.JitterDraw]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -496,14 +508,17 @@ class TileFileSource(_TileFiles):
             self.ras.train_tiles(images, images, jobs_a, jobs_b, per_sample, aug, batch, out, jitter=jitter)
 
     def __iter__(self):
-        plan = plan_epoch(len(self.data_list), self.batch_size, "train" if self.split == "train" else "val", self.gen)
+        # the whole epoch is planned (the generator stands where the single process's stands), then cut to this rank's rows
+        plan, self._rows = train_feed.shard_plan(plan_epoch(len(self.data_list), self.batch_size, "train" if self.split == "train" else "val", self.gen),
+                                                 self.rank, self.world)
         if not self.read_ahead:
-            for idx in plan:
-                yield self.batch(idx, self.draws(len(idx)), self.jitter_draws(len(idx)))
+            for b, idx in enumerate(plan):
+                yield self.batch(idx, *self._shard_draws(b))
         else:
             with contextlib.closing(self._batches(plan)) as batches:
-                for idx, images, position in batches:   # (the draws now: Python's `random` is consumed batch by batch, as above)
-                    yield self._tile(np.asarray(idx, dtype=np.int64), self.draws(len(idx)), images, position, self.jitter_draws(len(idx)))
+                for b, (idx, images, position) in enumerate(batches):   # (the draws now: Python's `random` is consumed batch by batch, as above)
+                    draws, jitter = self._shard_draws(b)
+                    yield self._tile(np.asarray(idx, dtype=np.int64), draws, images, position, jitter)
         self._check_epoch(f"tile files, {self.split} batches")
 
 
@@ -513,13 +528,14 @@ class TileFileLoader(_TileFiles):
     batch), is_match int64 [B], and the two lists of tile paths that name the hypothesis (the floor pair where there is one).  In order,
     nothing dropped.  data_list: `ZindData(...).data_list`, or a slice of it (a rank's block of whole batches).
     read_ahead=True: TileFileSource's, with the same cost in device memory.  photometric: TileFileSource's keyword, checked and without
-    effect: evaluation never jitters."""
+    effect: evaluation never jitters.  rank, world: rows [lo, hi) of every batch (train_feed.shard_bounds), as TileFileSource's val split."""
 
     def __init__(self, device, data_list: Sequence[tuple], batch_size: int, resize_hw: Tuple[int, int], crop_hw: Tuple[int, int],
-                 read_threads: int = MAX_READ_THREADS, entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None) -> None:
+                 read_threads: int = MAX_READ_THREADS, entropy: str = "image", read_ahead: bool = False, photometric: Optional[str] = None,
+                 rank: int = 0, world: int = 1) -> None:
         train_feed.check_arguments(batch_size)
         train_feed.check_photometric(photometric)   # (accepted so that one set of keywords builds every loader; evaluation batches never jitter)
-        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead)
+        super().__init__(device, data_list, resize_hw, crop_hw, read_threads, entropy, read_ahead, rank=rank, world=world)
         self.batch_size = int(batch_size)
 
     def __len__(self) -> int:
@@ -527,7 +543,8 @@ class TileFileLoader(_TileFiles):
 
     def __iter__(self):
         E = self.images_per_example
-        with contextlib.closing(self._batches(plan_epoch(len(self.data_list), self.batch_size, "val"))) as batches:
+        plan, _ = train_feed.shard_plan(plan_epoch(len(self.data_list), self.batch_size, "val"), self.rank, self.world)
+        with contextlib.closing(self._batches(plan)) as batches:
             for idx, images, position in batches:
                 B = len(idx)
                 out = torch.empty((E, B, 3, self.ras.crop, self.ras.crop), dtype=torch.float32, device=self.device)

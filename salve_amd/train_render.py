@@ -113,14 +113,22 @@ class RenderedTrainSource:
     (DESIGN.md 4.17).  It runs on the compute stream: prefetch and the resident pool are unaffected.
     photometric: None (default), or "device": train batches take the reference's PhotometricShift -- ColorJitter on every resized image,
     with draws of its own, in front of the crop -- inside the train-tile call (salve_bev_train_tiles_jitter), the draws
-    those of `TrainTransform.draw_jitter` per image in x1 .. x6 order from torch's global generator.  Val batches never jitter."""
+    those of `TrainTransform.draw_jitter` per image in x1 .. x6 order from torch's global generator.  Val batches never jitter.
+    rank, world (data-parallel training): the source plans the whole epoch and takes the whole batch's draws, then yields
+    rows [lo, hi) of every batch (train_feed.shard_bounds) -- bit for bit those rows of the world-1 source's batch; the pool plans for
+    this rank's panoramas only.  `len()` stays the number of whole batches; a train batch size must be a multiple of `world`; a val
+    batch that leaves the rank no row is not yielded."""
 
     def __init__(self, device, modalities: Sequence[str], pano_hw: Tuple[int, int] = (512, 1024), batch_size: int = 256,
                  precision: str = "fp32", split: str = "train", seed: int = 0, resize_hw: Tuple[int, int] = (234, 234),
                  crop_hw: Tuple[int, int] = (224, 224), identity: str = "kept", resident_panos: Optional[int] = None, layouts=None,
-                 prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None, photometric: Optional[str] = None) -> None:
+                 prefetch: bool = False, gather_threads: int = 4, jpeg_quality: Optional[int] = None, photometric: Optional[str] = None,
+                 rank: int = 0, world: int = 1) -> None:
         train_feed.check_arguments(batch_size, split, SPLITS, precision)
         train_feed.check_photometric(photometric)
+        train_feed.check_shard(batch_size, split, rank, world)
+        self.rank, self.world = int(rank), int(world)
+        self._rows: List[Tuple[int, int, int]] = []   # the running epoch: (rows of the whole batch, lo, hi) per batch of this rank
         if identity not in IDENTITIES:
             raise ValueError(f"identity must be one of {IDENTITIES}, got {identity!r}")
         if resident_panos is not None:
@@ -356,7 +364,8 @@ class RenderedTrainSource:
                     ready = pool.drain(raise_errors=True)
                     if ready is not None:
                         torch.cuda.current_stream(self.device).wait_event(ready)
-                out = self.batch(idx, self.draws(len(idx)), next_use, planned=planned, jitter=self.jitter_draws(len(idx)))
+                draws, jitter = self._shard_draws(b)
+                out = self.batch(idx, draws, next_use, planned=planned, jitter=jitter)
                 next_use[panos[b]] = after[b]
                 before = pool.mark_done()
                 planned = b + 1 < len(plan)
@@ -365,6 +374,11 @@ class RenderedTrainSource:
                 yield out
         finally:
             pool.end(mine)
+
+    def _shard_draws(self, b: int):
+        """(draws, jitter draws) of batch `b` of this rank's plan: the whole batch's are taken, this rank's rows are kept."""
+        n, lo, hi = self._rows[b]
+        return train_feed.shard_draws(self.draws(n), self.jitter_draws(n), 2 * self.per_sample, lo, hi)
 
     def batch(self, idx: np.ndarray, draws: Sequence[Tuple[int, int, bool, bool]], next_use: Optional[np.ndarray] = None,
               planned: bool = False, jitter: Optional[Sequence[train_feed.JitterDraw]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -482,17 +496,20 @@ class RenderedTrainSource:
     def __iter__(self):
         if self.examples is None:
             raise RuntimeError("set_examples first")
-        plan = plan_epoch(len(self.examples["i1"]), self.batch_size, self.split, self.gen)
+        # the whole epoch is planned (the generator stands where the single process's stands), then cut to this rank's rows
+        plan, self._rows = train_feed.shard_plan(plan_epoch(len(self.examples["i1"]), self.batch_size, self.split, self.gen), self.rank, self.world)
         if self.pool is None:
-            for idx in plan:
-                yield self.batch(idx, self.draws(len(idx)), jitter=self.jitter_draws(len(idx)))
+            for b, idx in enumerate(plan):
+                draws, jitter = self._shard_draws(b)
+                yield self.batch(idx, draws, jitter=jitter)
         elif self.pool.prefetch:
             yield from self._iter_prefetch(plan)
         else:   # the epoch's order is known here, before its first batch: every panorama's next use, for the planner
             panos = [self.batch_panos(idx) for idx in plan]
             next_use, after = epoch_next_use(panos, self.n_panos)
             for b, idx in enumerate(plan):
-                out = self.batch(idx, self.draws(len(idx)), next_use, jitter=self.jitter_draws(len(idx)))
+                draws, jitter = self._shard_draws(b)
+                out = self.batch(idx, draws, next_use, jitter=jitter)
                 next_use[panos[b]] = after[b]
                 yield out
         status.check(self.device, f"rendered {self.split} batches")

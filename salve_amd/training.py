@@ -8,8 +8,8 @@ salve_amd.models.trainable.TrainableEarlyFusionCEResnet (its checkpoints load in
 strict=True).  salve_amd.train_utils stays inference-only and keeps refusing the train split: training is reached through this
 module (and `python -m salve_amd.train`) only.
 
-Differences from the reference, all deliberate: one GPU (`dataparallel` is accepted and ignored, the state dict carries no
-`module.` prefix), num_workers = 0 (the transforms launch GPU kernels), photometric augmentation (False in every released config; opt-in: photometric="device")
+Differences from the reference, all deliberate: one GPU per process (`dataparallel` is accepted and ignored, the state dict carries
+no `module.` prefix; several GPUs train data-parallel with one process each: `dist=`, salve_amd.dist_train, `--gpus N`), num_workers = 0 (the transforms launch GPU kernels), photometric augmentation (False in every released config; opt-in: photometric="device")
 and crop-with-padding are refused, the shuffle order comes from a seeded torch.Generator.
 """
 
@@ -27,6 +27,7 @@ import numpy as np
 import torch
 from torch import Tensor, nn
 
+from salve_amd.dist_train import DataParallel, bn_statistics
 from salve_amd.evaluate import ClassAccuracyMeter, DeviceClassMeter
 from salve_amd.models.trainable import TRAIN_HEADS, TRAIN_NORMS, TRAIN_PRECISIONS, TrainableEarlyFusionCEResnet
 from salve_amd.optim import OPTIMS, HipAdam
@@ -56,7 +57,8 @@ def _check_head(head: str) -> None:
 
 
 def get_model(args: TrainingConfig, precision: str = "fp32", norm: str = "torch", head: str = "torch") -> nn.Module:
-    """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored.
+    """TrainableEarlyFusionCEResnet on the GPU (salve/train_utils.py:205-217).  `args.dataparallel` is accepted and ignored: the
+    model is never wrapped; data-parallel training is one process per GPU around the same model (`train(..., dist=)`).
     precision: "fp32" (the reference's) or "bf16" (opt-in mixed precision: TrainableEarlyFusionCEResnet.set_train_precision).
     norm: "torch" (nn.BatchNorm2d) or "hip" (opt-in fused HIP BatchNorm: TrainableEarlyFusionCEResnet.set_train_norm).
     head: "torch" (avgpool, fc, softmax, cross_entropy) or "hip" (opt-in fused HIP classifier head with the loss and the accuracy
@@ -102,7 +104,7 @@ def cross_entropy_forward(model: nn.Module, split: str, x1: Tensor, x2: Tensor, 
         with torch.no_grad():
             logits = model(x1, x2, x3, x4, x5, x6)
     probs = torch.nn.functional.softmax(logits.detach().clone(), dim=1)
-    loss = torch.nn.functional.cross_entropy(logits, is_match.squeeze())
+    loss = torch.nn.functional.cross_entropy(logits, is_match.reshape(-1))   # ([B, 1] or [B]; a one-row batch -- a rank's slice of a short one -- stays [1])
     return probs, loss
 
 
@@ -118,7 +120,7 @@ def cross_entropy_forward_packed(model: nn.Module, split: str, x_packed: Tensor,
         with torch.no_grad():
             logits = model.forward_packed(x_packed)
     probs = torch.nn.functional.softmax(logits.detach().clone(), dim=1)
-    loss = torch.nn.functional.cross_entropy(logits, is_match.squeeze())
+    loss = torch.nn.functional.cross_entropy(logits, is_match.reshape(-1))   # ([B, 1] or [B]; a one-row batch -- a rank's slice of a short one -- stays [1])
     return probs, loss
 
 
@@ -156,10 +158,11 @@ def _check_decode(decode: str) -> None:
 
 
 def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precision: str = "fp32", entropy: str = "image",
-                         read_ahead: bool = False, photometric: Optional[str] = None):
+                         read_ahead: bool = False, photometric: Optional[str] = None, rank: int = 0, world: int = 1):
     """`get_dataloader`'s examples in its order as a train_files.TileFileSource: whole batches of the data set's JPEG tiles decoded
     on the device, `(x_packed, is_match)` for `run_epoch`.  Grouping and ordering are ZindData's.  entropy, read_ahead: TileFileSource's.
-    photometric: `get_train_transform`'s keyword (the train split jitters iff the config's field is True)."""
+    photometric: `get_train_transform`'s keyword (the train split jitters iff the config's field is True).
+    rank, world: TileFileSource's (data-parallel training: this rank's rows of every batch)."""
     from salve_amd.dataset.zind_data import ZindData
     from salve_amd.train_files import TileFileSource
 
@@ -167,7 +170,7 @@ def get_tile_file_source(args: TrainingConfig, split: str, seed: int = 0, precis
     data = ZindData(split=split, transform=None, args=args)
     return TileFileSource(torch.device("cuda", torch.cuda.current_device()), data.data_list, batch_size=args.batch_size, precision=precision,
                           split=split, seed=seed, resize_hw=(args.resize_h, args.resize_w), crop_hw=(args.train_h, args.train_w), entropy=entropy,
-                          read_ahead=read_ahead, photometric=_jitter(args, photometric))
+                          read_ahead=read_ahead, photometric=_jitter(args, photometric), rank=rank, world=world)
 
 
 def get_dataloader(args: TrainingConfig, split: str, seed: int = 0, photometric: Optional[str] = None) -> torch.utils.data.DataLoader:
@@ -198,13 +201,27 @@ def _unpack(args: TrainingConfig, example):
     return (x1, x2, x3, x4, x5, x6), is_match
 
 
-def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
+def _log(dist: Optional[DataParallel]) -> bool:
+    """Whether this process logs and writes files: rank 0 does."""
+    return dist is None or dist.is_main
+
+
+def _local(dist: Optional[DataParallel]) -> str:
+    """What a per-iteration log line says of its loss when several ranks train: it is this rank's rows' alone."""
+    return f" (rank 0's rows of {dist.world} ranks)" if dist is not None and dist.world > 1 else ""
+
+
+def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str,
+              dist: Optional[DataParallel] = None) -> Dict[str, float]:
     """One pass over a split (scripts/train.py:169-278): train mode + Adam steps + the poly schedule for "train", eval mode
     otherwise.  Returns {"avg_loss", "mAcc"}; as in the reference, avg_loss counts training batches only (0 for val).
     `data_loader`: a DataLoader over ZindData, or a train_render.RenderedTrainSource (2-tuples, through `model.forward_packed`).
-    A model whose head is "hip" runs `_run_epoch_device`: the same pass without a wait for the device between batches."""
+    A model whose head is "hip" runs `_run_epoch_device`: the same pass without a wait for the device between batches.
+    dist (data-parallel training): the loader yields this rank's rows; the ranks' gradients are averaged between backward and step
+    (DataParallel.all_reduce_gradients), counts and loss sums are summed over the ranks once, at the end of the pass, so every rank
+    returns the same dict; only rank 0 logs, and the loss it logs per iteration is its own rows'."""
     if getattr(model, "train_head", "torch") == "hip":
-        return _run_epoch_device(args, epoch, model, data_loader, optimizer, split)
+        return _run_epoch_device(args, epoch, model, data_loader, optimizer, split, dist)
     model.train() if split == "train" else model.eval()
     loss_sum, loss_n = 0.0, 0
     meter = ClassAccuracyMeter(args.num_ce_classes)
@@ -225,6 +242,8 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
         if split == "train":
             optimizer.zero_grad()
             loss.backward()
+            if dist is not None:
+                dist.all_reduce_gradients(model.parameters())
             optimizer.step()
             if args.lr_annealing_strategy == "poly":   # decayed after the step, as the reference does
                 lr = poly_learning_rate(args.base_lr, current_iter, max_iter, power=args.poly_lr_power)
@@ -233,18 +252,22 @@ def run_epoch(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, o
             n = xs[0].shape[0]
             loss_sum += float(loss.item()) * n
             loss_n += n
-            if it % max(1, args.print_every) == 0:
-                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f} ({time.time() - t0:.1f} s)")
+            if it % max(1, args.print_every) == 0 and _log(dist):
+                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f}{_local(dist)} ({time.time() - t0:.1f} s)")
+    if dist is not None:
+        loss_sum, loss_n = dist.reduce_meter(meter, loss=(loss_sum, loss_n))
     accs, mAcc = meter.get_metrics()
-    logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
+    if _log(dist):
+        logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
     return {"avg_loss": loss_sum / loss_n if loss_n else 0.0, "mAcc": float(mAcc)}
 
 
-def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str) -> Dict[str, float]:
+def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_loader, optimizer: torch.optim.Optimizer, split: str,
+                      dist: Optional[DataParallel] = None) -> Dict[str, float]:
     """`run_epoch` for a model with the HIP head: the loss sum and the per-class counts live in a DeviceClassMeter that the head's
     forward updates, so no batch copies anything to the host -- the host enqueues batch after batch and reads the meter once at the
     end of the pass.  Only the iterations that log (`it % print_every == 0`, training) read their loss.  Same schedule, same
-    returned dict."""
+    returned dict.  dist: `run_epoch`'s; the device record is summed over the ranks before its one read."""
     model.train() if split == "train" else model.eval()
     dev = next(model.parameters()).device
     meter = DeviceClassMeter(args.num_ce_classes, dev)
@@ -262,21 +285,26 @@ def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_l
         if train:
             optimizer.zero_grad()
             loss.backward()
+            if dist is not None:
+                dist.all_reduce_gradients(model.parameters())
             optimizer.step()
             if args.lr_annealing_strategy == "poly":   # decayed after the step, as the reference does
                 lr = poly_learning_rate(args.base_lr, current_iter, max_iter, power=args.poly_lr_power)
                 for group in optimizer.param_groups:
                     group["lr"] = lr
-            if it % max(1, args.print_every) == 0:
-                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f} ({time.time() - t0:.1f} s)")
+            if it % max(1, args.print_every) == 0 and _log(dist):
+                logging.info(f"\t{split} iter [{it + 1}/{len(data_loader)}] loss {loss.item():.4f}{_local(dist)} ({time.time() - t0:.1f} s)")
+    if dist is not None:
+        dist.reduce_meter(meter)
     accs, mAcc, avg_loss = meter.read()
-    logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
+    if _log(dist):
+        logging.info(f"{split} result at epoch [{epoch + 1}/{args.num_epochs}]: mAcc {mAcc:.4f}, class accuracies {accs.tolist()}")
     return {"avg_loss": avg_loss, "mAcc": float(mAcc)}
 
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
           norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image",
-          read_ahead: bool = False, photometric: Optional[str] = None) -> Dict[str, list]:
+          read_ahead: bool = False, photometric: Optional[str] = None, dist: Optional[DataParallel] = None) -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
@@ -291,7 +319,10 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     read_ahead (decode="device" only; default False): the next batches' files are read, and the next batch decoded on a side stream,
     while the current batch trains (TileFileSource(read_ahead=True)) -- the same batches once more.
     photometric: None (default) or "device" -- a config with apply_photometric_augmentation=True trains only with "device": the
-    reference's PhotometricShift on the device in every train batch of either decode; val batches never jitter."""
+    reference's PhotometricShift on the device in every train batch of either decode; val batches never jitter.
+    dist: None (default), or a dist_train.DataParallel: this process is one of `dist.world` ranks, each of which trains its rows of
+    every batch; needs decode="device" in a world larger than one -- the host DataLoader draws inside its worker
+    processes and is not sharded.  Rank 0 logs and writes the checkpoint and the results JSON; every rank returns the same dict."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
@@ -301,25 +332,30 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
         raise ValueError(f'entropy={entropy!r} selects the device decoder\'s entropy stage: it needs decode="device"')
     if read_ahead and decode != "device":
         raise ValueError('read_ahead=True reads the device decoder\'s next batch ahead: it needs decode="device"')
+    rank, world = (dist.rank, dist.world) if dist is not None else (0, 1)
+    if world > 1 and decode != "device":
+        raise ValueError(f'data-parallel training over {world} ranks needs decode="device" (--decode device): the host DataLoader feed '
+                         "(decode=\"host\") takes its draws inside worker processes and is not sharded")
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
     if decode == "device":
-        with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead, photometric) as train_source, \
-                get_tile_file_source(args, "val", seed, precision, entropy, read_ahead, photometric) as val_source:
-            return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)   # (leaving ends their reader threads)
+        with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead, photometric, rank, world) as train_source, \
+                get_tile_file_source(args, "val", seed, precision, entropy, read_ahead, photometric, rank, world) as val_source:
+            return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist)   # (leaving ends their reader threads)
     return _fit(args, get_dataloader(args, "train", seed=seed, photometric=photometric), get_dataloader(args, "val"), results_dir, init_ckpt,
-                precision, norm, optim, head)
+                precision, norm, optim, head, dist)
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
                    precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch",
-                   jpeg_quality: Optional[int] = None, photometric: Optional[str] = None) -> Dict[str, list]:
+                   jpeg_quality: Optional[int] = None, photometric: Optional[str] = None, dist: Optional[DataParallel] = None) -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
     split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON.  jpeg_quality: the
     sources' own argument (the reference's JPEG round trip of every rendered image, on the device); the two sources must agree, and
     an integer given here must be what they were built with.  photometric: `train`'s keyword; the train source must have been built
-    with what the config and the keyword amount to (RenderedTrainSource(photometric=))."""
+    with what the config and the keyword amount to (RenderedTrainSource(photometric=)).  dist: `train`'s; both sources must have been
+    built with its rank and world (RenderedTrainSource(rank=, world=))."""
     _check_precision(precision)
     _check_norm(norm)
     _check_optim(optim)
@@ -329,6 +365,11 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
         raise RuntimeError(f"the train source was built with photometric={getattr(train_source, 'photometric', None)!r}; the config's "
                            f"apply_photometric_augmentation={args.apply_photometric_augmentation} and photometric={photometric!r} ask for "
                            f"{_jitter(args, photometric)!r}")
+    rank, world = (dist.rank, dist.world) if dist is not None else (0, 1)
+    for src in (train_source, val_source):
+        if (getattr(src, "rank", 0), getattr(src, "world", 1)) != (rank, world):
+            raise RuntimeError(f"a batch source was built for rank {getattr(src, 'rank', 0)} of {getattr(src, 'world', 1)}, this process is "
+                               f"rank {rank} of {world}")
     want = torch.bfloat16 if precision == "bf16" else torch.float32
     for src in (train_source, val_source):
         if src.dtype != want:
@@ -340,12 +381,14 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head)
+    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist)
 
 
 def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str,
-         optim: str = "torch", head: str = "torch") -> Dict[str, list]:
-    """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources."""
+         optim: str = "torch", head: str = "torch", dist: Optional[DataParallel] = None) -> Dict[str, list]:
+    """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources.  dist: every rank starts from
+    rank 0's parameters (one broadcast), validates with rank 0's BatchNorm statistics (one broadcast in front of every val pass: the
+    reference's DataParallel keeps replica 0's), and rank 0 alone writes the checkpoint and the results JSON."""
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
     model = get_model(args, precision, norm, head)
@@ -353,17 +396,25 @@ def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_
         from salve_amd import train_utils
 
         train_utils.load_model_checkpoint(init_ckpt, model, args)
+    if dist is not None:
+        dist.broadcast(list(model.parameters()))
     optimizer = get_optimizer(args, model, optim)
     out = Path(results_dir)
-    out.mkdir(parents=True, exist_ok=True)
+    if _log(dist):
+        out.mkdir(parents=True, exist_ok=True)
     results: Dict[str, list] = defaultdict(list)
     for epoch in range(args.num_epochs):
-        logging.info(f"On epoch {epoch}")
-        for k, v in run_epoch(args, epoch, model, train_loader, optimizer, "train").items():
+        if _log(dist):
+            logging.info(f"On epoch {epoch}")
+        for k, v in run_epoch(args, epoch, model, train_loader, optimizer, "train", dist).items():
             results[f"train_{k}"].append(v)
+        if dist is not None:
+            dist.broadcast(bn_statistics(model))
         with torch.no_grad():
-            for k, v in run_epoch(args, epoch, model, val_loader, optimizer, "val").items():
+            for k, v in run_epoch(args, epoch, model, val_loader, optimizer, "val", dist).items():
                 results[f"val_{k}"].append(v)
+        if not _log(dist):
+            continue
         crit = results[CRIT_ACC_STAT]
         if epoch == 0 or crit[-1] > max(crit[:-1]):
             torch.save({
