@@ -50,7 +50,8 @@ typedef enum {
                                         salve_bev_jpeg_decode_lanes (with salve_bev_jpeg_decode_lanes_workspace_bytes, salve_bev_jpeg_subseq_bytes
                                         and salve_jpeg_segment_t), salve_bev_jpeg_decode_sampled / _lanes_sampled (with their two
                                         _workspace_bytes queries and SALVE_JPEG_SAMPLING_*), salve_bev_train_tiles_jitter (with
-                                        salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t) */
+                                        salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t), salve_bev_pair_overlap (with
+                                        salve_overlap_job_t) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -65,7 +66,7 @@ typedef enum {
                                           which are not implemented) -- that segment is not drawn */
 #define SALVE_STATUS_BAD_TILE_JOB 16 /* bev_train_tiles: a job names another sample, channels outside the sample, an image outside its array, or
                                         a draw carries unknown flag bits (bev_train_tiles_jitter: or a jitter record is malformed) -- that
-                                        sample is not written */
+                                        sample is not written; bev_pair_overlap: a job names an image outside its array -- its row is -1 */
 #define SALVE_STATUS_BAD_PANO_SLOT 32 /* bev_pano_index_update: the slot list names a slot outside [0, n_panos) -- that entry is skipped, the
                                          other listed slots are updated */
 #define SALVE_STATUS_BAD_LAYOUT 64 /* layout_pose: an image record names a panorama outside [0, n_panos), offsets outside the output capacities,
@@ -391,6 +392,25 @@ int salve_bev_train_tiles_jitter(const uint32_t* bev_a, int32_t n_bev_a, const u
                                  int32_t batch, const int32_t* coef_y, const int32_t* coef_x, int32_t resize, int32_t crop, const float* lut,
                                  void* out, int32_t out_format, int32_t out_c, const salve_tile_jitter_t* jitter, void* workspace,
                                  size_t workspace_bytes, int32_t* status, void* stream);
+
+/* The visual overlap of image pairs: stands behind salve/utils/iou_utils.py:14-37 (texture_map_iou -> binary_mask_iou), which
+ * scripts/measure_acc_vs_overlap.py:77-80 calls on the two tile files of every scored pair.  The images are still in device memory as
+ * uint32 0x00BBGGRR, so the reference's occupancy test np.amax(f, axis=2) > 0 is (pixel & 0x00FFFFFF) != 0 -- a stray top byte does not
+ * make a pixel occupied -- and the counts are exact integers; IoU = intersection / (union + 1e-12) is left to the caller.
+ *   bev_a / bev_b   two arrays of n_bev_a / n_bev_b images of bev_h x bev_w, 4-byte aligned; only read, so they may be the same array
+ *   jobs            device salve_overlap_job_t [n_jobs]: job j compares image .a of bev_a with image .b of bev_b
+ *   out             device int32 [n_jobs, 4], 16-byte aligned: row j = {intersection, union, occupied_a, occupied_b}, written by ONE
+ *                   16-byte store.  No atomics, no zeroing needed, one summation order: the same bytes on every run.
+ *   status          device int32 status word or NULL.  The job table is device memory, so the kernel checks it before it forms an
+ *                   address: a job whose .a or .b lies outside [0, n_bev_*) reads nothing, writes {-1, -1, -1, -1} and raises
+ *                   SALVE_STATUS_BAD_TILE_JOB.
+ * One launch on `stream`, one workgroup per job; n_jobs == 0 launches nothing.  SALVE_ERR_BAD_ARG for bev_h or bev_w < 1,
+ * bev_h * bev_w >= 2^31, a negative count, and -- with n_jobs > 0 -- a null pointer or a misaligned one. */
+typedef struct {
+    int32_t a, b; /* image index into bev_a / bev_b */
+} salve_overlap_job_t;
+int salve_bev_pair_overlap(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
+                           const salve_overlap_job_t* jobs, int32_t n_jobs, int32_t* out, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

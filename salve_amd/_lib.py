@@ -94,6 +94,7 @@ EXPORTED_SYMBOLS = (
     "salve_bev_train_tiles_jitter",
     "salve_flat_pack",
     "salve_flat_unpack",
+    "salve_bev_pair_overlap",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -139,6 +140,8 @@ JPEG_MAX_SEGMENTS = 1 << 24
 TILE_AUG_DTYPE = np.dtype([("crop_y", "<i4"), ("crop_x", "<i4"), ("flags", "<i4"), ("reserved", "<i4")])
 TILE_HFLIP, TILE_VFLIP = 1, 2
 assert LAYOUT_POSE_DTYPE.itemsize == 48 and HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
+OVERLAP_JOB_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4")])   # salve_overlap_job_t (salve_bev_pair_overlap): image index into bev_a / bev_b
+assert OVERLAP_JOB_DTYPE.itemsize == 8
 # salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
 TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
                               ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
@@ -280,6 +283,8 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_train_tiles_jitter_workspace_bytes.restype = sz
     lib.salve_bev_train_tiles_jitter.argtypes = [vp, i32, vp, i32, i32, i32, vp, vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, i32, i32, vp, vp, sz, vp, vp]
     lib.salve_bev_train_tiles_jitter.restype = ctypes.c_int
+    lib.salve_bev_pair_overlap.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]   # bev_a, n_a, bev_b, n_b, h, w, jobs, n_jobs, out, status, stream
+    lib.salve_bev_pair_overlap.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -362,7 +367,8 @@ def check_status_word(word: int, what: str) -> None:
         raise SalveHipError(f"{what}: a layout segment of 19 pixels or more was left out (its OpenCV end caps are not implemented)")
     if word & STATUS_BAD_TILE_JOB:
         raise SalveHipError(f"{what}: a train-tile job names another sample, channels or an image outside its arrays (or a draw has unknown "
-                            "flag bits, or a jitter record is malformed); that sample was not written")
+                            "flag bits, or a jitter record is malformed); that sample was not written -- or a pair-overlap job names an image "
+                            "outside its arrays; its row is -1")
     if word & STATUS_BAD_PANO_SLOT:
         raise SalveHipError(f"{what}: a panorama-index update names a slot outside the resident pool; that slot's index was not rebuilt")
     if word & STATUS_BAD_LAYOUT:

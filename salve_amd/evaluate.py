@@ -88,9 +88,10 @@ class DeviceClassMeter:
 
 
 def save_edge_classifications_to_disk(serialization_save_dir: str, batch_idx: int, y_hat: torch.Tensor, y_true: torch.Tensor,
-                                      probs: torch.Tensor, fp0: Sequence[str], fp1: Sequence[str]) -> None:
+                                      probs: torch.Tensor, fp0: Sequence[str], fp1: Sequence[str], overlap=None) -> None:
     """scripts/test.py:52-81: `y_hat_probs` is the probability of the PREDICTED class; JSON with indent 4
-    (salve/utils/io.py:24-36)."""
+    (salve/utils/io.py:24-36).  overlap (run_fused_epoch(visual_overlap=True) only): one (intersection, union) pixel count per row, written
+    as one more key, "overlap", behind the reference's five."""
     n = y_hat.shape[0]
     save_dict = {
         "y_hat": y_hat.cpu().numpy().tolist(),
@@ -99,6 +100,8 @@ def save_edge_classifications_to_disk(serialization_save_dir: str, batch_idx: in
         "fp0": list(fp0),
         "fp1": list(fp1),
     }
+    if overlap is not None:
+        save_dict["overlap"] = [[int(i), int(u)] for i, u in overlap]
     os.makedirs(serialization_save_dir, exist_ok=True)
     with open(f"{serialization_save_dir}/batch_{batch_idx}.json", "w") as f:
         json.dump(save_dict, f, indent=4)
@@ -219,7 +222,8 @@ def evaluate_model(serialization_save_dir: str, ckpt_fpath: str, args, split: st
 
 @torch.no_grad()
 def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_true: Optional[np.ndarray], serialization_save_dir: str,
-                    batch_size: int = 64, ckpt_fpath: str = "", split: str = "test", world: int = 1, rank: int = 0) -> Dict[str, Any]:
+                    batch_size: int = 64, ckpt_fpath: str = "", split: str = "test", world: int = 1, rank: int = 0,
+                    visual_overlap: bool = False) -> Dict[str, Any]:
     """Render + verify a hypothesis table on the GPU (pipeline.RenderVerifyPipeline) and write the SAME prediction
     files as run_test_epoch.  `hypotheses`, `tile_names` and `y_true` describe the WHOLE table on every rank;
     `tile_names[j]` = (fp0, fp1): the tile paths the un-fused path would have written for hypothesis j
@@ -228,18 +232,37 @@ def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_tru
     block (HypothesisTable.shard) and rank 0 writes the files after the path's one all-gather.
 
     Hypotheses with a render that has no point inside the BEV window are dropped: the reference writes no tile for them
-    (bev_rendering_utils.py:279-280, 623-627), so they never reach scripts/test.py nor the pose-graph stage."""
+    (bev_rendering_utils.py:279-280, 623-627), so they never reach scripts/test.py nor the pose-graph stage.
+
+    visual_overlap: every `batch_{i}.json` gains one key, "overlap": [intersection, union] per row, the pixel counts behind the IoU that the
+    reference's overlap analysis takes from the two tile files fp0 / fp1 name (scripts/measure_acc_vs_overlap.py:77-80) -- counted on the
+    device (RenderVerifyPipeline.score(visual_overlap=True)) for the surface those names carry: the floor where the model has a floor
+    surface, else the ceiling (zind_data.py:290-328).  salve_amd.overlap reads the key.  The other keys and their values are unchanged.
+    With world > 1 the two counts ride in the one all-gather as two more fp32 columns, exact up to 2^24 pixels per image."""
     from salve_amd.pipeline import gather_logits
 
     n_all = len(hypotheses)
+    if visual_overlap and world > 1 and pipe.ras.bev_hw[0] * pipe.ras.bev_hw[1] > 2 ** 24:
+        raise RuntimeError(f"visual_overlap with world > 1 carries the pixel counts as fp32: exact for images of at most 2^24 pixels, these have "
+                           f"{pipe.ras.bev_hw[0]} x {pipe.ras.bev_hw[1]}")
     shard = hypotheses.shard(rank, world) if world > 1 else hypotheses
     prepared = pipe.prepare(shard)
-    local = pipe.score(prepared)
+    local = pipe.score(prepared, visual_overlap=True) if visual_overlap else pipe.score(prepared)
     valid_local = torch.from_numpy(pipe.valid_mask(prepared).astype(np.float32)).to(local.device)
     pipe.check("run_fused_epoch")
-    # one collective: the validity flag rides along as an extra column of the logits
-    both = gather_logits(torch.cat([local, valid_local[:, None]], dim=1), world, total=n_all)
-    logits, valid = both[:, :-1], both[:, -1] > 0.5
+    C = int(local.shape[1])
+    columns = [local, valid_local[:, None]]
+    counts = None
+    if visual_overlap:
+        named = pipe.surfaces.index("floor") if "floor" in pipe.surfaces else 0   # the surface of the names in fp0 / fp1
+        counts = pipe.visual_overlap(prepared)[:, named, :]                       # int64 [n, 2] on the host
+        if world > 1:
+            columns.append(torch.from_numpy(counts.astype(np.float32)).to(local.device))
+    # one collective: the validity flag (and the two counts) ride along as extra columns of the logits
+    both = gather_logits(torch.cat(columns, dim=1), world, total=n_all)
+    logits, valid = both[:, :C], both[:, C] > 0.5
+    if visual_overlap and world > 1:
+        counts = both[:, C + 1:C + 3].cpu().numpy().astype(np.int64)
     keep = torch.nonzero(valid).reshape(-1)
     probs = torch.softmax(logits[keep], dim=1)  # train_utils.py:31
     y_hat = torch.argmax(probs, dim=1)
@@ -254,7 +277,8 @@ def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_tru
         for b, lo in enumerate(range(0, n, batch_size)):
             hi = min(lo + batch_size, n)
             save_edge_classifications_to_disk(serialization_save_dir, b, y_hat[lo:hi], gt[lo:hi], probs[lo:hi],
-                                              [tile_names[kept[j]][0] for j in range(lo, hi)], [tile_names[kept[j]][1] for j in range(lo, hi)])
+                                              [tile_names[kept[j]][0] for j in range(lo, hi)], [tile_names[kept[j]][1] for j in range(lo, hi)],
+                                              overlap=None if counts is None else counts[kept[lo:hi]])
     out = _summary(split, ckpt_fpath, cls, pr)
     out["num_hypotheses"] = n_all
     out["num_dropped_no_points_in_window"] = n_all - n

@@ -279,11 +279,14 @@ def load_floor_hypotheses(hypotheses_save_root: str, building_id: str, floor_id:
 
 def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypotheses_save_root: str, bev_save_root: str,
                 building_id: str, floor_id: str, serialization_save_dir: str, batch_size: int = 64, chunk: Optional[int] = None,
-                decode: str = "host", samplings: Sequence[str] = ("4:2:0",)):
+                decode: str = "host", samplings: Sequence[str] = ("4:2:0",), visual_overlap: bool = False, jpeg_quality: Optional[int] = None):
     """Disk -> predictions for one floor without writing a tile: the fused counterpart of running
     scripts/render_dataset_bev.py and then scripts/test.py on that floor.  chunk = hypotheses per launch; None: the pipeline picks the
     largest launch that fits the free HBM (pipeline.pick_launch).  decode: PanoStore.load's ("device": the panoramas' JPEG files are
-    decoded on the GPU; the same prediction files), and so is samplings (which JPEG samplings stay on the device)."""
+    decoded on the GPU; the same prediction files), and so is samplings (which JPEG samplings stay on the device).
+    visual_overlap: evaluate.run_fused_epoch's -- every prediction file also carries "overlap", the pixel counts of the pair's visual overlap
+    (what `python -m salve_amd.overlap` bins accuracy by).  jpeg_quality: RenderVerifyPipeline's (75: tiles and counts are those of the
+    reference's JPEG files)."""
     from salve_amd import evaluate
     from salve_amd.pipeline import RenderVerifyPipeline
 
@@ -292,7 +295,7 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
         return None
     img_fpaths = floor_pano_fpaths(raw_dataset_dir, building_id)
     store = PanoStore(device).load(img_fpaths, depth_save_root, building_id, np.concatenate([hyps.i1, hyps.i2]), decode=decode, samplings=samplings)
-    pipe = RenderVerifyPipeline(model, device, pano_hw=store.pano_hw, chunk=chunk, n_hypotheses=len(hyps))
+    pipe = RenderVerifyPipeline(model, device, pano_hw=store.pano_hw, chunk=chunk, n_hypotheses=len(hyps), jpeg_quality=jpeg_quality)
     pipe.set_panos(store.rgb, store.depth)
     return evaluate.run_fused_epoch(pipe, hyps.table(store, img_fpaths), hyps.tile_names(bev_save_root, img_fpaths), hyps.label,
-                                    serialization_save_dir, batch_size=batch_size)
+                                    serialization_save_dir, batch_size=batch_size, visual_overlap=visual_overlap)

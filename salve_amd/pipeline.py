@@ -384,11 +384,35 @@ class RenderVerifyPipeline:
             e1.record()
             vtimers.append((e0, e1, n))
 
-    def score(self, prepared, out: Optional[torch.Tensor] = None, timers=None, vtimers=None) -> torch.Tensor:
+    def _overlap_tables(self, prepared) -> None:
+        """The first score(visual_overlap=True) of a shard: its pair-overlap job table (hypothesis-major, a chunk a contiguous slice: job
+        (j, si) compares render rank[j] % chunk * S + si of the chunk's image buffer with the kept identity render i2[j] * S + si) and its
+        int32 [N, S, 4] count buffer (never zeroed: every row is written by every score)."""
+        N, S = prepared["n"], len(self.surfaces)
+        rslot = np.asarray(prepared["rank"]) % self.chunk
+        si = np.arange(S)
+        prepared["overlap_jobs"] = self.ras.upload_overlap_jobs((rslot[:, None] * S + si).reshape(-1), (prepared["i2"][:, None] * S + si).reshape(-1))
+        prepared["overlap"] = torch.empty((N, S, 4), dtype=torch.int32, device=self.device)
+        prepared["overlap_ready"] = torch.cuda.Event()   # the table is on the device: the render stream waits for it
+        prepared["overlap_ready"].record(torch.cuda.current_stream(self.device))
+
+    def _overlap_chunk(self, prepared, lo: int, n: int, buf: int) -> None:
+        S = len(self.surfaces)
+        with tracing.range("salve.pair_overlap"):
+            self.ras.pair_overlap(self.bevs[buf], self.ref_bev, prepared["overlap_jobs"][lo * S * _lib.OVERLAP_JOB_DTYPE.itemsize:], n * S,
+                                  out=prepared["overlap"][lo:lo + n].view(n * S, 4))
+
+    def score(self, prepared, out: Optional[torch.Tensor] = None, timers=None, vtimers=None, visual_overlap: bool = False) -> torch.Tensor:
         """Render + verify every hypothesis of a prepared shard.  Returns fp32 logits [N, num_classes] (complete once the
         CURRENT stream has caught up).  `timers` / `vtimers` = lists: receive (start event, end event, units, "scatter" |
         "densify") for the rasteriser launches / (start, end, units) for the verifier forward of every chunk (benchmark
         rooflines; the events are recorded on the stream the kernels are launched on).
+
+        visual_overlap (default False: launches, uploads and logits are exactly those without it): every chunk's posed renders are also
+        compared with the kept identity renders of their pairs -- one BevRasteriser.pair_overlap launch per chunk on the stream of the
+        densify kernel, behind the chunk's tiles (and behind its JPEG round trip, where one is set: the counts are then those of the
+        reference's files) and in front of the event that gives the image buffer back to the next scatter.  The verifier does not wait
+        for it; `visual_overlap(prepared)` does, and returns the counts.  (The constructor's `overlap=` is STREAM overlap.)
 
         Streams: the verifier always runs on the current stream; with overlap the scatter and the densify + tile kernels run
         on their own streams, ordered by events only -- a workspace slot is reused once the densify that read it is done, a
@@ -403,6 +427,11 @@ class RenderVerifyPipeline:
         ss = self.scatter_stream or rs
         n_slots = 2 if self.scatter_stream is not None else 1
         self.last_chunk_buffer = {}
+        if visual_overlap:
+            if len(self.surfaces) == 0:
+                raise RuntimeError("visual_overlap counts the pixels of texture maps; a layout-only model renders none (the overlap of layout images is not computed)")
+            if "overlap_jobs" not in prepared:
+                self._overlap_tables(prepared)
         for ci, lo in enumerate(range(0, N, self.chunk)):
             n = min(self.chunk, N - lo)
             seq = self._seq
@@ -428,15 +457,36 @@ class RenderVerifyPipeline:
                 if self._consumed[buf] is not None:
                     rs.wait_event(self._consumed[buf])        # the verifier that read this buffer set is done
                 self._densify_chunk(prepared, lo, n, buf, slot, timers)
+                tiles_ready = None
+                if visual_overlap:
+                    if rs is not main:   # the verifier waits for the tiles only, not for the counts
+                        tiles_ready = torch.cuda.Event()
+                        tiles_ready.record(rs)
+                        rs.wait_event(prepared["overlap_ready"])
+                    self._overlap_chunk(prepared, lo, n, buf)
+                # (recorded BEHIND the overlap launch: it is the last reader of this chunk's images)
                 self._densified[slot] = torch.cuda.Event()
                 self._densified[slot].record(rs)
             if rs is not main:
-                main.wait_event(self._densified[slot])
+                main.wait_event(tiles_ready if tiles_ready is not None else self._densified[slot])
             self._verify_chunk(buf, n, out[lo:lo + n], vtimers)
             self._consumed[buf] = torch.cuda.Event()
             self._consumed[buf].record(main)
+        if visual_overlap:
+            prepared["overlap_done"] = torch.cuda.Event()   # behind every overlap launch of this call
+            prepared["overlap_done"].record(rs)
         self.ras.ws_slot = 0
         return out
+
+    def visual_overlap(self, prepared) -> np.ndarray:
+        """int64 [N, S, 2] (host): (intersection, union) in pixels of every hypothesis's posed render of surface s with the identity
+        render of its second panorama -- the two counts behind the reference's texture_map_iou of the pair's two tile files
+        (salve/utils/iou_utils.py:14-37; scripts/measure_acc_vs_overlap.py:77-80), in hypothesis order.  Call after
+        score(prepared, visual_overlap=True); synchronises (with the stream of the overlap launches)."""
+        if "overlap_done" not in prepared:
+            raise RuntimeError("visual_overlap(prepared) needs a score(prepared, visual_overlap=True) first")
+        prepared["overlap_done"].synchronize()
+        return prepared["overlap"][:, :, :2].cpu().numpy().astype(np.int64)
 
     def valid_mask(self, prepared) -> np.ndarray:
         """bool [N] (host): hypotheses for which the reference writes tiles at all -- both renders of every surface have

@@ -590,6 +590,44 @@ class BevRasteriser:
         _lib.check(st, "salve_bev_tile_pairs")
         return out
 
+    def upload_overlap_jobs(self, a_index: Sequence[int], b_index: Sequence[int]) -> torch.Tensor:
+        """`pair_overlap`'s job table: job j compares image a_index[j] of its first array with image b_index[j] of its second."""
+        a = np.asarray(a_index, dtype=np.int64).reshape(-1)
+        b = np.asarray(b_index, dtype=np.int64).reshape(-1)
+        if a.shape != b.shape:
+            raise _lib.SalveHipError(f"upload_overlap_jobs: {a.shape[0]} first and {b.shape[0]} second images")
+        if a.size and (min(int(a.min()), int(b.min())) < -2 ** 31 or max(int(a.max()), int(b.max())) >= 2 ** 31):
+            raise _lib.SalveHipError("upload_overlap_jobs: an image index does not fit 32 bits")
+        j = np.zeros(a.shape[0], dtype=_lib.OVERLAP_JOB_DTYPE)
+        j["a"], j["b"] = a, b
+        return torch.from_numpy(j.view(np.uint8)).to(self.device)
+
+    def pair_overlap(self, bev_a: torch.Tensor, bev_b: torch.Tensor, jobs: torch.Tensor, n_jobs: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [n_jobs, 4] = (intersection, union, occupied in a, occupied in b) of the image pairs `jobs` (upload_overlap_jobs) names:
+        the pixel counts behind the reference's texture_map_iou (salve/utils/iou_utils.py:14-37; include/salve_hip.h:
+        salve_bev_pair_overlap), occupied = a colour byte is non-zero.  bev_a / bev_b: contiguous int32 [n, H, W] images (0x00BBGGRR) of one
+        size on this device; they may be the same tensor.  One launch on the current stream, nothing is read back; exact, and the same
+        bytes on every run.  A job that names an image outside its array gets the row -1 and is reported through the device status
+        word (`check`)."""
+        self._jpeg_images("pair_overlap: bev_a", bev_a)
+        self._jpeg_images("pair_overlap: bev_b", bev_b, (bev_b.shape[0],) + tuple(bev_a.shape[1:]) if bev_b.dim() == 3 else None)
+        n_jobs = int(n_jobs)
+        if jobs.dtype != torch.uint8 or jobs.dim() != 1 or not jobs.is_contiguous() or jobs.device != self.device:
+            raise _lib.SalveHipError(f"pair_overlap: jobs must be upload_overlap_jobs' contiguous uint8 table on {self.device}, got {jobs.dtype} "
+                                     f"{tuple(jobs.shape)} on {jobs.device}")
+        if n_jobs < 0 or n_jobs * _lib.OVERLAP_JOB_DTYPE.itemsize > jobs.numel():
+            raise _lib.SalveHipError(f"pair_overlap: {n_jobs} jobs asked for, the table holds {jobs.numel() // _lib.OVERLAP_JOB_DTYPE.itemsize}")
+        if out is None:
+            out = torch.empty((n_jobs, 4), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.device != self.device or out.numel() != n_jobs * 4:
+            raise _lib.SalveHipError(f"pair_overlap: out must be contiguous int32 [{n_jobs}, 4] on {self.device}, got {out.dtype} {tuple(out.shape)} on {out.device}")
+        n_a, h, w = (int(v) for v in bev_a.shape)
+        p = lambda t: ctypes.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            st = self.lib.salve_bev_pair_overlap(p(bev_a), n_a, p(bev_b), int(bev_b.shape[0]), h, w, p(jobs), n_jobs, p(out), status.ptr(self.device), self._stream())
+        _lib.check(st, "salve_bev_pair_overlap")
+        return out
+
     def train_tiles(self, bev_a: torch.Tensor, bev_b: torch.Tensor, jobs_a: torch.Tensor, jobs_b: torch.Tensor, per_sample: int,
                     aug: torch.Tensor, batch: int, out: torch.Tensor, jitter: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The train transform of a whole batch in one launch (include/salve_hip.h: salve_bev_train_tiles): `out` is the trainable
