@@ -1,6 +1,8 @@
 #!/bin/bash
 # Development (CPU box): registers, scratch and LDS of every kernel of one translation unit, from `hipcc -S`.
 # usage: tools/measure/isa_regs.sh resnet.hip [name filter]        (writes /tmp/isa/<file>.s)
+# A kernel that lives in a header is listed under the .hip that includes it: bottleneck_kernel (bottleneck.h), conv8_kernel (conv8.h),
+# stem_pool_kernel (stem_pool.h) and expand_chain_kernel (expand_chain.h) under resnet.hip, e.g.  isa_regs.sh resnet.hip bottleneck
 set -e
 src="$(cd "$(dirname "$0")/../.." && pwd)/salve_amd/csrc/$1"
 mkdir -p /tmp/isa

@@ -1,5 +1,5 @@
 // conv_wide.h -- ALTERNATIVE implicit-GEMM convolution kernels of the verifier (included by resnet.hip inside its
-// namespace).  Selected with SALVE_CONV_WIDE=d|e|f; the default network does not use them (resnet.hip: choose_wide).
+// namespace).  Selected with SALVE_CONV_WIDE=d|e|f; the default network does not use them (resnet_plan.h: choose_wide).
 //
 // Same GEMM as conv_igemm_kernel (out[m, n] = sum_k A[m, k] W[n, k], m = (b, oy, ox), k = (kh, kw, ci), NHWC fp16, fp32
 // accumulation, v_mfma_f32_16x16x32_f16 with swapped operands, same k order: bit-identical results) on a 256 x BN block
