@@ -644,6 +644,55 @@ int salve_bn_bf16_backward(const salve_bn_desc_t* d, const uint16_t* dy, const u
                            size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Synchronised training BatchNorm: the passes of the entries above as entries of their own (additive within ABI 7): opt-in.
+ * `world` data-parallel ranks each hold some rows of one batch; between the passes every rank gathers the others' per-channel
+ * results (one all-gather forward, one backward: salve_amd/models/trainable.py: SyncBatchNormHipFunction, --sync-bn), so that
+ * every BatchNorm normalises over the rows of ALL ranks.  The kernels are the fused entries' own; no entry adds a pass over x.
+ *   Descriptor: salve_bn_desc_t as above, except that rows is THIS RANK's rows and may be 0 or 1 (a rank that got little or none
+ *            of a short batch: nothing is launched on the activations, outputs per channel are still written).  SALVE_BN_RELU and
+ *            SALVE_BN_ADD as above; SALVE_BN_EVAL: SALVE_ERR_UNSUPPORTED from every entry here (the eval form reads no batch
+ *            statistics).  The other refusals are the fused entries'.  world: 1 .. SALVE_BN_MAX_WORLD.
+ *   salve_bn_*_stats:  partial float [2][C] = the mean and M2 = sum (x - mean)^2 of this rank's rows: the fused forward's
+ *            statistics pass, the same Welford + Chan arithmetic in the same order.  rows == 0 writes zeros.
+ *   salve_bn_combine:  partials float [world][2][C], the ranks' `partial` in rank order; rows: HOST int64 [world], the ranks' row
+ *            counts (read before the call returns; their sum must be at least 2).  The partials are combined with Chan's formula
+ *            in rank order, ranks without rows skipped; mean[C], invstd[C] = 1 / sqrt(M2 / R + eps) over the R rows of all ranks,
+ *            running = (1 - momentum) * running + momentum * statistic with the unbiased variance M2 / (R - 1) (running_mean /
+ *            running_var may be NULL).  d->rows is not read.  With world == 1 mean, invstd and the running statistics are the
+ *            fused forward's save_mean, save_invstd and update, bit for bit.  Every rank that combines the same partials gets the
+ *            same bits.
+ *   salve_bn_*_apply:  y from x, residual, gamma, beta and the combined mean and invstd: the fused forward's apply pass.
+ *   salve_bn_*_backward_reduce:  sums float [2][C] = sum g, sum g * xhat over this rank's rows (g masked by y > 0 with
+ *            SALVE_BN_RELU; xhat from the combined mean and invstd): the fused backward's first pass.  sums[0] is this rank's
+ *            share of dbeta, sums[1] of dgamma.  rows == 0 writes zeros.
+ *   salve_bn_*_backward_apply:  sums float [world][2][C], the ranks' sums in rank order, which the kernel adds in that order
+ *            itself; total_rows = R.  dx = gamma * invstd * (g - sum g / R - xhat * sum (g * xhat) / R), dres = g with
+ *            SALVE_BN_ADD.  With world == 1 dx and dres are the fused backward's, bit for bit.
+ *   Workspace: salve_bn_workspace_bytes(d, SALVE_BN_STATS) for salve_bn_*_stats, (d, SALVE_BN_BWD_REDUCE) for
+ *            salve_bn_*_backward_reduce; the other entries take none.  No atomics; element offsets are 64-bit.
+ * ------------------------------------------------------------------------------------------------ */
+#define SALVE_BN_MAX_WORLD 64
+#define SALVE_BN_STATS 16
+#define SALVE_BN_BWD_REDUCE 17
+int salve_bn_f32_stats(const salve_bn_desc_t* d, const float* x, float* partial, void* ws, size_t ws_bytes, void* stream);
+int salve_bn_bf16_stats(const salve_bn_desc_t* d, const uint16_t* x, float* partial, void* ws, size_t ws_bytes, void* stream);
+int salve_bn_combine(const salve_bn_desc_t* d, const float* partials, const int64_t* rows, int32_t world, float* running_mean, float* running_var,
+                     float* mean, float* invstd, void* stream);
+int salve_bn_f32_apply(const salve_bn_desc_t* d, const float* x, const float* residual, const float* gamma, const float* beta, const float* mean,
+                       const float* invstd, float* y, void* stream);
+int salve_bn_bf16_apply(const salve_bn_desc_t* d, const uint16_t* x, const uint16_t* residual, const float* gamma, const float* beta,
+                        const float* mean, const float* invstd, uint16_t* y, void* stream);
+int salve_bn_f32_backward_reduce(const salve_bn_desc_t* d, const float* dy, const float* x, const float* y, const float* mean, const float* invstd,
+                                 float* sums, void* ws, size_t ws_bytes, void* stream);
+int salve_bn_bf16_backward_reduce(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* mean,
+                                  const float* invstd, float* sums, void* ws, size_t ws_bytes, void* stream);
+int salve_bn_f32_backward_apply(const salve_bn_desc_t* d, const float* dy, const float* x, const float* y, const float* gamma, const float* mean,
+                                const float* invstd, const float* sums, int32_t world, int64_t total_rows, float* dx, float* dres, void* stream);
+int salve_bn_bf16_backward_apply(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* gamma,
+                                 const float* mean, const float* invstd, const float* sums, int32_t world, int64_t total_rows, uint16_t* dx,
+                                 uint16_t* dres, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Adam over every parameter tensor in one launch, with the bf16 copy of a weight written alongside (additive within ABI 7):
  * opt-in.  The reference trains with torch.optim.Adam(lr, weight_decay) (salve/train_utils.py:173-180) under a poly schedule
  * that changes lr every iteration (scripts/train.py).  This entry performs one step of that optimiser (amsgrad=False,

@@ -67,6 +67,15 @@ EXPORTED_SYMBOLS = (
     "salve_bn_f32_backward",
     "salve_bn_bf16_forward",
     "salve_bn_bf16_backward",
+    "salve_bn_f32_stats",
+    "salve_bn_bf16_stats",
+    "salve_bn_combine",
+    "salve_bn_f32_apply",
+    "salve_bn_bf16_apply",
+    "salve_bn_f32_backward_reduce",
+    "salve_bn_bf16_backward_reduce",
+    "salve_bn_f32_backward_apply",
+    "salve_bn_bf16_backward_apply",
     "salve_bev_train_tiles",
     "salve_bev_pano_index_update",
     "salve_layout_pose",
@@ -162,6 +171,8 @@ class ConvDesc(ctypes.Structure):
 # salve_bn_* flags and passes (include/salve_hip.h: SALVE_BN_*)
 BN_RELU, BN_ADD, BN_EVAL = 1, 2, 4
 BN_FWD, BN_BWD = 0, 1
+BN_STATS, BN_BWD_REDUCE = 16, 17   # the split (synchronised) entries' workspace passes
+BN_MAX_WORLD = 64
 
 
 class BnDesc(ctypes.Structure):
@@ -301,6 +312,16 @@ def load() -> ctypes.CDLL:
     for name in ("salve_bn_f32_backward", "salve_bn_bf16_backward"):   # d, dy, x, y, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta
         getattr(lib, name).argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 10 + [vp, sz, vp]
         getattr(lib, name).restype = ctypes.c_int
+    for t in ("f32", "bf16"):   # the split entries (SyncBatchNormHipFunction)
+        getattr(lib, f"salve_bn_{t}_stats").argtypes = [ctypes.POINTER(BnDesc), vp, vp, vp, sz, vp]   # d, x, partial
+        getattr(lib, f"salve_bn_{t}_apply").argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 7 + [vp]   # d, x, residual, gamma, beta, mean, invstd, y
+        getattr(lib, f"salve_bn_{t}_backward_reduce").argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 6 + [vp, sz, vp]   # d, dy, x, y, mean, invstd, sums
+        # d, dy, x, y, gamma, mean, invstd, sums, world, total_rows, dx, dres
+        getattr(lib, f"salve_bn_{t}_backward_apply").argtypes = [ctypes.POINTER(BnDesc)] + [vp] * 7 + [i32, ctypes.c_int64, vp, vp, vp]
+        for e in ("stats", "apply", "backward_reduce", "backward_apply"):
+            getattr(lib, f"salve_bn_{t}_{e}").restype = ctypes.c_int
+    lib.salve_bn_combine.argtypes = [ctypes.POINTER(BnDesc), vp, vp, i32, vp, vp, vp, vp, vp]   # d, partials, HOST rows, world, running_mean, running_var, mean, invstd
+    lib.salve_bn_combine.restype = ctypes.c_int
     lib.salve_adam_step.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     lib.salve_adam_step.restype = ctypes.c_int
     for name in ("salve_flat_pack", "salve_flat_unpack"):   # table, n_segments, chunk_map, n_chunks, HOST table, HOST chunk_map, flat, flat_elems, scale, stream

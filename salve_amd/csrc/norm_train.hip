@@ -19,6 +19,15 @@
 //                    bn_bwd_finalise_kernel: one wave per channel, the same fixed order: dbeta, dgamma.
 //                    bn_bwd_dx_kernel: dx = gamma * invstd * (g - dbeta / rows - xhat * dgamma / rows); dres = g with a residual.
 //
+//   synchronised (data-parallel ranks; salve_amd/models/trainable.py: SyncBatchNormHipFunction) -- the same kernels behind split
+//   entries, with room between the phases for the other ranks' results, and no further pass over x:
+//                    salve_bn_*_stats            bn_stats_kernel + bn_stats_finalise_kernel writing the rows' (mean, M2) instead
+//                                                of finishing them
+//                    salve_bn_combine            bn_combine_kernel: the ranks' (mean, M2) by Chan in rank order, then the same finish
+//                    salve_bn_*_apply            bn_apply_kernel
+//                    salve_bn_*_backward_reduce  bn_bwd_reduce_kernel + bn_bwd_finalise_kernel
+//                    salve_bn_*_backward_apply   bn_bwd_dx_kernel, which adds the ranks' sums in rank order itself
+//
 // No atomics anywhere; the split of rows over workgroups is a function of (rows, C, dtype) only, so the same inputs give
 // bit-identical results.  Element offsets are 64-bit.
 #include <hip/hip_runtime.h>
@@ -191,11 +200,23 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_kernel(const T* __restric
     }
 }
 
-// one wave per channel: lane l takes the partials l, l + 64, ... in order, then a fixed shuffle tree over the lanes
+// channel c's (mean, M2) over `rows` rows -> save_mean, save_invstd and the momentum update of the running statistics
+__device__ __forceinline__ void bn_finish(int c, float m, float q, long long rows, float eps, float momentum, float* __restrict__ save_mean,
+                                          float* __restrict__ save_invstd, float* __restrict__ running_mean, float* __restrict__ running_var) {
+    const float var = q / (float)rows;
+    save_mean[c] = m;
+    save_invstd[c] = 1.f / sqrtf(var + eps);
+    if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
+    if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (q / (float)(rows - 1));
+}
+
+// one wave per channel: lane l takes the partials l, l + 64, ... in order, then a fixed shuffle tree over the lanes.
+// local: float [2][C], or NULL.  Given, the channel's (mean, M2) go there and nothing is finished (salve_bn_*_stats: the ranks'
+// statistics are combined first, bn_combine_kernel).
 __global__ __launch_bounds__(BN_THREADS) void bn_stats_finalise_kernel(const float* __restrict__ partial, int S, int C, int rows, float eps,
                                                                        float momentum, float* __restrict__ save_mean,
                                                                        float* __restrict__ save_invstd, float* __restrict__ running_mean,
-                                                                       float* __restrict__ running_var) {
+                                                                       float* __restrict__ running_var, float* __restrict__ local) {
     const int lane = threadIdx.x & 63;
     const int c = blockIdx.x * (BN_THREADS / 64) + (threadIdx.x >> 6);
     if (c >= C) return;   // whole waves leave together
@@ -210,12 +231,34 @@ __global__ __launch_bounds__(BN_THREADS) void bn_stats_finalise_kernel(const flo
         chan(n, m, q, nb, mb, qb);
     }
     if (lane == 0) {
-        const float var = q / (float)rows;
-        save_mean[c] = m;
-        save_invstd[c] = 1.f / sqrtf(var + eps);
-        if (running_mean) running_mean[c] = (1.f - momentum) * running_mean[c] + momentum * m;
-        if (running_var) running_var[c] = (1.f - momentum) * running_var[c] + momentum * (q / (float)(rows - 1));
+        if (local) {
+            local[c] = m;
+            local[C + c] = q;
+        } else {
+            bn_finish(c, m, q, rows, eps, momentum, save_mean, save_invstd, running_mean, running_var);
+        }
     }
+}
+
+// The ranks' statistics, float [world][2][C] = (mean, M2) of rank r's counts.n[r] rows, combined with Chan's formula in rank order
+// (a rank without rows is skipped), then finished over the `rows` rows of all ranks.  One thread per channel; with one rank the
+// result is the fused forward's.
+struct BnCounts { float n[SALVE_BN_MAX_WORLD]; };
+
+__global__ __launch_bounds__(BN_THREADS) void bn_combine_kernel(const float* __restrict__ partials, BnCounts counts, int world, int C, long long rows,
+                                                                float eps, float momentum, float* __restrict__ mean, float* __restrict__ invstd,
+                                                                float* __restrict__ running_mean, float* __restrict__ running_var) {
+    const int c = blockIdx.x * BN_THREADS + threadIdx.x;
+    if (c >= C) return;
+    float n = 0.f, m = 0.f, q = 0.f;
+    for (int r = 0; r < world; r++) {
+        const float* p = partials + (size_t)r * 2 * C + c;
+        const float nb = counts.n[r];
+        if (nb == 0.f) continue;
+        if (n == 0.f) { n = nb; m = p[0]; q = p[C]; }   // the first rank with rows: its statistics as they are
+        else chan(n, m, q, nb, p[0], p[C]);
+    }
+    bn_finish(c, m, q, rows, eps, momentum, mean, invstd, running_mean, running_var);
 }
 
 // ---- forward: apply --------------------------------------------------------------------------------------------------------
@@ -374,12 +417,15 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_finalise_kernel(const float
 }
 
 // ---- backward: dx ----------------------------------------------------------------------------------------------------------
+// dbeta, dgamma: `world` ranks' sums of g and of g * xhat, rank r's at [r * rank_stride + c], added here in rank order (the fused
+// backward: world 1, its own dbeta and dgamma); total_rows: the rows of all ranks, `rows` this launch's.
 template <typename T, bool RELU, bool ADD>
 __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T* __restrict__ dy, const T* __restrict__ x, const T* __restrict__ y,
                                                                const float* __restrict__ mean_p, const float* __restrict__ invstd_p,
                                                                const float* __restrict__ gamma, const float* __restrict__ dgamma,
-                                                               const float* __restrict__ dbeta, T* __restrict__ dx, T* __restrict__ dres, int rows,
-                                                               int C, int G, int gx, int rpc) {
+                                                               const float* __restrict__ dbeta, int world, long long rank_stride,
+                                                               long long total_rows, T* __restrict__ dx, T* __restrict__ dres, int rows, int C,
+                                                               int G, int gx, int rpc) {
     constexpr int N = Group<T>::N;
     const int ry = BN_THREADS / gx;
     const int tx = threadIdx.x & (gx - 1), ty = threadIdx.x / gx;
@@ -387,7 +433,7 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T* __restri
     if (g >= G) return;
     const long long r0 = (long long)blockIdx.x * rpc;
     const long long r1 = r0 + rpc < rows ? r0 + rpc : rows;
-    const float inv_rows = 1.f / (float)rows;
+    const float inv_rows = 1.f / (float)total_rows;
     float mean[N], invstd[N], a[N], k1[N], k2[N];
 #pragma unroll
     for (int i = 0; i < N; i++) {
@@ -395,8 +441,13 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T* __restri
         mean[i] = mean_p[c];
         invstd[i] = invstd_p[c];
         a[i] = gamma[c] * invstd[i];
-        k1[i] = dbeta[c] * inv_rows;
-        k2[i] = dgamma[c] * inv_rows;
+        float sb = dbeta[c], sg = dgamma[c];
+        for (int r = 1; r < world; r++) {
+            sb += dbeta[(size_t)r * rank_stride + c];
+            sg += dgamma[(size_t)r * rank_stride + c];
+        }
+        k1[i] = sb * inv_rows;
+        k2[i] = sg * inv_rows;
     }
     long long r = r0 + ty;
     for (; r + ry < r1; r += 2ll * ry) {   // two rows in flight (up to six 16-byte loads)
@@ -439,12 +490,21 @@ __global__ __launch_bounds__(BN_THREADS) void bn_bwd_dx_kernel(const T* __restri
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
-int check_bn_desc(const salve_bn_desc_t* d, const char* who) {
+// min_rows: 2 for the fused entries; 0 for the split ones, whose rows are one rank's (the ranks' total is checked where it is known)
+int check_bn_desc(const salve_bn_desc_t* d, const char* who, int min_rows = 2) {
     if (!d) { salve_fail(who); return SALVE_ERR_BAD_ARG; }
     if (d->C < 8 || d->C > 4096 || d->C % 8 != 0) { salve_fail("bn: C must be a multiple of 8 from 8 to 4096"); return SALVE_ERR_BAD_ARG; }
-    if (d->rows < 2) { salve_fail("bn: rows must be at least 2"); return SALVE_ERR_BAD_ARG; }
+    if (d->rows < min_rows) { salve_fail(min_rows == 2 ? "bn: rows must be at least 2" : "bn: a rank's rows must not be negative"); return SALVE_ERR_BAD_ARG; }
     if (d->flags & ~BN_ALL_FLAGS) { salve_fail("bn: unknown flag bit"); return SALVE_ERR_BAD_ARG; }
     if (!(d->eps >= 0.f) || !(d->momentum >= 0.f && d->momentum <= 1.f)) { salve_fail("bn: eps must be >= 0 and momentum in [0, 1]"); return SALVE_ERR_BAD_ARG; }
+    return SALVE_OK;
+}
+
+// the split entries: train mode only (the eval form reads no batch statistics: salve_bn_*_forward alone serves it)
+int check_split_desc(const salve_bn_desc_t* d, const char* who) {
+    const int st = check_bn_desc(d, who, 0);
+    if (st != SALVE_OK) return st;
+    if (d->flags & SALVE_BN_EVAL) { salve_fail("bn: the split entries synchronise batch statistics; the eval form has none"); return SALVE_ERR_UNSUPPORTED; }
     return SALVE_OK;
 }
 
@@ -454,9 +514,11 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 // The workspace serves both dtypes: sized for the fp32 split, which is never smaller than the bf16 one.
 size_t bn_ws(const salve_bn_desc_t* d, int pass) {
     if (pass == SALVE_BN_FWD && (d->flags & SALVE_BN_EVAL)) return 256;
+    if (d->rows == 0) return 256;   // (a split pass of a rank without rows launches nothing)
+    const bool fwd = pass == SALVE_BN_FWD || pass == SALVE_BN_STATS;
     const Geom g4 = geometry(d->rows, d->C, 4), g8 = geometry(d->rows, d->C, 8);
     const size_t S = (size_t)(g4.S > g8.S ? g4.S : g8.S);
-    return align256(S * (pass == SALVE_BN_FWD ? 3 : 2) * d->C * sizeof(float)) + 256;
+    return align256(S * (fwd ? 3 : 2) * d->C * sizeof(float)) + 256;
 }
 
 template <typename T, bool RELU, bool ADD>
@@ -467,11 +529,35 @@ void launch_apply(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const 
 }
 
 template <typename T>
+void dispatch_apply(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const T* x, const T* residual, T* y, const float* mean, const float* scale,
+                    const float* gamma, const float* beta, int scale_is_var) {
+    const bool relu = d->flags & SALVE_BN_RELU, add = d->flags & SALVE_BN_ADD;
+    if (relu && add) launch_apply<T, true, true>(g, s, d, x, residual, y, mean, scale, gamma, beta, scale_is_var);
+    else if (relu) launch_apply<T, true, false>(g, s, d, x, residual, y, mean, scale, gamma, beta, scale_is_var);
+    else if (add) launch_apply<T, false, true>(g, s, d, x, residual, y, mean, scale, gamma, beta, scale_is_var);
+    else launch_apply<T, false, false>(g, s, d, x, residual, y, mean, scale, gamma, beta, scale_is_var);
+}
+
+// The statistics pass and its finalise.  local NULL: save_mean, save_invstd and the running update over d->rows (the fused forward);
+// local given: the rows' (mean, M2) go there and nothing else is written (salve_bn_*_stats).
+template <typename T>
+int launch_stats(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const T* x, void* ws, float* save_mean, float* save_invstd,
+                 float* running_mean, float* running_var, float* local) {
+    float* partial = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    hipLaunchKernelGGL(bn_stats_kernel<T>, dim3((unsigned)g.S, (unsigned)g.ctiles), dim3(BN_THREADS), 0, s, x, partial, d->rows, d->C, g.G, g.gx, g.rpc);
+    SALVE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bn_stats_finalise_kernel, dim3((unsigned)((d->C + 3) / 4)), dim3(BN_THREADS), 0, s, partial, g.S, d->C, d->rows, d->eps,
+                       d->momentum, save_mean, save_invstd, running_mean, running_var, local);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
+template <typename T>
 int bn_forward(const char* who, const salve_bn_desc_t* d, const T* x, const T* residual, const float* gamma, const float* beta, float* running_mean,
                float* running_var, T* y, float* save_mean, float* save_invstd, void* ws, size_t ws_bytes, void* stream) {
     int st = check_bn_desc(d, who);
     if (st != SALVE_OK) return st;
-    const bool relu = d->flags & SALVE_BN_RELU, add = d->flags & SALVE_BN_ADD, eval = d->flags & SALVE_BN_EVAL;
+    const bool add = d->flags & SALVE_BN_ADD, eval = d->flags & SALVE_BN_EVAL;
     if (!x || !gamma || !beta || !y || !ws || (add && !residual) || (eval ? (!running_mean || !running_var) : (!save_mean || !save_invstd)) ||
         !aligned16(x) || !aligned16(y) || !aligned16(residual)) {
         salve_fail("salve_bn_*_forward: null or not 16-byte aligned pointer");
@@ -482,29 +568,80 @@ int bn_forward(const char* who, const salve_bn_desc_t* d, const T* x, const T* r
     hipStream_t s = (hipStream_t)stream;
     const float *mean = running_mean, *scale = running_var;
     if (!eval) {
-        float* partial = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-        hipLaunchKernelGGL(bn_stats_kernel<T>, dim3((unsigned)g.S, (unsigned)g.ctiles), dim3(BN_THREADS), 0, s, x, partial, d->rows, d->C, g.G, g.gx, g.rpc);
-        SALVE_HIP_CHECK(hipGetLastError());
-        hipLaunchKernelGGL(bn_stats_finalise_kernel, dim3((unsigned)((d->C + 3) / 4)), dim3(BN_THREADS), 0, s, partial, g.S, d->C, d->rows, d->eps,
-                           d->momentum, save_mean, save_invstd, running_mean, running_var);
-        SALVE_HIP_CHECK(hipGetLastError());
+        st = launch_stats<T>(g, s, d, x, ws, save_mean, save_invstd, running_mean, running_var, nullptr);
+        if (st != SALVE_OK) return st;
         mean = save_mean;
         scale = save_invstd;
     }
-    const int var = eval ? 1 : 0;
-    if (relu && add) launch_apply<T, true, true>(g, s, d, x, residual, y, mean, scale, gamma, beta, var);
-    else if (relu) launch_apply<T, true, false>(g, s, d, x, residual, y, mean, scale, gamma, beta, var);
-    else if (add) launch_apply<T, false, true>(g, s, d, x, residual, y, mean, scale, gamma, beta, var);
-    else launch_apply<T, false, false>(g, s, d, x, residual, y, mean, scale, gamma, beta, var);
+    dispatch_apply<T>(g, s, d, x, residual, y, mean, scale, gamma, beta, eval ? 1 : 0);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
+// ---- the split forward: statistics | combine (salve_bn_combine) | apply ----------------------------------------------------------
+template <typename T>
+int bn_stats(const char* who, const salve_bn_desc_t* d, const T* x, float* partial, void* ws, size_t ws_bytes, void* stream) {
+    const int st = check_split_desc(d, who);
+    if (st != SALVE_OK) return st;
+    if (!partial || (d->rows > 0 && (!x || !ws || !aligned16(x)))) {
+        salve_fail("salve_bn_*_stats: null or not 16-byte aligned pointer");
+        return SALVE_ERR_BAD_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (d->rows == 0) {   // a rank that got none of a short batch: zeros, which salve_bn_combine skips
+        SALVE_HIP_CHECK(hipMemsetAsync(partial, 0, (size_t)2 * d->C * sizeof(float), s));
+        return SALVE_OK;
+    }
+    if (ws_bytes < bn_ws(d, SALVE_BN_STATS)) { salve_fail("salve_bn_*_stats: workspace too small"); return SALVE_ERR_WORKSPACE; }
+    return launch_stats<T>(geometry(d->rows, d->C, Group<T>::N), s, d, x, ws, nullptr, nullptr, nullptr, nullptr, partial);
+}
+
+template <typename T>
+int bn_apply(const char* who, const salve_bn_desc_t* d, const T* x, const T* residual, const float* gamma, const float* beta, const float* mean,
+             const float* invstd, T* y, void* stream) {
+    const int st = check_split_desc(d, who);
+    if (st != SALVE_OK) return st;
+    const bool add = d->flags & SALVE_BN_ADD;
+    if (!gamma || !beta || !mean || !invstd || (d->rows > 0 && (!x || !y || (add && !residual))) || !aligned16(x) || !aligned16(y) ||
+        !aligned16(residual)) {
+        salve_fail("salve_bn_*_apply: null or not 16-byte aligned pointer");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (d->rows == 0) return SALVE_OK;
+    dispatch_apply<T>(geometry(d->rows, d->C, Group<T>::N), (hipStream_t)stream, d, x, residual, y, mean, invstd, gamma, beta, 0);
     SALVE_HIP_CHECK(hipGetLastError());
     return SALVE_OK;
 }
 
 template <typename T, bool RELU, bool ADD>
 void launch_dx(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
-               const float* gamma, const float* dgamma, const float* dbeta, T* dx, T* dres) {
+               const float* gamma, const float* dgamma, const float* dbeta, int world, long long rank_stride, long long total_rows, T* dx, T* dres) {
     hipLaunchKernelGGL((bn_bwd_dx_kernel<T, RELU, ADD>), dim3((unsigned)g.apply_chunks, (unsigned)g.ctiles), dim3(BN_THREADS), 0, s, dy, x, y, mean,
-                       invstd, gamma, dgamma, dbeta, dx, dres, d->rows, d->C, g.G, g.gx, g.apply_rpc);
+                       invstd, gamma, dgamma, dbeta, world, rank_stride, total_rows, dx, dres, d->rows, d->C, g.G, g.gx, g.apply_rpc);
+}
+
+template <typename T>
+void dispatch_dx(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
+                 const float* gamma, const float* dgamma, const float* dbeta, int world, long long rank_stride, long long total_rows, T* dx, T* dres) {
+    const bool relu = d->flags & SALVE_BN_RELU, add = d->flags & SALVE_BN_ADD;
+    if (relu && add) launch_dx<T, true, true>(g, s, d, dy, x, y, mean, invstd, gamma, dgamma, dbeta, world, rank_stride, total_rows, dx, dres);
+    else if (relu) launch_dx<T, true, false>(g, s, d, dy, x, y, mean, invstd, gamma, dgamma, dbeta, world, rank_stride, total_rows, dx, dres);
+    else if (add) launch_dx<T, false, true>(g, s, d, dy, x, y, mean, invstd, gamma, dgamma, dbeta, world, rank_stride, total_rows, dx, dres);
+    else launch_dx<T, false, false>(g, s, d, dy, x, y, mean, invstd, gamma, dgamma, dbeta, world, rank_stride, total_rows, dx, dres);
+}
+
+// The reduce pass and its finalise: dbeta = sum g, dgamma = sum g * xhat over d->rows.
+template <typename T>
+int launch_reduce(const Geom& g, hipStream_t s, const salve_bn_desc_t* d, const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
+                  void* ws, float* dgamma, float* dbeta) {
+    float* partial = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+    const dim3 grid((unsigned)g.S, (unsigned)g.ctiles);
+    if (d->flags & SALVE_BN_RELU) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), grid, dim3(BN_THREADS), 0, s, dy, x, y, mean, invstd, partial, d->rows, d->C, g.G, g.gx, g.rpc);
+    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false>), grid, dim3(BN_THREADS), 0, s, dy, x, y, mean, invstd, partial, d->rows, d->C, g.G, g.gx, g.rpc);
+    SALVE_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bn_bwd_finalise_kernel, dim3((unsigned)((d->C + 3) / 4)), dim3(BN_THREADS), 0, s, partial, g.S, d->C, dgamma, dbeta);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
 }
 
 template <typename T>
@@ -522,17 +659,49 @@ int bn_backward(const char* who, const salve_bn_desc_t* d, const T* dy, const T*
     if (ws_bytes < bn_ws(d, SALVE_BN_BWD)) { salve_fail("salve_bn_*_backward: workspace too small"); return SALVE_ERR_WORKSPACE; }
     const Geom g = geometry(d->rows, d->C, Group<T>::N);
     hipStream_t s = (hipStream_t)stream;
-    float* partial = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
-    const dim3 grid((unsigned)g.S, (unsigned)g.ctiles);
-    if (relu) hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, true>), grid, dim3(BN_THREADS), 0, s, dy, x, y, save_mean, save_invstd, partial, d->rows, d->C, g.G, g.gx, g.rpc);
-    else hipLaunchKernelGGL((bn_bwd_reduce_kernel<T, false>), grid, dim3(BN_THREADS), 0, s, dy, x, y, save_mean, save_invstd, partial, d->rows, d->C, g.G, g.gx, g.rpc);
+    st = launch_reduce<T>(g, s, d, dy, x, y, save_mean, save_invstd, ws, dgamma, dbeta);
+    if (st != SALVE_OK) return st;
+    dispatch_dx<T>(g, s, d, dy, x, y, save_mean, save_invstd, gamma, dgamma, dbeta, 1, 0, d->rows, dx, dres);
     SALVE_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(bn_bwd_finalise_kernel, dim3((unsigned)((d->C + 3) / 4)), dim3(BN_THREADS), 0, s, partial, g.S, d->C, dgamma, dbeta);
-    SALVE_HIP_CHECK(hipGetLastError());
-    if (relu && add) launch_dx<T, true, true>(g, s, d, dy, x, y, save_mean, save_invstd, gamma, dgamma, dbeta, dx, dres);
-    else if (relu) launch_dx<T, true, false>(g, s, d, dy, x, y, save_mean, save_invstd, gamma, dgamma, dbeta, dx, dres);
-    else if (add) launch_dx<T, false, true>(g, s, d, dy, x, y, save_mean, save_invstd, gamma, dgamma, dbeta, dx, dres);
-    else launch_dx<T, false, false>(g, s, d, dy, x, y, save_mean, save_invstd, gamma, dgamma, dbeta, dx, dres);
+    return SALVE_OK;
+}
+
+// ---- the split backward: reduce | (the ranks' sums gathered) | apply ---------------------------------------------------------------
+template <typename T>
+int bn_backward_reduce(const char* who, const salve_bn_desc_t* d, const T* dy, const T* x, const T* y, const float* mean, const float* invstd,
+                       float* sums, void* ws, size_t ws_bytes, void* stream) {
+    const int st = check_split_desc(d, who);
+    if (st != SALVE_OK) return st;
+    const bool relu = d->flags & SALVE_BN_RELU;
+    if (!sums || !mean || !invstd || (d->rows > 0 && (!dy || !x || !ws || (relu && !y))) || !aligned16(dy) || !aligned16(x) || !aligned16(y)) {
+        salve_fail("salve_bn_*_backward_reduce: null or not 16-byte aligned pointer");
+        return SALVE_ERR_BAD_ARG;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (d->rows == 0) {
+        SALVE_HIP_CHECK(hipMemsetAsync(sums, 0, (size_t)2 * d->C * sizeof(float), s));
+        return SALVE_OK;
+    }
+    if (ws_bytes < bn_ws(d, SALVE_BN_BWD_REDUCE)) { salve_fail("salve_bn_*_backward_reduce: workspace too small"); return SALVE_ERR_WORKSPACE; }
+    return launch_reduce<T>(geometry(d->rows, d->C, Group<T>::N), s, d, dy, x, y, mean, invstd, ws, sums + d->C, sums);
+}
+
+template <typename T>
+int bn_backward_apply(const char* who, const salve_bn_desc_t* d, const T* dy, const T* x, const T* y, const float* gamma, const float* mean,
+                      const float* invstd, const float* sums, int world, long long total_rows, T* dx, T* dres, void* stream) {
+    const int st = check_split_desc(d, who);
+    if (st != SALVE_OK) return st;
+    if (world < 1 || world > SALVE_BN_MAX_WORLD) { salve_fail("bn: world must be 1 .. SALVE_BN_MAX_WORLD"); return SALVE_ERR_BAD_ARG; }
+    if (total_rows < 2 || total_rows < d->rows) { salve_fail("bn: the ranks' rows must be at least 2 together, and no fewer than this rank's"); return SALVE_ERR_BAD_ARG; }
+    const bool relu = d->flags & SALVE_BN_RELU, add = d->flags & SALVE_BN_ADD;
+    if (!gamma || !mean || !invstd || !sums || (d->rows > 0 && (!dy || !x || !dx || (relu && !y) || (add && !dres))) || !aligned16(dy) ||
+        !aligned16(x) || !aligned16(y) || !aligned16(dx) || !aligned16(dres)) {
+        salve_fail("salve_bn_*_backward_apply: null or not 16-byte aligned pointer");
+        return SALVE_ERR_BAD_ARG;
+    }
+    if (d->rows == 0) return SALVE_OK;
+    dispatch_dx<T>(geometry(d->rows, d->C, Group<T>::N), (hipStream_t)stream, d, dy, x, y, mean, invstd, gamma, sums + d->C, sums, world,
+                   2ll * d->C, total_rows, dx, dres);
     SALVE_HIP_CHECK(hipGetLastError());
     return SALVE_OK;
 }
@@ -542,8 +711,10 @@ int bn_backward(const char* who, const salve_bn_desc_t* d, const T* dy, const T*
 extern "C" {
 
 size_t salve_bn_workspace_bytes(const salve_bn_desc_t* d, int32_t pass) {
+    if (pass == SALVE_BN_STATS || pass == SALVE_BN_BWD_REDUCE)   // the split passes: the rows are one rank's, which may have none
+        return check_split_desc(d, "salve_bn_workspace_bytes: null descriptor") == SALVE_OK ? bn_ws(d, pass) : 0;
     if (check_bn_desc(d, "salve_bn_workspace_bytes: null descriptor") != SALVE_OK) return 0;
-    if (pass != SALVE_BN_FWD && pass != SALVE_BN_BWD) { salve_fail("salve_bn_workspace_bytes: pass must be SALVE_BN_FWD or SALVE_BN_BWD"); return 0; }
+    if (pass != SALVE_BN_FWD && pass != SALVE_BN_BWD) { salve_fail("salve_bn_workspace_bytes: pass must be one of SALVE_BN_FWD, _BWD, _STATS, _BWD_REDUCE"); return 0; }
     if (pass == SALVE_BN_BWD && (d->flags & SALVE_BN_EVAL)) { salve_fail("salve_bn_workspace_bytes: the eval form has no backward pass"); return 0; }
     return bn_ws(d, pass);
 }
@@ -573,6 +744,67 @@ int salve_bn_bf16_backward(const salve_bn_desc_t* d, const uint16_t* dy, const u
                            size_t ws_bytes, void* stream) {
     return bn_backward<uint16_t>("salve_bn_bf16_backward: null descriptor", d, dy, x, y, gamma, save_mean, save_invstd, dx, dres, dgamma, dbeta, ws,
                                  ws_bytes, stream);
+}
+
+int salve_bn_f32_stats(const salve_bn_desc_t* d, const float* x, float* partial, void* ws, size_t ws_bytes, void* stream) {
+    return bn_stats<float>("salve_bn_f32_stats: null descriptor", d, x, partial, ws, ws_bytes, stream);
+}
+
+int salve_bn_bf16_stats(const salve_bn_desc_t* d, const uint16_t* x, float* partial, void* ws, size_t ws_bytes, void* stream) {
+    return bn_stats<uint16_t>("salve_bn_bf16_stats: null descriptor", d, x, partial, ws, ws_bytes, stream);
+}
+
+int salve_bn_combine(const salve_bn_desc_t* d, const float* partials, const int64_t* rows, int32_t world, float* running_mean, float* running_var,
+                     float* mean, float* invstd, void* stream) {
+    const int st = check_split_desc(d, "salve_bn_combine: null descriptor");
+    if (st != SALVE_OK) return st;
+    if (world < 1 || world > SALVE_BN_MAX_WORLD) { salve_fail("bn: world must be 1 .. SALVE_BN_MAX_WORLD"); return SALVE_ERR_BAD_ARG; }
+    if (!partials || !rows || !mean || !invstd) { salve_fail("salve_bn_combine: null pointer"); return SALVE_ERR_BAD_ARG; }
+    BnCounts counts = {};
+    long long total = 0;
+    for (int r = 0; r < world; r++) {
+        if (rows[r] < 0 || rows[r] > INT32_MAX) { salve_fail("salve_bn_combine: a rank's rows must be 0 .. 2^31 - 1"); return SALVE_ERR_BAD_ARG; }
+        counts.n[r] = (float)rows[r];
+        total += rows[r];
+    }
+    if (total < 2) { salve_fail("bn: rows must be at least 2"); return SALVE_ERR_BAD_ARG; }
+    hipLaunchKernelGGL(bn_combine_kernel, dim3((unsigned)((d->C + BN_THREADS - 1) / BN_THREADS)), dim3(BN_THREADS), 0, (hipStream_t)stream, partials,
+                       counts, world, d->C, total, d->eps, d->momentum, mean, invstd, running_mean, running_var);
+    SALVE_HIP_CHECK(hipGetLastError());
+    return SALVE_OK;
+}
+
+int salve_bn_f32_apply(const salve_bn_desc_t* d, const float* x, const float* residual, const float* gamma, const float* beta, const float* mean,
+                       const float* invstd, float* y, void* stream) {
+    return bn_apply<float>("salve_bn_f32_apply: null descriptor", d, x, residual, gamma, beta, mean, invstd, y, stream);
+}
+
+int salve_bn_bf16_apply(const salve_bn_desc_t* d, const uint16_t* x, const uint16_t* residual, const float* gamma, const float* beta,
+                        const float* mean, const float* invstd, uint16_t* y, void* stream) {
+    return bn_apply<uint16_t>("salve_bn_bf16_apply: null descriptor", d, x, residual, gamma, beta, mean, invstd, y, stream);
+}
+
+int salve_bn_f32_backward_reduce(const salve_bn_desc_t* d, const float* dy, const float* x, const float* y, const float* mean, const float* invstd,
+                                 float* sums, void* ws, size_t ws_bytes, void* stream) {
+    return bn_backward_reduce<float>("salve_bn_f32_backward_reduce: null descriptor", d, dy, x, y, mean, invstd, sums, ws, ws_bytes, stream);
+}
+
+int salve_bn_bf16_backward_reduce(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* mean,
+                                  const float* invstd, float* sums, void* ws, size_t ws_bytes, void* stream) {
+    return bn_backward_reduce<uint16_t>("salve_bn_bf16_backward_reduce: null descriptor", d, dy, x, y, mean, invstd, sums, ws, ws_bytes, stream);
+}
+
+int salve_bn_f32_backward_apply(const salve_bn_desc_t* d, const float* dy, const float* x, const float* y, const float* gamma, const float* mean,
+                                const float* invstd, const float* sums, int32_t world, int64_t total_rows, float* dx, float* dres, void* stream) {
+    return bn_backward_apply<float>("salve_bn_f32_backward_apply: null descriptor", d, dy, x, y, gamma, mean, invstd, sums, world, total_rows, dx,
+                                    dres, stream);
+}
+
+int salve_bn_bf16_backward_apply(const salve_bn_desc_t* d, const uint16_t* dy, const uint16_t* x, const uint16_t* y, const float* gamma,
+                                 const float* mean, const float* invstd, const float* sums, int32_t world, int64_t total_rows, uint16_t* dx,
+                                 uint16_t* dres, void* stream) {
+    return bn_backward_apply<uint16_t>("salve_bn_bf16_backward_apply: null descriptor", d, dy, x, y, gamma, mean, invstd, sums, world, total_rows,
+                                       dx, dres, stream);
 }
 
 }  // extern "C"

@@ -7,7 +7,8 @@ The contract is exact.  Rank r's batch is rows [lo_r, hi_r) of the batch the sin
 packed, scaled, into one flat fp32 buffer by ONE HIP launch (salve_amd/csrc/flat_bucket.hip: salve_flat_pack), the buffer is summed
 by ONE collective, and every `p.grad` becomes its view of the buffer -- no unpack launch: torch.optim.Adam and HipAdam read
 contiguous fp32 views as they read any gradient.  As under the reference's DataParallel, BatchNorm statistics are not synchronised:
-every rank normalises its own rows, and rank 0's running statistics are the ones validation and the checkpoint see.
+every rank normalises its own rows, and rank 0's running statistics are the ones validation and the checkpoint see -- unless the
+opt-in `sync_bn` is set (models/trainable.py: SyncBatchNormHipFunction), which gathers through `_gather` here.
 
   FlatBucket       the tables and the flat buffer of a list of fp32 device tensors; pack / unpack / views.
   DataParallel     the process group and the three things a step needs of it: all_reduce_gradients, broadcast, reduce_meter.
@@ -16,7 +17,7 @@ Backends: "nccl" (RCCL) reduces the device buffer.  "gloo" stages the buffer thr
 that the feature does not depend on whether the installed gloo takes device tensors -- it is what several ranks on ONE GPU use,
 since RCCL wants a GPU per rank.  A world of one without `force=True` is the identity everywhere and runs no collective.
 
-Not here: SyncBatchNorm, overlap of the all-reduce with the backward pass, several buckets, a bf16 wire format, more than one node,
+Not here: overlap of the all-reduce with the backward pass, several buckets, a bf16 wire format, more than one node,
 gradient accumulation, the host DataLoader feed in a world larger than one.
 """
 

@@ -11,7 +11,9 @@ gradients, BatchNorm in fp32 (upcast at its input), fp32 logits and loss.  bf16 
 
 Opt-in HIP BatchNorm (`set_train_norm("hip")`): every BatchNorm runs on salve_amd/csrc/norm_train.hip (salve_bn_*) through
 `BatchNormHipFunction`, with the ReLU and the residual add that follow it fused in, forward and backward, in either precision;
-in bf16 no cast remains around BatchNorm.  torch's BatchNorm stays the default.
+in bf16 no cast remains around BatchNorm.  torch's BatchNorm stays the default.  On top of it `set_sync_norm(dist)` (`--sync-bn`)
+takes the train-mode statistics over the rows of all data-parallel ranks: `SyncBatchNormHipFunction`, the same kernels behind split
+entries with one all-gather between them, forward and backward.
 
 With the opt-in HIP Adam (salve_amd/optim.py: HipAdam, `--optim hip`) the bf16 convolutions read the bf16 copy of a weight that
 the optimiser's step wrote, instead of casting the fp32 master on every call, while that copy is provably current
@@ -30,7 +32,7 @@ There is no CPU path: a CPU tensor raises (no F.conv2d fallback).
 from __future__ import annotations
 
 import ctypes
-from typing import Optional
+from typing import List, Optional
 
 import torch
 import torch.nn.functional as F
@@ -258,11 +260,128 @@ class BatchNormHipFunction(torch.autograd.Function):
         return dxn.permute(0, 3, 1, 2), dres, dgamma, dbeta, None, None, None, None, None, None, None
 
 
-def batch_norm_hip(bn: nn.BatchNorm2d, x: Tensor, residual: Optional[Tensor] = None, relu: bool = False) -> Tensor:
+def _call_bn(fn: str, desc: "_lib.BnDesc", args, ws_pass: Optional[int], device) -> None:
+    """One split salve_bn_* call: `args` are its arguments behind the descriptor in order (tensors, None or ctypes values); ws_pass:
+    the workspace pass of an entry that takes one (the workspace then goes in front of the stream)."""
+    lib = _lib.load()
+    args = [a if isinstance(a, ctypes._SimpleCData) else ctypes.c_void_p(None if a is None else a.data_ptr()) for a in args]
+    if ws_pass is not None:
+        nbytes = int(lib.salve_bn_workspace_bytes(ctypes.byref(desc), ws_pass))
+        if nbytes == 0:
+            raise _lib.SalveHipError(f"{fn}: refused: {lib.salve_last_error().decode('utf-8', 'replace')}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        args += [ctypes.c_void_p(ws.data_ptr()), ctypes.c_size_t(nbytes)]
+    st = getattr(lib, fn)(ctypes.byref(desc), *args, ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(st, fn)
+
+
+class SyncBatchNormHipFunction(torch.autograd.Function):
+    """BatchNormHipFunction in train mode over the rows of ALL data-parallel ranks (opt-in: set_sync_norm, --sync-bn), on the split
+    HIP entries: forward salve_bn_*_stats -> ONE all-gather of [2, C] -> salve_bn_combine -> salve_bn_*_apply, backward
+    salve_bn_*_backward_reduce -> ONE all-gather of [2, C] -> salve_bn_*_backward_apply.  The gathers, not reductions, on purpose:
+    every rank adds the same numbers in the same (rank) order, so mean, invstd and the running statistics are bit-identical on every
+    rank whatever the backend's reduction order.
+
+    The arguments of BatchNormHipFunction up to `momentum`, then group: what runs the all-gather -- `rank`, `world` and
+    `_gather(t) -> [world, *t.shape]` on t's device, in rank order (a dist_train.DataParallel: its group, stream and tensor
+    handling); batches: the batch rows of every rank, [world] (from the batch plan, no collective), of which this rank's must be
+    x's.  Returns what BatchNormHipFunction returns.  Backward: dx and the residual's gradient over the whole batch's statistics;
+    dweight and dbias are THIS rank's sums, which the gradient all-reduce adds like every other parameter gradient's."""
+
+    @staticmethod
+    def forward(ctx, x: Tensor, residual: Optional[Tensor], weight: Tensor, bias: Tensor, running_mean: Optional[Tensor],
+                running_var: Optional[Tensor], num_batches_tracked: Optional[Tensor], relu: bool, eps: float, momentum: Optional[float],
+                group, batches) -> Tensor:
+        who = "SyncBatchNormHipFunction"
+        if x.dtype not in _BN_ENTRY:
+            raise RuntimeError(f"{who}: x must be float32 or bfloat16, got {x.dtype}")
+        if x.device.type != "cuda":
+            raise RuntimeError(f"{who}: x is on {x.device}; the HIP BatchNorm runs on the HIP device only (no CPU fallback)")
+        if residual is not None and (residual.dtype != x.dtype or residual.shape != x.shape or residual.device != x.device):
+            raise RuntimeError(f"{who}: residual must match x ({x.dtype}, {tuple(x.shape)}, {x.device}), got {residual.dtype}, "
+                               f"{tuple(residual.shape)}, {residual.device}")
+        for name, t in (("weight", weight), ("bias", bias), ("running_mean", running_mean), ("running_var", running_var)):
+            if t is None:
+                if name in ("weight", "bias"):
+                    raise RuntimeError(f"{who}: {name} is required")
+                continue
+            if t.device != x.device:
+                raise RuntimeError(f"{who}: {name} is on {t.device}, x on {x.device} (no CPU fallback)")
+            if t.dtype != torch.float32 or t.numel() != x.shape[1]:
+                raise RuntimeError(f"{who}: {name} must be float32 [{x.shape[1]}], got {t.dtype} {tuple(t.shape)}")
+        b, c, h, w = x.shape
+        world, rank = int(group.world), int(group.rank)
+        batches = [int(n) for n in batches]
+        if len(batches) != world or batches[rank] != b or world > _lib.BN_MAX_WORLD:
+            raise RuntimeError(f"{who}: rank {rank} of {world} (at most {_lib.BN_MAX_WORLD}) holds {b} batch rows, the batch plan says {batches}")
+        factor = 0.0
+        if running_mean is not None:
+            if num_batches_tracked is not None:
+                num_batches_tracked.add_(1)
+            factor = momentum if momentum is not None else 1.0 / float(num_batches_tracked)
+        flags = (_lib.BN_RELU if relu else 0) | (_lib.BN_ADD if residual is not None else 0)
+        desc = (b * h * w, c, flags, eps, factor)
+        rows = (ctypes.c_int64 * world)(*[n * h * w for n in batches])
+        entry, dev = _BN_ENTRY[x.dtype], x.device
+        xn = _nhwc(x.detach(), c)
+        rn = None if residual is None else _nhwc(residual.detach(), c)
+        y = torch.empty((b, c, h, w), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
+        weight, bias = weight.detach().contiguous(), bias.detach().contiguous()
+        partial = torch.empty((2, c), dtype=torch.float32, device=dev)
+        mean = torch.empty(c, dtype=torch.float32, device=dev)
+        invstd = torch.empty(c, dtype=torch.float32, device=dev)
+        _call_bn(entry + "_stats", _lib.BnDesc(*desc), (xn, partial), _lib.BN_STATS, dev)
+        partials = group._gather(partial).contiguous()
+        _call_bn("salve_bn_combine", _lib.BnDesc(*desc), (partials, ctypes.cast(rows, ctypes.c_void_p), ctypes.c_int32(world), running_mean,
+                                                          running_var, mean, invstd), None, dev)
+        _call_bn(entry + "_apply", _lib.BnDesc(*desc), (xn, rn, weight, bias, mean, invstd, y.permute(0, 2, 3, 1)), None, dev)
+        ctx.desc, ctx.relu, ctx.add, ctx.group, ctx.total_rows = desc, relu, residual is not None, group, sum(rows)
+        ctx.save_for_backward(xn, weight, mean, invstd, y if relu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy: Tensor):
+        xn, weight, mean, invstd, y = ctx.saved_tensors
+        b, h, w, c = xn.shape
+        entry, dev = _BN_ENTRY[xn.dtype], xn.device
+        gyn = gy.to(xn.dtype).permute(0, 2, 3, 1).contiguous()
+        dxn = torch.empty_like(xn)
+        dresn = torch.empty_like(xn) if ctx.add else None
+        sums = torch.empty((2, c), dtype=torch.float32, device=dev)   # this rank's dbeta, dgamma
+        yn = None if y is None else y.permute(0, 2, 3, 1)
+        _call_bn(entry + "_backward_reduce", _lib.BnDesc(*ctx.desc), (gyn, xn, yn, mean, invstd, sums), _lib.BN_BWD_REDUCE, dev)
+        every = ctx.group._gather(sums).contiguous()
+        _call_bn(entry + "_backward_apply", _lib.BnDesc(*ctx.desc), (gyn, xn, yn, weight, mean, invstd, every, ctypes.c_int32(int(ctx.group.world)),
+                                                                     ctypes.c_int64(int(ctx.total_rows)), dxn, dresn), None, dev)
+        dres = None if dresn is None else dresn.permute(0, 3, 1, 2)
+        return dxn.permute(0, 3, 1, 2), dres, sums[1], sums[0], None, None, None, None, None, None, None, None
+
+
+class SyncNorm:
+    """What batch_norm_hip needs to synchronise a train-mode BatchNorm: the group (SyncBatchNormHipFunction's) and the batch plan.
+    batch_size: the rows of the WHOLE batch, split over the ranks as the feeds split it (train_feed.shard_bounds); None: every rank
+    holds as many rows as this one -- the train feeds' contract (train_feed.check_shard)."""
+
+    def __init__(self, group, batch_size: Optional[int] = None) -> None:
+        self.group, self.batch_size = group, None if batch_size is None else int(batch_size)
+
+    def batches(self, local: int) -> List[int]:
+        world = int(self.group.world)
+        if self.batch_size is None:
+            return [int(local)] * world
+        return [(r + 1) * self.batch_size // world - r * self.batch_size // world for r in range(world)]
+
+
+def batch_norm_hip(bn: nn.BatchNorm2d, x: Tensor, residual: Optional[Tensor] = None, relu: bool = False, sync: Optional[SyncNorm] = None) -> Tensor:
     """relu?(bn(x) + residual?) on BatchNormHipFunction: batch statistics when the module is in train mode (or tracks none),
-    running statistics otherwise."""
+    running statistics otherwise.  sync: batch statistics are taken over the rows of all ranks (SyncBatchNormHipFunction); the
+    running-statistics form is untouched."""
     training = bn.training or bn.running_mean is None
     tracked = bn.training and bn.track_running_stats
+    if sync is not None and training:
+        return SyncBatchNormHipFunction.apply(x, residual, bn.weight, bn.bias, bn.running_mean if tracked else None,
+                                              bn.running_var if tracked else None, bn.num_batches_tracked if tracked else None,
+                                              relu, bn.eps, bn.momentum, sync.group, sync.batches(x.shape[0]))
     return BatchNormHipFunction.apply(x, residual, bn.weight, bn.bias, bn.running_mean if (tracked or not training) else None,
                                       bn.running_var if (tracked or not training) else None, bn.num_batches_tracked if tracked else None,
                                       relu, bn.eps, bn.momentum, training)
@@ -373,17 +492,17 @@ def _bottleneck(blk, x: Tensor, conv, bn) -> Tensor:
     return F.relu(out + idt)
 
 
-def _basic_hip(blk, x: Tensor, conv) -> Tensor:
-    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True)
-    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]))
-    return batch_norm_hip(blk.bn2, conv(out, blk.conv2), residual=idt, relu=True)
+def _basic_hip(blk, x: Tensor, conv, sync: Optional[SyncNorm] = None) -> Tensor:
+    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True, sync=sync)
+    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]), sync=sync)
+    return batch_norm_hip(blk.bn2, conv(out, blk.conv2), residual=idt, relu=True, sync=sync)
 
 
-def _bottleneck_hip(blk, x: Tensor, conv) -> Tensor:
-    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True)
-    out = batch_norm_hip(blk.bn2, conv(out, blk.conv2), relu=True)
-    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]))
-    return batch_norm_hip(blk.bn3, conv(out, blk.conv3), residual=idt, relu=True)
+def _bottleneck_hip(blk, x: Tensor, conv, sync: Optional[SyncNorm] = None) -> Tensor:
+    out = batch_norm_hip(blk.bn1, conv(x, blk.conv1), relu=True, sync=sync)
+    out = batch_norm_hip(blk.bn2, conv(out, blk.conv2), relu=True, sync=sync)
+    idt = x if blk.downsample is None else batch_norm_hip(blk.downsample[1], conv(x, blk.downsample[0]), sync=sync)
+    return batch_norm_hip(blk.bn3, conv(out, blk.conv3), residual=idt, relu=True, sync=sync)
 
 
 class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
@@ -401,6 +520,7 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     conv2, plain bn on the downsample branch, bn + add + relu at the end of a block), in fp32 and in bf16 (no casts around
     BatchNorm then).  Train mode uses batch statistics; eval mode under torch.no_grad() (the validation pass) the eval form; eval
     mode with gradients enabled runs the torch path, which has a backward pass.  The same parameters and buffers either way.
+    `set_sync_norm(dist)` on top of it synchronises the train-mode statistics over the data-parallel ranks.
 
     `set_train_head("hip")` opts into the HIP classifier head for `forward_loss` / `forward_packed_loss`, which return (probs,
     loss): the last block's output goes through ClassifierHeadHipFunction (average pool, fc, softmax, cross-entropy and the
@@ -410,6 +530,7 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     _train_precision = "fp32"
     _train_norm = "torch"
     _train_head = "torch"
+    _sync_norm: Optional[SyncNorm] = None
 
     def set_train_precision(self, precision: str) -> "TrainableEarlyFusionCEResnet":
         """"fp32" (the default, the reference's precision) or "bf16" (opt-in mixed precision).  Returns self."""
@@ -433,6 +554,20 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
     @property
     def train_norm(self) -> str:
         return self._train_norm
+
+    def set_sync_norm(self, dist, batch_size: Optional[int] = None) -> "TrainableEarlyFusionCEResnet":
+        """Opt-in: every train-mode BatchNorm normalises over the rows of all data-parallel ranks (SyncBatchNormHipFunction: two
+        all-gathers of [2, C] per BatchNorm and step, through `dist`, a dist_train.DataParallel).  Needs the HIP norm.  batch_size:
+        SyncNorm's.  Eval mode is untouched: running statistics, no collective.  A `dist` that runs no collectives (None, or a world
+        of one that is not forced) switches it off: the fused entries.  Returns self."""
+        if dist is not None and self._train_norm != "hip":
+            raise ValueError("BatchNorm statistics are synchronised by the HIP BatchNorm only: choose --norm hip (set_train_norm(\"hip\"))")
+        self._sync_norm = SyncNorm(dist, batch_size) if dist is not None and getattr(dist, "active", True) else None
+        return self
+
+    @property
+    def sync_norm(self) -> Optional[SyncNorm]:
+        return self._sync_norm
 
     def set_train_head(self, head: str) -> "TrainableEarlyFusionCEResnet":
         """"torch" (the default: avgpool, fc, softmax and cross_entropy as separate torch operations) or "hip" (opt-in:
@@ -528,11 +663,12 @@ class TrainableEarlyFusionCEResnet(EarlyFusionCEResnet):
         r = self.resnet
         x = conv(x, self.conv1, True) if packed else conv(x, self.conv1)
         if self._train_norm == "hip" and (self.training or not torch.is_grad_enabled()):
-            x = r.maxpool(batch_norm_hip(r.bn1, x, relu=True))
+            sync = self._sync_norm
+            x = r.maxpool(batch_norm_hip(r.bn1, x, relu=True, sync=sync))
             block = _bottleneck_hip if r.block_kind == "bottleneck" else _basic_hip
             for layer in (r.layer1, r.layer2, r.layer3, r.layer4):
                 for blk in layer:
-                    x = block(blk, x, conv)
+                    x = block(blk, x, conv, sync)
         else:
             x = r.maxpool(F.relu(bn(r.bn1, x)))
             block = _bottleneck if r.block_kind == "bottleneck" else _basic

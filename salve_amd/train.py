@@ -1,6 +1,6 @@
 """Train the verifier (scripts/train.py's command line; one GPU, or --gpus N of one node data-parallel):
 
-    python -m salve_amd.train --config <reference yaml> [--gpus N [--dist-backend {nccl,gloo}] [--dist-timeout S]] [--epochs N] [--batch-size B] [--data-root DIR]
+    python -m salve_amd.train --config <reference yaml> [--gpus N [--dist-backend {nccl,gloo}] [--dist-timeout S] [--sync-bn]] [--epochs N] [--batch-size B] [--data-root DIR]
                               [--layout-data-root DIR] [--seed S] [--init-ckpt CKPT] [--out DIR] [--precision {fp32,bf16}]
                               [--norm {torch,hip}] [--optim {torch,hip}] [--head {torch,hip}] [--decode {host,device}]
                               [--decode-entropy {image,lanes}] [--decode-read-ahead] [--photometric device]
@@ -39,6 +39,9 @@ process -- before anything touches a GPU -- and relays its exit code; a node tha
 Every rank trains its rows of each batch (the batch size must be a multiple of N), the gradients are averaged by one all-reduce per
 step, rank 0 logs and writes the checkpoint and the results JSON.  Needs --render-from or --decode device.  --dist-backend: nccl
 (default: RCCL, a GPU per rank) or gloo (the buffer is reduced on the host).
+--sync-bn (with --norm hip; refused without it) makes every BatchNorm of the train pass normalise over the rows of all N ranks
+(DESIGN.md 4.26): two small all-gathers per BatchNorm and step, the same running statistics on every rank.  With one rank it changes
+nothing.
 """
 
 from __future__ import annotations
@@ -108,12 +111,16 @@ def main(argv=None) -> None:
     ap.add_argument("--dist-backend", choices=("nccl", "gloo"), default="nccl",
                     help="--gpus: nccl (default: RCCL reduces the gradients on the devices) or gloo (they are reduced on the host)")
     ap.add_argument("--dist-timeout", type=float, default=600, metavar="S", help="--gpus: seconds a collective may wait for the other ranks (default 600)")
+    ap.add_argument("--sync-bn", action="store_true",
+                    help="--gpus with --norm hip: every BatchNorm normalises over the rows of all ranks, and all ranks keep the same running statistics")
     ap.add_argument("--force-dist", action="store_true", help=argparse.SUPPRESS)   # under a launcher: run the collectives in a world of one too
     argv = sys.argv[1:] if argv is None else list(argv)
     a = ap.parse_args(argv)
     training._check_head(a.head)
     from salve_amd.dist_train import MAX_GPUS
 
+    if a.sync_bn and a.norm != "hip":
+        raise SystemExit("--sync-bn synchronises the statistics of the HIP BatchNorm: add --norm hip; nothing was launched")
     if not 1 <= a.gpus <= MAX_GPUS:
         raise SystemExit(f"salve_amd.train: --gpus must be 1 .. {MAX_GPUS}, got {a.gpus}; nothing was launched")
     launched = "WORLD_SIZE" in os.environ
@@ -206,10 +213,11 @@ def _train(a, args, out: str, identity: str, dist, rank: int, world: int):
             src.set_examples(*examples[split])
             sources[split] = src
         return training.train_rendered(args, sources["train"], sources["val"], out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision,
-                                       norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality, photometric=a.photometric, dist=dist)
+                                       norm=a.norm, optim=a.optim, head=a.head, jpeg_quality=a.jpeg_quality, photometric=a.photometric, dist=dist,
+                                       sync_bn=a.sync_bn)
     return training.train(args, out, seed=a.seed, init_ckpt=a.init_ckpt, precision=a.precision, norm=a.norm, optim=a.optim,
                           head=a.head, decode=a.decode, entropy=a.decode_entropy, read_ahead=a.decode_read_ahead,
-                          photometric=a.photometric, dist=dist)
+                          photometric=a.photometric, dist=dist, sync_bn=a.sync_bn)
 
 
 if __name__ == "__main__":

@@ -46,6 +46,11 @@ def _check_norm(norm: str) -> None:
         raise ValueError(f"training norm must be one of {TRAIN_NORMS}, got {norm!r}")
 
 
+def _check_sync_bn(sync_bn: bool, norm: str) -> None:
+    if sync_bn and norm != "hip":
+        raise ValueError(f'sync_bn=True (--sync-bn) synchronises the statistics of the HIP BatchNorm: it needs norm="hip" (--norm hip), got {norm!r}')
+
+
 def _check_optim(optim: str) -> None:
     if optim not in OPTIMS:
         raise ValueError(f"training optimiser must be one of {OPTIMS}, got {optim!r}")
@@ -304,7 +309,8 @@ def _run_epoch_device(args: TrainingConfig, epoch: int, model: nn.Module, data_l
 
 def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None, precision: str = "fp32",
           norm: str = "torch", optim: str = "torch", head: str = "torch", decode: str = "host", entropy: str = "image",
-          read_ahead: bool = False, photometric: Optional[str] = None, dist: Optional[DataParallel] = None) -> Dict[str, list]:
+          read_ahead: bool = False, photometric: Optional[str] = None, dist: Optional[DataParallel] = None,
+          sync_bn: bool = False) -> Dict[str, list]:
     """scripts/train.py:41-119: seeds, loaders, model, optimiser, then per epoch a train pass and a val pass under no_grad.  On
     epoch 0 and on every improvement of val_mAcc, `{results_dir}/train_ckpt.pth` is written with the reference's keys; the
     results JSON (`results-{cfg_stem}.json`, train_* / val_* series) is rewritten every epoch.  init_ckpt: fine-tune from a
@@ -322,9 +328,13 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     reference's PhotometricShift on the device in every train batch of either decode; val batches never jitter.
     dist: None (default), or a dist_train.DataParallel: this process is one of `dist.world` ranks, each of which trains its rows of
     every batch; needs decode="device" in a world larger than one -- the host DataLoader draws inside its worker
-    processes and is not sharded.  Rank 0 logs and writes the checkpoint and the results JSON; every rank returns the same dict."""
+    processes and is not sharded.  Rank 0 logs and writes the checkpoint and the results JSON; every rank returns the same dict.
+    sync_bn (default False; needs norm="hip"): every train-mode BatchNorm normalises over the rows of all `dist.world` ranks
+    (SyncBatchNormHipFunction), and every rank keeps the same running statistics; without a `dist` that runs
+    collectives (None, or a world of one that is not forced) it changes nothing."""
     _check_precision(precision)
     _check_norm(norm)
+    _check_sync_bn(sync_bn, norm)
     _check_optim(optim)
     _check_head(head)
     _check_decode(decode)
@@ -342,22 +352,24 @@ def train(args: TrainingConfig, results_dir: str, seed: int = 0, init_ckpt: Opti
     if decode == "device":
         with get_tile_file_source(args, "train", seed, precision, entropy, read_ahead, photometric, rank, world) as train_source, \
                 get_tile_file_source(args, "val", seed, precision, entropy, read_ahead, photometric, rank, world) as val_source:
-            return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist)   # (leaving ends their reader threads)
+            return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist, sync_bn)   # (leaving ends their reader threads)
     return _fit(args, get_dataloader(args, "train", seed=seed, photometric=photometric), get_dataloader(args, "val"), results_dir, init_ckpt,
-                precision, norm, optim, head, dist)
+                precision, norm, optim, head, dist, sync_bn)
 
 
 def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: str, seed: int = 0, init_ckpt: Optional[str] = None,
                    precision: str = "fp32", norm: str = "torch", optim: str = "torch", head: str = "torch",
-                   jpeg_quality: Optional[int] = None, photometric: Optional[str] = None, dist: Optional[DataParallel] = None) -> Dict[str, list]:
+                   jpeg_quality: Optional[int] = None, photometric: Optional[str] = None, dist: Optional[DataParallel] = None,
+                   sync_bn: bool = False) -> Dict[str, list]:
     """`train` fed by two train_render.RenderedTrainSource objects (split "train", built with the same `seed` and `precision`, and
     split "val") instead of the rendered dataset on disk: the same epoch loop, checkpoint and results JSON.  jpeg_quality: the
     sources' own argument (the reference's JPEG round trip of every rendered image, on the device); the two sources must agree, and
     an integer given here must be what they were built with.  photometric: `train`'s keyword; the train source must have been built
     with what the config and the keyword amount to (RenderedTrainSource(photometric=)).  dist: `train`'s; both sources must have been
-    built with its rank and world (RenderedTrainSource(rank=, world=))."""
+    built with its rank and world (RenderedTrainSource(rank=, world=)).  sync_bn: `train`'s."""
     _check_precision(precision)
     _check_norm(norm)
+    _check_sync_bn(sync_bn, norm)
     _check_optim(optim)
     _check_head(head)
     get_train_transform(args, photometric)   # (the refusals of the on-disk path: photometric augmentation without the keyword, crop-with-padding)
@@ -381,17 +393,22 @@ def train_rendered(args: TrainingConfig, train_source, val_source, results_dir: 
     np.random.seed(seed)
     random.seed(seed)
     torch.manual_seed(seed)
-    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist)
+    return _fit(args, train_source, val_source, results_dir, init_ckpt, precision, norm, optim, head, dist, sync_bn)
 
 
 def _fit(args: TrainingConfig, train_loader, val_loader, results_dir: str, init_ckpt: Optional[str], precision: str, norm: str,
-         optim: str = "torch", head: str = "torch", dist: Optional[DataParallel] = None) -> Dict[str, list]:
+         optim: str = "torch", head: str = "torch", dist: Optional[DataParallel] = None, sync_bn: bool = False) -> Dict[str, list]:
     """The epoch loop of `train` / `train_rendered` (scripts/train.py:60-119) on two batch sources.  dist: every rank starts from
     rank 0's parameters (one broadcast), validates with rank 0's BatchNorm statistics (one broadcast in front of every val pass: the
-    reference's DataParallel keeps replica 0's), and rank 0 alone writes the checkpoint and the results JSON."""
+    reference's DataParallel keeps replica 0's), and rank 0 alone writes the checkpoint and the results JSON.  sync_bn: the train
+    batches' BatchNorm statistics are taken over all ranks' rows (the train batch is `args.batch_size` rows, split in equal
+    blocks); every rank then holds rank 0's running statistics already, and the broadcast copies what is there."""
     if len(train_loader) == 0:
         raise RuntimeError(f"the train split has fewer than batch_size={args.batch_size} examples")
+    _check_sync_bn(sync_bn, norm)
     model = get_model(args, precision, norm, head)
+    if sync_bn and dist is not None:
+        model.set_sync_norm(dist, batch_size=args.batch_size)
     if init_ckpt:
         from salve_amd import train_utils
 

@@ -1,6 +1,6 @@
 """Data-parallel training's two costs on one MI355X (profiles/r15_data_parallel.txt):
 
-    python tools/measure/bench_data_parallel.py [--layers 152] [--batch 256] [--steps 10] [--repeats 5] [--skip-step]
+    python tools/measure/bench_data_parallel.py [--layers 152] [--batch 256] [--steps 10] [--repeats 5] [--skip-step] [--sync-bn]
 
 1. Pack throughput: `FlatBucket.pack` over the gradient set of one real backward pass of the ResNet (the parameters that received
    a gradient), timed with device events over windows of 50 launches, --repeats windows per scale (1 / 2: a multiply; 1: the bit
@@ -11,7 +11,11 @@
    (pack at scale 1, the all-reduce of the flat buffer, the gradients re-pointed), in alternating windows of --steps steps, each
    ending in a device synchronise; medians and the spread between the windows.
 
-One GPU: nothing here measures scaling."""
+3. --sync-bn (instead of 1 and 2; profiles/r17_sync_bn.txt): the same step in the forced RCCL world of one, without and with
+   `set_sync_norm` -- the split BatchNorm entries in place of the fused ones (three more small launches per BatchNorm and pass) plus
+   two all-gathers of [2, C] per BatchNorm and step, 310 collectives of one rank for ResNet-152 -- in the same alternating windows.
+
+One GPU: nothing here measures scaling, nor what the collectives cost between several GPUs."""
 
 from __future__ import annotations
 
@@ -39,6 +43,7 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=10, help="steps per timed window")
     ap.add_argument("--repeats", type=int, default=5, help="windows per variant")
     ap.add_argument("--skip-step", action="store_true", help="pack throughput only")
+    ap.add_argument("--sync-bn", action="store_true", help="the step in a forced world of one with and without synchronised BatchNorm, nothing else")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_data_parallel.py measures on the HIP device; none is visible")
@@ -63,6 +68,9 @@ def main() -> None:
         if dist is not None:
             dist.all_reduce_gradients(model.parameters())
         opt.step()
+
+    if a.sync_bn:
+        return sync_bn_step(a, model, step)
 
     # ---- 1. pack throughput over the real gradient set
     step(rows=2)
@@ -114,6 +122,40 @@ def main() -> None:
                   f"{min(t) * 1e3:.2f} .. {max(t) * 1e3:.2f} ms)")
         print(f"difference of the medians: {(statistics.median(times['world of one']) - statistics.median(times['plain'])) * 1e3:+.2f} ms")
     finally:
+        dist.close()
+
+
+def sync_bn_step(a, model, step) -> None:
+    """3.: the step in a forced world of one, fused BatchNorm entries against the split entries with their collectives."""
+    with socket.socket() as s:
+        s.bind(("127.0.0.1", 0))
+        os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(s.getsockname()[1]), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0")
+    dist = DataParallel.from_env("nccl", timeout_s=60, force=True)
+    variants = (("fused", None), ("sync-bn", dist))
+    try:
+        for _ in range(2):   # warm-up: code objects, the allocator, RCCL's first collectives
+            for _, sync in variants:
+                model.set_sync_norm(sync, batch_size=a.batch)
+                step(dist)
+        torch.cuda.synchronize()
+        times = {name: [] for name, _ in variants}
+        for _ in range(a.repeats):
+            for name, sync in variants:
+                model.set_sync_norm(sync, batch_size=a.batch)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(a.steps):
+                    step(dist)
+                torch.cuda.synchronize()
+                times[name].append((time.perf_counter() - t0) / a.steps)
+        norms = sum(isinstance(m, torch.nn.BatchNorm2d) for m in model.modules())
+        print(f"ResNet-{a.layers} bf16, HIP norm / optimiser / head, forced RCCL world of one; {norms} BatchNorms, {2 * norms} all-gathers per step with sync-bn")
+        for name, t in times.items():
+            print(f"step, {name:8s} batch {a.batch}: median {statistics.median(t) * 1e3:8.2f} ms  (windows of {a.steps} steps: "
+                  f"{min(t) * 1e3:.2f} .. {max(t) * 1e3:.2f} ms)")
+        print(f"difference of the medians: {(statistics.median(times['sync-bn']) - statistics.median(times['fused'])) * 1e3:+.2f} ms")
+    finally:
+        model.set_sync_norm(None)
         dist.close()
 
 
