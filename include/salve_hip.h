@@ -537,6 +537,34 @@ int salve_resnet_f32_forward(void* handle, const float* input, int32_t batch, fl
                              size_t workspace_bytes, int32_t* status, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Verifier in bf16x3 (additive within ABI 7): the fp32 engine's program, input, activations and logits with the
+ * convolutions' multiplications on the bf16 matrix cores, opt-in.
+ * Everything above about the fp32 engine holds -- fp32 NCHW input, fp32 NHWC activations in the workspace (no storage
+ * rounding), fp32 bias / residual / ReLU / pools / head, NaN propagated, no status bit -- except the convolution's products:
+ * every fp32 operand x is split into two bf16 pieces,
+ *     hi = bf16(x), round to nearest even;   lo = bf16(x - float(hi)), the subtraction being exact in fp32;
+ *     NaN -> hi = NaN, lo = 0;   +-inf -> hi = +-inf, lo = 0 (inf - inf is never computed);
+ *     a finite x whose rounding would give inf -> hi = the largest finite bf16 of its sign (lo takes the rest),
+ * and a product a * w is computed as ah * wh + ah * wl + al * wh by three v_mfma_f32_32x32x16_bf16 into fp32
+ * accumulators, in that order per k-step, without atomics or split-K: the same input gives the same bits on every run.
+ * Activations are split on their way into LDS, weights once inside create (the caller's blob is the fp32 engine's).
+ * bf16 has fp32's exponent range, so the fp32 engine's range is kept.  (An infinite activation can give NaN where one
+ * fp32 product gives inf: ah * wl is inf * 0 for a weight whose lo piece is 0, and of the other sign where wl's is.)
+ *   Error: a product loses three pieces (al * wl and the residue of each operand after its two pieces), each about
+ *          2^-18 |a| |w| (worst case 2^-16: bf16 keeps 8 significand bits; the pieces have mixed signs and average over K).
+ *          One convolution output is held to (3 * 2^-18 + 4e-6) * (sum |a| |w| + |bias| (+ |residual|)) of the exact sum,
+ *          4e-6 being the allowance of the fp32 accumulation as for the fp32 engine; an engine that loses a cross term
+ *          exceeds that 11 x or more.  Logits of the released ResNet-152 configurations (|logit| about 11) stay within
+ *          the absolute 1e-3 contract (emulated: 5.3e-5).
+ *   create: arguments and refusals of salve_resnet_f32_create, whose checks it runs (refusals of the program carry that
+ *           entry's name); flags must be 0.  The handle is used with salve_resnet_f32_workspace_bytes,
+ *           salve_resnet_f32_forward and salve_resnet_f32_destroy.
+ * ------------------------------------------------------------------------------------------------ */
+void* salve_resnet_bf16x3_create(int32_t num_layers, int32_t in_channels, const salve_resnet_op_t* ops, int32_t n_ops,
+                                 const float* weights_f32, size_t weights_bytes, const float* params_f32, size_t params_bytes,
+                                 const int32_t* ktab, size_t ktab_entries, int32_t flags);
+
+/* ------------------------------------------------------------------------------------------------
  * Training convolutions in fp32 (additive within ABI 7): forward, backward-data and backward-weight of ONE convolution, the
  * hot path of a training step of the verifier (the reference trains in fp32: scripts/train.py and the configs under salve/configs).
  * Everything around them -- BatchNorm with batch statistics, ReLU, residual adds, pooling, the fc layer, the loss and Adam --

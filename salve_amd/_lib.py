@@ -53,6 +53,7 @@ EXPORTED_SYMBOLS = (
     "salve_resnet_f32_destroy",
     "salve_resnet_f32_workspace_bytes",
     "salve_resnet_f32_forward",
+    "salve_resnet_bf16x3_create",
     "salve_bev_tiles_aug",
     "salve_conv_f32_workspace_bytes",
     "salve_conv_f32_forward",
@@ -280,6 +281,8 @@ def load() -> ctypes.CDLL:
     lib.salve_resnet_num_layers.restype = ctypes.c_int
     lib.salve_resnet_f32_create.argtypes = [i32, i32, vp, i32, vp, sz, vp, sz, vp, sz, i32]
     lib.salve_resnet_f32_create.restype = vp
+    lib.salve_resnet_bf16x3_create.argtypes = [i32, i32, vp, i32, vp, sz, vp, sz, vp, sz, i32]
+    lib.salve_resnet_bf16x3_create.restype = vp
     lib.salve_resnet_f32_destroy.argtypes = [vp]
     lib.salve_resnet_f32_destroy.restype = None
     lib.salve_resnet_f32_workspace_bytes.argtypes = [vp, i32]

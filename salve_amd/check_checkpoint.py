@@ -1,5 +1,5 @@
 """python -m salve_amd.check_checkpoint <train_ckpt.pth> [--layers 152] [--modalities ceiling_rgb_texture,floor_rgb_texture] [--tiles DIR] [-n 64]
-                                   [--precision fp16|fp32] [--jpeg-quality Q]
+                                   [--precision fp16|fp32|bf16x3] [--jpeg-quality Q]
 
 What fp16 storage costs THIS checkpoint: loads a reference-format checkpoint (`{"state_dict": ...}`, optional `module.` prefix --
 scripts/train.py:97-107, loaded strictly as salve/train_utils.py:229-242 does), runs N tile sets through the HIP engine (fp16
@@ -22,6 +22,8 @@ with textured regions, the input the verifier actually sees.
 reference's own precision): the tiles stay fp32 (no fp16 cast of the files' tiles; rendered tile sets come from the fp32 pipeline), the
 float32 evaluation sees the same fp32 tiles, and the contract is north_star's ABSOLUTE one:
     |logit error| <= 1e-3   and   equal arg-max,   at any logit magnitude.
+--precision bf16x3 checks the bf16x3 engine (the fp32 engine with every convolution product on the bf16 matrix cores, from bf16 hi / lo
+pieces of its fp32 operands) in the same way, on the same fp32 tiles, against the same absolute contract.
 
 --jpeg-quality Q (rendered tile sets only; the reference's files: 75) renders the same tile sets a second time through the reference's
 JPEG round trip on the device (RenderVerifyPipeline(jpeg_quality=Q)) and prints, beside the numbers above, how far the engine's logits
@@ -98,7 +100,7 @@ def report(st: dict, what: str) -> str:
                 f"  error / max(1, |logit|):      p99 {st['rel_err_p99']:.2e}  max {st['rel_err_max']:.2e}\n"
                 f"  softmax probabilities:        max error {st['prob_err_max']:.2e}\n"
                 f"  arg-max equal:                {st['argmax_equal']} / {st['n']}\n"
-                f"  contract (fp32 engine: absolute 1e-3) {'MET' if st['contract_holds'] else 'NOT MET'}")
+                f"  contract ({st.get('engine', 'fp32')} engine: absolute 1e-3) {'MET' if st['contract_holds'] else 'NOT MET'}")
     return (f"{what}: {st['n']} tile sets\n"
             f"  |logit| (largest per sample): min {st['logit_abs_min']:.2f}  median {st['logit_abs_median']:.2f}  max {st['logit_abs_max']:.2f}\n"
             f"  logit error, absolute:        median {st['err_median']:.2e}  p99 {st['err_p99']:.2e}  max {st['err_max']:.2e}"
@@ -185,20 +187,21 @@ def run(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 0) -
     return compare(got, ref)
 
 
-def run_f32(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 0) -> dict:
-    """The fp32 engine against the float32 evaluation on the same fp32 NCHW tiles [N, 3 n, 224, 224] on `device`; absolute contract."""
+def run_f32(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 0, precision: str = "fp32") -> dict:
+    """The fp32 engine (or, precision="bf16x3", the bf16x3 engine) against the float32 evaluation on the same fp32 NCHW tiles
+    [N, 3 n, 224, 224] on `device`; absolute contract."""
     import copy
 
     n_img = model.num_images
     prev = model.precision
     with torch.no_grad():
-        model.set_precision("fp32")
+        model.set_precision(precision)
         try:
             xs = [tiles[:, 3 * k:3 * k + 3].contiguous() for k in range(n_img)]
             got = model(*(xs + [None] * (6 - n_img))).cpu()
         finally:
             model.set_precision(prev)
-        model.check(device, "check_checkpoint: HIP fp32 forward")
+        model.check(device, f"check_checkpoint: HIP {precision} forward")
         if threads:
             torch.set_num_threads(threads)
         cpu_model = model
@@ -207,16 +210,16 @@ def run_f32(model, tiles: torch.Tensor, device, batch: int = 16, threads: int = 
             cpu_model._compiled = None
         x = tiles.cpu()
         ref = torch.cat([float32_forward(cpu_model, [x[lo:lo + batch, 3 * k:3 * k + 3] for k in range(n_img)]) for lo in range(0, x.shape[0], batch)])
-    return compare(got, ref, absolute=True)
+    return dict(compare(got, ref, absolute=True), engine=precision)
 
 
 def jpeg_shift(model, lossless: torch.Tensor, roundtripped: torch.Tensor, precision: str = "fp16") -> dict:
     """How far the engine's logits move between lossless tiles and the same tiles after the JPEG round trip (both as `_rendered_tiles`
     gives them): {"n", "max_abs_dlogit", "argmax_flips"}."""
     with torch.no_grad():
-        if precision == "fp32":
+        if precision in ("fp32", "bf16x3"):
             prev = model.precision
-            model.set_precision("fp32")
+            model.set_precision(precision)
             try:
                 a, b = (model(*([t[:, 3 * k:3 * k + 3].contiguous() for k in range(model.num_images)] + [None] * (6 - model.num_images))).float().cpu()
                         for t in (lossless, roundtripped))
@@ -240,8 +243,9 @@ def main(argv: List[str] = None) -> int:
     ap.add_argument("--tiles", default=None, help="directory of rendered BEV tiles; default: render synthetic tile sets here")
     ap.add_argument("-n", type=int, default=64, help="tile sets to run")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--precision", choices=("fp16", "fp32"), default="fp16",
-                    help="verifier engine to check: fp16 (the default engine; relative contract) or fp32 (the reference's precision; absolute 1e-3)")
+    ap.add_argument("--precision", choices=("fp16", "fp32", "bf16x3"), default="fp16",
+                    help="verifier engine to check: fp16 (the default engine; relative contract), fp32 (the reference's precision; absolute 1e-3) "
+                         "or bf16x3 (the fp32 engine on the bf16 matrix cores; absolute 1e-3)")
     ap.add_argument("--jpeg-quality", type=int, default=None, metavar="Q",
                     help="also report how far the logits move when the rendered tiles take the reference's JPEG round trip at quality Q (its files: 75)")
     args = ap.parse_args(argv)
@@ -260,13 +264,13 @@ def main(argv: List[str] = None) -> int:
     dev = torch.device(args.device)
     if dev.type != "cuda" or not torch.cuda.is_available():
         raise SystemExit("check_checkpoint: needs the HIP device (the engine under test has no CPU path)")
-    if args.precision == "fp32":
-        tiles = _tiles_from_dir_f32(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev, "fp32")
-        st = run_f32(model, tiles, dev)
+    if args.precision in ("fp32", "bf16x3"):
+        tiles = _tiles_from_dir_f32(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev, args.precision)
+        st = run_f32(model, tiles, dev, precision=args.precision)
     else:
         tiles = _tiles_from_dir(args.tiles, model.num_images, args.n, dev) if args.tiles else _rendered_tiles(model, args.n, dev)
         st = run(model, tiles, dev)
-    print(report(st, f"{args.checkpoint} (ResNet-{args.layers}, {model.num_images} images per set, {'fp32 engine, ' if args.precision == 'fp32' else ''}"
+    print(report(st, f"{args.checkpoint} (ResNet-{args.layers}, {model.num_images} images per set, {args.precision + ' engine, ' if args.precision != 'fp16' else ''}"
                      f"{'tiles from ' + args.tiles if args.tiles else 'tile sets rendered from synthetic panoramas'})"))
     if args.jpeg_quality is not None:
         shifted = _rendered_tiles(model, args.n, dev, args.precision, jpeg_quality=args.jpeg_quality)

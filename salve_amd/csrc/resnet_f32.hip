@@ -10,6 +10,8 @@
 //   input_nchw_to_nhwc_kernel  the caller's fp32 NCHW [B, C, H, W] -> NHWC [B, H, W, Cpad] in the workspace (pad channels 0)
 //   conv_f32_kernel            every SALVE_OP_CONV row: implicit GEMM, M = B * Ho * Wo pixels, N = Cout, K walked through ktab
 //                              (conv_f32.h: shared with the per-convolution training entries of conv_train_f32.hip)
+//   conv_bf16x3_kernel         the same rows in a handle of salve_resnet_bf16x3_create: every fp32 operand as two bf16 pieces, three
+//                              v_mfma_f32_32x32x16_bf16 per k-step (conv_bf16x3.h); everything else in this list is shared
 //   maxpool_f32_kernel         3 x 3 / 2 / pad 1
 //   avgpool_fc_f32_kernel      fp32 mean over the pixels, then the linear layer in fp32
 #include <hip/hip_runtime.h>
@@ -20,6 +22,7 @@
 #include "../../include/salve_hip.h"
 #include "salve_common.h"
 #include "conv_f32.h"
+#include "conv_bf16x3.h"
 
 namespace {
 
@@ -109,6 +112,7 @@ struct ResnetF32Handle {
     size_t in_elems = 0;        // per sample, floats of the padded NHWC input
     int n_bufs = 0;
     int num_layers = 0, in_channels = 0, in_pad = 0, ncls = 0;
+    bool bf16x3 = false;        // salve_resnet_bf16x3_create: d_weights holds the split bf16 planes (conv_bf16x3.h), same offsets
 };
 
 bool check_op_f32(const salve_resnet_op_t& o, size_t w_elems, size_t p_elems, size_t ktab_entries) {
@@ -233,6 +237,43 @@ void* salve_resnet_f32_create(int32_t num_layers, int32_t in_channels, const sal
     return h;
 }
 
+void* salve_resnet_bf16x3_create(int32_t num_layers, int32_t in_channels, const salve_resnet_op_t* ops, int32_t n_ops,
+                                 const float* weights_f32, size_t weights_bytes, const float* params_f32, size_t params_bytes,
+                                 const int32_t* ktab, size_t ktab_entries, int32_t flags) {
+    if (flags != 0) {
+        salve_fail("salve_resnet_bf16x3_create: flags must be 0 (the bf16x3 engine has one kernel selection)");
+        return nullptr;
+    }
+    // the fp32 engine's checks, program and uploads (its refusals carry its name); then the weights are split in place of the fp32 blob
+    ResnetF32Handle* h = reinterpret_cast<ResnetF32Handle*>(salve_resnet_f32_create(num_layers, in_channels, ops, n_ops, weights_f32, weights_bytes,
+                                                                                    params_f32, params_bytes, ktab, ktab_entries, 0));
+    if (!h) return nullptr;
+    uint16_t* split = nullptr;
+    if (hipMalloc(&split, weights_bytes) != hipSuccess) {
+        salve_fail("salve_resnet_bf16x3_create: hipMalloc failed");
+        salve_resnet_f32_destroy(h);
+        return nullptr;
+    }
+    bool ok = hipMemset(split, 0, weights_bytes) == hipSuccess;
+    for (const salve_resnet_op_t& o : h->ops) {
+        if (!ok || o.op != SALVE_OP_CONV) continue;
+        const long long n = (long long)o.Cout * ((long long)o.KH * o.KW * o.Cin + (o.in2_buf != SALVE_NO_BUF ? o.Cin2 : 0));
+        hipLaunchKernelGGL(split_weights_bf16x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, h->d_weights + o.w_off,
+                           split + 2 * (size_t)o.w_off, n);
+        ok = hipGetLastError() == hipSuccess;
+    }
+    ok = ok && hipDeviceSynchronize() == hipSuccess;
+    (void)hipFree(h->d_weights);
+    h->d_weights = reinterpret_cast<float*>(split);
+    h->bf16x3 = true;
+    if (!ok) {
+        salve_fail("salve_resnet_bf16x3_create: splitting the weights failed");
+        salve_resnet_f32_destroy(h);
+        return nullptr;
+    }
+    return h;
+}
+
 void salve_resnet_f32_destroy(void* handle) {
     ResnetF32Handle* h = reinterpret_cast<ResnetF32Handle*>(handle);
     if (!h) return;
@@ -294,10 +335,10 @@ int salve_resnet_f32_forward(void* handle, const float* input, int32_t batch, fl
             int st;
             if (o.Cout % 128 == 0) {
                 a.n_tiles = o.Cout / 128;
-                st = launch_conv<128>(a, s);
+                st = h->bf16x3 ? launch_conv_bf16x3<128>(a, s) : launch_conv<128>(a, s);
             } else {
                 a.n_tiles = o.Cout / 64;
-                st = launch_conv<64>(a, s);
+                st = h->bf16x3 ? launch_conv_bf16x3<64>(a, s) : launch_conv<64>(a, s);
             }
             if (st != SALVE_OK) return st;
         } else if (o.op == SALVE_OP_MAXPOOL) {

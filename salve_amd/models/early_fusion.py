@@ -9,7 +9,9 @@ salve_amd/csrc/resnet.hip.  There is no CPU or eager fallback: without the HIP l
 
 Precision: "fp16" (default; fp16 weights and activations, fp32 accumulation -- DESIGN.md section 2) or, after
 `model.set_precision("fp32")`, the reference's own float32 evaluation (salve/train_utils.py:18-41 uses no AMP) on the fp32
-engine of salve_amd/csrc/resnet_f32.hip: the input is passed as the fp32 tensor it is, with no fp16 rounding.
+engine of salve_amd/csrc/resnet_f32.hip: the input is passed as the fp32 tensor it is, with no fp16 rounding.  "bf16x3" is that
+engine with its convolutions' products on the bf16 matrix cores (three bf16 MFMAs over the operands' hi / lo pieces): the same input,
+the same fp32 activations, logits within the absolute 1e-3 contract at the released models' magnitudes.
 """
 
 from __future__ import annotations
@@ -20,7 +22,7 @@ import torch
 from torch import Tensor, nn
 
 import salve_amd.models.resnet_factory as resnet_factory
-from salve_amd.models.hip_resnet import PRECISIONS, HipResNet, HipResNetF32, nchw_to_input
+from salve_amd.models.hip_resnet import F32_FAMILY, PRECISIONS, HipResNet, HipResNetBf16x3, HipResNetF32, nchw_to_input
 
 _TWO = [{"layout"}, {"ceiling_rgb_texture"}, {"floor_rgb_texture"}]
 _FOUR = {"ceiling_rgb_texture", "floor_rgb_texture"}
@@ -56,7 +58,8 @@ class EarlyFusionCEResnet(nn.Module):
         self._compiled_key = None
 
     def set_precision(self, precision: str) -> "EarlyFusionCEResnet":
-        """"fp16" (default) or "fp32" (the reference's precision: fp32 weights, activations and arithmetic).  Returns self."""
+        """"fp16" (default), "fp32" (the reference's precision: fp32 weights, activations and arithmetic) or "bf16x3" (the fp32
+        engine with bf16 hi / lo pieces on the bf16 matrix cores).  Returns self."""
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self.precision = precision
@@ -67,17 +70,17 @@ class EarlyFusionCEResnet(nn.Module):
         return (str(device), tuple((k, v._version, v.data_ptr()) for k, v in self.state_dict().items()))
 
     def compiled(self, device: torch.device, flags: int = 0, precision: Optional[str] = None):
-        """Fold + pack the current weights for `device` (cached per weights, flags and precision): a HipResNet (fp16) or a
-        HipResNetF32 (fp32).  precision: None = the model's (`set_precision`); the pipeline passes its own.  flags: the fp16
+        """Fold + pack the current weights for `device` (cached per weights, flags and precision): a HipResNet (fp16), a
+        HipResNetF32 (fp32) or a HipResNetBf16x3 (bf16x3).  precision: None = the model's (`set_precision`); the pipeline passes its own.  flags: the fp16
         library's kernel selection (_lib.RESNET_*; 0 = the product's -- development tools and the bit-identity tests pass
-        others); the fp32 engine accepts 0 only."""
+        others); the fp32 and bf16x3 engines accept 0 only."""
         precision = self.precision if precision is None else precision
         if precision not in PRECISIONS:
             raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         key = (self._state_key(device), int(flags), precision)
         if self._compiled is None or self._compiled_key != key:
             self._compiled = None   # (the old handle's device memory goes before the new one is allocated)
-            engine = HipResNetF32 if precision == "fp32" else HipResNet
+            engine = {"fp32": HipResNetF32, "bf16x3": HipResNetBf16x3}.get(precision, HipResNet)
             self._compiled = engine(self.state_dict(), self.num_layers, device, flags=flags)
             self._compiled_key = key
         return self._compiled
@@ -87,7 +90,7 @@ class EarlyFusionCEResnet(nn.Module):
         """Early fusion = concatenation along channels (early_fusion.py:55-65), then the ResNet.
         fp16 (default): inputs must be finite -- the HIP kernels' ReLUs turn a NaN activation into 0 instead of propagating it
         to the logits as torch does (salve_amd/csrc/resnet.hip: track4) -- and magnitudes beyond fp16 are reported through
-        `check()`.  fp32 (`set_precision("fp32")`): torch.cat(xs, 1) goes to the fp32 engine unrounded; NaN propagates."""
+        `check()`.  fp32 / bf16x3 (`set_precision`): torch.cat(xs, 1) goes to the engine unrounded; NaN propagates."""
         n = num_input_images(self.modalities)  # raises RuntimeError on unsupported sets, like the reference
         xs = [x1, x2, x3, x4, x5, x6][:n]
         if any(x is None for x in xs):
@@ -97,7 +100,7 @@ class EarlyFusionCEResnet(nn.Module):
         if self.training and torch.is_grad_enabled():
             raise RuntimeError("the HIP verifier is inference-only: call model.eval() / use torch.no_grad()")
         eng = self.compiled(x1.device)
-        if self.precision == "fp32":
+        if self.precision in F32_FAMILY:
             return eng.forward_nchw(torch.cat(xs, dim=1))
         return eng.forward_nhwc(nchw_to_input(xs, eng.in_channels))
 
@@ -111,7 +114,7 @@ class EarlyFusionCEResnet(nn.Module):
 
     def forward_nhwc(self, x: Tensor) -> Tensor:
         """Fused-pipeline entry: fp16 [B,224,224,Cpad] tiles written by the rasteriser -> fp32 logits (fp16 precision only)."""
-        if self.precision == "fp32":
+        if self.precision in F32_FAMILY:
             raise RuntimeError("EarlyFusionCEResnet.forward_nhwc takes fp16 NHWC tiles: it is the fp16 engine's entry and the model is "
-                               "set to fp32 -- call forward(x1..x6) with the fp32 NCHW tensors, or set_precision(\"fp16\")")
+                               f"set to {self.precision} -- call forward(x1..x6) with the fp32 NCHW tensors, or set_precision(\"fp16\")")
         return self.compiled(x.device).forward_nhwc(x)

@@ -2,7 +2,8 @@
 
 No arithmetic of the forward pass happens here -- this module only prepares the immutable weight blobs
 (once per checkpoint) and owns the workspace; the network runs in salve_amd/csrc/resnet.hip (fp16 storage, the product's
-default) or salve_amd/csrc/resnet_f32.hip (fp32 throughout, the reference's precision: `precision="fp32"`).
+default) or salve_amd/csrc/resnet_f32.hip (fp32 throughout, the reference's precision: `precision="fp32"`; or, with
+`precision="bf16x3"`, the same engine with its convolutions' products on the bf16 matrix cores: salve_amd/csrc/conv_bf16x3.h).
 """
 
 from __future__ import annotations
@@ -39,7 +40,8 @@ def fold_bn(w: torch.Tensor, bn: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor,
     return w.float() * scale[:, None, None, None], bn["bias"].float() - bn["running_mean"].float() * scale
 
 
-PRECISIONS = ("fp16", "fp32")
+PRECISIONS = ("fp16", "fp32", "bf16x3")
+F32_FAMILY = ("fp32", "bf16x3")   # one program, one fp32 blob, fp32 NCHW input: the engines of resnet_f32.hip
 
 
 def _check_precision(precision: str) -> str:
@@ -49,7 +51,7 @@ def _check_precision(precision: str) -> str:
 
 
 class _Builder:
-    """precision "fp16" (default): `weights` holds the fp16 BITS (int16 arrays); "fp32": the same layout as float32."""
+    """precision "fp16" (default): `weights` holds the fp16 BITS (int16 arrays); "fp32" / "bf16x3": the same layout as float32."""
 
     def __init__(self, precision: str = "fp16") -> None:
         self.precision = _check_precision(precision)
@@ -62,7 +64,7 @@ class _Builder:
         self.k_elems = 0
 
     def _pack(self, w: torch.Tensor) -> np.ndarray:
-        if self.precision == "fp32":
+        if self.precision in F32_FAMILY:
             return w.float().numpy().copy()
         return w.to(torch.float16).view(torch.int16).numpy().copy()
 
@@ -146,7 +148,8 @@ def _bn(sd: Dict[str, torch.Tensor], prefix: str) -> Dict[str, torch.Tensor]:
 def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: Tuple[int, int] = (224, 224), precision: str = "fp16"):
     """state_dict with the reference's keys (conv1.weight, fc.*, resnet.*; an optional `module.` prefix from
     DataParallel is stripped) -> (ops array, fp16 weight bits, fp32 params, ktab, padded input channels).
-    precision="fp32": the same program and ktab with the weights as float32 (the fp32 engine's blob) instead of fp16 bits."""
+    precision="fp32" / "bf16x3": the same program and ktab with the weights as float32 (the fp32 engine's blob, which the bf16x3
+    engine splits on the device) instead of fp16 bits."""
     sd = {(k[len("module."):] if k.startswith("module.") else k): v.detach().cpu() for k, v in state_dict.items()}
     kind, blocks = RESNET_SPECS[num_layers]
     b = _Builder(_check_precision(precision))
@@ -188,7 +191,7 @@ def build_program(state_dict: Dict[str, torch.Tensor], num_layers: int, in_hw: T
     feat = sd["fc.weight"].shape[1]
     b.fc(sd["fc.weight"], sd["fc.bias"], x, H, W, feat)
     ops = np.array(b.ops, dtype=OP_DTYPE)
-    if precision == "fp32":
+    if precision in F32_FAMILY:
         # the fp32 engine propagates NaN as torch does, but a non-finite weight is a diverged checkpoint either way: refused as in
         # fp16.  Magnitudes beyond 65504 are fp32's to hold.
         weights = np.concatenate(b.weights).astype(np.float32)
@@ -266,12 +269,14 @@ class HipResNetF32:
     weights, activations and MFMA arithmetic, NaN propagated, no fp16 range.  Same op program as HipResNet; immutable device
     weights inside a library handle + a workspace this object owns."""
 
+    CREATE = "salve_resnet_f32_create"
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], num_layers: int, device: torch.device, flags: int = 0) -> None:
         """flags: must be 0 (the library refuses anything else; the argument exists so that callers see the refusal)."""
         self.lib = _lib.load()
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise _lib.SalveHipError("HipResNetF32 needs a HIP device ('cuda:N'); there is no CPU path")
+            raise _lib.SalveHipError(f"{type(self).__name__} needs a HIP device ('cuda:N'); there is no CPU path")
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in state_dict.items()}
         ops, weights, params, ktab, cin_p = build_program(state_dict, num_layers, precision="fp32")
         self.in_channels = int(sd["conv1.weight"].shape[1])   # the real count (6, 12, 18): the input is the reference's NCHW tensor
@@ -280,13 +285,13 @@ class HipResNetF32:
         self.n_ops = len(ops)
         self.in_hw = (int(ops[0]["Hi"]), int(ops[0]["Wi"]))
         with torch.cuda.device(self.device):
-            h = self.lib.salve_resnet_f32_create(
+            h = getattr(self.lib, self.CREATE)(
                 num_layers, self.in_channels, ops.ctypes.data_as(ctypes.c_void_p), len(ops),
                 weights.ctypes.data_as(ctypes.c_void_p), weights.nbytes, params.ctypes.data_as(ctypes.c_void_p), params.nbytes,
                 ktab.ctypes.data_as(ctypes.c_void_p), ktab.size, int(flags),
             )
         if not h:
-            _lib.check(-1, "salve_resnet_f32_create")
+            _lib.check(-1, self.CREATE)
         self.handle = ctypes.c_void_p(h)
         self._ws = None
 
@@ -323,6 +328,14 @@ class HipResNetF32:
             )
         _lib.check(st, "salve_resnet_f32_forward")
         return out
+
+
+class HipResNetBf16x3(HipResNetF32):
+    """The bf16x3 verifier on one GPU (salve_resnet_bf16x3_create): HipResNetF32's program, fp32 weight blob, fp32 input and fp32
+    activations; every convolution product a * w as ah * wh + ah * wl + al * wh on the bf16 matrix cores (salve_amd/csrc/conv_bf16x3.h).
+    Differs from HipResNetF32 in the create call only: workspace, forward and destroy are the fp32 engine's entries."""
+
+    CREATE = "salve_resnet_bf16x3_create"
 
 
 def nchw_to_input(xs: List[torch.Tensor], in_channels: int) -> torch.Tensor:

@@ -30,6 +30,7 @@ import numpy as np
 import torch
 
 from salve_amd import _lib, status, tracing
+from salve_amd.models.hip_resnet import F32_FAMILY, PRECISIONS
 from salve_amd.rasteriser import SURFACES, BevRasteriser, pack_hypotheses
 from salve_amd.synthetic import HypothesisTable
 
@@ -102,14 +103,17 @@ class RenderVerifyPipeline:
         precision: "fp16" (default: fp16 NHWC tiles, the fp16 verifier engine) or "fp32" -- the reference's precision: fp32 NCHW tiles
         [chunk, 3 n, 224, 224] (salve_bev_tiles, SALVE_TILE_F32_NCHW: the same LUT values, not rounded to fp16) into the fp32 engine.
         fp32 renders its tiles with launches of their own (fuse_tiles is forced off) and does not support the layout modality.
+        "bf16x3": exactly the fp32 mode's tile path (the same fp32 NCHW tiles, the same refusal of the layout modality) into the bf16x3
+        engine (HipResNetBf16x3).
         jpeg_quality: None (default): the tiles come from the lossless renders.  An integer (the reference's files: 75): every render and
         layout image goes through the reference's JPEG round trip on the device first (BevRasteriser.jpeg_roundtrip; the posed images
         per launch, the kept identity images once), so the tiles equal those of the files scripts/test.py reads; the tiles then come
         from launches of their own (fuse_tiles is forced off).  Both precisions."""
         self.device = torch.device(device)
-        if precision not in ("fp16", "fp32"):
-            raise ValueError(f"precision must be 'fp16' or 'fp32', got {precision!r}")
+        if precision not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
         self.precision = precision
+        self.f32_tiles = precision in F32_FAMILY   # "fp32" and "bf16x3": one tile path, fp32 NCHW into an engine of resnet_f32.hip
         # the status word is one per device: a bit an earlier, unchecked caller left behind must be reported as ITS failure,
         # not raised later by this pipeline's check() under the wrong name
         status.check(self.device, "a launch issued before this RenderVerifyPipeline was created")
@@ -120,8 +124,8 @@ class RenderVerifyPipeline:
         self.fuse_tiles = bool(fuse_tiles) and precision == "fp16" and self.jpeg_quality is None
         self.surfaces = surfaces_for(model.modalities)
         self.has_layout = "layout" in set(model.modalities)
-        if precision == "fp32" and self.has_layout:
-            raise ValueError('RenderVerifyPipeline(precision="fp32") does not support the "layout" modality (its tiles are fp16 only)')
+        if self.f32_tiles and self.has_layout:
+            raise ValueError(f'RenderVerifyPipeline(precision="{precision}") does not support the "layout" modality (its tiles are fp16 only)')
         self.engine = model.compiled(self.device, precision=precision)
         self.ras = BevRasteriser(self.device, pano_hw=pano_hw)
         S = len(self.surfaces)
@@ -139,7 +143,7 @@ class RenderVerifyPipeline:
         self.nbuf = nbuf
         self.bevs = [torch.empty((chunk * S, Hb, Wb), dtype=torch.int32, device=self.device) for _ in range(self.nbuf)]
         # tiles: fp16 NHWC, pad channels (never written) stay zero; fp32: NCHW with the real channel count, every channel written
-        if precision == "fp32":
+        if self.f32_tiles:
             self.tile_bufs = [torch.zeros((chunk, self.engine.in_channels, self.ras.crop, self.ras.crop), dtype=torch.float32,
                                           device=self.device) for _ in range(self.nbuf)]
         else:
@@ -171,7 +175,7 @@ class RenderVerifyPipeline:
         Hb, Wb = self.ras.bev_hw
         lib = self.ras.lib
         ws_render = lib.salve_bev_workspace_bytes(ctypes.byref(self.ras.cfg), 2) - lib.salve_bev_workspace_bytes(ctypes.byref(self.ras.cfg), 1)
-        if self.precision == "fp32":
+        if self.f32_tiles:
             act = self.engine.workspace_bytes(2) - self.engine.workspace_bytes(1)
             tile = self.ras.crop * self.ras.crop * self.engine.in_channels * 4
         else:
@@ -278,7 +282,7 @@ class RenderVerifyPipeline:
             "rjobs_a": self.ras.upload_tile_jobs(np.zeros(N * S, dtype=np.int64), rj_slot, rj_chan_a),
             "rjobs_b": self.ras.upload_tile_jobs(rj_ident, rj_slot, rj_chan_b, pretiled=True),
             # fp32 tiles: the identity renders' tiles straight from self.ref_bev (salve_bev_tiles has no pretiled input)
-            "jobs2_bev": self.ras.upload_tile_jobs(st(jobs2_bev), st(jobs2_slot), st(jobs2_chan)) if self.precision == "fp32" else None,
+            "jobs2_bev": self.ras.upload_tile_jobs(st(jobs2_bev), st(jobs2_slot), st(jobs2_chan)) if self.f32_tiles else None,
             "in_window": torch.zeros(N * S, dtype=torch.int32, device=self.device),  # posed renders IN RENDER ORDER, filled by score()
             "ready": torch.cuda.Event(),   # the tables are on the device: launches on other streams wait for it
         }
@@ -348,7 +352,7 @@ class RenderVerifyPipeline:
             if self.jpeg_quality is not None:
                 with tracing.range("salve.jpeg"):
                     self.ras.jpeg_roundtrip(bev[:n * S], self.jpeg_quality, out=bev[:n * S])
-            if self.precision == "fp32":
+            if self.f32_tiles:
                 with tracing.range("salve.tiles"):
                     # fp32 NCHW tiles of the posed renders (this chunk's images) and of the identity renders (ref_bev), in the channel
                     # and pair order of the fp16 job tables; a call takes at most 65535 jobs
@@ -376,7 +380,7 @@ class RenderVerifyPipeline:
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
         with tracing.range("salve.verify"):
-            if self.precision == "fp32":
+            if self.f32_tiles:
                 self.engine.forward_nchw(self.tile_bufs[buf][:n], out=out)
             else:
                 self.engine.forward_nhwc(self.tile_bufs[buf][:n], out=out)
