@@ -51,7 +51,8 @@ typedef enum {
                                         and salve_jpeg_segment_t), salve_bev_jpeg_decode_sampled / _lanes_sampled (with their two
                                         _workspace_bytes queries and SALVE_JPEG_SAMPLING_*), salve_bev_train_tiles_jitter (with
                                         salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t), salve_bev_pair_overlap (with
-                                        salve_overlap_job_t) */
+                                        salve_overlap_job_t), salve_pose_graph_solve (with salve_pose_graph_workspace_bytes, the salve_graph_*_t
+                                        records and SALVE_STATUS_BAD_GRAPH_ROW) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -71,6 +72,9 @@ typedef enum {
                                          other listed slots are updated */
 #define SALVE_STATUS_BAD_LAYOUT 64 /* layout_pose: an image record names a panorama outside [0, n_panos), offsets outside the output capacities,
                                       or a posed coordinate lies beyond 2^24 pixels -- that image's record is written empty, the others are posed */
+#define SALVE_STATUS_BAD_GRAPH_ROW 128 /* pose_graph_solve: a floor's rows are not sorted by (i1, i2), a row has i1 >= i2 or an index outside
+                                          [0, n_nodes), the floor's row range is malformed or its n_nodes lies outside [0, max_nodes] -- that
+                                          floor's outputs are written EMPTY (no chosen row, nothing localized, origin -1), the others are solved */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -411,6 +415,77 @@ typedef struct {
 } salve_overlap_job_t;
 int salve_bev_pair_overlap(const uint32_t* bev_a, int32_t n_bev_a, const uint32_t* bev_b, int32_t n_bev_b, int32_t bev_h, int32_t bev_w,
                            const salve_overlap_job_t* jobs, int32_t n_jobs, int32_t* out, int32_t* status, void* stream);
+
+/* The floor pose graph: scored alignment hypotheses -> one global Sim(2) pose per panorama, for any number of floors in ONE launch.  Stands
+ * behind the `spanning_tree` method of the reference's scripts/run_sfm.py:112-152 and :440-446 (with and without the cycle filter):
+ *   salve/common/edge_classification.py:213-251  get_conf_thresholded_edge_measurements   (phase A: candidate rows)
+ *   salve/common/edge_classification.py:254-311  get_most_likely_relative_pose_per_edge   (phase A: the best row of a pair)
+ *   salve/algorithms/cycle_consistency.py:26-91   extract_triplets, create_adjacency_list   (phase B: adjacency bitmasks)
+ *   salve/algorithms/cycle_consistency.py:172-222 compute_SE2_cycle_error                   (phase B: the error of one 3-cycle)
+ *   salve/algorithms/cycle_consistency.py:225-303 filter_to_SE2_cycle_consistent_edges      (phase B: consistent edges)
+ *   salve/algorithms/spanning_tree.py:73-141      greedily_construct_st_Sim2                (phases C, D: component, tree, poses)
+ * A, best row per pair: a row is a candidate iff y_hat == 1 && prob >= confidence_threshold (a NaN prob never is); a pair's chosen row is
+ *    its candidate of largest prob, among equal probs the FIRST in row order (np.argmax; the reference's order among equals is its glob order).
+ * B, 3-cycles: for every cycle a < b < c of chosen edges, i0Si0 = (inverse(S_ac).compose(S_bc)).compose(S_ab) under the rules of the
+ *    reference's Sim2 (R, t float32, products and sums unfused; (float)(1.0 / s) and (float)s enter the float32 products; scales float64);
+ *    rot_err = |atan2f(R10, R00)| * (float)(180 / pi), trans_err = sqrtf(tx * tx + ty * ty); the cycle is consistent iff rot_err <
+ *    rot_threshold_deg && trans_err < trans_threshold (NaN never is; trans_threshold = +inf is the rotation-only filter).  An edge is
+ *    consistent iff it lies in a consistent cycle.
+ * C, component: the graph is the consistent edges (cycle_filter = 1) or the chosen edges (0).  The largest connected component wins, among
+ *    equally large ones the one that holds the lowest node (the reference's tie is networkx's iteration order); its lowest node is the origin.
+ * D, tree: level-synchronous BFS from the origin; a node's parent is its LOWEST-index neighbour in the previous level; wS_v =
+ *    wS_parent.compose(parentS_v), parentS_v = inverse(S_(p, v)) for p < v and S_(v, p) otherwise; the origin is (I, 0, 1).  That is the
+ *    reference's left fold along a shortest path, bit for bit where the shortest path is unique; among several the reference takes whichever
+ *    networkx's bidirectional search returns.
+ *   rows            device salve_graph_row_t [floor_start[n_floors]], 8-byte aligned: one scored hypothesis each.  The rows of floor f are
+ *                   floor_start[f] .. floor_start[f + 1] - 1, sorted by (i1, i2), with 0 <= i1 < i2 < n_nodes[f] (compact node indices).
+ *   n_rows          the length of `rows`: a floor_start entry outside [0, n_rows] or a decreasing one is a malformed floor
+ *   floor_start     device int32 [n_floors + 1];  n_nodes: device int32 [n_floors]
+ *   max_nodes       the caller's bound on n_nodes[]: sizes the workgroup's LDS and the stride of out_nodes.  1 .. 256 (SALVE_GRAPH_MAX_NODES);
+ *                   more is SALVE_ERR_BAD_ARG before anything is launched.  A floor with n_nodes[f] > max_nodes is a malformed floor.
+ *   out_rows        device salve_graph_row_out_t [n_rows], 8-byte aligned: row r's flags and, for a chosen row, its edge's statistics over the
+ *                   3-cycles through it (a row that is not chosen, or an edge in no cycle: 0, 0, +inf, +inf)
+ *   out_nodes       device salve_graph_node_out_t [n_floors * max_nodes], 8-byte aligned: node v of floor f is record f * max_nodes + v; the
+ *                   records v >= n_nodes[f] are NOT written.  A node that is not localized: 0, -1, -1, zeros.
+ *   out_floors      device salve_graph_floor_out_t [n_floors]
+ *   status          device int32 status word or NULL.  The tables are device memory, so the kernel verifies them before it forms an address
+ *                   from them: a malformed floor is written EMPTY and raises SALVE_STATUS_BAD_GRAPH_ROW.
+ *   workspace       unused today (salve_pose_graph_workspace_bytes returns 0; NULL is accepted): the floor's graph lives in LDS
+ * One launch on `stream`, one workgroup of 256 threads per floor; n_floors == 0 launches nothing.  Every output the call documents is
+ * written, none needs zeroing, and no value depends on an arrival order: the same bytes on every run.  SALVE_ERR_BAD_ARG for a negative
+ * count, max_nodes outside 1 .. 256, cycle_filter outside {0, 1}, a NaN threshold, and -- with n_floors > 0 -- a null or misaligned pointer
+ * (rows and out_rows may be null while n_rows == 0). */
+#define SALVE_GRAPH_MAX_NODES 256
+typedef struct {
+    int32_t i1, i2;  /* compact node indices within the floor, i1 < i2 */
+    float prob;      /* probability of the predicted class (the prediction files' y_hat_probs) */
+    int32_t y_hat;   /* predicted class */
+    float R[4];      /* i2Si1: rotation, row-major */
+    float t[2];      /*        translation */
+    double s;        /*        scale */
+} salve_graph_row_t;
+typedef struct {
+    int32_t chosen, consistent;    /* 0 / 1 */
+    int32_t n_triplets;            /* 3-cycles of chosen edges through this edge */
+    int32_t n_consistent;          /* ... of which consistent */
+    float min_rot_err, min_trans_err; /* the smallest errors over those cycles (each on its own), +inf without one; a NaN error never lowers them */
+} salve_graph_row_out_t;
+typedef struct {
+    int32_t localized;             /* 0 / 1 */
+    int32_t parent, depth;         /* BFS tree: the origin has parent -1 and depth 0 */
+    int32_t reserved;              /* written 0 */
+    float R[4];                    /* wSi */
+    float t[2];
+    double s;
+} salve_graph_node_out_t;
+typedef struct {
+    int32_t n_chosen, n_triplets, n_consistent_triplets, n_consistent_edges, n_localized, origin; /* origin: -1 when the graph has no edge */
+} salve_graph_floor_out_t;
+size_t salve_pose_graph_workspace_bytes(int32_t n_floors, int32_t max_nodes);
+int salve_pose_graph_solve(const salve_graph_row_t* rows, int32_t n_rows, const int32_t* floor_start, const int32_t* n_nodes, int32_t n_floors,
+                           int32_t max_nodes, float confidence_threshold, float rot_threshold_deg, float trans_threshold, int32_t cycle_filter,
+                           salve_graph_row_out_t* out_rows, salve_graph_node_out_t* out_nodes, salve_graph_floor_out_t* out_floors,
+                           void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

@@ -105,6 +105,8 @@ EXPORTED_SYMBOLS = (
     "salve_flat_pack",
     "salve_flat_unpack",
     "salve_bev_pair_overlap",
+    "salve_pose_graph_workspace_bytes",
+    "salve_pose_graph_solve",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -119,6 +121,7 @@ STATUS_LAYOUT_THICKNESS = 8
 STATUS_BAD_TILE_JOB = 16
 STATUS_BAD_PANO_SLOT = 32
 STATUS_BAD_LAYOUT = 64
+STATUS_BAD_GRAPH_ROW = 128
 
 
 class BevConfig(ctypes.Structure):
@@ -152,6 +155,16 @@ TILE_HFLIP, TILE_VFLIP = 1, 2
 assert LAYOUT_POSE_DTYPE.itemsize == 48 and HYP_DTYPE.itemsize == 40 and TILE_JOB_DTYPE.itemsize == 16 and TILE_AUG_DTYPE.itemsize == 16
 OVERLAP_JOB_DTYPE = np.dtype([("a", "<i4"), ("b", "<i4")])   # salve_overlap_job_t (salve_bev_pair_overlap): image index into bev_a / bev_b
 assert OVERLAP_JOB_DTYPE.itemsize == 8
+# salve_pose_graph_solve (include/salve_hip.h: salve_graph_row_t and the three output records)
+GRAPH_MAX_NODES = 256
+GRAPH_ROW_DTYPE = np.dtype([("i1", "<i4"), ("i2", "<i4"), ("prob", "<f4"), ("y_hat", "<i4"), ("R", "<f4", (4,)), ("t", "<f4", (2,)), ("s", "<f8")])
+GRAPH_ROW_OUT_DTYPE = np.dtype([("chosen", "<i4"), ("consistent", "<i4"), ("n_triplets", "<i4"), ("n_consistent", "<i4"), ("min_rot_err", "<f4"),
+                                ("min_trans_err", "<f4")])
+GRAPH_NODE_OUT_DTYPE = np.dtype([("localized", "<i4"), ("parent", "<i4"), ("depth", "<i4"), ("reserved", "<i4"), ("R", "<f4", (4,)), ("t", "<f4", (2,)),
+                                 ("s", "<f8")])
+GRAPH_FLOOR_OUT_DTYPE = np.dtype([("n_chosen", "<i4"), ("n_triplets", "<i4"), ("n_consistent_triplets", "<i4"), ("n_consistent_edges", "<i4"),
+                                  ("n_localized", "<i4"), ("origin", "<i4")])
+assert GRAPH_ROW_DTYPE.itemsize == 48 and GRAPH_ROW_OUT_DTYPE.itemsize == 24 and GRAPH_NODE_OUT_DTYPE.itemsize == 48 and GRAPH_FLOOR_OUT_DTYPE.itemsize == 24
 # salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
 TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
                               ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
@@ -299,6 +312,11 @@ def load() -> ctypes.CDLL:
     lib.salve_bev_train_tiles_jitter.restype = ctypes.c_int
     lib.salve_bev_pair_overlap.argtypes = [vp, i32, vp, i32, i32, i32, vp, i32, vp, vp, vp]   # bev_a, n_a, bev_b, n_b, h, w, jobs, n_jobs, out, status, stream
     lib.salve_bev_pair_overlap.restype = ctypes.c_int
+    lib.salve_pose_graph_workspace_bytes.argtypes = [i32, i32]
+    lib.salve_pose_graph_workspace_bytes.restype = sz
+    # rows, n_rows, floor_start, n_nodes, n_floors, max_nodes, confidence, rot_deg, trans, cycle_filter, out_rows, out_nodes, out_floors, ws, ws_bytes, status, stream
+    lib.salve_pose_graph_solve.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32, vp, vp, vp, vp, sz, vp, vp]
+    lib.salve_pose_graph_solve.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -398,6 +416,9 @@ def check_status_word(word: int, what: str) -> None:
     if word & STATUS_BAD_LAYOUT:
         raise SalveHipError(f"{what}: a layout image record names a panorama outside the layout tables or output outside its tables, or a "
                             "posed coordinate lies more than 2^24 pixels away; that layout image is empty")
+    if word & STATUS_BAD_GRAPH_ROW:
+        raise SalveHipError(f"{what}: a floor's pose-graph rows are not sorted by (i1, i2), name a node outside the floor or have i1 >= i2 (or the "
+                            "floor's extents are malformed); that floor was written empty")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

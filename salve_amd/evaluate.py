@@ -223,7 +223,7 @@ def evaluate_model(serialization_save_dir: str, ckpt_fpath: str, args, split: st
 @torch.no_grad()
 def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_true: Optional[np.ndarray], serialization_save_dir: str,
                     batch_size: int = 64, ckpt_fpath: str = "", split: str = "test", world: int = 1, rank: int = 0,
-                    visual_overlap: bool = False) -> Dict[str, Any]:
+                    visual_overlap: bool = False, return_rows: bool = False) -> Dict[str, Any]:
     """Render + verify a hypothesis table on the GPU (pipeline.RenderVerifyPipeline) and write the SAME prediction
     files as run_test_epoch.  `hypotheses`, `tile_names` and `y_true` describe the WHOLE table on every rank;
     `tile_names[j]` = (fp0, fp1): the tile paths the un-fused path would have written for hypothesis j
@@ -238,7 +238,11 @@ def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_tru
     reference's overlap analysis takes from the two tile files fp0 / fp1 name (scripts/measure_acc_vs_overlap.py:77-80) -- counted on the
     device (RenderVerifyPipeline.score(visual_overlap=True)) for the surface those names carry: the floor where the model has a floor
     surface, else the ceiling (zind_data.py:290-328).  salve_amd.overlap reads the key.  The other keys and their values are unchanged.
-    With world > 1 the two counts ride in the one all-gather as two more fp32 columns, exact up to 2^24 pixels per image."""
+    With world > 1 the two counts ride in the one all-gather as two more fp32 columns, exact up to 2^24 pixels per image.
+
+    return_rows: the result also carries "rows" = {"kept": indices of the hypotheses that were written, in file order, "y_hat", "prob": their
+    predicted class and its probability, as the files hold them} -- what salve_amd.pose_graph.EdgeMeasurements.from_floor takes, without reading
+    the files back.  Launches, files and the other keys are unchanged."""
     from salve_amd.pipeline import gather_logits
 
     n_all = len(hypotheses)
@@ -282,4 +286,7 @@ def run_fused_epoch(pipe, hypotheses, tile_names: Sequence[Sequence[str]], y_tru
     out = _summary(split, ckpt_fpath, cls, pr)
     out["num_hypotheses"] = n_all
     out["num_dropped_no_points_in_window"] = n_all - n
+    if return_rows:
+        out["rows"] = {"kept": keep.cpu().numpy(), "y_hat": y_hat.cpu().numpy(),
+                       "prob": probs[torch.arange(n, device=probs.device), y_hat].cpu().numpy()}
     return out
