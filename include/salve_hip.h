@@ -52,7 +52,8 @@ typedef enum {
                                         _workspace_bytes queries and SALVE_JPEG_SAMPLING_*), salve_bev_train_tiles_jitter (with
                                         salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t), salve_bev_pair_overlap (with
                                         salve_overlap_job_t), salve_pose_graph_solve (with salve_pose_graph_workspace_bytes, the salve_graph_*_t
-                                        records and SALVE_STATUS_BAD_GRAPH_ROW) */
+                                        records and SALVE_STATUS_BAD_GRAPH_ROW), salve_pose_graph_sample_trees (with
+                                        salve_pose_graph_sample_workspace_bytes, salve_graph_tree_out_t and salve_graph_sample_floor_out_t) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -486,6 +487,68 @@ int salve_pose_graph_solve(const salve_graph_row_t* rows, int32_t n_rows, const 
                            int32_t max_nodes, float confidence_threshold, float rot_threshold_deg, float trans_threshold, int32_t cycle_filter,
                            salve_graph_row_out_t* out_rows, salve_graph_node_out_t* out_nodes, salve_graph_floor_out_t* out_floors,
                            void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
+/* RANSAC over random spanning trees: the `random_spanning_trees` method of the reference's scripts/run_sfm.py and its edge filter
+ * --filter_edges_by_random_spanning_trees, for any number of floors and hypotheses in ONE call (two launches on `stream`).  Stands behind
+ *   salve/algorithms/spanning_tree.py:179-334  ransac_spanning_trees
+ *   salve/algorithms/spanning_tree.py:337-384  compute_hypothesis_errors
+ *   salve/algorithms/spanning_tree.py:144-176  compute_objective_function_improvement
+ * The subsets are DRAWN BY THE CALLER (salve_amd.pose_graph.draw_hypotheses draws the reference's); the device never draws, so every output
+ * is the same bytes on every run.  rows, n_rows, floor_start, n_nodes, max_nodes: exactly salve_pose_graph_solve's, verified the same way.
+ *   hyp_start   device int32 [n_floors + 1]: the hypotheses of floor f are hyp_start[f] .. hyp_start[f + 1] - 1
+ *   hyp_mask    device uint32 [n_hyps][mask_words]: bit k (word k / 32, bit k % 32) of a hypothesis's mask stands for the floor's row
+ *               floor_start[f] + k.  Bits at or beyond the floor's row count and bits on rows that are not candidates are IGNORED; a row
+ *               beyond 32 * mask_words has no bit.  May be null while mask_words == 0.
+ * Launch 1, one workgroup of 256 threads per hypothesis:
+ * A', edges: a row is a candidate iff y_hat == 1 && prob >= confidence_threshold (a NaN prob never is).  Of a pair's contiguous rows the
+ *    hypothesis takes the LAST candidate whose mask bit is set -- the reference's dict overwrite in measurement order (:256-258), NOT the
+ *    largest prob as salve_pose_graph_solve does.
+ * C, D: salve_pose_graph_solve's, over those edges, with its tie rules.  The node records go to the workspace.
+ * E, errors against ALL candidate rows of the floor, masked or not.  A row whose two ends are localized is MEASURED:
+ *    Z = inverse(wS_i2).compose(wS_i1); th_sim = (double)(atan2f(Z.R10, Z.R00) * C), th_m the same from the row's own R, where C is the
+ *    float32 quotient 180.0f / (float)pi = 57.295776 (numpy's float32 rad2deg; not the (float)(180 / pi) of phase B);
+ *    d = fmod(th_m - th_sim + 180.0, 360.0), + 360.0 if d < 0; rot_err = fabs(d - 180.0), all float64;
+ *    trans_err = (double)sqrtf(dx * dx + dy * dy) on the float32 differences of the two translations.
+ *    The sums are float64 in ONE order: thread t adds its rows lo + t, lo + t + 256, ... ascending from 0.0; the 256 partial sums are folded
+ *    by halving (p[t] += p[t + 128], then 64, ... 1).  avg = sum / (double)n_measured: NaN without a measured row (np.mean([])), NaN with a
+ *    NaN error; every NaN average is written as the quiet NaN 0x7FF8000000000000.  The reference's medians are not computed.
+ * Launch 2, one workgroup per floor: one thread scans the floor's hypotheses in order, in float64, from best_rot = best_trans = +inf,
+ *    best_n = 0: obj = ((best_rot - rot) / 5 + (best_trans - trans) / 1) + 1.33 * (-(best_n - n) / (best_n + 1e-10)); the hypothesis
+ *    replaces the best iff obj > 0 (a NaN never does).  The winner's node records are copied to out_nodes, and out_inlier[r] = 1 for the
+ *    rows that are candidates AND in the winner's mask (the reference's best_hypothesis), 0 for every other row of the floor.
+ *    A floor without a hypothesis, or whose every hypothesis scores NaN, has best == -1, empty nodes and no inlier (the reference would
+ *    crash at len(None): a documented deviation).
+ *   out_trees   device salve_graph_tree_out_t [n_hyps], 8-byte aligned.  A hypothesis in no floor's extent: empty, floor == -1.
+ *   out_inlier  device int32 [n_rows];  out_nodes: as salve_pose_graph_solve's, the WINNER's;  out_floors: 8-byte aligned
+ *   workspace   salve_pose_graph_sample_workspace_bytes(n_hyps, max_nodes) bytes, 8-byte aligned: a node record per hypothesis and node
+ * Malformed floors: a bad row extent or node count, rows that break the row contract, a hyp_start extent outside [0, n_hyps] or decreasing,
+ * or one that overlaps a LOWER floor's extent (a hypothesis belongs to the lowest floor whose well-formed extent holds it).  Such a floor is
+ * written EMPTY (its hypotheses' records too) and raises SALVE_STATUS_BAD_GRAPH_ROW; the other floors are solved.  Every table is verified
+ * before an address is formed from it.  n_floors == 0 or n_hyps == 0 launches nothing and writes nothing.
+ * SALVE_ERR_BAD_ARG for a negative count, max_nodes outside 1 .. 256, a NaN threshold, and -- with something to launch -- a null or
+ * misaligned pointer (rows and out_inlier may be null while n_rows == 0); SALVE_ERR_WORKSPACE for a short workspace. */
+typedef struct {
+    double avg_rot_err, avg_trans_err; /* mean over the measured rows, degrees and metres */
+    int32_t n_localized;               /* the size of the tree's component (the reference's num_poses_estimated) */
+    int32_t n_measured;                /* candidate rows with both ends localized */
+    int32_t n_edges;                   /* distinct pairs of the hypothesis */
+    int32_t origin;                    /* -1: no edge */
+    int32_t floor;                     /* the floor it was evaluated for; -1: none */
+    int32_t reserved;                  /* written 0 */
+} salve_graph_tree_out_t;
+typedef struct {
+    int32_t best;                      /* index within the floor's hypotheses; -1: none */
+    int32_t n_candidates;              /* the reference's K */
+    int32_t n_hyps;
+    int32_t n_improvements;            /* how often the scan replaced its best */
+    double avg_rot_err, avg_trans_err; /* the winner's; NaN without one */
+} salve_graph_sample_floor_out_t;
+size_t salve_pose_graph_sample_workspace_bytes(int32_t n_hyps, int32_t max_nodes);
+int salve_pose_graph_sample_trees(const salve_graph_row_t* rows, int32_t n_rows, const int32_t* floor_start, const int32_t* n_nodes,
+                                  int32_t n_floors, int32_t max_nodes, float confidence_threshold, const int32_t* hyp_start,
+                                  const uint32_t* hyp_mask, int32_t n_hyps, int32_t mask_words, salve_graph_tree_out_t* out_trees,
+                                  int32_t* out_inlier, salve_graph_node_out_t* out_nodes, salve_graph_sample_floor_out_t* out_floors,
+                                  void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

@@ -107,6 +107,8 @@ EXPORTED_SYMBOLS = (
     "salve_bev_pair_overlap",
     "salve_pose_graph_workspace_bytes",
     "salve_pose_graph_solve",
+    "salve_pose_graph_sample_workspace_bytes",
+    "salve_pose_graph_sample_trees",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -165,6 +167,12 @@ GRAPH_NODE_OUT_DTYPE = np.dtype([("localized", "<i4"), ("parent", "<i4"), ("dept
 GRAPH_FLOOR_OUT_DTYPE = np.dtype([("n_chosen", "<i4"), ("n_triplets", "<i4"), ("n_consistent_triplets", "<i4"), ("n_consistent_edges", "<i4"),
                                   ("n_localized", "<i4"), ("origin", "<i4")])
 assert GRAPH_ROW_DTYPE.itemsize == 48 and GRAPH_ROW_OUT_DTYPE.itemsize == 24 and GRAPH_NODE_OUT_DTYPE.itemsize == 48 and GRAPH_FLOOR_OUT_DTYPE.itemsize == 24
+# salve_pose_graph_sample_trees (salve_graph_tree_out_t, salve_graph_sample_floor_out_t)
+GRAPH_TREE_OUT_DTYPE = np.dtype([("avg_rot_err", "<f8"), ("avg_trans_err", "<f8"), ("n_localized", "<i4"), ("n_measured", "<i4"), ("n_edges", "<i4"),
+                                 ("origin", "<i4"), ("floor", "<i4"), ("reserved", "<i4")])
+GRAPH_SAMPLE_FLOOR_OUT_DTYPE = np.dtype([("best", "<i4"), ("n_candidates", "<i4"), ("n_hyps", "<i4"), ("n_improvements", "<i4"), ("avg_rot_err", "<f8"),
+                                         ("avg_trans_err", "<f8")])
+assert GRAPH_TREE_OUT_DTYPE.itemsize == 40 and GRAPH_SAMPLE_FLOOR_OUT_DTYPE.itemsize == 32
 # salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
 TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
                               ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
@@ -317,6 +325,12 @@ def load() -> ctypes.CDLL:
     # rows, n_rows, floor_start, n_nodes, n_floors, max_nodes, confidence, rot_deg, trans, cycle_filter, out_rows, out_nodes, out_floors, ws, ws_bytes, status, stream
     lib.salve_pose_graph_solve.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, ctypes.c_float, i32, vp, vp, vp, vp, sz, vp, vp]
     lib.salve_pose_graph_solve.restype = ctypes.c_int
+    lib.salve_pose_graph_sample_workspace_bytes.argtypes = [i32, i32]
+    lib.salve_pose_graph_sample_workspace_bytes.restype = sz
+    # rows, n_rows, floor_start, n_nodes, n_floors, max_nodes, confidence, hyp_start, hyp_mask, n_hyps, mask_words, out_trees, out_inlier, out_nodes,
+    # out_floors, ws, ws_bytes, status, stream
+    lib.salve_pose_graph_sample_trees.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp, vp]
+    lib.salve_pose_graph_sample_trees.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]

@@ -289,8 +289,9 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     (what `python -m salve_amd.overlap` bins accuracy by).  jpeg_quality: RenderVerifyPipeline's (75: tiles and counts are those of the
     reference's JPEG files).
     pose_graph: None, or the keyword arguments of salve_amd.pose_graph.solve (confidence_threshold is required; cycle_filter,
-    rot_threshold_deg, trans_threshold) -- the floor's pose graph is solved right behind scoring, from the rows still in memory: the result
-    gains "pose_graph" (a pose_graph.FloorSolution; None when no hypothesis was scored) and `serialization_save_dir` one more file,
+    rot_threshold_deg, trans_threshold) and of pose_graph.run (method, filter_by_random_spanning_trees, num_hypotheses, sampling_fraction,
+    seed: the best of many random spanning trees, as a method or as an edge filter) -- the floor's pose graph is solved right behind scoring, from the rows still in memory: the result
+    gains "pose_graph" (a pose_graph.FloorSolution, or a TreeSampleSolution for method "random_spanning_trees"; None when no hypothesis was scored) and `serialization_save_dir` one more file,
     pose_graph_{building}_{floor}.json, equal to what `python -m salve_amd.pose_graph` makes of the prediction files.  None: launches, files
     and the returned dict are unchanged."""
     from salve_amd import evaluate
@@ -310,7 +311,7 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     from salve_amd import pose_graph as pg
 
     rows = out.pop("rows")
-    solved = pg.solve(pg.EdgeMeasurements.from_floor(hyps, rows["kept"], rows["y_hat"], rows["prob"]), device=device, **pose_graph)
+    solved = pg.run(pg.EdgeMeasurements.from_floor(hyps, rows["kept"], rows["y_hat"], rows["prob"]), device=device, **pose_graph)
     out["pose_graph"] = solved[0] if solved else None
     if solved:
         pg.write_json(solved[0], serialization_save_dir)

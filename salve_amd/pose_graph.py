@@ -3,6 +3,7 @@ scripts/run_sfm.py:112-152 and :440-446, with and without its cycle filter, for 
 (include/salve_hip.h: salve_pose_graph_solve; salve_amd/csrc/pose_graph.hip).
 
     python -m salve_amd.pose_graph PRED_DIR --hypotheses ROOT --confidence-threshold X [--no-cycle-filter] [--rot-deg D] [--trans T] [--out DIR]
+        [--method {spanning_tree,random_spanning_trees}] [--filter-by-random-spanning-trees] [--num-hypotheses H] [--sampling-fraction F] [--seed S]
 
 reads the `batch_*.json` prediction files of PRED_DIR (evaluate.run_test_epoch, evaluate.run_fused_epoch, ingest.score_floor), looks every
 prediction's alignment hypothesis up under ROOT, and writes one `pose_graph_{building}_{floor}.json` per floor.
@@ -14,8 +15,15 @@ The steps, and the reference functions they stand behind:
   4. the relative poses are chained along a spanning tree of the largest component   (spanning_tree.py:73-141)
 Where the reference leaves a choice to an unspecified iteration order, this module fixes it: among equally probable
 predictions of a pair the first in row order, among equally large components the one with the lowest panorama, among several shortest paths
-the one through the lowest-index neighbour of the previous BFS level.  Pose-graph optimisation, RANSAC over spanning trees, axis alignment
-and the evaluation against ground truth are NOT here.  A floor may have at most 256 panoramas.
+the one through the lowest-index neighbour of the previous BFS level.
+
+The second method, `random_spanning_trees` (spanning_tree.py:179-384): `draw_hypotheses` draws the reference's random
+subsets of the thresholded predictions on the host, `sample_trees` builds every subset's spanning tree, scores it against ALL thresholded
+predictions and picks the reference's winner, all floors and hypotheses in one call (salve_pose_graph_sample_trees;
+salve_amd/csrc/pose_graph_sample.hip).  The winner's subset is also the reference's edge filter in front of the first method:
+`solve(meas, thr, keep_rows=combined_inlier_mask(sample_trees(meas, thr)))`.
+
+Pose-graph optimisation, axis alignment and the evaluation against ground truth are NOT here.  A floor may have at most 256 panoramas.
 """
 
 from __future__ import annotations
@@ -24,6 +32,7 @@ import argparse
 import ctypes
 import glob
 import json
+import math
 import os
 import re
 import sys
@@ -187,12 +196,33 @@ def _align8(n: int) -> int:
     return (n + 7) & ~7
 
 
+def _device_table(meas: EdgeMeasurements, floors: List[Dict[str, Any]], what: str):
+    """(rows as GRAPH_ROW_DTYPE records in the floors' sorted order, floor_start, n_nodes, max_nodes) of `floors` (EdgeMeasurements.compact)."""
+    order = np.concatenate([fl["rows"] for fl in floors]).astype(np.int64)
+    N = len(order)
+    table = np.zeros(N, dtype=_lib.GRAPH_ROW_DTYPE)
+    table["i1"], table["i2"] = np.concatenate([fl["c1"] for fl in floors]), np.concatenate([fl["c2"] for fl in floors])
+    table["prob"], table["y_hat"] = meas.prob[order], meas.y_hat[order]
+    table["R"], table["t"], table["s"] = meas.R[order].reshape(N, 4), meas.t[order], meas.s[order]
+    floor_start = np.concatenate([[0], np.cumsum([len(fl["rows"]) for fl in floors])]).astype(np.int32)
+    n_nodes = np.array([len(fl["pano_ids"]) for fl in floors], dtype=np.int32)
+    M = int(n_nodes.max())
+    if M > _lib.GRAPH_MAX_NODES:   # (the library refuses it as well: SALVE_ERR_BAD_ARG)
+        worst = floors[int(n_nodes.argmax())]
+        raise _lib.SalveHipError(f"{what}: floor {worst['building_id']} {worst['floor_id']} has {M} panoramas, more than the "
+                                 f"{_lib.GRAPH_MAX_NODES} a floor may have")
+    return table, floor_start, n_nodes, M
+
+
 def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: bool = True, rot_threshold_deg: float = ROT_THRESHOLD_DEG,
-          trans_threshold: float = TRANS_THRESHOLD, device="cuda:0") -> List[FloorSolution]:
+          trans_threshold: float = TRANS_THRESHOLD, device="cuda:0", keep_rows: Optional[np.ndarray] = None) -> List[FloorSolution]:
     """One FloorSolution per floor of `meas` (in `meas.floors()` order): one upload, one launch for all floors, one read of the device status
     word, one download.  confidence_threshold has no default: the reference's run_sfm.py takes it from the command line.  rot_threshold_deg
     and trans_threshold are filter_to_SE2_cycle_consistent_edges' own; trans_threshold=inf gives the rotation-only filter.  cycle_filter=False
-    chains the chosen edges as they are (run_sfm.py:440-446).  A floor of more than 256 panoramas is refused before anything is launched."""
+    chains the chosen edges as they are (run_sfm.py:440-446).  A floor of more than 256 panoramas is refused before anything is launched.
+    keep_rows: None, or a boolean mask over `meas`; a row outside it is never a candidate (it is not uploaded; the floors keep the panorama
+    numbering of the whole table, and n_rows counts the kept rows).  With a sample_trees inlier mask this is the reference's
+    --filter_edges_by_random_spanning_trees."""
     import torch
 
     from salve_amd import status
@@ -203,19 +233,15 @@ def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: boo
     F = len(floors)
     if F == 0:
         return []
-    N = len(meas)
-    order = np.concatenate([fl["rows"] for fl in floors])
-    table = np.zeros(N, dtype=_lib.GRAPH_ROW_DTYPE)
-    table["i1"], table["i2"] = np.concatenate([fl["c1"] for fl in floors]), np.concatenate([fl["c2"] for fl in floors])
-    table["prob"], table["y_hat"] = meas.prob[order], meas.y_hat[order]
-    table["R"], table["t"], table["s"] = meas.R[order].reshape(N, 4), meas.t[order], meas.s[order]
-    floor_start = np.concatenate([[0], np.cumsum([len(fl["rows"]) for fl in floors])]).astype(np.int32)
-    n_nodes = np.array([len(fl["pano_ids"]) for fl in floors], dtype=np.int32)
-    M = int(n_nodes.max())
-    if M > _lib.GRAPH_MAX_NODES:   # (the library refuses it as well: SALVE_ERR_BAD_ARG)
-        worst = floors[int(n_nodes.argmax())]
-        raise _lib.SalveHipError(f"pose_graph.solve: floor {worst['building_id']} {worst['floor_id']} has {M} panoramas, more than the "
-                                 f"{_lib.GRAPH_MAX_NODES} a floor may have")
+    if keep_rows is not None:
+        keep_rows = np.asarray(keep_rows, dtype=bool).reshape(-1)
+        if len(keep_rows) != len(meas):
+            raise ValueError(f"pose_graph.solve: keep_rows has {len(keep_rows)} entries for {len(meas)} rows")
+        for fl in floors:
+            k = keep_rows[fl["rows"]]
+            fl["rows"], fl["c1"], fl["c2"] = fl["rows"][k], fl["c1"][k], fl["c2"][k]
+    table, floor_start, n_nodes, M = _device_table(meas, floors, "pose_graph.solve")
+    N = len(table)
 
     # one upload: rows | floor_start | n_nodes; one output buffer: out_rows | out_nodes | out_floors
     blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
@@ -274,11 +300,253 @@ def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: boo
     return solutions
 
 
-def json_fname(sol: FloorSolution) -> str:
+@dataclass
+class HypothesisDraw:
+    """The random subsets of one floor, as ransac_spanning_trees draws them (spanning_tree.py:213-244)."""
+
+    building_id: str
+    floor_id: str
+    candidates: np.ndarray        # [K] indices into the measurement table, in measurement order: the reference's `measurements`
+    subsets: List[np.ndarray]     # per hypothesis: the drawn indices INTO `candidates`, in the order numpy drew them
+    masks: np.ndarray             # [H, words] uint32: bit k = the floor's k-th row in sorted order (EdgeMeasurements.compact)
+
+
+def _subset_masks(fl: Dict[str, Any], subsets_rows: Sequence[np.ndarray], words: Optional[int] = None) -> np.ndarray:
+    """uint32 [H, words]: bit k of hypothesis h is set iff the floor's k-th sorted row is one of subsets_rows[h] (indices into the table)."""
+    n = len(fl["rows"])
+    words = (n + 31) // 32 if words is None else words
+    position = {int(r): k for k, r in enumerate(fl["rows"])}
+    masks = np.zeros((len(subsets_rows), words), dtype=np.uint32)
+    for h, rows in enumerate(subsets_rows):
+        for r in rows:
+            k = position[int(r)]
+            masks[h, k >> 5] |= np.uint32(1 << (k & 31))
+    return masks
+
+
+def draw_hypotheses(meas: EdgeMeasurements, confidence_threshold: float, num_hypotheses: int = 100, sampling_fraction: float = 0.5,
+                    min_num_edges: Optional[int] = None, seed: int = 0) -> List[HypothesisDraw]:
+    """Host only: per floor (in `meas.floors()` order) the subsets ransac_spanning_trees would draw from the floor's thresholded
+    measurements after np.random.seed(seed) -- K candidates in measurement order, m = ceil(sampling_fraction * K) of them per subset unless
+    min_num_edges is given, min(int(binom(K, m)), num_hypotheses) subsets (1000 where the binomial overflows, as the reference's `except`),
+    drawn without replacement with p proportional to 1 / |i2 - i1| on the pano ids.  One RandomState(seed) per floor; a floor without a
+    candidate has no hypothesis (the reference raises ValueError for it)."""
+    try:
+        from scipy.special import binom   # (the reference's; a float, inf where it overflows)
+    except ImportError:                   # without scipy: the exact binomial, overflowing where a float does
+        binom = lambda K, m: float(math.comb(K, m))
+
+    thr = np.float32(confidence_threshold)
+    candidate = (meas.y_hat == 1) & (meas.prob >= thr)
+    draws = []
+    for fl in meas.compact():
+        cand = np.sort(fl["rows"][candidate[fl["rows"]]])   # (measurement order)
+        K = len(cand)
+        subsets: List[np.ndarray] = []
+        if K > 0:
+            m = int(math.ceil(sampling_fraction * K)) if min_num_edges is None else int(min_num_edges)
+            try:
+                max_unique = int(binom(K, m))
+            except (OverflowError, ValueError):
+                max_unique = 1000
+            p = 1 / np.absolute(meas.i2[cand] - meas.i1[cand])
+            p = p / np.sum(p)
+            rs = np.random.RandomState(seed)
+            subsets = [rs.choice(a=K, size=m, replace=False, p=p) for _ in range(min(max_unique, num_hypotheses))]
+        draws.append(HypothesisDraw(fl["building_id"], fl["floor_id"], cand, subsets, _subset_masks(fl, [cand[h] for h in subsets])))
+    return draws
+
+
+@dataclass
+class TreeSampleSolution:
+    building_id: str
+    floor_id: str
+    pano_ids: np.ndarray
+    options: Dict[str, Any]                               # method, confidence_threshold and what the hypotheses were drawn with
+    best: Optional[int]                                   # the winning hypothesis of the floor; None: no hypothesis, or every one scored NaN
+    wSi_list: Optional[List[Optional[Sim2]]]              # the winner's, by pano id, in greedily_construct_st_Sim2's shape and length
+    inlier_rows: np.ndarray                               # the reference's best_hypothesis: indices into the measurement table, ascending
+    hypotheses: List[Dict[str, Any]]                      # per hypothesis: avg_rot_err, avg_trans_err, n_localized, n_measured, n_edges, origin
+    n_measurements: int                                   # the length of the measurement table (of all floors): inlier_mask's
+    parent: Dict[int, int] = field(default_factory=dict)
+    depth: Dict[int, int] = field(default_factory=dict)
+    counts: Dict[str, int] = field(default_factory=dict)  # n_nodes, n_rows, n_candidates, n_hyps, n_improvements, n_localized, n_inliers
+    origin: Optional[int] = None
+    avg_rot_err: Optional[float] = None                   # the winner's
+    avg_trans_err: Optional[float] = None
+
+    @property
+    def inlier_mask(self) -> np.ndarray:
+        """bool over the measurement table: this floor's inlier rows (OR the floors' masks: combined_inlier_mask)."""
+        mask = np.zeros(self.n_measurements, dtype=bool)
+        mask[self.inlier_rows] = True
+        return mask
+
+    def summary(self) -> str:
+        c = self.counts
+        return (f"{self.building_id} {self.floor_id}: hypothesis {self.best} of {c['n_hyps']} keeps {c['n_inliers']} / {c['n_candidates']} measurements, "
+                f"localized {c['n_localized']} / {c['n_nodes']} panoramas")
+
+    def to_json(self) -> Dict[str, Any]:
+        fin = lambda x: None if x is None or x != x else float(x)
+        sim = lambda S: {"R": S.rotation.flatten().tolist(), "t": S.translation.flatten().tolist(), "s": S.scale}
+        return {"building_id": self.building_id, "floor_id": self.floor_id, "options": dict(self.options), "pano_ids": [int(p) for p in self.pano_ids],
+                "counts": {k: int(v) for k, v in self.counts.items()}, "origin": self.origin, "best": self.best,
+                "avg_rot_err": fin(self.avg_rot_err), "avg_trans_err": fin(self.avg_trans_err), "n_measurements": int(self.n_measurements),
+                "n_poses": None if self.wSi_list is None else len(self.wSi_list), "inlier_rows": [int(r) for r in self.inlier_rows],
+                "hypotheses": [{k: (fin(v) if k.startswith("avg_") else v) for k, v in h.items()} for h in self.hypotheses],
+                "poses": {str(p): {**sim(S), "parent": self.parent[p], "depth": self.depth[p]}
+                          for p, S in enumerate(self.wSi_list or []) if S is not None}}
+
+    @classmethod
+    def from_json(cls, d: Dict[str, Any]) -> "TreeSampleSolution":
+        nan = lambda x: float("nan") if x is None else x
+        sim = lambda r: Sim2(np.array(r["R"], dtype=np.float32).reshape(2, 2), np.array(r["t"], dtype=np.float32), float(r["s"]))
+        wSi = None
+        if d["n_poses"] is not None:
+            wSi = [None] * d["n_poses"]
+            for p, r in d["poses"].items():
+                wSi[int(p)] = sim(r)
+        hyps = [{k: (nan(v) if k.startswith("avg_") else v) for k, v in h.items()} for h in d["hypotheses"]]
+        return cls(d["building_id"], d["floor_id"], np.array(d["pano_ids"], dtype=np.int64), dict(d["options"]), d["best"], wSi,
+                   np.array(d["inlier_rows"], dtype=np.int64), hyps, d["n_measurements"], {int(p): r["parent"] for p, r in d["poses"].items()},
+                   {int(p): r["depth"] for p, r in d["poses"].items()}, dict(d["counts"]), d["origin"],
+                   None if d["best"] is None else nan(d["avg_rot_err"]), None if d["best"] is None else nan(d["avg_trans_err"]))
+
+
+def combined_inlier_mask(solutions: Sequence[TreeSampleSolution]) -> Optional[np.ndarray]:
+    """The floors' inlier masks ORed: solve's keep_rows.  None for no floor."""
+    mask = None
+    for sol in solutions:
+        mask = sol.inlier_mask if mask is None else (mask | sol.inlier_mask)
+    return mask
+
+
+def sample_trees(meas: EdgeMeasurements, confidence_threshold: float, hypotheses: Optional[Sequence[HypothesisDraw]] = None,
+                 num_hypotheses: int = 100, sampling_fraction: float = 0.5, min_num_edges: Optional[int] = None, seed: int = 0,
+                 device="cuda:0") -> List[TreeSampleSolution]:
+    """One TreeSampleSolution per floor of `meas` (in `meas.floors()` order): the reference's ransac_spanning_trees for every floor in one
+    upload, one call (two launches), one read of the device status word and one download.  hypotheses: None -- draw_hypotheses(meas,
+    confidence_threshold, num_hypotheses, sampling_fraction, min_num_edges, seed) -- or its result, or subsets of the caller's own in that
+    form (only `masks` is uploaded).  A floor without a hypothesis, or whose every hypothesis has a NaN error, has best None, no pose and no
+    inlier, where the reference would crash."""
+    import torch
+
+    from salve_amd import status
+
+    device = torch.device(device)
+    lib = _lib.load()
+    floors = meas.compact()
+    F = len(floors)
+    if F == 0:
+        return []
+    if hypotheses is None:
+        hypotheses = draw_hypotheses(meas, confidence_threshold, num_hypotheses, sampling_fraction, min_num_edges, seed)
+    if [(h.building_id, h.floor_id) for h in hypotheses] != [(fl["building_id"], fl["floor_id"]) for fl in floors]:
+        raise ValueError("pose_graph.sample_trees: `hypotheses` must name the floors of the measurements, in their order")
+    table, floor_start, n_nodes, M = _device_table(meas, floors, "pose_graph.sample_trees")
+    N = len(table)
+    hyp_start = np.concatenate([[0], np.cumsum([len(h.masks) for h in hypotheses])]).astype(np.int32)
+    H = int(hyp_start[-1])
+    words = max([1] + [(len(fl["rows"]) + 31) // 32 for fl in floors])
+    masks = np.zeros((H, words), dtype=np.uint32)
+    for f, h in enumerate(hypotheses):
+        if h.masks.shape[1] > words or (len(h.masks) and h.masks.shape[1] != (len(floors[f]["rows"]) + 31) // 32):
+            raise ValueError(f"pose_graph.sample_trees: floor {h.building_id} {h.floor_id}: the masks do not have one bit per row of the floor")
+        masks[hyp_start[f]:hyp_start[f + 1], :h.masks.shape[1]] = h.masks
+
+    tree_dt, floor_dt, node_dt = _lib.GRAPH_TREE_OUT_DTYPE, _lib.GRAPH_SAMPLE_FLOOR_OUT_DTYPE, _lib.GRAPH_NODE_OUT_DTYPE
+    out_trees = np.zeros(H, dtype=tree_dt)
+    out_inlier = np.zeros(N, dtype=np.int32)
+    out_nodes = np.zeros((F, M), dtype=node_dt)
+    out_floors = np.zeros(F, dtype=floor_dt)
+    out_floors["best"] = -1
+    if H > 0:
+        # one upload: rows | masks | floor_start | n_nodes | hyp_start; one output buffer: out_trees | out_nodes | out_floors | out_inlier
+        parts = [table.view(np.uint8), masks.reshape(-1).view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8), hyp_start.view(np.uint8)]
+        offs = np.concatenate([[0], np.cumsum([len(x) for x in parts])])   # (48 N, then 4-byte tables: every offset is 4-byte aligned)
+        off_nodes = H * tree_dt.itemsize
+        off_floors = off_nodes + F * M * node_dt.itemsize
+        off_inlier = off_floors + F * floor_dt.itemsize
+        out_bytes = off_inlier + 4 * N
+        with torch.cuda.device(device):
+            dev_in = torch.from_numpy(np.concatenate(parts)).to(device)
+            dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+            ws_bytes = int(lib.salve_pose_graph_sample_workspace_bytes(H, M))
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+            p_in, p_out = dev_in.data_ptr(), dev_out.data_ptr()
+            vp = ctypes.c_void_p
+            _lib.check(lib.salve_pose_graph_sample_trees(vp(p_in), N, vp(p_in + int(offs[2])), vp(p_in + int(offs[3])), F, M, float(confidence_threshold),
+                                                         vp(p_in + int(offs[4])), vp(p_in + int(offs[1])), H, words, vp(p_out), vp(p_out + off_inlier),
+                                                         vp(p_out + off_nodes), vp(p_out + off_floors), vp(ws.data_ptr()), ws_bytes,
+                                                         status.ptr(device), vp(torch.cuda.current_stream(device).cuda_stream)),
+                       "salve_pose_graph_sample_trees")
+            status.check(device, "pose_graph.sample_trees")   # (the one synchronising read)
+            host = dev_out.cpu().numpy()
+        out_trees = host[:off_nodes].view(tree_dt)
+        out_nodes = host[off_nodes:off_floors].view(node_dt).reshape(F, M)
+        out_floors = host[off_floors:off_inlier].view(floor_dt)
+        out_inlier = host[off_inlier:].view(np.int32)
+    else:   # nothing to launch: the candidates are counted here
+        thr = np.float32(confidence_threshold)
+        for f in range(F):
+            r = table[floor_start[f]:floor_start[f + 1]]
+            out_floors["n_candidates"][f] = int(((r["y_hat"] == 1) & (r["prob"] >= thr)).sum())
+
+    options = {"method": "random_spanning_trees", "confidence_threshold": float(confidence_threshold), "num_hypotheses": int(num_hypotheses),
+               "sampling_fraction": float(sampling_fraction), "min_num_edges": min_num_edges, "seed": int(seed)}
+    sim = lambda R, t, s: Sim2(np.array(R, dtype=np.float32).reshape(2, 2), np.array(t, dtype=np.float32), float(s))
+    solutions = []
+    for f, fl in enumerate(floors):
+        lo, hi = int(floor_start[f]), int(floor_start[f + 1])
+        ids, fo, nodes = fl["pano_ids"], out_floors[f], out_nodes[f, :len(fl["pano_ids"])]
+        best = int(fo["best"]) if fo["best"] >= 0 else None
+        inliers = np.sort(fl["rows"][np.nonzero(out_inlier[lo:hi])[0]]).astype(np.int64)
+        stats = [{"avg_rot_err": float(t["avg_rot_err"]), "avg_trans_err": float(t["avg_trans_err"]), "n_localized": int(t["n_localized"]),
+                  "n_measured": int(t["n_measured"]), "n_edges": int(t["n_edges"]), "origin": int(ids[t["origin"]]) if t["origin"] >= 0 else None}
+                 for t in out_trees[hyp_start[f]:hyp_start[f + 1]]]
+        wSi, parent, depth, origin = None, {}, {}, None
+        if best is not None and stats[best]["origin"] is not None:
+            origin = stats[best]["origin"]
+            wSi = [None] * (int(meas.i2[inliers].max()) + 1)   # greedily_construct_st_Sim2's length (spanning_tree.py:104, 110)
+            for v in np.nonzero(nodes["localized"])[0]:
+                p = int(ids[v])
+                wSi[p] = sim(nodes["R"][v], nodes["t"][v], nodes["s"][v])
+                parent[p], depth[p] = (int(ids[nodes["parent"][v]]) if nodes["parent"][v] >= 0 else -1), int(nodes["depth"][v])
+        counts = {"n_nodes": len(ids), "n_rows": hi - lo, "n_candidates": int(fo["n_candidates"]), "n_hyps": int(hyp_start[f + 1] - hyp_start[f]),
+                  "n_improvements": int(fo["n_improvements"]), "n_localized": len(parent), "n_inliers": len(inliers)}
+        solutions.append(TreeSampleSolution(fl["building_id"], fl["floor_id"], ids, dict(options), best, wSi, inliers, stats, len(meas), parent, depth,
+                                            counts, origin, float(fo["avg_rot_err"]) if best is not None else None,
+                                            float(fo["avg_trans_err"]) if best is not None else None))
+    return solutions
+
+
+def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "spanning_tree", filter_by_random_spanning_trees: bool = False,
+        num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", **solve_options):
+    """What the command line and ingest.score_floor(pose_graph=...) do with their options.  method "spanning_tree": solve(meas,
+    confidence_threshold, **solve_options), behind the random-spanning-trees edge filter if filter_by_random_spanning_trees; method
+    "random_spanning_trees": sample_trees.  With the defaults this IS solve: the same launches and values."""
+    if method not in ("spanning_tree", "random_spanning_trees"):
+        raise ValueError(f"pose_graph.run: unknown method {method!r}")
+    sampling = {"num_hypotheses": num_hypotheses, "sampling_fraction": sampling_fraction, "seed": seed}
+    if method == "random_spanning_trees":
+        if solve_options or filter_by_random_spanning_trees:
+            raise ValueError("pose_graph.run: method random_spanning_trees takes neither the cycle filter's options nor the edge filter")
+        return sample_trees(meas, confidence_threshold, device=device, **sampling)
+    if not filter_by_random_spanning_trees:
+        return solve(meas, confidence_threshold, device=device, **solve_options)
+    samples = sample_trees(meas, confidence_threshold, device=device, **sampling)
+    solutions = solve(meas, confidence_threshold, device=device, keep_rows=combined_inlier_mask(samples), **solve_options)
+    for sol in solutions:
+        sol.options["filter_by_random_spanning_trees"] = dict(sampling)
+    return solutions
+
+
+def json_fname(sol) -> str:
     return f"pose_graph_{sol.building_id}_{sol.floor_id}.json"
 
 
-def write_json(sol: FloorSolution, out_dir: str) -> str:
+def write_json(sol, out_dir: str) -> str:
     os.makedirs(out_dir, exist_ok=True)
     fp = f"{out_dir}/{json_fname(sol)}"
     with open(fp, "w") as f:
@@ -288,7 +556,8 @@ def write_json(sol: FloorSolution, out_dir: str) -> str:
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="python -m salve_amd.pose_graph",
-                                 description="Global panorama poses per floor from prediction files: best pair, cycle filter, spanning tree.")
+                                 description="Global panorama poses per floor from prediction files: best pair, cycle filter, spanning tree; or "
+                                             "the best of many random spanning trees.")
     ap.add_argument("pred_dir", metavar="PRED_DIR", help="directory of batch_*.json prediction files")
     ap.add_argument("--hypotheses", required=True, metavar="ROOT", help="directory of the alignment hypotheses (export_alignment_hypotheses.py)")
     ap.add_argument("--confidence-threshold", type=float, required=True, help="least probability of a positive prediction that counts")
@@ -297,10 +566,23 @@ def main(argv=None) -> int:
     ap.add_argument("--trans", type=float, default=TRANS_THRESHOLD, help="3-cycle translation threshold (default %(default)s; inf: rotation only)")
     ap.add_argument("--out", metavar="DIR", default=None, help="where the pose_graph_*.json files go (default: PRED_DIR)")
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--method", choices=("spanning_tree", "random_spanning_trees"), default="spanning_tree",
+                    help="random_spanning_trees: the best of --num-hypotheses random subsets' trees (the cycle filter's options do not apply)")
+    ap.add_argument("--filter-by-random-spanning-trees", action="store_true",
+                    help="method spanning_tree: keep only the predictions of the best random subset before anything else")
+    ap.add_argument("--num-hypotheses", type=int, default=100, help="random subsets per floor (default %(default)s)")
+    ap.add_argument("--sampling-fraction", type=float, default=0.5, help="share of a floor's thresholded predictions per subset (default %(default)s)")
+    ap.add_argument("--seed", type=int, default=0, help="seed of every floor's draws (default %(default)s)")
     args = ap.parse_args(argv)
     meas = EdgeMeasurements.from_prediction_files(args.pred_dir, args.hypotheses)
-    for sol in solve(meas, args.confidence_threshold, cycle_filter=not args.no_cycle_filter, rot_threshold_deg=args.rot_deg,
-                     trans_threshold=args.trans, device=args.device):
+    if args.method == "random_spanning_trees":
+        if args.filter_by_random_spanning_trees:
+            ap.error("--filter-by-random-spanning-trees belongs to --method spanning_tree")
+        options = {}
+    else:
+        options = {"cycle_filter": not args.no_cycle_filter, "rot_threshold_deg": args.rot_deg, "trans_threshold": args.trans}
+    for sol in run(meas, args.confidence_threshold, method=args.method, filter_by_random_spanning_trees=args.filter_by_random_spanning_trees,
+                   num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options):
         write_json(sol, args.out or args.pred_dir)
         print(sol.summary())
     return 0
