@@ -53,7 +53,9 @@ typedef enum {
                                         salve_bev_train_tiles_jitter_workspace_bytes and salve_tile_jitter_t), salve_bev_pair_overlap (with
                                         salve_overlap_job_t), salve_pose_graph_solve (with salve_pose_graph_workspace_bytes, the salve_graph_*_t
                                         records and SALVE_STATUS_BAD_GRAPH_ROW), salve_pose_graph_sample_trees (with
-                                        salve_pose_graph_sample_workspace_bytes, salve_graph_tree_out_t and salve_graph_sample_floor_out_t) */
+                                        salve_pose_graph_sample_workspace_bytes, salve_graph_tree_out_t and salve_graph_sample_floor_out_t),
+                                        salve_floor_align and salve_floor_iou (with salve_floor_iou_workspace_bytes, the salve_floor_*_out_t
+                                        records and SALVE_STATUS_BAD_FLOOR_TABLE) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -76,6 +78,10 @@ typedef enum {
 #define SALVE_STATUS_BAD_GRAPH_ROW 128 /* pose_graph_solve: a floor's rows are not sorted by (i1, i2), a row has i1 >= i2 or an index outside
                                           [0, n_nodes), the floor's row range is malformed or its n_nodes lies outside [0, max_nodes] -- that
                                           floor's outputs are written EMPTY (no chosen row, nothing localized, origin -1), the others are solved */
+#define SALVE_STATUS_BAD_FLOOR_TABLE 256 /* floor_align: a floor's panorama extent or hypothesis extent is malformed (or overlaps a lower floor's) --
+                                            that floor is written EMPTY (best -1, NaN errors); floor_iou: a floor's panorama extent or a room's
+                                            vertex extent is malformed, or a posed vertex is not finite or lies beyond 2^24 pixels -- that
+                                            floor's counts are 0 and its IoU NaN.  The other floors are reported */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -549,6 +555,114 @@ int salve_pose_graph_sample_trees(const salve_graph_row_t* rows, int32_t n_rows,
                                   const uint32_t* hyp_mask, int32_t n_hyps, int32_t mask_words, salve_graph_tree_out_t* out_trees,
                                   int32_t* out_inlier, salve_graph_node_out_t* out_nodes, salve_graph_sample_floor_out_t* out_floors,
                                   void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
+/* The floor reconstruction report, part 1: the estimated poses of any number of floors aligned to the truth by the reference's RANSAC, and
+ * the pose errors, in ONE call (two launches on `stream`).  Stands behind
+ *   salve/utils/ransac.py:14-129            ransac_align_poses_sim3_ignore_missing, compute_pose_errors_3d
+ *   salve/common/posegraph2d.py:281-383     measure_aligned_abs_pose_error, align_by_Sim3_to_ref_pose_graph, apply_Sim3
+ *   gtsfm's align_poses_sim3_ignore_missing and gtsam's Similarity3.Align of pose pairs, restated as the rules below (neither is installed
+ *   where this is built; the restatement reproduces the numbers the reference's own tests record -- tests/test_floor_report_host.py).
+ * The subsets are DRAWN BY THE CALLER (salve_amd.floor_report.draw_alignment_subsets draws the reference's); the device never draws.
+ *   node_start   device int32 [n_floors + 1]: the panoramas of floor f are the records node_start[f] .. node_start[f + 1] - 1 of the two pose
+ *                tables, at most 256 (SALVE_GRAPH_MAX_NODES); index k within the floor is the floor's COMPACT panorama index
+ *   truth, est   device salve_graph_node_out_t [n_nodes], 8-byte aligned: `localized` (present), R, t (float32) and s are read; the estimate's
+ *                s is taken as 1 (PoseGraph2d.from_wSi_list)
+ *   hyp_start    device int32 [n_floors + 1]: the hypotheses of floor f are hyp_start[f] .. hyp_start[f + 1] - 1
+ *   hyp_mask     device uint32 [n_hyps][8]: bit k of a hypothesis's KEEP mask stands for compact index k; bits at or beyond the floor's
+ *                panorama count are ignored
+ *   gt_scale, metres_per_coordinate   device float64 [n_floors]: the scale the aligned poses carry, and scale_meters_per_coordinate
+ * Launch 1, one wavefront per hypothesis, four per workgroup.  Everything is float64 (R, t widened first), no product is fused into a sum.
+ * The hypothesis's PAIRS are the indices whose bit is set and that are present in both tables, ascending; n of them.
+ *  1. n < 2: R = I, t = 0, s = 1 (gtsfm's skip rule).  Otherwise:
+ *  2. aRb_i = Ra_i * Rb_i^T; R0 = the first pair's.
+ *  3. one Karcher step: M_i = R0^T * aRb_i, d_i = atan2(M10, M00), m = (sum d_i) / n, R = R0 * [[cos m, -sin m], [sin m, cos m]];
+ *  4. a second step from R.  Exactly two.
+ *  5. ca = (sum a_i) / n, cb = (sum b_i) / n (the translations).
+ *  6. y = sum (a_i - ca) . (R (b_i - cb)), x = sum |R (b_i - cb)|^2, s = y / x, t = (ca - s * (R cb)) / s: the convention s (R p + t).
+ *  7. s NaN or 0 (coincident translations): s = 1, t = ca - R cb.  This rule is this project's own: gtsfm has a fallback there whose text was
+ *     not available; NOT pinned against it.
+ *  8. errors over the hypothesis's OWN pairs: R_i' = R Rb_i, t_i' = s (R b_i + t); E = Ra_i^T R_i'; rot_i = |atan2(E10, E00)| * (180 / pi);
+ *     trans_i = sqrt(dx^2 + dy^2) of a_i - t_i'; the two means are the sums / n (NaN without a pair).
+ *  Sums: lane l of the wavefront adds the values of its indices l, l + 64, l + 128, l + 192 in ascending order from 0.0 (pairs only); the 64
+ *  partial sums fold by halving (p[l] += p[l + 32], then 16, ... 1).  No floating-point atomic: the same bytes on every run.
+ * Launch 2, one workgroup per floor.  Pick: the hypotheses in order from best_rot = best_trans = +inf; one replaces the best iff
+ *  trans <= best_trans && rot <= best_rot (of equals the LATER; a NaN never).  Apply: a_Sim2_b = ((float)R, (float)t, s) composed with
+ *  (R_i, t_i, 1.0) of every present estimated panorama under the float32 Sim2 rules of salve_pose_graph_solve's phase D; the record written
+ *  is (localized 1, parent -1, depth -1, R, t * (float)scale, gt_scale[f]).  Report: over the panoramas present in BOTH tables, rot_i and
+ *  trans_i by step 8's formulas on the aligned float32 pose widened (R = I, t = 0, s = 1); thread k holds panorama k's value (0.0 without
+ *  one), the 256 values fold by halving (128, 64, ... 1); avg_rot_err = sum / n_both, avg_trans_err = sum / n_both * metres_per_coordinate[f],
+ *  percent_localized = n_est / n_gt * 100 (the reference's order of operations).
+ *  A floor without a winner (no hypothesis, or every one NaN) is NOT ALIGNED: best -1, empty node records, NaN errors and NaN R, t, s, where
+ *  the reference would fail on None -- a documented deviation.
+ *   out_hyps        device salve_floor_hyp_out_t [n_hyps], 8-byte aligned.  A hypothesis in no floor's extent: identity, NaN, floor == -1.
+ *   out_nodes       device salve_graph_node_out_t [n_nodes]: the aligned estimate; a panorama absent from it: the empty record
+ *   out_rot_err, out_trans_err   device float64 [n_nodes]: per panorama (trans in coordinate units, as the reference's arrays), NaN where absent
+ *   out_floors      device salve_floor_align_out_t [n_floors], 8-byte aligned
+ * Malformed floors: a node extent outside [0, n_nodes], decreasing or longer than 256; a hyp_start extent outside [0, n_hyps] or decreasing,
+ * or one that overlaps a LOWER floor's (a hypothesis belongs to the lowest floor whose well-formed extent holds it).  Such a floor is written
+ * EMPTY (best -1, n_hyps 0, counts 0, NaN; its node records empty where its node extent is sound) and raises SALVE_STATUS_BAD_FLOOR_TABLE;
+ * the other floors are reported.  Every table is verified before an address is formed from it.  Records of panoramas in no floor's extent are
+ * not written.  n_floors == 0 launches nothing; n_hyps == 0 skips launch 1 (hyp_mask and out_hyps may then be null).
+ * SALVE_ERR_BAD_ARG for a negative count and -- with something to launch -- a null or misaligned pointer. */
+#define SALVE_FLOOR_MASK_WORDS 8
+typedef struct {
+    double R[4], t[2], s;       /* aSb of the hypothesis's own pairs */
+    double rot_err, trans_err;  /* the means over its own pairs, degrees and coordinate units; NaN without a pair */
+    int32_t n_pairs;
+    int32_t floor;              /* the floor it was evaluated for; -1: none */
+} salve_floor_hyp_out_t;
+typedef struct {
+    int32_t best;               /* index within the floor's hypotheses; -1: not aligned */
+    int32_t n_hyps;
+    int32_t n_est, n_gt;        /* panoramas present in the estimate, in the truth */
+    double avg_rot_err;         /* degrees */
+    double avg_trans_err;       /* METRES */
+    double percent_localized;
+    double R[4], t[2], s;       /* the winner's aSb; NaN without one */
+} salve_floor_align_out_t;
+int salve_floor_align(const int32_t* node_start, int32_t n_floors, int32_t n_nodes, const salve_graph_node_out_t* truth,
+                      const salve_graph_node_out_t* est, const int32_t* hyp_start, const uint32_t* hyp_mask, int32_t n_hyps, const double* gt_scale,
+                      const double* metres_per_coordinate, salve_floor_hyp_out_t* out_hyps, salve_graph_node_out_t* out_nodes, double* out_rot_err,
+                      double* out_trans_err, salve_floor_align_out_t* out_floors, int32_t* status, void* stream);
+
+/* The floor reconstruction report, part 2: the raster IoU of the estimated and the true floor plan of any number of floors in ONE call (two
+ * memsets and four launches on `stream`).  Stands behind salve/common/floor_reconstruction_report.py:271-338 (render_raster_occupancy,
+ * rasterize_room) and salve/utils/bev_rendering_utils.py:159-193; cv2.fillPoly is restated as oracle/layout_oracle.py's fill_poly, as
+ * salve_layout_rasterise's polygon is (parity with cv2 unpinned: it is not installed where this is built).
+ *   room_xy, room_off   device float64 [2 * n_room_xy] and int64 [n_nodes + 1]: the LOCAL room vertices (x already negated) of panorama i are
+ *                       room_off[i] .. room_off[i + 1] - 1, salve_layout_pose's form, indexed like the pose tables
+ *   node_start, est, truth, metres_per_coordinate   as salve_floor_align's; `est` is its out_nodes.  s is read from both tables.
+ *   img_h, img_w        the raster, 1 .. 32000 each (the reference: 501 x 501)
+ *   offset_x, offset_y, pixels_per_metre   bevimg_Sim2_world: a float32 translation, widened, and a float64 scale (the reference: 25, 25, 10)
+ * Launch 1 poses: per table and present panorama g = s_i * (v @ R_i^T + t_i) in float64 with R, t widened, every product and sum on its own;
+ *  g * metres_per_coordinate[f]; px = round_half_even((g + offset) * pixels_per_metre) as int32.
+ * Launch 2 rasterises: one workgroup per 16 x 16 pixel tile of a floor.  A pixel is occupied in a table iff SOME present panorama's polygon
+ *  covers it: even-odd on the 16.16 crossings united with the 8-connected line pixels of every edge (fill_poly).  Counting is by wave
+ *  ballots and one INTEGER atomic add per wave and counter: the same bytes on every run.
+ * Launch 3: iou = inter / (uni + 1e-12).
+ *   out         device salve_floor_iou_out_t [n_floors], 8-byte aligned
+ *   out_masks   NULL, or device uint32 [n_floors][2][img_h][(img_w + 31) / 32]: the estimate's mask, then the truth's; pixel (x, y) is bit
+ *               x % 32 of word x / 32 of row y (NOT flipped)
+ *   workspace   salve_floor_iou_workspace_bytes(n_room_xy, n_nodes) bytes, 16-byte aligned
+ * A floor with a malformed node extent (salve_floor_align's rule), or with a posed vertex that is not finite or beyond 2^24 pixels
+ * (pack_layouts' limit): bad = 1, counts 0, iou NaN, empty masks, and SALVE_STATUS_BAD_FLOOR_TABLE is raised; the other floors are
+ * rasterised.  room_off must ascend within [0, n_room_xy] over ALL n_nodes panoramas (a launch of its own verifies it first): the posed
+ * pixels live in the workspace by vertex index, so where two panoramas claim one vertex NO floor is rasterised -- every floor is bad.
+ * n_floors == 0 launches nothing.  SALVE_ERR_BAD_ARG for a negative count, an image size outside
+ * 1 .. 32000, a non-finite raster parameter, more than 2^31 - 1 tiles (floors x tiles of an image), a null or misaligned pointer (room_xy may be null
+ * while n_room_xy == 0); SALVE_ERR_WORKSPACE for a short workspace. */
+typedef struct {
+    int32_t n_est, n_gt;        /* occupied pixels of the estimate's mask, of the truth's */
+    int32_t inter, uni;
+    int32_t bad;                /* 0 / 1 */
+    int32_t reserved;           /* written 0 */
+    double iou;
+} salve_floor_iou_out_t;
+size_t salve_floor_iou_workspace_bytes(int64_t n_room_xy, int32_t n_nodes);
+int salve_floor_iou(const double* room_xy, const int64_t* room_off, int64_t n_room_xy, const int32_t* node_start, int32_t n_floors, int32_t n_nodes,
+                    const salve_graph_node_out_t* est, const salve_graph_node_out_t* truth, const double* metres_per_coordinate, int32_t img_h,
+                    int32_t img_w, float offset_x, float offset_y, double pixels_per_metre, salve_floor_iou_out_t* out, uint32_t* out_masks,
+                    void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

@@ -109,6 +109,9 @@ EXPORTED_SYMBOLS = (
     "salve_pose_graph_solve",
     "salve_pose_graph_sample_workspace_bytes",
     "salve_pose_graph_sample_trees",
+    "salve_floor_align",
+    "salve_floor_iou_workspace_bytes",
+    "salve_floor_iou",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -124,6 +127,7 @@ STATUS_BAD_TILE_JOB = 16
 STATUS_BAD_PANO_SLOT = 32
 STATUS_BAD_LAYOUT = 64
 STATUS_BAD_GRAPH_ROW = 128
+STATUS_BAD_FLOOR_TABLE = 256
 
 
 class BevConfig(ctypes.Structure):
@@ -173,6 +177,14 @@ GRAPH_TREE_OUT_DTYPE = np.dtype([("avg_rot_err", "<f8"), ("avg_trans_err", "<f8"
 GRAPH_SAMPLE_FLOOR_OUT_DTYPE = np.dtype([("best", "<i4"), ("n_candidates", "<i4"), ("n_hyps", "<i4"), ("n_improvements", "<i4"), ("avg_rot_err", "<f8"),
                                          ("avg_trans_err", "<f8")])
 assert GRAPH_TREE_OUT_DTYPE.itemsize == 40 and GRAPH_SAMPLE_FLOOR_OUT_DTYPE.itemsize == 32
+# salve_floor_align, salve_floor_iou (salve_floor_hyp_out_t, salve_floor_align_out_t, salve_floor_iou_out_t)
+FLOOR_MASK_WORDS = 8
+FLOOR_HYP_OUT_DTYPE = np.dtype([("R", "<f8", (4,)), ("t", "<f8", (2,)), ("s", "<f8"), ("rot_err", "<f8"), ("trans_err", "<f8"), ("n_pairs", "<i4"),
+                                ("floor", "<i4")])
+FLOOR_ALIGN_OUT_DTYPE = np.dtype([("best", "<i4"), ("n_hyps", "<i4"), ("n_est", "<i4"), ("n_gt", "<i4"), ("avg_rot_err", "<f8"),
+                                  ("avg_trans_err", "<f8"), ("percent_localized", "<f8"), ("R", "<f8", (4,)), ("t", "<f8", (2,)), ("s", "<f8")])
+FLOOR_IOU_OUT_DTYPE = np.dtype([("n_est", "<i4"), ("n_gt", "<i4"), ("inter", "<i4"), ("uni", "<i4"), ("bad", "<i4"), ("reserved", "<i4"), ("iou", "<f8")])
+assert FLOOR_HYP_OUT_DTYPE.itemsize == 80 and FLOOR_ALIGN_OUT_DTYPE.itemsize == 96 and FLOOR_IOU_OUT_DTYPE.itemsize == 32
 # salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
 TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
                               ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
@@ -331,6 +343,17 @@ def load() -> ctypes.CDLL:
     # out_floors, ws, ws_bytes, status, stream
     lib.salve_pose_graph_sample_trees.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.salve_pose_graph_sample_trees.restype = ctypes.c_int
+    # (node_start, n_floors, n_nodes, truth, est, hyp_start, hyp_mask, n_hyps, gt_scale, metres, out_hyps, out_nodes, out_rot_err, out_trans_err,
+    #  out_floors, status, stream)
+    lib.salve_floor_align.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.salve_floor_align.restype = ctypes.c_int
+    lib.salve_floor_iou_workspace_bytes.argtypes = [ctypes.c_int64, i32]
+    lib.salve_floor_iou_workspace_bytes.restype = sz
+    # (room_xy, room_off, n_room_xy, node_start, n_floors, n_nodes, est, truth, metres, img_h, img_w, offset_x, offset_y, pixels_per_metre, out,
+    #  out_masks, workspace, workspace_bytes, status, stream)
+    lib.salve_floor_iou.argtypes = [vp, vp, ctypes.c_int64, vp, i32, i32, vp, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, ctypes.c_double, vp, vp,
+                                    vp, sz, vp, vp]
+    lib.salve_floor_iou.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -433,6 +456,9 @@ def check_status_word(word: int, what: str) -> None:
     if word & STATUS_BAD_GRAPH_ROW:
         raise SalveHipError(f"{what}: a floor's pose-graph rows are not sorted by (i1, i2), name a node outside the floor or have i1 >= i2 (or the "
                             "floor's extents are malformed); that floor was written empty")
+    if word & STATUS_BAD_FLOOR_TABLE:
+        raise SalveHipError(f"{what}: a floor-report table is malformed (a floor's panorama or hypothesis extent, a room's vertex extent) or a "
+                            "posed room vertex is not finite or lies more than 2^24 pixels away; that floor was written empty")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

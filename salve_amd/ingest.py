@@ -293,7 +293,9 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     seed: the best of many random spanning trees, as a method or as an edge filter) -- the floor's pose graph is solved right behind scoring, from the rows still in memory: the result
     gains "pose_graph" (a pose_graph.FloorSolution, or a TreeSampleSolution for method "random_spanning_trees"; None when no hypothesis was scored) and `serialization_save_dir` one more file,
     pose_graph_{building}_{floor}.json, equal to what `python -m salve_amd.pose_graph` makes of the prediction files.  None: launches, files
-    and the returned dict are unchanged."""
+    and the returned dict are unchanged.  With "truth" (a salve_amd.floor_report.FloorTruth; "report": floor_report.report's num_iters,
+    delete_frac, seed) the floor's reconstruction report follows: the result gains "floor_report" and the directory
+    floor_report_{building}_{floor}.json.  Without "truth" nothing changes."""
     from salve_amd import evaluate
     from salve_amd.pipeline import RenderVerifyPipeline
 
@@ -311,8 +313,16 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     from salve_amd import pose_graph as pg
 
     rows = out.pop("rows")
-    solved = pg.run(pg.EdgeMeasurements.from_floor(hyps, rows["kept"], rows["y_hat"], rows["prob"]), device=device, **pose_graph)
+    options = dict(pose_graph)
+    truth = options.pop("truth", None)   # a floor_report.FloorTruth: the floor's report follows its pose graph
+    report_options = options.pop("report", None) or {}   # floor_report.report's num_iters, delete_frac, seed
+    solved = pg.run(pg.EdgeMeasurements.from_floor(hyps, rows["kept"], rows["y_hat"], rows["prob"]), device=device, **options)
     out["pose_graph"] = solved[0] if solved else None
     if solved:
         pg.write_json(solved[0], serialization_save_dir)
+    if truth is not None:
+        from salve_amd import floor_report
+
+        out["floor_report"] = floor_report.report([solved[0] if solved else None], [truth], device=device, **report_options)[0]
+        floor_report.write_json(out["floor_report"], serialization_save_dir)
     return out

@@ -4,6 +4,7 @@ scripts/run_sfm.py:112-152 and :440-446, with and without its cycle filter, for 
 
     python -m salve_amd.pose_graph PRED_DIR --hypotheses ROOT --confidence-threshold X [--no-cycle-filter] [--rot-deg D] [--trans T] [--out DIR]
         [--method {spanning_tree,random_spanning_trees}] [--filter-by-random-spanning-trees] [--num-hypotheses H] [--sampling-fraction F] [--seed S]
+        [--zind-root DIR] [--report-seed S] [--report-iters K]
 
 reads the `batch_*.json` prediction files of PRED_DIR (evaluate.run_test_epoch, evaluate.run_fused_epoch, ingest.score_floor), looks every
 prediction's alignment hypothesis up under ROOT, and writes one `pose_graph_{building}_{floor}.json` per floor.
@@ -23,7 +24,8 @@ predictions and picks the reference's winner, all floors and hypotheses in one c
 salve_amd/csrc/pose_graph_sample.hip).  The winner's subset is also the reference's edge filter in front of the first method:
 `solve(meas, thr, keep_rows=combined_inlier_mask(sample_trees(meas, thr)))`.
 
-Pose-graph optimisation, axis alignment and the evaluation against ground truth are NOT here.  A floor may have at most 256 panoramas.
+The evaluation against ground truth is salve_amd.floor_report: `run(..., truth=)` and `--zind-root DIR` end in one
+floor_report_{building}_{floor}.json per floor.  Pose-graph optimisation and axis alignment are NOT here.  A floor may have at most 256 panoramas.
 """
 
 from __future__ import annotations
@@ -522,10 +524,20 @@ def sample_trees(meas: EdgeMeasurements, confidence_threshold: float, hypotheses
 
 
 def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "spanning_tree", filter_by_random_spanning_trees: bool = False,
-        num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", **solve_options):
+        num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", truth=None, report_options=None, **solve_options):
     """What the command line and ingest.score_floor(pose_graph=...) do with their options.  method "spanning_tree": solve(meas,
     confidence_threshold, **solve_options), behind the random-spanning-trees edge filter if filter_by_random_spanning_trees; method
-    "random_spanning_trees": sample_trees.  With the defaults this IS solve: the same launches and values."""
+    "random_spanning_trees": sample_trees.  With the defaults this IS solve: the same launches and values.
+    truth: None, or the floors' ground truth -- salve_amd.floor_report.FloorTruth objects, as a list in `meas.floors()` order or a dict keyed by
+    (building_id, floor_id).  Then the result is (solutions, reports): floor_report.report(solutions, truths, **report_options) follows the
+    solve."""
+    if truth is not None:
+        from salve_amd import floor_report
+
+        solutions = run(meas, confidence_threshold, method=method, filter_by_random_spanning_trees=filter_by_random_spanning_trees,
+                        num_hypotheses=num_hypotheses, sampling_fraction=sampling_fraction, seed=seed, device=device, **solve_options)
+        truths = [truth[(s.building_id, s.floor_id)] for s in solutions] if isinstance(truth, dict) else list(truth)
+        return solutions, floor_report.report(solutions, truths, device=device, **(report_options or {}))
     if method not in ("spanning_tree", "random_spanning_trees"):
         raise ValueError(f"pose_graph.run: unknown method {method!r}")
     sampling = {"num_hypotheses": num_hypotheses, "sampling_fraction": sampling_fraction, "seed": seed}
@@ -573,6 +585,11 @@ def main(argv=None) -> int:
     ap.add_argument("--num-hypotheses", type=int, default=100, help="random subsets per floor (default %(default)s)")
     ap.add_argument("--sampling-fraction", type=float, default=0.5, help="share of a floor's thresholded predictions per subset (default %(default)s)")
     ap.add_argument("--seed", type=int, default=0, help="seed of every floor's draws (default %(default)s)")
+    ap.add_argument("--zind-root", metavar="DIR", default=None,
+                    help="the ZInD data set ({DIR}/{building}/zind_data.json): also write floor_report_{building}_{floor}.json per floor -- rotation and "
+                         "translation error against the ground truth, percent localized, floor-plan IoU -- and print the summary")
+    ap.add_argument("--report-seed", type=int, default=0, help="seed of the report's alignment RANSAC (default %(default)s)")
+    ap.add_argument("--report-iters", type=int, default=1000, help="alignment subsets per floor (default %(default)s)")
     args = ap.parse_args(argv)
     meas = EdgeMeasurements.from_prediction_files(args.pred_dir, args.hypotheses)
     if args.method == "random_spanning_trees":
@@ -581,10 +598,20 @@ def main(argv=None) -> int:
         options = {}
     else:
         options = {"cycle_filter": not args.no_cycle_filter, "rot_threshold_deg": args.rot_deg, "trans_threshold": args.trans}
-    for sol in run(meas, args.confidence_threshold, method=args.method, filter_by_random_spanning_trees=args.filter_by_random_spanning_trees,
-                   num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options):
+    solutions = run(meas, args.confidence_threshold, method=args.method, filter_by_random_spanning_trees=args.filter_by_random_spanning_trees,
+                    num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options)
+    for sol in solutions:
         write_json(sol, args.out or args.pred_dir)
         print(sol.summary())
+    if args.zind_root is not None:
+        from salve_amd import floor_report
+
+        reports = floor_report.report(solutions, floor_report.load_truths(args.zind_root, solutions), num_iters=args.report_iters, seed=args.report_seed,
+                                      device=args.device)
+        for rep in reports:
+            floor_report.write_json(rep, args.out or args.pred_dir)
+            print(rep.summary())
+        print(json.dumps(floor_report.summarize(reports)))
     return 0
 
 
