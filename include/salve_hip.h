@@ -55,7 +55,8 @@ typedef enum {
                                         records and SALVE_STATUS_BAD_GRAPH_ROW), salve_pose_graph_sample_trees (with
                                         salve_pose_graph_sample_workspace_bytes, salve_graph_tree_out_t and salve_graph_sample_floor_out_t),
                                         salve_floor_align and salve_floor_iou (with salve_floor_iou_workspace_bytes, the salve_floor_*_out_t
-                                        records and SALVE_STATUS_BAD_FLOOR_TABLE) */
+                                        records and SALVE_STATUS_BAD_FLOOR_TABLE), salve_pose_graph_optimise (with
+                                        salve_pose_graph_optimise_workspace_bytes, salve_graph_pgo_floor_out_t and SALVE_PGO_*) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -555,6 +556,79 @@ int salve_pose_graph_sample_trees(const salve_graph_row_t* rows, int32_t n_rows,
                                   const uint32_t* hyp_mask, int32_t n_hyps, int32_t mask_words, salve_graph_tree_out_t* out_trees,
                                   int32_t* out_inlier, salve_graph_node_out_t* out_nodes, salve_graph_sample_floor_out_t* out_floors,
                                   void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
+
+/* Pose-graph optimisation: the `pgo` method of the reference's scripts/run_sfm.py (:448-451), a robust Levenberg-Marquardt refinement of a
+ * floor's spanning-tree poses over ALL its thresholded predictions, for any number of floors in ONE launch.  Stands behind
+ *   salve/algorithms/pose2_slam.py:57-172    planar_slam (optimize_poses_only: no landmark, no bearing-range factor)
+ *   salve/algorithms/pose2_slam.py:175-286   execute_planar_slam (without axis alignment)
+ * and gtsam's PriorFactorPose2, BetweenFactorPose2, noiseModel.Robust(Huber) and LevenbergMarquardtOptimizer, restated as the rules below.
+ * gtsam is not installed where this is built.  Its default build, as far as its source is recalled, linearises the between factor without
+ * the chart's derivative and adds a model-fidelity test to the acceptance rule: parity with gtsam's ITERATES and stopping point is therefore
+ * UNPINNED.  What is pinned is the objective -- exactly the reference's factor graph -- and that the result minimises it.
+ * rows, n_rows, floor_start, n_nodes, max_nodes, confidence_threshold: exactly salve_pose_graph_solve's, verified the same way.
+ *   init   device salve_graph_node_out_t [n_floors * max_nodes], 8-byte aligned: the tree's out_nodes (solve and optimise chain on the device).
+ * Unknowns: (x, y, theta) in float64 per LOCALIZED node of `init` (localized != 0), in ascending node order; at most 256 nodes, 768 scalars.
+ *    Initial value x, y = (double)t[0], (double)t[1], theta = atan2((double)R[2], (double)R[0]).  (The reference goes through theta_deg and
+ *    Rot2.fromDegrees: about an ulp apart.  A documented deviation.)  theta is never wrapped: it stays continuous from its initial value.
+ * Odometry factors: one per CANDIDATE row (y_hat == 1 && prob >= confidence_threshold; a NaN prob never is) whose two ends are localized
+ *    (pose2_slam.py:109-117) -- ALL such rows of a pair, not the most confident one.  m = ((double)t[0], (double)t[1], atan2((double)R[2],
+ *    (double)R[0])) of the row's i2Si1; its scale is ignored (the reference builds a Pose2).  Residual of BetweenFactorPose2(X(i2), X(i1), m):
+ *    delta = R(theta2)^T (p1 - p2);  e_xy = R(m_theta)^T (delta - m_xy);  e_theta = wrap(theta1 - theta2 - m_theta),
+ *    wrap(a) = a - 2 pi ceil((a - pi) / (2 pi)), into (-pi, pi].  Sigmas odometry_sigmas (the reference: 0.2, 0.2, 0.1).
+ * Prior factor on the origin, the LOWEST localized node (np.argmax at :102): e = (x, y, wrap(theta)), sigmas prior_sigmas (0.3, 0.3, 0.1).
+ * Cost: r = e / sigma, n = ||r||, E = sum rho(n); robust = 1: rho = n^2 / 2 for n <= huber_k, huber_k (n - huber_k / 2) beyond (the
+ *    reference's run: 1.345); robust = 0: rho = n^2 / 2 (the reference's unit test).  The sum is float64 in ONE order: thread t of 256 adds the
+ *    rho of the floor's rows lo + t, lo + t + 256, ... ascending from 0.0 (thread 0 from the prior's rho); the 256 partial sums are folded by
+ *    halving (p[t] += p[t + 128], then 64, ... 1).
+ * Step: retraction p += R(theta) d_xy, theta += d_theta (gtsam's default Pose2 chart).  Each factor's exact Jacobian in that chart and its
+ *    whitened residual are scaled by sqrt(w), w = 1 for n <= huber_k (or robust = 0), huber_k / n otherwise (IRLS, as gtsam's Robust
+ *    linearises).  (J^T J + lambda I) d = -J^T r by a dense float64 Cholesky factorisation of the lower triangle (right-looking, column by
+ *    column), a forward and a backward substitution.  A pivot that is not finite and positive is a rejected step.
+ *    Order of the sums (no floating-point atomic anywhere): the 3 x 3 block of a pair of nodes is accumulated over the pair's (contiguous) rows
+ *    in row order by the thread of the pair's first row; a node's diagonal block and gradient segment by the node's thread over ALL rows of
+ *    the floor that touch it, in row order, the prior first.  The same bytes on every run, whichever floors share the launch.
+ * LM loop (gtsam's defaults): lambda = 1e-5; at most max_iterations linearisations; a step is ACCEPTED iff E(x + d) is finite and <= E(x):
+ *    then lambda /= 10, and the loop stops if the decrease is <= absolute_error_tol, else if decrease / E_old <= relative_error_tol.
+ *    Otherwise (REJECTED) lambda *= 10 and the same linearisation is solved again; the loop stops when lambda > 1e5.
+ *   out_nodes   device salve_graph_node_out_t [n_floors * max_nodes], 8-byte aligned (records v >= n_nodes[f] NOT written): localized,
+ *               parent, depth copied from `init`; R = (float) of (cos, -sin, sin, cos) of theta, t = (float) of x, y; s = 1.0.  A node that
+ *               is not localized: the empty record (0, -1, -1, zeros).
+ *   out_pose    device double [n_floors * max_nodes][3]: x, y, theta; quiet NaN where not localized; rows v >= n_nodes[f] NOT written
+ *   out_floors  device salve_graph_pgo_floor_out_t [n_floors], 8-byte aligned
+ *   workspace   salve_pose_graph_optimise_workspace_bytes(n_floors, max_nodes) bytes, 8-byte aligned.  A floor of at most
+ *               SALVE_PGO_LDS_NODES localized nodes keeps its system matrix in LDS; a larger one in its slice of the workspace (0 bytes and
+ *               NULL accepted while max_nodes <= SALVE_PGO_LDS_NODES).  Both go through the same code.
+ * Malformed floors -- a bad extent, a bad row, n_nodes > max_nodes, an `init` record whose parent lies outside [-1, n_nodes) -- are written
+ * EMPTY (empty nodes, NaN poses, a zero record with SALVE_PGO_STOP_EMPTY, NaN costs) and raise SALVE_STATUS_BAD_GRAPH_ROW; the other floors are
+ * unaffected.  A floor without a localized node is written empty and raises nothing.  A non-finite initial pose or measurement of a factor
+ * ends the floor with SALVE_PGO_STOP_NON_FINITE: the initial poses are written, costs NaN.  No address is formed from an unverified index.
+ * SALVE_ERR_BAD_ARG for a negative count, max_nodes outside 1 .. 256, a NaN threshold, robust outside {0, 1}, a sigma, huber_k or tolerance
+ * that is NaN or not positive, a negative max_iterations, and -- with n_floors > 0 -- a null or misaligned pointer (rows may be null while
+ * n_rows == 0); SALVE_ERR_WORKSPACE for a short workspace.  odometry_sigmas and prior_sigmas are HOST double [3]. */
+#define SALVE_PGO_LDS_NODES 56
+enum {
+    SALVE_PGO_STOP_EMPTY = 0,          /* nothing to optimise: malformed floor, or no localized node */
+    SALVE_PGO_STOP_ABSOLUTE = 1,       /* an accepted step's decrease <= absolute_error_tol */
+    SALVE_PGO_STOP_RELATIVE = 2,       /* ... decrease / E_old <= relative_error_tol */
+    SALVE_PGO_STOP_LAMBDA = 3,         /* lambda exceeded 1e5 */
+    SALVE_PGO_STOP_MAX_ITERATIONS = 4, /* max_iterations linearisations done */
+    SALVE_PGO_STOP_NON_FINITE = 5      /* a non-finite initial pose or measurement */
+};
+typedef struct {
+    int32_t n_unknown_nodes;           /* localized nodes */
+    int32_t n_factors;                 /* the prior and the odometry factors */
+    int32_t n_iterations;              /* linearisations */
+    int32_t n_rejected;                /* rejected steps */
+    int32_t n_downweighted;            /* factors with n > huber_k at the final poses (robust = 0: 0) */
+    int32_t stop_reason;               /* SALVE_PGO_STOP_* */
+    double lambda, cost_initial, cost_final;
+} salve_graph_pgo_floor_out_t;
+size_t salve_pose_graph_optimise_workspace_bytes(int32_t n_floors, int32_t max_nodes);
+int salve_pose_graph_optimise(const salve_graph_row_t* rows, int32_t n_rows, const int32_t* floor_start, const int32_t* n_nodes, int32_t n_floors,
+                              int32_t max_nodes, float confidence_threshold, const salve_graph_node_out_t* init, int32_t robust, double huber_k,
+                              const double* odometry_sigmas, const double* prior_sigmas, int32_t max_iterations, double relative_error_tol,
+                              double absolute_error_tol, salve_graph_node_out_t* out_nodes, double* out_pose,
+                              salve_graph_pgo_floor_out_t* out_floors, void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
 /* The floor reconstruction report, part 1: the estimated poses of any number of floors aligned to the truth by the reference's RANSAC, and
  * the pose errors, in ONE call (two launches on `stream`).  Stands behind

@@ -109,6 +109,8 @@ EXPORTED_SYMBOLS = (
     "salve_pose_graph_solve",
     "salve_pose_graph_sample_workspace_bytes",
     "salve_pose_graph_sample_trees",
+    "salve_pose_graph_optimise_workspace_bytes",
+    "salve_pose_graph_optimise",
     "salve_floor_align",
     "salve_floor_iou_workspace_bytes",
     "salve_floor_iou",
@@ -177,6 +179,13 @@ GRAPH_TREE_OUT_DTYPE = np.dtype([("avg_rot_err", "<f8"), ("avg_trans_err", "<f8"
 GRAPH_SAMPLE_FLOOR_OUT_DTYPE = np.dtype([("best", "<i4"), ("n_candidates", "<i4"), ("n_hyps", "<i4"), ("n_improvements", "<i4"), ("avg_rot_err", "<f8"),
                                          ("avg_trans_err", "<f8")])
 assert GRAPH_TREE_OUT_DTYPE.itemsize == 40 and GRAPH_SAMPLE_FLOOR_OUT_DTYPE.itemsize == 32
+# salve_pose_graph_optimise (salve_graph_pgo_floor_out_t, SALVE_PGO_*)
+GRAPH_PGO_FLOOR_OUT_DTYPE = np.dtype([("n_unknown_nodes", "<i4"), ("n_factors", "<i4"), ("n_iterations", "<i4"), ("n_rejected", "<i4"),
+                                      ("n_downweighted", "<i4"), ("stop_reason", "<i4"), ("lambda", "<f8"), ("cost_initial", "<f8"), ("cost_final", "<f8")])
+assert GRAPH_PGO_FLOOR_OUT_DTYPE.itemsize == 48
+PGO_LDS_NODES = 56
+PGO_STOP_EMPTY, PGO_STOP_ABSOLUTE, PGO_STOP_RELATIVE, PGO_STOP_LAMBDA, PGO_STOP_MAX_ITERATIONS, PGO_STOP_NON_FINITE = 0, 1, 2, 3, 4, 5
+PGO_STOP_NAMES = ("empty", "absolute_error_tol", "relative_error_tol", "lambda_bound", "max_iterations", "non_finite")
 # salve_floor_align, salve_floor_iou (salve_floor_hyp_out_t, salve_floor_align_out_t, salve_floor_iou_out_t)
 FLOOR_MASK_WORDS = 8
 FLOOR_HYP_OUT_DTYPE = np.dtype([("R", "<f8", (4,)), ("t", "<f8", (2,)), ("s", "<f8"), ("rot_err", "<f8"), ("trans_err", "<f8"), ("n_pairs", "<i4"),
@@ -343,6 +352,13 @@ def load() -> ctypes.CDLL:
     # out_floors, ws, ws_bytes, status, stream
     lib.salve_pose_graph_sample_trees.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, vp, vp, i32, i32, vp, vp, vp, vp, vp, sz, vp, vp]
     lib.salve_pose_graph_sample_trees.restype = ctypes.c_int
+    lib.salve_pose_graph_optimise_workspace_bytes.argtypes = [i32, i32]
+    lib.salve_pose_graph_optimise_workspace_bytes.restype = sz
+    # rows, n_rows, floor_start, n_nodes, n_floors, max_nodes, confidence, init, robust, huber_k, HOST odometry_sigmas, HOST prior_sigmas, max_iterations,
+    # relative_error_tol, absolute_error_tol, out_nodes, out_pose, out_floors, ws, ws_bytes, status, stream
+    lib.salve_pose_graph_optimise.argtypes = [vp, i32, vp, vp, i32, i32, ctypes.c_float, vp, i32, ctypes.c_double, vp, vp, i32, ctypes.c_double,
+                                              ctypes.c_double, vp, vp, vp, vp, sz, vp, vp]
+    lib.salve_pose_graph_optimise.restype = ctypes.c_int
     # (node_start, n_floors, n_nodes, truth, est, hyp_start, hyp_mask, n_hyps, gt_scale, metres, out_hyps, out_nodes, out_rot_err, out_trans_err,
     #  out_floors, status, stream)
     lib.salve_floor_align.argtypes = [vp, i32, i32, vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -290,7 +290,8 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     reference's JPEG files).
     pose_graph: None, or the keyword arguments of salve_amd.pose_graph.solve (confidence_threshold is required; cycle_filter,
     rot_threshold_deg, trans_threshold) and of pose_graph.run (method, filter_by_random_spanning_trees, num_hypotheses, sampling_fraction,
-    seed: the best of many random spanning trees, as a method or as an edge filter) -- the floor's pose graph is solved right behind scoring, from the rows still in memory: the result
+    seed: the best of many random spanning trees, as a method or as an edge filter; method "pgo" with pose_graph.optimise's robust, max_iterations
+    and tolerances: the tree refined by pose-graph optimisation, a PgoSolution) -- the floor's pose graph is solved right behind scoring, from the rows still in memory: the result
     gains "pose_graph" (a pose_graph.FloorSolution, or a TreeSampleSolution for method "random_spanning_trees"; None when no hypothesis was scored) and `serialization_save_dir` one more file,
     pose_graph_{building}_{floor}.json, equal to what `python -m salve_amd.pose_graph` makes of the prediction files.  None: launches, files
     and the returned dict are unchanged.  With "truth" (a salve_amd.floor_report.FloorTruth; "report": floor_report.report's num_iters,

@@ -3,8 +3,8 @@ scripts/run_sfm.py:112-152 and :440-446, with and without its cycle filter, for 
 (include/salve_hip.h: salve_pose_graph_solve; salve_amd/csrc/pose_graph.hip).
 
     python -m salve_amd.pose_graph PRED_DIR --hypotheses ROOT --confidence-threshold X [--no-cycle-filter] [--rot-deg D] [--trans T] [--out DIR]
-        [--method {spanning_tree,random_spanning_trees}] [--filter-by-random-spanning-trees] [--num-hypotheses H] [--sampling-fraction F] [--seed S]
-        [--zind-root DIR] [--report-seed S] [--report-iters K]
+        [--method {spanning_tree,random_spanning_trees,pgo}] [--filter-by-random-spanning-trees] [--num-hypotheses H] [--sampling-fraction F] [--seed S]
+        [--pgo-max-iterations K] [--pgo-no-robust] [--zind-root DIR] [--report-seed S] [--report-iters K]
 
 reads the `batch_*.json` prediction files of PRED_DIR (evaluate.run_test_epoch, evaluate.run_fused_epoch, ingest.score_floor), looks every
 prediction's alignment hypothesis up under ROOT, and writes one `pose_graph_{building}_{floor}.json` per floor.
@@ -24,8 +24,16 @@ predictions and picks the reference's winner, all floors and hypotheses in one c
 salve_amd/csrc/pose_graph_sample.hip).  The winner's subset is also the reference's edge filter in front of the first method:
 `solve(meas, thr, keep_rows=combined_inlier_mask(sample_trees(meas, thr)))`.
 
+The third method, `pgo` (run_sfm.py:448-451; pose2_slam.py:57-286): `optimise` builds the spanning tree and refines it
+by pose-graph optimisation -- a robust Levenberg-Marquardt over ALL thresholded predictions between localized panoramas, every second
+hypothesis of a pair and every loop closure included -- in two device calls on the same buffers (salve_pose_graph_solve, then
+salve_pose_graph_optimise; salve_amd/csrc/pose_graph_pgo.hip).  The objective is exactly the reference's factor graph and the result minimises
+it; gtsam is not installed where this was built, so parity with gtsam's iterates and stopping point is unpinned.  `--no-cycle-filter --method
+pgo` is the reference's pipeline.
+
 The evaluation against ground truth is salve_amd.floor_report: `run(..., truth=)` and `--zind-root DIR` end in one
-floor_report_{building}_{floor}.json per floor.  Pose-graph optimisation and axis alignment are NOT here.  A floor may have at most 256 panoramas.
+floor_report_{building}_{floor}.json per floor.  Axis alignment by vanishing angle (it needs MHNet's predictions), landmark SLAM (the
+reference's `pose2_slam` method) and filter_edges_by_global_local_consistency are NOT here.  A floor may have at most 256 panoramas.
 """
 
 from __future__ import annotations
@@ -268,6 +276,13 @@ def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: boo
     out_nodes = host[off_nodes:off_floors].view(_lib.GRAPH_NODE_OUT_DTYPE).reshape(F, M)
     out_floors = host[off_floors:].view(_lib.GRAPH_FLOOR_OUT_DTYPE)
 
+    return _floor_solutions(meas, floors, floor_start, out_rows, out_nodes, out_floors, confidence_threshold, cycle_filter, rot_threshold_deg,
+                            trans_threshold)
+
+
+def _floor_solutions(meas, floors, floor_start, out_rows, out_nodes, out_floors, confidence_threshold, cycle_filter, rot_threshold_deg,
+                     trans_threshold) -> List[FloorSolution]:
+    """salve_pose_graph_solve's three output tables as one FloorSolution per floor."""
     options = {"confidence_threshold": float(confidence_threshold), "cycle_filter": bool(cycle_filter), "rot_threshold_deg": float(rot_threshold_deg),
                "trans_threshold": float(trans_threshold)}
     sim = lambda R, t, s: Sim2(np.array(R, dtype=np.float32).reshape(2, 2), np.array(t, dtype=np.float32), float(s))
@@ -299,6 +314,161 @@ def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: boo
                                                                                     "n_consistent_edges", "n_localized")}}
         solutions.append(FloorSolution(fl["building_id"], fl["floor_id"], ids, dict(options), rel, rel_consistent, wSi, edges, parent, depth, counts,
                                        origin))
+    return solutions
+
+
+PGO_OPTIONS = ("robust", "max_iterations", "relative_error_tol", "absolute_error_tol", "huber_k", "odometry_sigmas", "prior_sigmas")   # optimise's own
+HUBER_K, ODOMETRY_SIGMAS, PRIOR_SIGMAS = 1.345, (0.2, 0.2, 0.1), (0.3, 0.3, 0.1)   # planar_slam's own (pose2_slam.py:87-93)
+
+
+@dataclass
+class PgoSolution:
+    """A floor's spanning tree refined by pose-graph optimisation (salve_pose_graph_optimise)."""
+
+    building_id: str
+    floor_id: str
+    pano_ids: np.ndarray
+    options: Dict[str, Any]                               # method, the tree's options and the optimiser's
+    tree: FloorSolution                                   # the initial estimate, as `solve` returns it
+    wSi_list: Optional[List[Optional[Sim2]]]              # by pano id, in the tree's shape and length: float32 Sim2 of scale 1
+    pose: Dict[int, Tuple[float, float, float]]           # by pano id: x, y, theta in float64 (theta continuous from the tree's, not wrapped)
+    record: Dict[str, Any]                                # the floor record: counts, stop_reason (a name of _lib.PGO_STOP_NAMES), lambda, costs
+
+    @property
+    def counts(self) -> Dict[str, int]:
+        return self.tree.counts
+
+    @property
+    def origin(self) -> Optional[int]:
+        return self.tree.origin
+
+    def summary(self) -> str:
+        r, fin = self.record, lambda x: "nan" if x is None else f"{x:.6g}"
+        return (f"{self.building_id} {self.floor_id}: pgo over {r['n_factors']} factors, {r['n_unknown_nodes']} / {self.tree.counts['n_nodes']} panoramas, "
+                f"cost {fin(r['cost_initial'])} -> {fin(r['cost_final'])} in {r['n_iterations']} iterations ({r['n_rejected']} rejected, "
+                f"{r['n_downweighted']} down-weighted), stopped by {r['stop_reason']}")
+
+    def to_json(self) -> Dict[str, Any]:
+        sim = lambda S: {"R": S.rotation.flatten().tolist(), "t": S.translation.flatten().tolist(), "s": S.scale}
+        opts = dict(self.options)
+        opts["trans_threshold"] = opts["trans_threshold"] if np.isfinite(opts["trans_threshold"]) else None   # (as the tree's)
+        return {"building_id": self.building_id, "floor_id": self.floor_id, "options": opts, "pano_ids": [int(p) for p in self.pano_ids],
+                "pgo": dict(self.record), "n_poses": None if self.wSi_list is None else len(self.wSi_list),
+                "poses": {str(p): {**sim(S), "pose": list(self.pose[p])} for p, S in enumerate(self.wSi_list or []) if S is not None},
+                "tree": self.tree.to_json()}
+
+    @classmethod
+    def from_json(cls, d: Dict[str, Any]) -> "PgoSolution":
+        sim = lambda r: Sim2(np.array(r["R"], dtype=np.float32).reshape(2, 2), np.array(r["t"], dtype=np.float32), float(r["s"]))
+        wSi = None
+        if d["n_poses"] is not None:
+            wSi = [None] * d["n_poses"]
+            for p, r in d["poses"].items():
+                wSi[int(p)] = sim(r)
+        opts = dict(d["options"])
+        opts["trans_threshold"] = float("inf") if opts["trans_threshold"] is None else opts["trans_threshold"]
+        return cls(d["building_id"], d["floor_id"], np.array(d["pano_ids"], dtype=np.int64), opts, FloorSolution.from_json(d["tree"]), wSi,
+                   {int(p): tuple(r["pose"]) for p, r in d["poses"].items()}, dict(d["pgo"]))
+
+
+def optimise(meas: EdgeMeasurements, confidence_threshold: float, robust: bool = True, max_iterations: int = 100, relative_error_tol: float = 1e-5,
+             absolute_error_tol: float = 1e-5, keep_rows: Optional[np.ndarray] = None, device="cuda:0", huber_k: float = HUBER_K,
+             odometry_sigmas: Sequence[float] = ODOMETRY_SIGMAS, prior_sigmas: Sequence[float] = PRIOR_SIGMAS, **solve_options) -> List[PgoSolution]:
+    """One PgoSolution per floor of `meas` (in `meas.floors()` order): the reference's `--method pgo` (run_sfm.py:448-451; pose2_slam.py:57-286
+    with optimize_poses_only, without axis alignment).  One upload; salve_pose_graph_solve builds every floor's spanning tree and
+    salve_pose_graph_optimise refines it over ALL thresholded predictions whose two panoramas the tree localizes, on the same device buffers
+    with no download between them; one read of the device status word; one download.  solve_options: solve's cycle_filter, rot_threshold_deg,
+    trans_threshold -- they shape the initial tree only (cycle_filter=False is the reference's pipeline).  keep_rows: solve's; the factors are
+    then the kept rows only.  The defaults of robust, huber_k, the sigmas, max_iterations and the tolerances are the reference's and gtsam's;
+    parity with gtsam's iterates is unpinned: the objective is the reference's, and the result minimises it."""
+    import torch
+
+    from salve_amd import status
+
+    unknown = set(solve_options) - {"cycle_filter", "rot_threshold_deg", "trans_threshold"}
+    if unknown:
+        raise TypeError(f"pose_graph.optimise: unknown options {sorted(unknown)}")
+    cycle_filter = bool(solve_options.get("cycle_filter", True))
+    rot_threshold_deg, trans_threshold = solve_options.get("rot_threshold_deg", ROT_THRESHOLD_DEG), solve_options.get("trans_threshold", TRANS_THRESHOLD)
+    if int(max_iterations) < 0:
+        raise ValueError("pose_graph.optimise: max_iterations is negative")
+    for name, v in (("relative_error_tol", relative_error_tol), ("absolute_error_tol", absolute_error_tol), ("huber_k", huber_k),
+                    *((f"odometry_sigmas[{i}]", x) for i, x in enumerate(odometry_sigmas)), *((f"prior_sigmas[{i}]", x) for i, x in enumerate(prior_sigmas))):
+        if not float(v) > 0.0:
+            raise ValueError(f"pose_graph.optimise: {name} must be positive, not {v}")
+    if len(odometry_sigmas) != 3 or len(prior_sigmas) != 3:
+        raise ValueError("pose_graph.optimise: three sigmas each (x, y, theta)")
+    device = torch.device(device)
+    lib = _lib.load()
+    floors = meas.compact()
+    F = len(floors)
+    if F == 0:
+        return []
+    if keep_rows is not None:
+        keep_rows = np.asarray(keep_rows, dtype=bool).reshape(-1)
+        if len(keep_rows) != len(meas):
+            raise ValueError(f"pose_graph.optimise: keep_rows has {len(keep_rows)} entries for {len(meas)} rows")
+        for fl in floors:
+            k = keep_rows[fl["rows"]]
+            fl["rows"], fl["c1"], fl["c2"] = fl["rows"][k], fl["c1"][k], fl["c2"][k]
+    table, floor_start, n_nodes, M = _device_table(meas, floors, "pose_graph.optimise")
+    N = len(table)
+
+    # one upload: rows | floor_start | n_nodes; one output buffer: out_rows | tree nodes | tree floors | pgo nodes | pgo floors | poses
+    node_dt, pgo_dt = _lib.GRAPH_NODE_OUT_DTYPE, _lib.GRAPH_PGO_FLOOR_OUT_DTYPE
+    blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
+    off_nodes = _align8(N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize)
+    off_floors = off_nodes + F * M * node_dt.itemsize
+    off_pgo_nodes = _align8(off_floors + F * _lib.GRAPH_FLOOR_OUT_DTYPE.itemsize)
+    off_pgo_floors = off_pgo_nodes + F * M * node_dt.itemsize
+    off_pose = off_pgo_floors + F * pgo_dt.itemsize
+    out_bytes = off_pose + F * M * 24
+    sig_o, sig_p = (ctypes.c_double * 3)(*map(float, odometry_sigmas)), (ctypes.c_double * 3)(*map(float, prior_sigmas))
+    with torch.cuda.device(device):
+        dev_in = torch.from_numpy(blob).to(device)
+        dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        p_in, p_out = dev_in.data_ptr(), dev_out.data_ptr()
+        vp = ctypes.c_void_p
+        stream = vp(torch.cuda.current_stream(device).cuda_stream)
+        ws_bytes = max(int(lib.salve_pose_graph_workspace_bytes(F, M)), int(lib.salve_pose_graph_optimise_workspace_bytes(F, M)))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
+        p_ws = vp(ws.data_ptr()) if ws is not None else None
+        p_rows, p_start, p_n = vp(p_in), vp(p_in + table.nbytes), vp(p_in + table.nbytes + floor_start.nbytes)
+        _lib.check(lib.salve_pose_graph_solve(p_rows, N, p_start, p_n, F, M, float(confidence_threshold), float(rot_threshold_deg), float(trans_threshold),
+                                              int(cycle_filter), vp(p_out), vp(p_out + off_nodes), vp(p_out + off_floors), p_ws, ws_bytes,
+                                              status.ptr(device), stream), "salve_pose_graph_solve")
+        _lib.check(lib.salve_pose_graph_optimise(p_rows, N, p_start, p_n, F, M, float(confidence_threshold), vp(p_out + off_nodes), int(bool(robust)),
+                                                 float(huber_k), sig_o, sig_p, int(max_iterations), float(relative_error_tol), float(absolute_error_tol),
+                                                 vp(p_out + off_pgo_nodes), vp(p_out + off_pose), vp(p_out + off_pgo_floors), p_ws, ws_bytes,
+                                                 status.ptr(device), stream), "salve_pose_graph_optimise")
+        status.check(device, "pose_graph.optimise")   # (the one synchronising read)
+        host = dev_out.cpu().numpy()
+    trees = _floor_solutions(meas, floors, floor_start, host[:N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize].view(_lib.GRAPH_ROW_OUT_DTYPE),
+                             host[off_nodes:off_floors].view(node_dt).reshape(F, M),
+                             host[off_floors:off_floors + F * _lib.GRAPH_FLOOR_OUT_DTYPE.itemsize].view(_lib.GRAPH_FLOOR_OUT_DTYPE), confidence_threshold,
+                             cycle_filter, rot_threshold_deg, trans_threshold)
+    pgo_nodes = host[off_pgo_nodes:off_pgo_floors].view(node_dt).reshape(F, M)
+    pgo_floors = host[off_pgo_floors:off_pose].view(pgo_dt)
+    poses = host[off_pose:].view(np.float64).reshape(F, M, 3)
+
+    options = {"method": "pgo", "robust": bool(robust), "huber_k": float(huber_k), "odometry_sigmas": [float(x) for x in odometry_sigmas],
+               "prior_sigmas": [float(x) for x in prior_sigmas], "max_iterations": int(max_iterations), "relative_error_tol": float(relative_error_tol),
+               "absolute_error_tol": float(absolute_error_tol)}
+    fin = lambda x: float(x) if np.isfinite(x) else None
+    solutions = []
+    for f, (fl, tree) in enumerate(zip(floors, trees)):
+        ids, fo = fl["pano_ids"], pgo_floors[f]
+        wSi, pose = None, {}
+        if tree.wSi_list is not None:
+            wSi = [None] * len(tree.wSi_list)
+            for v in np.nonzero(pgo_nodes[f, :len(ids)]["localized"])[0]:
+                o, p = pgo_nodes[f, v], int(ids[v])
+                wSi[p] = Sim2(np.array(o["R"], dtype=np.float32).reshape(2, 2), np.array(o["t"], dtype=np.float32), float(o["s"]))
+                pose[p] = tuple(float(x) for x in poses[f, v])
+        record = {**{k: int(fo[k]) for k in ("n_unknown_nodes", "n_factors", "n_iterations", "n_rejected", "n_downweighted")},
+                  "stop_reason": _lib.PGO_STOP_NAMES[int(fo["stop_reason"])], "lambda": float(fo["lambda"]), "cost_initial": fin(fo["cost_initial"]),
+                  "cost_final": fin(fo["cost_final"])}
+        solutions.append(PgoSolution(fl["building_id"], fl["floor_id"], ids, {**tree.options, **options}, tree, wSi, pose, record))
     return solutions
 
 
@@ -527,7 +697,9 @@ def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "span
         num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", truth=None, report_options=None, **solve_options):
     """What the command line and ingest.score_floor(pose_graph=...) do with their options.  method "spanning_tree": solve(meas,
     confidence_threshold, **solve_options), behind the random-spanning-trees edge filter if filter_by_random_spanning_trees; method
-    "random_spanning_trees": sample_trees.  With the defaults this IS solve: the same launches and values.
+    "random_spanning_trees": sample_trees; method "pgo": optimise(meas, confidence_threshold, **solve_options) -- the spanning tree refined by
+    pose-graph optimisation, behind the same edge filter if asked; robust, max_iterations, relative_error_tol, absolute_error_tol (and huber_k, the
+    sigmas) among the options are optimise's own and belong to this method alone.  With the defaults this IS solve: the same launches and values.
     truth: None, or the floors' ground truth -- salve_amd.floor_report.FloorTruth objects, as a list in `meas.floors()` order or a dict keyed by
     (building_id, floor_id).  Then the result is (solutions, reports): floor_report.report(solutions, truths, **report_options) follows the
     solve."""
@@ -538,9 +710,21 @@ def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "span
                         num_hypotheses=num_hypotheses, sampling_fraction=sampling_fraction, seed=seed, device=device, **solve_options)
         truths = [truth[(s.building_id, s.floor_id)] for s in solutions] if isinstance(truth, dict) else list(truth)
         return solutions, floor_report.report(solutions, truths, device=device, **(report_options or {}))
-    if method not in ("spanning_tree", "random_spanning_trees"):
+    if method not in ("spanning_tree", "random_spanning_trees", "pgo"):
         raise ValueError(f"pose_graph.run: unknown method {method!r}")
     sampling = {"num_hypotheses": num_hypotheses, "sampling_fraction": sampling_fraction, "seed": seed}
+    pgo_options = {k: solve_options.pop(k) for k in PGO_OPTIONS if k in solve_options}
+    if pgo_options and method != "pgo":
+        raise ValueError(f"pose_graph.run: {sorted(pgo_options)} belong to method pgo")
+    if method == "pgo":
+        keep = None
+        if filter_by_random_spanning_trees:   # the factors are then the kept rows only (run_sfm.py passes high_conf_inlier_measurements on)
+            keep = combined_inlier_mask(sample_trees(meas, confidence_threshold, device=device, **sampling))
+        solutions = optimise(meas, confidence_threshold, keep_rows=keep, device=device, **pgo_options, **solve_options)
+        for sol in solutions:
+            if filter_by_random_spanning_trees:
+                sol.options["filter_by_random_spanning_trees"] = dict(sampling)
+        return solutions
     if method == "random_spanning_trees":
         if solve_options or filter_by_random_spanning_trees:
             raise ValueError("pose_graph.run: method random_spanning_trees takes neither the cycle filter's options nor the edge filter")
@@ -578,10 +762,14 @@ def main(argv=None) -> int:
     ap.add_argument("--trans", type=float, default=TRANS_THRESHOLD, help="3-cycle translation threshold (default %(default)s; inf: rotation only)")
     ap.add_argument("--out", metavar="DIR", default=None, help="where the pose_graph_*.json files go (default: PRED_DIR)")
     ap.add_argument("--device", default="cuda:0")
-    ap.add_argument("--method", choices=("spanning_tree", "random_spanning_trees"), default="spanning_tree",
-                    help="random_spanning_trees: the best of --num-hypotheses random subsets' trees (the cycle filter's options do not apply)")
+    ap.add_argument("--method", choices=("spanning_tree", "random_spanning_trees", "pgo"), default="spanning_tree",
+                    help="random_spanning_trees: the best of --num-hypotheses random subsets' trees (the cycle filter's options do not apply); "
+                         "pgo: the spanning tree refined by pose-graph optimisation over all thresholded predictions -- the cycle filter's options "
+                         "still shape the initial tree, and --no-cycle-filter gives the reference's pgo pipeline (run_sfm.py:448-451)")
+    ap.add_argument("--pgo-max-iterations", type=int, default=None, help="method pgo: most linearisations per floor (default 100)")
+    ap.add_argument("--pgo-no-robust", action="store_true", help="method pgo: plain least squares instead of the Huber loss")
     ap.add_argument("--filter-by-random-spanning-trees", action="store_true",
-                    help="method spanning_tree: keep only the predictions of the best random subset before anything else")
+                    help="methods spanning_tree and pgo: keep only the predictions of the best random subset before anything else")
     ap.add_argument("--num-hypotheses", type=int, default=100, help="random subsets per floor (default %(default)s)")
     ap.add_argument("--sampling-fraction", type=float, default=0.5, help="share of a floor's thresholded predictions per subset (default %(default)s)")
     ap.add_argument("--seed", type=int, default=0, help="seed of every floor's draws (default %(default)s)")
@@ -594,10 +782,19 @@ def main(argv=None) -> int:
     meas = EdgeMeasurements.from_prediction_files(args.pred_dir, args.hypotheses)
     if args.method == "random_spanning_trees":
         if args.filter_by_random_spanning_trees:
-            ap.error("--filter-by-random-spanning-trees belongs to --method spanning_tree")
+            ap.error("--filter-by-random-spanning-trees belongs to --method spanning_tree or pgo")
         options = {}
     else:
         options = {"cycle_filter": not args.no_cycle_filter, "rot_threshold_deg": args.rot_deg, "trans_threshold": args.trans}
+    if args.method == "pgo":
+        if args.pgo_max_iterations is not None:
+            if args.pgo_max_iterations < 0:
+                ap.error("--pgo-max-iterations must not be negative")
+            options["max_iterations"] = args.pgo_max_iterations
+        if args.pgo_no_robust:
+            options["robust"] = False
+    elif args.pgo_max_iterations is not None or args.pgo_no_robust:
+        ap.error("--pgo-max-iterations and --pgo-no-robust belong to --method pgo")
     solutions = run(meas, args.confidence_threshold, method=args.method, filter_by_random_spanning_trees=args.filter_by_random_spanning_trees,
                     num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options)
     for sol in solutions:
