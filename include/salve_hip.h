@@ -738,6 +738,78 @@ int salve_floor_iou(const double* room_xy, const int64_t* room_off, int64_t n_ro
                     int32_t img_w, float offset_x, float offset_y, double pixels_per_metre, salve_floor_iou_out_t* out, uint32_t* out_masks,
                     void* workspace, size_t workspace_bytes, int32_t* status, void* stream);
 
+/* Alignment hypotheses: every W/D/O alignment of every panorama pair of any number of floors in ONE launch (additive within ABI 7).  Stands
+ * behind the inferred-W/D/O path (`--wdo_source horizon_net`) of the reference's scripts/export_alignment_hypotheses.py:93-273:
+ *   salve/utils/wdo_alignment.py:107-284           align_rooms_by_wd (transform_type SE2, use_inferred_wdos_layout)   enumeration, fit, acceptance
+ *   salve/utils/se2_estimation.py:11-41            align_points_SE2 (gtsam's Pose2::Align)                           the fit
+ *   salve/utils/wdo_alignment.py:394-415           determine_invalid_width_ratio                                     acceptance
+ *   salve/common/alignment_hypothesis.py:29-56     prune_to_unique_sim2_objs (Sim2.__eq__, sim2.py)                  pruning
+ *   salve/utils/wdo_alignment.py:418-454           obj_almost_equal (rotation_utils.angle_is_equal)                  the label
+ *   scripts/export_alignment_hypotheses.py:43-72   are_visibly_adjacent (shapely's hausdorff_distance)               adjacency
+ *   scripts/export_alignment_hypotheses.py:205     i2Ti1_gt = wTi2.inverse().compose(wTi1)                           the truth of a pair
+ * The host names the pairs: one salve_hyp_pair_t per panorama pair, in any order (the floors, the ascending panorama ids and the pairs the
+ * reference leaves out are the host's business).  Per pair the candidates are enumerated doors, windows, openings (wdo_type 1, 0, 2 --
+ * salve_layout_pose's codes); within a type i over pano1's objects of the type, j over pano2's (both in table order), and for doors and
+ * openings the configuration identity (0) then rotated (1: pano2's two vertices swapped); windows have identity only.  capacity must equal
+ * that count: 2 d1 d2 + w1 w2 + 2 o1 o2.
+ * Fit, all float64, no product fused into a sum: a = pano2's polygon [p1, p1, p2, p2, p1] (p1 counts three times, p2 twice: the rotation is
+ *  the two-point fit's, the translation is not when the widths differ), b = pano1's; ca, cb = (the sum in point order) / 5; over the five
+ *  points in order c += db.x da.x + db.y da.y and s += -db.y da.x + db.x da.y; h = sqrt(c c + s s); R = [[c / h, -s / h], [s / h, c / h]],
+ *  R = I when h == 0; t = ca - R cb; R and t are rounded to float32 once.  (gtsam takes cos / sin of atan2(s, c): a stated deviation of a
+ *  few float64 ulps)
+ * Accept: w = sqrt(dx dx + dy dy) of each object; min(w1, w2) / max(w1, w2) >= min_width_ratio (a NaN ratio rejects).
+ * Prune, greedily in candidate order over all three types: an accepted candidate x is kept unless |x - k| <= 1e-8 + 1e-5 |k| holds in all four
+ *  entries of R and both of t for some k kept before it (float32 values widened to float64; NaN is unequal).
+ * Label of a kept row against G = inverse(wS_pano2).compose(wS_pano1) (the float32 Sim(2) arithmetic of salve_pose_graph_solve): 1 iff
+ *  |t - G.t| <= 0.35 + 1e-5 |G.t| in both entries, |1 - G.s| <= 0.35 + 1e-5 |G.s|, and the angle difference d = fmod(th_G - th + 180, 360)
+ *  (+ 360 when negative) - 180, + 360 if < -180, has |d| <= 7 (doors, windows) or 9 (openings); th = atan2(R10, R00) * (180 / pi) in float64.
+ * Adjacency: the pair is visibly adjacent iff some segment of pano1's and some of pano2's GLOBAL ground-truth W/D/Os lie at a Hausdorff
+ *  distance < 0.1 (the larger of the two directed maxima over endpoints of the point-to-segment distance, GEOS' rule).
+ *   wdo_xy, wdo_type, wdo_off   device float64 [n_wdo][2][2], uint8 [n_wdo], int64 [n_panos + 1]: the inferred W/D/Os, local frames
+ *   gt_xy, gt_off               device float64 [n_gt][2][2], int64 [n_panos + 1]: the ground-truth W/D/Os in the GLOBAL frame
+ *   poses                       device salve_graph_node_out_t [n_panos]: wS_pano in R, t, s (the other fields are not read)
+ *   pairs                       device salve_hyp_pair_t [n_pairs], 8-byte aligned
+ *   max_capacity                the caller's bound on pairs[].capacity: sizes the workgroup's LDS (24 bytes per candidate); 0 .. 5120
+ *   out_rows                    device salve_hyp_row_t [n_rows]: the kept rows of pair p are row_offset .. row_offset + n_kept - 1, in
+ *                               candidate order; the rows behind them up to row_offset + capacity are NOT written
+ *   out_pairs                   device salve_hyp_pair_out_t [n_pairs], 8-byte aligned
+ * One launch on `stream`, one workgroup of one wavefront per pair; n_pairs == 0 launches nothing.  No floating-point atomic and no atomic append:
+ * a kept row's place is its rank in candidate order, so the same bytes on every run.  The tables are device memory, so the kernel verifies a
+ * pair before it forms an address from it: with a panorama outside [0, n_panos), an offset table that steps back or leaves its array, more
+ * than 32 objects of a type, a capacity other than the candidate count or above max_capacity, or rows outside [0, n_rows], the pair's
+ * record is written n_kept = -1 (zeros elsewhere) and none of its rows.  SALVE_ERR_BAD_ARG for a negative count, max_capacity outside
+ * 0 .. 5120, a NaN ratio, and -- with n_pairs > 0 -- a null or misaligned pointer (the W/D/O arrays and out_rows may be null while empty). */
+#define SALVE_HYP_MAX_WDO_PER_TYPE 32
+#define SALVE_HYP_MAX_CAPACITY 5120 /* 2 * 32 * 32 + 32 * 32 + 2 * 32 * 32 */
+typedef struct {
+    int32_t pano1, pano2;  /* indices into the panorama tables */
+    int32_t capacity;      /* the pair's candidate count */
+    int32_t reserved;      /* not read */
+    int64_t row_offset;    /* the pair's first row in out_rows */
+} salve_hyp_pair_t;
+typedef struct {
+    float R[4];            /* i2Ti1: rotation, row-major */
+    float t[2];
+    int32_t type;          /* 1 door, 0 window, 2 opening */
+    int32_t i, j;          /* the object's rank within its type in pano1, in pano2 */
+    int32_t configuration; /* 0 identity, 1 rotated */
+    int32_t label;         /* 1 gt_alignment_approx, 0 incorrect_alignment */
+    int32_t reserved;      /* written 0 */
+} salve_hyp_row_t;
+typedef struct {
+    int32_t n_kept;           /* -1: a malformed pair */
+    int32_t n_valid;          /* accepted candidates, before pruning */
+    int32_t n_rejected;       /* candidates the width ratio rejected */
+    int32_t visibly_adjacent; /* 0 / 1 */
+    float R[4];               /* i2Ti1_gt */
+    float t[2];
+    double s;
+} salve_hyp_pair_out_t;
+int salve_hypotheses_generate(const double* wdo_xy, const uint8_t* wdo_type, const int64_t* wdo_off, int64_t n_wdo, const double* gt_xy,
+                              const int64_t* gt_off, int64_t n_gt, const salve_graph_node_out_t* poses, int32_t n_panos,
+                              const salve_hyp_pair_t* pairs, int64_t n_pairs, int32_t max_capacity, double min_width_ratio,
+                              salve_hyp_row_t* out_rows, int64_t n_rows, salve_hyp_pair_out_t* out_pairs, void* stream);
+
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,
  * both go to sample jobs_a[k].slot ( == jobs_b[k].slot), channels jobs_a[k].chan .. + 2 and jobs_b[k].chan .. + 2, which

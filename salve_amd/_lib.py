@@ -114,6 +114,7 @@ EXPORTED_SYMBOLS = (
     "salve_floor_align",
     "salve_floor_iou_workspace_bytes",
     "salve_floor_iou",
+    "salve_hypotheses_generate",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -194,6 +195,15 @@ FLOOR_ALIGN_OUT_DTYPE = np.dtype([("best", "<i4"), ("n_hyps", "<i4"), ("n_est", 
                                   ("avg_trans_err", "<f8"), ("percent_localized", "<f8"), ("R", "<f8", (4,)), ("t", "<f8", (2,)), ("s", "<f8")])
 FLOOR_IOU_OUT_DTYPE = np.dtype([("n_est", "<i4"), ("n_gt", "<i4"), ("inter", "<i4"), ("uni", "<i4"), ("bad", "<i4"), ("reserved", "<i4"), ("iou", "<f8")])
 assert FLOOR_HYP_OUT_DTYPE.itemsize == 80 and FLOOR_ALIGN_OUT_DTYPE.itemsize == 96 and FLOOR_IOU_OUT_DTYPE.itemsize == 32
+# salve_hypotheses_generate (salve_hyp_pair_t, salve_hyp_row_t, salve_hyp_pair_out_t)
+HYP_MAX_WDO_PER_TYPE = 32
+HYP_MAX_CAPACITY = 5120
+HYP_PAIR_DTYPE = np.dtype([("pano1", "<i4"), ("pano2", "<i4"), ("capacity", "<i4"), ("reserved", "<i4"), ("row_offset", "<i8")])
+HYP_ROW_DTYPE = np.dtype([("R", "<f4", (4,)), ("t", "<f4", (2,)), ("type", "<i4"), ("i", "<i4"), ("j", "<i4"), ("configuration", "<i4"), ("label", "<i4"),
+                          ("reserved", "<i4")])
+HYP_PAIR_OUT_DTYPE = np.dtype([("n_kept", "<i4"), ("n_valid", "<i4"), ("n_rejected", "<i4"), ("visibly_adjacent", "<i4"), ("R", "<f4", (4,)),
+                               ("t", "<f4", (2,)), ("s", "<f8")])
+assert HYP_PAIR_DTYPE.itemsize == 24 and HYP_ROW_DTYPE.itemsize == 48 and HYP_PAIR_OUT_DTYPE.itemsize == 48
 # salve_tile_jitter_t (salve_bev_train_tiles_jitter): one ColorJitter draw per image; the operation codes are torchvision's fn_id and the mask's bit numbers
 TILE_JITTER_DTYPE = np.dtype([("order", "u1", (4,)), ("mask", "<i4"), ("brightness", "<f4"), ("contrast", "<f4"), ("saturation", "<f4"), ("hue", "<f4"),
                               ("brightness_c", "<f4"), ("contrast_c", "<f4"), ("saturation_c", "<f4"), ("reserved", "<i4")])
@@ -370,6 +380,10 @@ def load() -> ctypes.CDLL:
     lib.salve_floor_iou.argtypes = [vp, vp, ctypes.c_int64, vp, i32, i32, vp, vp, vp, i32, i32, ctypes.c_float, ctypes.c_float, ctypes.c_double, vp, vp,
                                     vp, sz, vp, vp]
     lib.salve_floor_iou.restype = ctypes.c_int
+    # wdo_xy, wdo_type, wdo_off, n_wdo, gt_xy, gt_off, n_gt, poses, n_panos, pairs, n_pairs, max_capacity, min_width_ratio, out_rows, n_rows, out_pairs, stream
+    lib.salve_hypotheses_generate.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, vp, ctypes.c_int64, i32, ctypes.c_double, vp,
+                                              ctypes.c_int64, vp, vp]
+    lib.salve_hypotheses_generate.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]

@@ -207,6 +207,22 @@ class PanoStore:
 
 
 @dataclass
+class FloorPairs:
+    """Per panorama pair (i1 < i2) of a floor what the reference's exporter computes beside the hypothesis files
+    (scripts/export_alignment_hypotheses.py:177-208): filled by salve_amd.hypotheses.generate, absent from files."""
+
+    i1: np.ndarray                 # [M] pano ids
+    i2: np.ndarray
+    n_kept: np.ndarray             # [M] hypotheses of the pair after pruning
+    n_valid: np.ndarray            # [M] configurations the width ratio accepted (floor_n_valid_configurations sums them)
+    n_rejected: np.ndarray         # [M] ... rejected (floor_n_invalid_configurations)
+    visibly_adjacent: np.ndarray   # [M] bool: are_visibly_adjacent on the ground truth's W/D/Os (the pairs of gt_alignment_exact/)
+    gt_R: np.ndarray               # [M,2,2] float32: i2Ti1_gt = wTi2.inverse().compose(wTi1)
+    gt_t: np.ndarray               # [M,2] float32
+    gt_s: np.ndarray               # [M] float64
+
+
+@dataclass
 class FloorHypotheses:
     """Alignment hypotheses of one floor, in the order the reference renders them."""
 
@@ -221,6 +237,7 @@ class FloorHypotheses:
     pair_idx: np.ndarray    # [N] index within its label directory
     pair_uuid: List[str]    # e.g. door_0_0_identity
     fpaths: List[str]
+    pairs: Optional[FloorPairs] = None   # salve_amd.hypotheses.generate's: the per-pair counts, visibly_adjacent and i2Ti1_gt
 
     def __len__(self) -> int:
         return len(self.fpaths)
@@ -280,7 +297,7 @@ def load_floor_hypotheses(hypotheses_save_root: str, building_id: str, floor_id:
 def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypotheses_save_root: str, bev_save_root: str,
                 building_id: str, floor_id: str, serialization_save_dir: str, batch_size: int = 64, chunk: Optional[int] = None,
                 decode: str = "host", samplings: Sequence[str] = ("4:2:0",), visual_overlap: bool = False, jpeg_quality: Optional[int] = None,
-                pose_graph: Optional[Dict[str, Any]] = None):
+                pose_graph: Optional[Dict[str, Any]] = None, hypotheses: Optional[FloorHypotheses] = None):
     """Disk -> predictions for one floor without writing a tile: the fused counterpart of running
     scripts/render_dataset_bev.py and then scripts/test.py on that floor.  chunk = hypotheses per launch; None: the pipeline picks the
     largest launch that fits the free HBM (pipeline.pick_launch).  decode: PanoStore.load's ("device": the panoramas' JPEG files are
@@ -296,11 +313,16 @@ def score_floor(model, device, raw_dataset_dir: str, depth_save_root: str, hypot
     pose_graph_{building}_{floor}.json, equal to what `python -m salve_amd.pose_graph` makes of the prediction files.  None: launches, files
     and the returned dict are unchanged.  With "truth" (a salve_amd.floor_report.FloorTruth; "report": floor_report.report's num_iters,
     delete_frac, seed) the floor's reconstruction report follows: the result gains "floor_report" and the directory
-    floor_report_{building}_{floor}.json.  Without "truth" nothing changes."""
+    floor_report_{building}_{floor}.json.  Without "truth" nothing changes.
+    hypotheses: None, or the floor's FloorHypotheses as salve_amd.hypotheses.generate made them on the device: nothing is read from
+    `hypotheses_save_root` then -- the floor goes from layouts to predictions (and with pose_graph= on to the report) without a hypothesis file.
+    The prediction files are those of the same rows read from write_tree's directory.  None: launches, files and the returned dict are unchanged."""
     from salve_amd import evaluate
     from salve_amd.pipeline import RenderVerifyPipeline
 
-    hyps = load_floor_hypotheses(hypotheses_save_root, building_id, floor_id)
+    if hypotheses is not None and (hypotheses.building_id, hypotheses.floor_id) != (building_id, floor_id):
+        raise ValueError(f"hypotheses are those of building {hypotheses.building_id}, {hypotheses.floor_id}, not of {building_id}, {floor_id}")
+    hyps = hypotheses if hypotheses is not None else load_floor_hypotheses(hypotheses_save_root, building_id, floor_id)
     if len(hyps) == 0:
         return None
     img_fpaths = floor_pano_fpaths(raw_dataset_dir, building_id)
