@@ -102,8 +102,13 @@ const char* salve_last_error(void);
 typedef struct {
     int32_t pano_h, pano_w;     /* working pano resolution: 512 x 1024 (bev_rendering_utils.py:373-374) */
     int32_t crop_rows;          /* int(pano_h * crop_ratio) rows dropped top and bottom (:397-401); 80 */
-    int32_t bev_h, bev_w;       /* BEVParams.img_h + 1, img_w + 1 (:292-293); 501, 501 */
-    int32_t mask_k;             /* box-filter size of remove_hallucinated_content; 11 */
+    int32_t bev_h, bev_w;       /* BEVParams.img_h + 1, img_w + 1 (:292-293); 501, 501.  Accepted: 2 <= bev_h, bev_w < 2048 with
+                                   ceil(bev_h / 16) * ceil(bev_w / 32) <= 512 (the densify stage's mask pass: one thread per 16 rows of one
+                                   32-pixel column word) -- 512 x 512, 1024 x 256, 2047 x 127 and 127 x 2047 are the largest of their
+                                   aspect.  Anything else: SALVE_ERR_BAD_ARG from every entry that takes the struct, 0 from its size queries.
+                                   (Every accepted image fits the densify stage's LDS block -- two bits per pixel, 4 bytes per row and
+                                   12.1 KB, at most 85 KB of the 160 --, so its SALVE_ERR_UNSUPPORTED for an image that does not is never met.) */
+    int32_t mask_k;             /* box-filter size of remove_hallucinated_content; 11.  Accepted: odd, 1 .. 17; else SALVE_ERR_BAD_ARG */
     float depth_scale;          /* uint16 depth -> metres, applied in float32 (:367); 0.001f */
     int32_t out_flags;          /* 0 for render_bev_image; 1: no vertical flip, 2: no mask (plain interpolation), 4: the renders of a
                                    launch are densified in the order given (default: the costly ones first -- same images, shorter tail).
@@ -172,7 +177,8 @@ int salve_bev_pano_index_update(const salve_bev_config_t* cfg, const uint16_t* p
  *               (-1, -1) if the point is cropped / pruned (row a4: the bit-exact index contract)
  *   dbg_keys    device uint64 [n, bev_h*bev_w] or NULL: z-order winner per pixel (unflipped):
  *               0 = empty, else ((slice+1) << 45) | (point_index << 24) | 0xBBGGRR
- *   dbg_mask    device uint8 [n, bev_h, bev_w] or NULL: hallucination mask (unflipped)
+ *   dbg_mask    device uint8 [n, bev_h, bev_w] or NULL: hallucination mask (unflipped; also under out_flags bit 2, which only
+ *               keeps the stage from applying it)
  *   dbg_stats   device int32 [n, 8] or NULL: {n_sites, min x, max x, occupied rows, walk iterations, error flag,
  *               sites handed to the general walk, queued triangles}
  *   out_in_window device int32 [n] or NULL: points inside the window per render (0 => the reference returns None, :279,

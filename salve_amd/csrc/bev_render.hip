@@ -551,6 +551,15 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
     }
     __syncthreads();
 
+    // (development output: the dilated mask as computed, whether or not out_flags bit 2 then switches it off -- exported here, before
+    //  that bit overwrites the bitmap)
+    if (dbg_mask) {
+        for (int i = tid; i < H * W; i += DENSIFY_THREADS) {
+            const int y = i / W, x = i % W;
+            dbg_mask[(size_t)rid * H * W + i] = (uint8_t)((msk[y * wpr + (x >> 5)] >> (x & 31)) & 1u);
+        }
+        __syncthreads();
+    }
     if (c.out_flags & 2) {
         for (int i = tid; i < H * wpr; i += DENSIFY_THREADS) msk[i] = 0xFFFFFFFFu;
         __syncthreads();
@@ -820,12 +829,6 @@ __global__ __launch_bounds__(DENSIFY_THREADS, 4) void bev_densify_kernel(
                     }
                 }
             }
-        }
-    }
-    if (dbg_mask) {
-        for (int i = tid; i < H * W; i += DENSIFY_THREADS) {
-            const int y = i / W, x = i % W;
-            dbg_mask[(size_t)rid * H * W + i] = (uint8_t)((msk[y * wpr + (x >> 5)] >> (x & 31)) & 1u);
         }
     }
     if (dbg_stats) {
