@@ -56,7 +56,9 @@ typedef enum {
                                         salve_pose_graph_sample_workspace_bytes, salve_graph_tree_out_t and salve_graph_sample_floor_out_t),
                                         salve_floor_align and salve_floor_iou (with salve_floor_iou_workspace_bytes, the salve_floor_*_out_t
                                         records and SALVE_STATUS_BAD_FLOOR_TABLE), salve_pose_graph_optimise (with
-                                        salve_pose_graph_optimise_workspace_bytes, salve_graph_pgo_floor_out_t and SALVE_PGO_*) */
+                                        salve_pose_graph_optimise_workspace_bytes, salve_graph_pgo_floor_out_t and SALVE_PGO_*),
+                                        salve_pose_graph_axis_align (with salve_axis_wdo_t, salve_axis_row_out_t, salve_axis_floor_out_t, SALVE_AXIS_* and
+                                        SALVE_STATUS_BAD_AXIS_ROW) */
 
 /* Device status word: an optional device int32 the caller zeroes once and passes to the launches below.  Kernels OR bits
  * into it when something went wrong that an int return value cannot report (the launch is asynchronous); the caller
@@ -83,6 +85,10 @@ typedef enum {
                                             that floor is written EMPTY (best -1, NaN errors); floor_iou: a floor's panorama extent or a room's
                                             vertex extent is malformed, or a posed vertex is not finite or lies beyond 2^24 pixels -- that
                                             floor's counts are 0 and its IoU NaN.  The other floors are reported */
+#define SALVE_STATUS_BAD_AXIS_ROW 512 /* pose_graph_axis_align: a row names a panorama outside its floor, a W/D/O type outside 0 .. 2 or a W/D/O
+                                         its panorama does not hold, a panorama's W/D/O or room extent leaves its table, or the floor's panorama
+                                         extent leaves the panorama tables -- that row is copied unchanged with SALVE_AXIS_MALFORMED; or a
+                                         floor's row extent is malformed -- none of its rows is written.  The other rows are aligned */
 
 /* Library / ABI version (SALVE_HIP_ABI_VERSION). */
 int salve_hip_version(void);
@@ -815,6 +821,79 @@ int salve_hypotheses_generate(const double* wdo_xy, const uint8_t* wdo_type, con
                               const int64_t* gt_off, int64_t n_gt, const salve_graph_node_out_t* poses, int32_t n_panos,
                               const salve_hyp_pair_t* pairs, int64_t n_pairs, int32_t max_capacity, double min_width_ratio,
                               salve_hyp_row_t* out_rows, int64_t n_rows, salve_hyp_pair_out_t* out_pairs, void* stream);
+
+/* Axis alignment by vanishing angle: every scored hypothesis i2Si1 turned about the W/D/O it was aligned on until the two panoramas' vanishing
+ * angles agree, for any number of floors in ONE launch (additive within ABI 7).  Stands behind --use_axis_alignment (default True) of the
+ * reference's scripts/run_sfm.py:421-426 and salve/algorithms/pose2_slam.py:217-231:
+ *   salve/utils/axis_alignment_utils.py:175-263   align_pair_measurement_by_vanishing_angle
+ *   salve/utils/axis_alignment_utils.py:266-284   compute_vp_correction
+ *   salve/utils/axis_alignment_utils.py:295-323   compute_i2Ti1 (gtsam's Similarity3.Align over point pairs, the degree round trip)
+ *   salve/utils/rotation_utils.py:14-42, 87-103   rotmat2d, rotmat2theta_deg, rotate_polygon_about_pt
+ *   salve/common/sim2.py:135-160, wdo.py:35-37    Sim2.transform_from, WDO.centroid
+ * A pure map over the rows: out_rows[r] is rows[r] with R, t, s replaced where the correction applies; salve_pose_graph_solve and
+ * salve_pose_graph_optimise take out_rows in place of rows.  Row r was aligned on W/D/O row_wdo[r] of panorama i1.  Everything is float64 with R
+ * and t widened first, no product fused into a sum, every sum in ascending vertex order from 0.0 -- but for the row's own angle:
+ *  angle:   theta = (double)(atan2f(R10, R00) * (float)(180 / pi)): float32, as numpy evaluates it on Sim2's float32 entries.
+ *  move:    a point p of i1's frame goes to ((p.x R00 + p.y R01) + tx) s, ((p.x R10 + p.y R11) + ty) s (Sim2.transform_from, per entry).
+ *  centre:  c = move(((x1 + x2) / 2, (y1 + y2) / 2)) of the W/D/O's two endpoints.
+ *  room:    the tables hold rooms CLOSED (layout.PanoLayouts); the polygon used is the OPEN one, all vertices but the last, n of them.
+ *  correct: corr = -((vp2 - vp1) + theta); corr = fmod(corr, 90), + 90 when negative (Python's %: [0, 90)); - 90 when > 45.
+ *           |corr| > 15 (MAX_ALLOWED_CORRECTION_DEG): SALVE_AXIS_TOO_LARGE, the row stays.
+ *  turn:    cs = cos(corr pi / 180), sn = sin(..); a_k = ((d.x cs + d.y (-sn)) + c.x, (d.x sn + d.y cs) + c.y), d = move(v_k) - c; b_k = v_k.
+ *  align:   ca = (sum a_k) / n, cb = (sum b_k) / n; H = sum (a_k - ca) (b_k - cb)^T; phi = atan2(H10 - H01, H00 + H11) (the planar closest
+ *           rotation); with R = [[cos phi, -sin phi], [sin phi, cos phi]]: x = sum (a_k - ca) . (R (b_k - cb)), y = sum |R (b_k - cb)|^2,
+ *           s' = x / y, T = (ca - s' (R cb)) / s' (gtsam's convention s (R p + T)).
+ *  result:  theta' = atan2(sin phi, cos phi) (180 / pi) degrees, th = theta' (pi / 180) (rotmat2theta_deg, then Rot2.fromDegrees); the row
+ *           written is R = (float)[cos th, -sin th, sin th, cos th], t = (float)T, s = 1.0; i1, i2, prob, y_hat are copied.
+ * Analytically R' = Rc R and T = (Rc (s t - c) + c) / s with Rc the rotation by corr.
+ * Deviations: a panorama without a finite vanishing angle gives SALVE_AXIS_NO_ANGLE (the reference fails on None); a room of fewer than 3
+ * open vertices gives SALVE_AXIS_NO_ROOM (gtsam throws); gtsam is not installed where this was built, so parity with Similarity3.Align's
+ * bits (its 3-D closest rotation by SVD) is unpinned.  In both cases, and for SALVE_AXIS_TOO_LARGE, the row is copied bit for bit.
+ *   rows, n_rows, floor_start, n_nodes   exactly salve_pose_graph_solve's (compact node indices; here no order among the rows is required and
+ *                   there is no max_nodes)
+ *   row_wdo         device salve_axis_wdo_t [n_rows]: the type code (0 window, 1 door, 2 opening -- salve_layout_pose's) and the index WITHIN
+ *                   the type, in table order, of the W/D/O of panorama i1 (EdgeWDOPair's alignment_object and i1_wdo_idx)
+ *   pano_base       device int32 [n_floors]: node v of floor f is panorama pano_base[f] + v of the tables below
+ *   room_off, room_xy, n_room_xy   device int64 [n_panos + 1], float64 [n_room_xy][2]: the rooms, closed
+ *   wdo_off, wdo_xy, wdo_type, n_wdo   device int64 [n_panos + 1], float64 [n_wdo][2][2], uint8 [n_wdo]: the W/D/Os (any order within a panorama)
+ *   vanishing_deg   device float64 [n_panos]: degrees; NaN (or an infinity) = the panorama has none
+ *   out_rows        device salve_graph_row_t [n_rows], 8-byte aligned; must not overlap rows
+ *   out_axis        device salve_axis_row_out_t [n_rows], 8-byte aligned;  out_floors: device salve_axis_floor_out_t [n_floors]
+ *   status          device int32 status word or NULL
+ * One launch on `stream`, one workgroup of 256 threads per floor, one thread per row; n_floors == 0 launches nothing.  Every output the call
+ * documents is written, none needs zeroing, and the same bytes come out on every run.  The tables are device memory, so the kernel verifies
+ * every index and offset before it forms an address from it: a row with a node outside [0, n_nodes[f]), a type outside 0 .. 2, a negative
+ * index or one the panorama does not hold, a W/D/O or room extent of panorama i1 that steps back or leaves its table, or a floor whose
+ * panoramas leave [0, n_panos) is copied unchanged with SALVE_AXIS_MALFORMED and raises SALVE_STATUS_BAD_AXIS_ROW.  A floor whose row extent
+ * is malformed (as salve_pose_graph_solve defines it) has no row that can be named: none is written, its record says bad_extent = 1, and the
+ * same bit is raised.  SALVE_ERR_BAD_ARG for a negative count and -- with n_floors > 0 -- a null or misaligned pointer (the row tables may
+ * be null while n_rows == 0, the panorama tables while n_panos == 0, room_xy / the W/D/O arrays while empty). */
+#define SALVE_AXIS_APPLIED 0
+#define SALVE_AXIS_TOO_LARGE 1
+#define SALVE_AXIS_NO_ANGLE 2
+#define SALVE_AXIS_NO_ROOM 3
+#define SALVE_AXIS_MALFORMED 4
+#define SALVE_AXIS_N_STATUS 5
+typedef struct {
+    int32_t type;   /* 0 window, 1 door, 2 opening */
+    int32_t index;  /* within the type */
+} salve_axis_wdo_t;
+typedef struct {
+    int32_t status;         /* SALVE_AXIS_* */
+    int32_t reserved;       /* written 0 */
+    double correction_deg;  /* the folded correction; NaN unless APPLIED or TOO_LARGE */
+    double theta_deg;       /* APPLIED: the new rotation angle in degrees and the new translation, before they are rounded; NaN otherwise */
+    double t[2];
+} salve_axis_row_out_t;
+typedef struct {
+    int32_t n_applied, n_too_large, n_no_angle, n_no_room, n_malformed;
+    int32_t bad_extent;     /* 1: the floor's row extent is malformed, the five counts are 0 */
+} salve_axis_floor_out_t;
+int salve_pose_graph_axis_align(const salve_graph_row_t* rows, int32_t n_rows, const int32_t* floor_start, const int32_t* n_nodes, int32_t n_floors,
+                                const salve_axis_wdo_t* row_wdo, const int32_t* pano_base, const int64_t* room_off, const double* room_xy,
+                                int64_t n_room_xy, const int64_t* wdo_off, const double* wdo_xy, const uint8_t* wdo_type, int64_t n_wdo,
+                                const double* vanishing_deg, int32_t n_panos, salve_graph_row_t* out_rows, salve_axis_row_out_t* out_axis,
+                                salve_axis_floor_out_t* out_floors, int32_t* status, void* stream);
 
 /* The two tiles of an early-fusion pair in ONE pass (the fused render -> verify driver's form of salve_bev_tiles, fp16 NHWC
  * only): pair k takes its first image from bev_a + jobs_a[k].bev_offset and its second from bev_b + jobs_b[k].bev_offset,

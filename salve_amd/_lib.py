@@ -115,6 +115,7 @@ EXPORTED_SYMBOLS = (
     "salve_floor_iou_workspace_bytes",
     "salve_floor_iou",
     "salve_hypotheses_generate",
+    "salve_pose_graph_axis_align",
 )
 # salve_resnet_create flags (include/salve_hip.h: SALVE_RESNET_*): kernel selection for the bit-identity tests; 0 = product
 RESNET_CONV_IGEMM_ONLY, RESNET_CONV8_WHEREVER, RESNET_ROUND_ROBIN_TILES, RESNET_NO_STEM_FUSE, RESNET_NO_BLOCK_FUSE = 1, 2, 4, 8, 16
@@ -131,6 +132,7 @@ STATUS_BAD_PANO_SLOT = 32
 STATUS_BAD_LAYOUT = 64
 STATUS_BAD_GRAPH_ROW = 128
 STATUS_BAD_FLOOR_TABLE = 256
+STATUS_BAD_AXIS_ROW = 512
 
 
 class BevConfig(ctypes.Structure):
@@ -187,6 +189,14 @@ assert GRAPH_PGO_FLOOR_OUT_DTYPE.itemsize == 48
 PGO_LDS_NODES = 56
 PGO_STOP_EMPTY, PGO_STOP_ABSOLUTE, PGO_STOP_RELATIVE, PGO_STOP_LAMBDA, PGO_STOP_MAX_ITERATIONS, PGO_STOP_NON_FINITE = 0, 1, 2, 3, 4, 5
 PGO_STOP_NAMES = ("empty", "absolute_error_tol", "relative_error_tol", "lambda_bound", "max_iterations", "non_finite")
+# salve_pose_graph_axis_align (salve_axis_wdo_t, salve_axis_row_out_t, salve_axis_floor_out_t, SALVE_AXIS_*)
+AXIS_WDO_DTYPE = np.dtype([("type", "<i4"), ("index", "<i4")])
+AXIS_ROW_OUT_DTYPE = np.dtype([("status", "<i4"), ("reserved", "<i4"), ("correction_deg", "<f8"), ("theta_deg", "<f8"), ("t", "<f8", (2,))])
+AXIS_FLOOR_OUT_DTYPE = np.dtype([("n_applied", "<i4"), ("n_too_large", "<i4"), ("n_no_angle", "<i4"), ("n_no_room", "<i4"), ("n_malformed", "<i4"),
+                                 ("bad_extent", "<i4")])
+assert AXIS_WDO_DTYPE.itemsize == 8 and AXIS_ROW_OUT_DTYPE.itemsize == 40 and AXIS_FLOOR_OUT_DTYPE.itemsize == 24
+AXIS_APPLIED, AXIS_TOO_LARGE, AXIS_NO_ANGLE, AXIS_NO_ROOM, AXIS_MALFORMED = 0, 1, 2, 3, 4
+AXIS_STATUS_NAMES = ("applied", "too_large", "no_angle", "no_room", "malformed")
 # salve_floor_align, salve_floor_iou (salve_floor_hyp_out_t, salve_floor_align_out_t, salve_floor_iou_out_t)
 FLOOR_MASK_WORDS = 8
 FLOOR_HYP_OUT_DTYPE = np.dtype([("R", "<f8", (4,)), ("t", "<f8", (2,)), ("s", "<f8"), ("rot_err", "<f8"), ("trans_err", "<f8"), ("n_pairs", "<i4"),
@@ -384,6 +394,11 @@ def load() -> ctypes.CDLL:
     lib.salve_hypotheses_generate.argtypes = [vp, vp, vp, ctypes.c_int64, vp, vp, ctypes.c_int64, vp, i32, vp, ctypes.c_int64, i32, ctypes.c_double, vp,
                                               ctypes.c_int64, vp, vp]
     lib.salve_hypotheses_generate.restype = ctypes.c_int
+    # rows, n_rows, floor_start, n_nodes, n_floors, row_wdo, pano_base, room_off, room_xy, n_room_xy, wdo_off, wdo_xy, wdo_type, n_wdo, vanishing_deg,
+    # n_panos, out_rows, out_axis, out_floors, status, stream
+    lib.salve_pose_graph_axis_align.argtypes = [vp, i32, vp, vp, i32, vp, vp, vp, vp, ctypes.c_int64, vp, vp, vp, ctypes.c_int64, vp, i32, vp, vp, vp,
+                                                vp, vp]
+    lib.salve_pose_graph_axis_align.restype = ctypes.c_int
     lib.salve_conv_f32_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
     lib.salve_conv_f32_workspace_bytes.restype = sz
     lib.salve_conv_bf16_workspace_bytes.argtypes = [ctypes.POINTER(ConvDesc), i32]
@@ -489,6 +504,9 @@ def check_status_word(word: int, what: str) -> None:
     if word & STATUS_BAD_FLOOR_TABLE:
         raise SalveHipError(f"{what}: a floor-report table is malformed (a floor's panorama or hypothesis extent, a room's vertex extent) or a "
                             "posed room vertex is not finite or lies more than 2^24 pixels away; that floor was written empty")
+    if word & STATUS_BAD_AXIS_ROW:
+        raise SalveHipError(f"{what}: an axis-alignment row names a panorama outside its floor or a W/D/O its panorama does not hold, or a table "
+                            "extent is malformed; that row was copied unchanged (a floor with a malformed row extent was not written)")
     if word:
         raise SalveHipError(f"{what}: device status word {word:#x}")
 

@@ -11,7 +11,8 @@ ingest.FloorHypotheses without a file in between.
     python -m salve_amd.hypotheses --raw-dataset-dir ZIND --mhnet-predictions-data-root DIR --hypotheses-save-root OUT --split test
 
 Not here: `--wdo_source ground_truth` (it needs overlap_utils.determine_invalid_wall_overlap, the freespace check on shrunk room polygons),
-AlignTransformType.Sim3, the debug plots, any use of the vanishing angle.  There is no CPU path: a missing kernel is an error."""
+AlignTransformType.Sim3, the debug plots.  The vanishing angles are carried (FloorInput.vanishing_angle_deg) and not read here: axis alignment
+is salve_amd.pose_graph's (AxisInputs.from_floors).  There is no CPU path: a missing kernel is an error."""
 
 from __future__ import annotations
 
@@ -51,9 +52,15 @@ class FloorInput:
     s: np.ndarray             # [P] float64
     gt_wdo_off: np.ndarray    # [P + 1] int64
     gt_wdo_xy: np.ndarray     # [*, 2, 2] float64: the ground truth's W/D/Os, LOCAL frame (any order within a panorama)
+    vanishing_angle_deg: Optional[np.ndarray] = None   # [P] float64, NaN where absent: MHNet's vanishing angles (the generator does not read them;
+                                                       # pose_graph.AxisInputs.from_floors does)
 
     def __post_init__(self) -> None:
         P = len(self.pano_ids)
+        if self.vanishing_angle_deg is not None:
+            self.vanishing_angle_deg = np.asarray(self.vanishing_angle_deg, dtype=np.float64).reshape(-1)
+            if len(self.vanishing_angle_deg) != P:
+                raise ValueError(f"building {self.building_id}, {self.floor_id}: {len(self.vanishing_angle_deg)} vanishing angles for {P} panoramas")
         self.pano_ids = np.asarray(self.pano_ids, dtype=np.int64).reshape(P)
         self.R, self.t = np.asarray(self.R, dtype=np.float32).reshape(P, 2, 2), np.asarray(self.t, dtype=np.float32).reshape(P, 2)
         self.s = np.asarray(self.s, dtype=np.float64).reshape(P)
@@ -97,7 +104,8 @@ class FloorInput:
         return cls(gt_graph.building_id, gt_graph.floor_id, np.array(ids, dtype=np.int64), layouts,
                    np.array([S.rotation for S in poses], dtype=np.float32).reshape(-1, 2, 2), np.array([S.translation for S in poses], dtype=np.float32).reshape(-1, 2),
                    np.array([S.scale for S in poses], dtype=np.float64), np.concatenate([[0], np.cumsum([len(ws) for ws in gt])]).astype(np.int64),
-                   np.stack(flat) if flat else np.zeros((0, 2, 2)))
+                   np.stack(flat) if flat else np.zeros((0, 2, 2)),
+                   np.array([np.nan if getattr(nodes[i], "vanishing_angle_deg", None) is None else nodes[i].vanishing_angle_deg for i in ids], dtype=np.float64))
 
 
 def _no_layouts() -> PanoLayouts:

@@ -5,6 +5,7 @@ scripts/run_sfm.py:112-152 and :440-446, with and without its cycle filter, for 
     python -m salve_amd.pose_graph PRED_DIR --hypotheses ROOT --confidence-threshold X [--no-cycle-filter] [--rot-deg D] [--trans T] [--out DIR]
         [--method {spanning_tree,random_spanning_trees,pgo}] [--filter-by-random-spanning-trees] [--num-hypotheses H] [--sampling-fraction F] [--seed S]
         [--pgo-max-iterations K] [--pgo-no-robust] [--zind-root DIR] [--report-seed S] [--report-iters K]
+        [--axis-alignment --mhnet-predictions-data-root DIR]
 
 reads the `batch_*.json` prediction files of PRED_DIR (evaluate.run_test_epoch, evaluate.run_fused_epoch, ingest.score_floor), looks every
 prediction's alignment hypothesis up under ROOT, and writes one `pose_graph_{building}_{floor}.json` per floor.
@@ -28,12 +29,17 @@ The third method, `pgo` (run_sfm.py:448-451; pose2_slam.py:57-286; DESIGN.md sec
 by pose-graph optimisation -- a robust Levenberg-Marquardt over ALL thresholded predictions between localized panoramas, every second
 hypothesis of a pair and every loop closure included -- in two device calls on the same buffers (salve_pose_graph_solve, then
 salve_pose_graph_optimise; salve_amd/csrc/pose_graph_pgo.hip).  The objective is exactly the reference's factor graph and the result minimises
-it; gtsam is not installed where this was built, so parity with gtsam's iterates and stopping point is unpinned.  `--no-cycle-filter --method
-pgo` is the reference's pipeline.
+it; gtsam is not installed where this was built, so parity with gtsam's iterates and stopping point is unpinned.
+
+Axis alignment by vanishing angle (run_sfm.py:421-426, pose2_slam.py:217-231, axis_alignment_utils.py:175-323) is on
+by default in the reference and off by default here: `axis=AxisInputs` on solve / optimise / run, `--axis-alignment` on the command line.
+Every row is then turned about the W/D/O it was aligned on until the two panoramas' vanishing angles agree, by at most 15 degrees, in one
+more launch in front of the others (salve_pose_graph_axis_align; salve_amd/csrc/pose_graph_axis.hip); `align_rows` is that step alone.
+`--no-cycle-filter --method pgo --axis-alignment` is the reference's default pipeline; without the last flag it is that pipeline with
+--use_axis_alignment off.
 
 The evaluation against ground truth is salve_amd.floor_report: `run(..., truth=)` and `--zind-root DIR` end in one
-floor_report_{building}_{floor}.json per floor.  Axis alignment by vanishing angle (it needs MHNet's predictions), landmark SLAM (the
-reference's `pose2_slam` method) and filter_edges_by_global_local_consistency are NOT here.  A floor may have at most 256 panoramas.
+floor_report_{building}_{floor}.json per floor.  Landmark SLAM (the reference's `pose2_slam` method) and filter_edges_by_global_local_consistency are NOT here.  A floor may have at most 256 panoramas.
 """
 
 from __future__ import annotations
@@ -224,15 +230,205 @@ def _device_table(meas: EdgeMeasurements, floors: List[Dict[str, Any]], what: st
     return table, floor_start, n_nodes, M
 
 
+AXIS_TYPE_CODES = {"window": 0, "door": 1, "opening": 2}   # EdgeWDOPair.alignment_object -> layout.WDO_TYPES' code (windows, doors, openings)
+
+
+class AxisInputs:
+    """What axis alignment by vanishing angle reads of every floor: per (building_id, floor_id) the panorama ids
+    (ascending), their layout.PanoLayouts -- the INFERRED rooms and W/D/Os, panorama k of the tables being pano_ids[k] -- and one vanishing
+    angle in degrees per panorama, NaN where MHNet gave none.  AxisInputs.from_floors(hypotheses.load_floors(...)), or add() floor by floor
+    from arrays."""
+
+    def __init__(self) -> None:
+        self.floors: Dict[Tuple[str, str], Tuple[np.ndarray, Any, np.ndarray]] = {}
+
+    def add(self, building_id: str, floor_id: str, pano_ids, layouts, vanishing_angle_deg) -> "AxisInputs":
+        where = f"building {building_id}, {floor_id}"
+        ids = np.asarray(pano_ids, dtype=np.int64).reshape(-1)
+        if vanishing_angle_deg is None:
+            raise ValueError(f"AxisInputs: {where}: no vanishing angles (FloorInput.vanishing_angle_deg is None)")
+        angles = np.asarray(vanishing_angle_deg, dtype=np.float64).reshape(-1)
+        if len(ids) and (np.diff(ids) <= 0).any():
+            raise ValueError(f"AxisInputs: {where}: pano_ids must ascend strictly")
+        if len(angles) != len(ids) or layouts.P != max(len(ids), 1):
+            raise ValueError(f"AxisInputs: {where}: {len(ids)} pano ids, {len(angles)} vanishing angles and layouts of {layouts.P} panoramas")
+        self.floors[(building_id, floor_id)] = (ids, layouts, angles)
+        return self
+
+    @classmethod
+    def from_floors(cls, floor_inputs) -> "AxisInputs":
+        """floor_inputs: salve_amd.hypotheses.FloorInput objects (load_floors' or from_pose_graphs')."""
+        axis = cls()
+        for f in floor_inputs:
+            axis.add(f.building_id, f.floor_id, f.pano_ids, f.layouts, f.vanishing_angle_deg)
+        return axis
+
+    @staticmethod
+    def parse_wdo_pair_uuid(wdo_pair_uuid: str) -> Tuple[int, int]:
+        """door_3_0 -> (type code of "door", 3): EdgeWDOPair.from_wdo_pair_uuid's split; the index counts within the type."""
+        parts = wdo_pair_uuid.split("_")
+        if len(parts) != 3 or parts[0] not in AXIS_TYPE_CODES:
+            raise ValueError(f"wdo_pair_uuid {wdo_pair_uuid!r} is not {{door,window,opening}}_{{i1 index}}_{{i2 index}}")
+        return AXIS_TYPE_CODES[parts[0]], int(parts[1])
+
+    def tables(self, meas: "EdgeMeasurements", floors: List[Dict[str, Any]]) -> Dict[str, np.ndarray]:
+        """Host: the tables of salve_pose_graph_axis_align for `floors` (EdgeMeasurements.compact, possibly thinned by keep_rows): the
+        per-panorama tables gathered in the floors' compact numbering, one W/D/O record per row in the floors' sorted order.  ValueError for a
+        floor or panorama these inputs do not hold and for a row whose W/D/O its panorama's layout does not hold -- before anything is uploaded."""
+        room_cnt, wdo_cnt, room_xy, wdo_xy, wdo_type, angles, pano_base, row_wdo = [], [], [], [], [], [], [], []
+        base = 0
+        for fl in floors:
+            where = f"building {fl['building_id']}, {fl['floor_id']}"
+            if (fl["building_id"], fl["floor_id"]) not in self.floors:
+                raise ValueError(f"AxisInputs: {where} is not among the floors given")
+            ids, lay, ang = self.floors[(fl["building_id"], fl["floor_id"])]
+            want = np.asarray(fl["pano_ids"], dtype=np.int64)
+            pos = np.minimum(np.searchsorted(ids, want), max(len(ids) - 1, 0))
+            if len(want) and (len(ids) == 0 or (ids[pos] != want).any()):
+                missing = [int(p) for p in want if p not in set(ids.tolist())]
+                raise ValueError(f"AxisInputs: {where}: no layout for panoramas {missing}")
+            per_type = np.zeros((len(want), 3), np.int64)
+            for k, p in enumerate(pos):
+                r0, r1, w0, w1 = int(lay.room_off[p]), int(lay.room_off[p + 1]), int(lay.wdo_off[p]), int(lay.wdo_off[p + 1])
+                room_cnt.append(r1 - r0); wdo_cnt.append(w1 - w0)
+                room_xy.append(lay.room_xy[r0:r1]); wdo_xy.append(lay.wdo_xy[w0:w1]); wdo_type.append(lay.wdo_type[w0:w1])
+                per_type[k] = np.bincount(lay.wdo_type[w0:w1], minlength=3)[:3]
+            angles.append(ang[pos] if len(want) else np.zeros(0))
+            rec = np.zeros(len(fl["rows"]), dtype=_lib.AXIS_WDO_DTYPE)
+            for k, (r, c1) in enumerate(zip(fl["rows"], fl["c1"])):
+                uuid = meas.wdo_pair_uuid[int(r)]
+                pair = f"pair ({int(meas.i1[r])}, {int(meas.i2[r])})"
+                try:
+                    code, index = self.parse_wdo_pair_uuid(uuid)
+                except ValueError as e:
+                    raise ValueError(f"AxisInputs: {where}, {pair}: {e}") from None
+                if not 0 <= index < per_type[c1, code]:
+                    raise ValueError(f"AxisInputs: {where}, {pair}: {uuid} names {ALLOWED_WDO_TYPES[(1, 0, 2)[code]]} {index} of panorama {int(meas.i1[r])}, "
+                                     f"whose layout holds {int(per_type[c1, code])}")
+                rec[k] = (code, index)
+            row_wdo.append(rec)
+            pano_base.append(base)
+            base += len(want)
+        cat = lambda parts, empty: np.ascontiguousarray(np.concatenate(parts)) if parts else empty
+        off = lambda cnt: np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+        return {"row_wdo": cat(row_wdo, np.zeros(0, dtype=_lib.AXIS_WDO_DTYPE)), "pano_base": np.asarray(pano_base, dtype=np.int32),
+                "room_off": off(room_cnt), "room_xy": cat(room_xy, np.zeros((0, 2))).astype(np.float64), "wdo_off": off(wdo_cnt),
+                "wdo_xy": cat(wdo_xy, np.zeros((0, 2, 2))).astype(np.float64), "wdo_type": cat(wdo_type, np.zeros(0, np.uint8)).astype(np.uint8),
+                "vanishing_deg": cat(angles, np.zeros(0)).astype(np.float64)}
+
+
+def _blob(parts: Sequence[Tuple[str, np.ndarray]]) -> Tuple[np.ndarray, Dict[str, int]]:
+    """One upload of named tables, each at an 8-byte aligned offset."""
+    chunks, offs, at = [], {}, 0
+    for name, a in parts:
+        b = np.ascontiguousarray(a).reshape(-1).view(np.uint8)
+        offs[name] = at
+        chunks += [b, np.zeros(_align8(len(b)) - len(b), np.uint8)]
+        at += _align8(len(b))
+    return np.concatenate(chunks), offs
+
+
+class _AxisCall:
+    """salve_pose_graph_axis_align in front of the other entries of one call: its tables ride in the call's one upload, its three outputs
+    (aligned rows | row records | floor records) in the call's one output buffer, and the next entries read the aligned rows on the device."""
+
+    NAMES = ("row_wdo", "pano_base", "room_off", "room_xy", "wdo_off", "wdo_xy", "wdo_type", "vanishing_deg")
+
+    def __init__(self, meas: EdgeMeasurements, floors: List[Dict[str, Any]], axis: AxisInputs, N: int) -> None:
+        self.tabs = axis.tables(meas, floors)
+        self.N, self.F = N, len(floors)
+        self.off_axis = N * _lib.GRAPH_ROW_DTYPE.itemsize
+        self.off_floors = self.off_axis + N * _lib.AXIS_ROW_OUT_DTYPE.itemsize
+        self.out_bytes = self.off_floors + self.F * _lib.AXIS_FLOOR_OUT_DTYPE.itemsize
+
+    def parts(self) -> List[Tuple[str, np.ndarray]]:
+        return [(k, self.tabs[k]) for k in self.NAMES]
+
+    def launch(self, lib, p_in: int, offs: Dict[str, int], p_out: int, status_ptr, stream) -> ctypes.c_void_p:
+        """p_out: the 8-byte aligned device address of this call's outputs -> the address of the aligned row table."""
+        vp, t = ctypes.c_void_p, self.tabs
+        at = lambda k: vp(p_in + offs[k]) if t[k].size else None
+        _lib.check(lib.salve_pose_graph_axis_align(vp(p_in + offs["rows"]) if self.N else None, self.N, vp(p_in + offs["floor_start"]), vp(p_in + offs["n_nodes"]),
+                                                   self.F, at("row_wdo"), vp(p_in + offs["pano_base"]), vp(p_in + offs["room_off"]), at("room_xy"), len(t["room_xy"]),
+                                                   vp(p_in + offs["wdo_off"]), at("wdo_xy"), at("wdo_type"), len(t["wdo_type"]), at("vanishing_deg"),
+                                                   len(t["vanishing_deg"]), vp(p_out), vp(p_out + self.off_axis), vp(p_out + self.off_floors), status_ptr, stream),
+                   "salve_pose_graph_axis_align")
+        return vp(p_out)
+
+    def decode(self, meas: EdgeMeasurements, floors: List[Dict[str, Any]], host: np.ndarray) -> Tuple[EdgeMeasurements, Dict[str, Any]]:
+        """host: this call's downloaded outputs -> (the measurements with the aligned R, t, s, the per-row records in `meas`' row order)."""
+        from dataclasses import replace
+
+        rows = host[:self.off_axis].view(_lib.GRAPH_ROW_DTYPE)
+        rec = host[self.off_axis:self.off_floors].view(_lib.AXIS_ROW_OUT_DTYPE)
+        fo = host[self.off_floors:self.out_bytes].view(_lib.AXIS_FLOOR_OUT_DTYPE)
+        order = np.concatenate([fl["rows"] for fl in floors]).astype(np.int64) if floors else np.zeros(0, np.int64)
+        n = len(meas)
+        R, t, s = meas.R.copy(), meas.t.copy(), meas.s.copy()
+        R[order], t[order], s[order] = rows["R"].reshape(-1, 2, 2), rows["t"], rows["s"]
+        info = {"status": np.full(n, -1, np.int32), "correction_deg": np.full(n, np.nan), "theta_deg": np.full(n, np.nan), "t": np.full((n, 2), np.nan)}
+        for k in ("status", "correction_deg", "theta_deg", "t"):
+            info[k][order] = rec[k]
+        info["counts"] = [{name: int(fo[f"n_{name}"][f]) for name in _lib.AXIS_STATUS_NAMES} for f in range(self.F)]
+        return replace(meas, R=R, t=t, s=s), info
+
+
+def align_rows(meas: EdgeMeasurements, axis: AxisInputs, device="cuda:0", keep_rows: Optional[np.ndarray] = None) -> Tuple[EdgeMeasurements, Dict[str, Any]]:
+    """Axis alignment by vanishing angle of every row of `meas` on its own (salve_pose_graph_axis_align; the reference's
+    align_pair_measurement_by_vanishing_angle, axis_alignment_utils.py:175-263): one upload, one launch for all floors, one read of the device
+    status word, one download -> (the measurements with R, t, s replaced where the correction applies and bit for bit the given ones where not,
+    the per-row records in `meas`' row order: "status" int32 (_lib.AXIS_*; -1: the row lies outside keep_rows and was not uploaded),
+    "correction_deg", "theta_deg", "t" float64 (the new pose before it is rounded; NaN where it does not apply), and "counts": per floor, in
+    `meas.floors()` order, the number of rows of each status by _lib.AXIS_STATUS_NAMES).  solve / optimise / run(axis=) do this in front of
+    their own entries without the download in between."""
+    import torch
+
+    from salve_amd import status
+
+    device = torch.device(device)
+    lib = _lib.load()
+    floors = meas.compact()
+    if not floors:
+        return meas, {"status": np.zeros(0, np.int32), "correction_deg": np.zeros(0), "theta_deg": np.zeros(0), "t": np.zeros((0, 2)), "counts": []}
+    floors = _keep(meas, floors, keep_rows, "pose_graph.align_rows")
+    table, floor_start, n_nodes, _ = _device_table(meas, floors, "pose_graph.align_rows")
+    call = _AxisCall(meas, floors, axis, len(table))
+    blob, offs = _blob([("rows", table), ("floor_start", floor_start), ("n_nodes", n_nodes)] + call.parts())
+    with torch.cuda.device(device):
+        dev_in = torch.from_numpy(blob).to(device)
+        dev_out = torch.empty(call.out_bytes, dtype=torch.uint8, device=device)
+        call.launch(lib, dev_in.data_ptr(), offs, dev_out.data_ptr(), status.ptr(device), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+        status.check(device, "pose_graph.align_rows")   # (the one synchronising read)
+        host = dev_out.cpu().numpy()
+    return call.decode(meas, floors, host)
+
+
+def _keep(meas: EdgeMeasurements, floors: List[Dict[str, Any]], keep_rows, what: str) -> List[Dict[str, Any]]:
+    if keep_rows is not None:
+        keep_rows = np.asarray(keep_rows, dtype=bool).reshape(-1)
+        if len(keep_rows) != len(meas):
+            raise ValueError(f"{what}: keep_rows has {len(keep_rows)} entries for {len(meas)} rows")
+        for fl in floors:
+            k = keep_rows[fl["rows"]]
+            fl["rows"], fl["c1"], fl["c2"] = fl["rows"][k], fl["c1"][k], fl["c2"][k]
+    return floors
+
+
 def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: bool = True, rot_threshold_deg: float = ROT_THRESHOLD_DEG,
-          trans_threshold: float = TRANS_THRESHOLD, device="cuda:0", keep_rows: Optional[np.ndarray] = None) -> List[FloorSolution]:
+          trans_threshold: float = TRANS_THRESHOLD, device="cuda:0", keep_rows: Optional[np.ndarray] = None,
+          axis: Optional[AxisInputs] = None) -> List[FloorSolution]:
     """One FloorSolution per floor of `meas` (in `meas.floors()` order): one upload, one launch for all floors, one read of the device status
     word, one download.  confidence_threshold has no default: the reference's run_sfm.py takes it from the command line.  rot_threshold_deg
     and trans_threshold are filter_to_SE2_cycle_consistent_edges' own; trans_threshold=inf gives the rotation-only filter.  cycle_filter=False
     chains the chosen edges as they are (run_sfm.py:440-446).  A floor of more than 256 panoramas is refused before anything is launched.
     keep_rows: None, or a boolean mask over `meas`; a row outside it is never a candidate (it is not uploaded; the floors keep the panorama
     numbering of the whole table, and n_rows counts the kept rows).  With a sample_trees inlier mask this is the reference's
-    --filter_edges_by_random_spanning_trees."""
+    --filter_edges_by_random_spanning_trees.
+    axis: None, or the AxisInputs of the floors: every uploaded row is first aligned by vanishing angle (salve_pose_graph_axis_align, on the same
+    stream; the reference's --use_axis_alignment, run_sfm.py:421-426) and salve_pose_graph_solve reads the aligned table on the device -- still one
+    upload, one read of the status word, one download.  i2Si1 then holds the aligned poses, every edge gains axis_status (a name of
+    _lib.AXIS_STATUS_NAMES) and axis_correction_deg (None where there is none), and the options axis_alignment: True.  keep_rows composes: the
+    kept rows are the aligned ones.  None: the launches, values and JSON are as they were."""
     import torch
 
     from salve_amd import status
@@ -243,48 +439,56 @@ def solve(meas: EdgeMeasurements, confidence_threshold: float, cycle_filter: boo
     F = len(floors)
     if F == 0:
         return []
-    if keep_rows is not None:
-        keep_rows = np.asarray(keep_rows, dtype=bool).reshape(-1)
-        if len(keep_rows) != len(meas):
-            raise ValueError(f"pose_graph.solve: keep_rows has {len(keep_rows)} entries for {len(meas)} rows")
-        for fl in floors:
-            k = keep_rows[fl["rows"]]
-            fl["rows"], fl["c1"], fl["c2"] = fl["rows"][k], fl["c1"][k], fl["c2"][k]
+    floors = _keep(meas, floors, keep_rows, "pose_graph.solve")
     table, floor_start, n_nodes, M = _device_table(meas, floors, "pose_graph.solve")
     N = len(table)
+    call = _AxisCall(meas, floors, axis, N) if axis is not None else None
 
-    # one upload: rows | floor_start | n_nodes; one output buffer: out_rows | out_nodes | out_floors
-    blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
+    # one upload: rows | floor_start | n_nodes; one output buffer: out_rows | out_nodes | out_floors (with axis: the axis tables; | its outputs)
+    if call is None:
+        blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
+        offs = {"rows": 0, "floor_start": table.nbytes, "n_nodes": table.nbytes + floor_start.nbytes}
+    else:
+        blob, offs = _blob([("rows", table), ("floor_start", floor_start), ("n_nodes", n_nodes)] + call.parts())
     off_nodes = _align8(N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize)
     off_floors = off_nodes + F * M * _lib.GRAPH_NODE_OUT_DTYPE.itemsize
     out_bytes = off_floors + F * _lib.GRAPH_FLOOR_OUT_DTYPE.itemsize
+    off_axis = _align8(out_bytes)
     with torch.cuda.device(device):
         dev_in = torch.from_numpy(blob).to(device)
-        dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        dev_out = torch.empty(out_bytes if call is None else off_axis + call.out_bytes, dtype=torch.uint8, device=device)
         p_in, p_out = dev_in.data_ptr(), dev_out.data_ptr()
         vp = ctypes.c_void_p
+        stream = vp(torch.cuda.current_stream(device).cuda_stream)
         ws_bytes = int(lib.salve_pose_graph_workspace_bytes(F, M))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
-        _lib.check(lib.salve_pose_graph_solve(vp(p_in), N, vp(p_in + table.nbytes), vp(p_in + table.nbytes + floor_start.nbytes), F, M,
+        p_rows = vp(p_in + offs["rows"]) if call is None else call.launch(lib, p_in, offs, p_out + off_axis, status.ptr(device), stream)
+        _lib.check(lib.salve_pose_graph_solve(p_rows, N, vp(p_in + offs["floor_start"]), vp(p_in + offs["n_nodes"]), F, M,
                                               float(confidence_threshold), float(rot_threshold_deg), float(trans_threshold), int(bool(cycle_filter)),
                                               vp(p_out), vp(p_out + off_nodes), vp(p_out + off_floors), vp(ws.data_ptr()) if ws is not None else None,
-                                              ws_bytes, status.ptr(device), vp(torch.cuda.current_stream(device).cuda_stream)),
+                                              ws_bytes, status.ptr(device), stream),
                    "salve_pose_graph_solve")
         status.check(device, "pose_graph.solve")   # (the one synchronising read)
         host = dev_out.cpu().numpy()
     out_rows = host[:N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize].view(_lib.GRAPH_ROW_OUT_DTYPE)
     out_nodes = host[off_nodes:off_floors].view(_lib.GRAPH_NODE_OUT_DTYPE).reshape(F, M)
-    out_floors = host[off_floors:].view(_lib.GRAPH_FLOOR_OUT_DTYPE)
+    out_floors = host[off_floors:out_bytes].view(_lib.GRAPH_FLOOR_OUT_DTYPE)
+    axis_info = None
+    if call is not None:
+        meas, axis_info = call.decode(meas, floors, host[off_axis:])
 
     return _floor_solutions(meas, floors, floor_start, out_rows, out_nodes, out_floors, confidence_threshold, cycle_filter, rot_threshold_deg,
-                            trans_threshold)
+                            trans_threshold, axis_info)
 
 
 def _floor_solutions(meas, floors, floor_start, out_rows, out_nodes, out_floors, confidence_threshold, cycle_filter, rot_threshold_deg,
-                     trans_threshold) -> List[FloorSolution]:
-    """salve_pose_graph_solve's three output tables as one FloorSolution per floor."""
+                     trans_threshold, axis_info=None) -> List[FloorSolution]:
+    """salve_pose_graph_solve's three output tables as one FloorSolution per floor.  axis_info: None, or _AxisCall.decode's records; `meas` then
+    holds the aligned poses."""
     options = {"confidence_threshold": float(confidence_threshold), "cycle_filter": bool(cycle_filter), "rot_threshold_deg": float(rot_threshold_deg),
                "trans_threshold": float(trans_threshold)}
+    if axis_info is not None:
+        options["axis_alignment"] = True
     sim = lambda R, t, s: Sim2(np.array(R, dtype=np.float32).reshape(2, 2), np.array(t, dtype=np.float32), float(s))
     solutions = []
     for f, fl in enumerate(floors):
@@ -300,6 +504,10 @@ def _floor_solutions(meas, floors, floor_start, out_rows, out_nodes, out_floors,
             edges[pair] = {"row": r, "prob": float(meas.prob[r]), "y_true": int(meas.y_true[r]), "wdo_pair_uuid": meas.wdo_pair_uuid[r],
                            "configuration": meas.configuration[r], "consistent": bool(o["consistent"]), "n_triplets": int(o["n_triplets"]),
                            "n_consistent": int(o["n_consistent"]), "min_rot_err": float(o["min_rot_err"]), "min_trans_err": float(o["min_trans_err"])}
+            if axis_info is not None:
+                corr = float(axis_info["correction_deg"][r])
+                edges[pair]["axis_status"] = _lib.AXIS_STATUS_NAMES[int(axis_info["status"][r])]
+                edges[pair]["axis_correction_deg"] = corr if np.isfinite(corr) else None
         fo, nodes = out_floors[f], out_nodes[f, :len(ids)]
         wSi, parent, depth, origin = None, {}, {}, None
         if fo["origin"] >= 0:
@@ -373,14 +581,18 @@ class PgoSolution:
 
 def optimise(meas: EdgeMeasurements, confidence_threshold: float, robust: bool = True, max_iterations: int = 100, relative_error_tol: float = 1e-5,
              absolute_error_tol: float = 1e-5, keep_rows: Optional[np.ndarray] = None, device="cuda:0", huber_k: float = HUBER_K,
-             odometry_sigmas: Sequence[float] = ODOMETRY_SIGMAS, prior_sigmas: Sequence[float] = PRIOR_SIGMAS, **solve_options) -> List[PgoSolution]:
+             odometry_sigmas: Sequence[float] = ODOMETRY_SIGMAS, prior_sigmas: Sequence[float] = PRIOR_SIGMAS, axis: Optional[AxisInputs] = None,
+             **solve_options) -> List[PgoSolution]:
     """One PgoSolution per floor of `meas` (in `meas.floors()` order): the reference's `--method pgo` (run_sfm.py:448-451; pose2_slam.py:57-286
     with optimize_poses_only, without axis alignment).  One upload; salve_pose_graph_solve builds every floor's spanning tree and
     salve_pose_graph_optimise refines it over ALL thresholded predictions whose two panoramas the tree localizes, on the same device buffers
     with no download between them; one read of the device status word; one download.  solve_options: solve's cycle_filter, rot_threshold_deg,
     trans_threshold -- they shape the initial tree only (cycle_filter=False is the reference's pipeline).  keep_rows: solve's; the factors are
     then the kept rows only.  The defaults of robust, huber_k, the sigmas, max_iterations and the tolerances are the reference's and gtsam's;
-    parity with gtsam's iterates is unpinned: the objective is the reference's, and the result minimises it."""
+    parity with gtsam's iterates is unpinned: the objective is the reference's, and the result minimises it.
+    axis: solve's -- salve_pose_graph_axis_align runs first on the same stream and both later entries read its table, so the tree AND the
+    factors are the aligned measurements (run_sfm.py:421-426 and pose2_slam.py:217-231: the step is a pure per-row map, so aligning every row
+    once gives both); the floor record gains axis_counts.  This is the reference's default `--method pgo` run."""
     import torch
 
     from salve_amd import status
@@ -404,36 +616,39 @@ def optimise(meas: EdgeMeasurements, confidence_threshold: float, robust: bool =
     F = len(floors)
     if F == 0:
         return []
-    if keep_rows is not None:
-        keep_rows = np.asarray(keep_rows, dtype=bool).reshape(-1)
-        if len(keep_rows) != len(meas):
-            raise ValueError(f"pose_graph.optimise: keep_rows has {len(keep_rows)} entries for {len(meas)} rows")
-        for fl in floors:
-            k = keep_rows[fl["rows"]]
-            fl["rows"], fl["c1"], fl["c2"] = fl["rows"][k], fl["c1"][k], fl["c2"][k]
+    floors = _keep(meas, floors, keep_rows, "pose_graph.optimise")
     table, floor_start, n_nodes, M = _device_table(meas, floors, "pose_graph.optimise")
     N = len(table)
+    call = _AxisCall(meas, floors, axis, N) if axis is not None else None
 
     # one upload: rows | floor_start | n_nodes; one output buffer: out_rows | tree nodes | tree floors | pgo nodes | pgo floors | poses
+    # (with axis: the axis tables behind the upload, its outputs behind the output buffer)
     node_dt, pgo_dt = _lib.GRAPH_NODE_OUT_DTYPE, _lib.GRAPH_PGO_FLOOR_OUT_DTYPE
-    blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
+    if call is None:
+        blob = np.concatenate([table.view(np.uint8), floor_start.view(np.uint8), n_nodes.view(np.uint8)])
+        offs = {"rows": 0, "floor_start": table.nbytes, "n_nodes": table.nbytes + floor_start.nbytes}
+    else:
+        blob, offs = _blob([("rows", table), ("floor_start", floor_start), ("n_nodes", n_nodes)] + call.parts())
     off_nodes = _align8(N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize)
     off_floors = off_nodes + F * M * node_dt.itemsize
     off_pgo_nodes = _align8(off_floors + F * _lib.GRAPH_FLOOR_OUT_DTYPE.itemsize)
     off_pgo_floors = off_pgo_nodes + F * M * node_dt.itemsize
     off_pose = off_pgo_floors + F * pgo_dt.itemsize
     out_bytes = off_pose + F * M * 24
+    off_axis = _align8(out_bytes)
     sig_o, sig_p = (ctypes.c_double * 3)(*map(float, odometry_sigmas)), (ctypes.c_double * 3)(*map(float, prior_sigmas))
     with torch.cuda.device(device):
         dev_in = torch.from_numpy(blob).to(device)
-        dev_out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        dev_out = torch.empty(out_bytes if call is None else off_axis + call.out_bytes, dtype=torch.uint8, device=device)
         p_in, p_out = dev_in.data_ptr(), dev_out.data_ptr()
         vp = ctypes.c_void_p
         stream = vp(torch.cuda.current_stream(device).cuda_stream)
         ws_bytes = max(int(lib.salve_pose_graph_workspace_bytes(F, M)), int(lib.salve_pose_graph_optimise_workspace_bytes(F, M)))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device) if ws_bytes else None
         p_ws = vp(ws.data_ptr()) if ws is not None else None
-        p_rows, p_start, p_n = vp(p_in), vp(p_in + table.nbytes), vp(p_in + table.nbytes + floor_start.nbytes)
+        p_rows, p_start, p_n = vp(p_in + offs["rows"]), vp(p_in + offs["floor_start"]), vp(p_in + offs["n_nodes"])
+        if call is not None:
+            p_rows = call.launch(lib, p_in, offs, p_out + off_axis, status.ptr(device), stream)
         _lib.check(lib.salve_pose_graph_solve(p_rows, N, p_start, p_n, F, M, float(confidence_threshold), float(rot_threshold_deg), float(trans_threshold),
                                               int(cycle_filter), vp(p_out), vp(p_out + off_nodes), vp(p_out + off_floors), p_ws, ws_bytes,
                                               status.ptr(device), stream), "salve_pose_graph_solve")
@@ -443,13 +658,16 @@ def optimise(meas: EdgeMeasurements, confidence_threshold: float, robust: bool =
                                                  status.ptr(device), stream), "salve_pose_graph_optimise")
         status.check(device, "pose_graph.optimise")   # (the one synchronising read)
         host = dev_out.cpu().numpy()
+    axis_info = None
+    if call is not None:
+        meas, axis_info = call.decode(meas, floors, host[off_axis:])
     trees = _floor_solutions(meas, floors, floor_start, host[:N * _lib.GRAPH_ROW_OUT_DTYPE.itemsize].view(_lib.GRAPH_ROW_OUT_DTYPE),
                              host[off_nodes:off_floors].view(node_dt).reshape(F, M),
                              host[off_floors:off_floors + F * _lib.GRAPH_FLOOR_OUT_DTYPE.itemsize].view(_lib.GRAPH_FLOOR_OUT_DTYPE), confidence_threshold,
-                             cycle_filter, rot_threshold_deg, trans_threshold)
+                             cycle_filter, rot_threshold_deg, trans_threshold, axis_info)
     pgo_nodes = host[off_pgo_nodes:off_pgo_floors].view(node_dt).reshape(F, M)
     pgo_floors = host[off_pgo_floors:off_pose].view(pgo_dt)
-    poses = host[off_pose:].view(np.float64).reshape(F, M, 3)
+    poses = host[off_pose:out_bytes].view(np.float64).reshape(F, M, 3)
 
     options = {"method": "pgo", "robust": bool(robust), "huber_k": float(huber_k), "odometry_sigmas": [float(x) for x in odometry_sigmas],
                "prior_sigmas": [float(x) for x in prior_sigmas], "max_iterations": int(max_iterations), "relative_error_tol": float(relative_error_tol),
@@ -468,6 +686,8 @@ def optimise(meas: EdgeMeasurements, confidence_threshold: float, robust: bool =
         record = {**{k: int(fo[k]) for k in ("n_unknown_nodes", "n_factors", "n_iterations", "n_rejected", "n_downweighted")},
                   "stop_reason": _lib.PGO_STOP_NAMES[int(fo["stop_reason"])], "lambda": float(fo["lambda"]), "cost_initial": fin(fo["cost_initial"]),
                   "cost_final": fin(fo["cost_final"])}
+        if axis_info is not None:
+            record["axis_counts"] = dict(axis_info["counts"][f])
         solutions.append(PgoSolution(fl["building_id"], fl["floor_id"], ids, {**tree.options, **options}, tree, wSi, pose, record))
     return solutions
 
@@ -694,7 +914,8 @@ def sample_trees(meas: EdgeMeasurements, confidence_threshold: float, hypotheses
 
 
 def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "spanning_tree", filter_by_random_spanning_trees: bool = False,
-        num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", truth=None, report_options=None, **solve_options):
+        num_hypotheses: int = 100, sampling_fraction: float = 0.5, seed: int = 0, device="cuda:0", truth=None, report_options=None,
+        axis: Optional[AxisInputs] = None, **solve_options):
     """What the command line and ingest.score_floor(pose_graph=...) do with their options.  method "spanning_tree": solve(meas,
     confidence_threshold, **solve_options), behind the random-spanning-trees edge filter if filter_by_random_spanning_trees; method
     "random_spanning_trees": sample_trees; method "pgo": optimise(meas, confidence_threshold, **solve_options) -- the spanning tree refined by
@@ -702,12 +923,15 @@ def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "span
     sigmas) among the options are optimise's own and belong to this method alone.  With the defaults this IS solve: the same launches and values.
     truth: None, or the floors' ground truth -- salve_amd.floor_report.FloorTruth objects, as a list in `meas.floors()` order or a dict keyed by
     (building_id, floor_id).  Then the result is (solutions, reports): floor_report.report(solutions, truths, **report_options) follows the
-    solve."""
+    solve.
+    axis: None, or the floors' AxisInputs: solve's and optimise's axis alignment by vanishing angle (the reference's
+    --use_axis_alignment, on by default there).  The random-spanning-trees edge filter samples the RAW rows and the alignment follows it, as in
+    run_sfm.py:354-426.  Method random_spanning_trees refuses it: the reference does not align there."""
     if truth is not None:
         from salve_amd import floor_report
 
         solutions = run(meas, confidence_threshold, method=method, filter_by_random_spanning_trees=filter_by_random_spanning_trees,
-                        num_hypotheses=num_hypotheses, sampling_fraction=sampling_fraction, seed=seed, device=device, **solve_options)
+                        num_hypotheses=num_hypotheses, sampling_fraction=sampling_fraction, seed=seed, device=device, axis=axis, **solve_options)
         truths = [truth[(s.building_id, s.floor_id)] for s in solutions] if isinstance(truth, dict) else list(truth)
         return solutions, floor_report.report(solutions, truths, device=device, **(report_options or {}))
     if method not in ("spanning_tree", "random_spanning_trees", "pgo"):
@@ -716,11 +940,14 @@ def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "span
     pgo_options = {k: solve_options.pop(k) for k in PGO_OPTIONS if k in solve_options}
     if pgo_options and method != "pgo":
         raise ValueError(f"pose_graph.run: {sorted(pgo_options)} belong to method pgo")
+    if axis is not None and method == "random_spanning_trees":
+        raise ValueError("pose_graph.run: method random_spanning_trees takes no axis alignment (the reference samples the raw measurements)")
+    axis_option = {} if axis is None else {"axis": axis}   # (None: solve and optimise are called exactly as before)
     if method == "pgo":
         keep = None
         if filter_by_random_spanning_trees:   # the factors are then the kept rows only (run_sfm.py passes high_conf_inlier_measurements on)
             keep = combined_inlier_mask(sample_trees(meas, confidence_threshold, device=device, **sampling))
-        solutions = optimise(meas, confidence_threshold, keep_rows=keep, device=device, **pgo_options, **solve_options)
+        solutions = optimise(meas, confidence_threshold, keep_rows=keep, device=device, **axis_option, **pgo_options, **solve_options)
         for sol in solutions:
             if filter_by_random_spanning_trees:
                 sol.options["filter_by_random_spanning_trees"] = dict(sampling)
@@ -730,9 +957,9 @@ def run(meas: EdgeMeasurements, confidence_threshold: float, method: str = "span
             raise ValueError("pose_graph.run: method random_spanning_trees takes neither the cycle filter's options nor the edge filter")
         return sample_trees(meas, confidence_threshold, device=device, **sampling)
     if not filter_by_random_spanning_trees:
-        return solve(meas, confidence_threshold, device=device, **solve_options)
+        return solve(meas, confidence_threshold, device=device, **axis_option, **solve_options)
     samples = sample_trees(meas, confidence_threshold, device=device, **sampling)
-    solutions = solve(meas, confidence_threshold, device=device, keep_rows=combined_inlier_mask(samples), **solve_options)
+    solutions = solve(meas, confidence_threshold, device=device, keep_rows=combined_inlier_mask(samples), **axis_option, **solve_options)
     for sol in solutions:
         sol.options["filter_by_random_spanning_trees"] = dict(sampling)
     return solutions
@@ -776,10 +1003,29 @@ def main(argv=None) -> int:
     ap.add_argument("--zind-root", metavar="DIR", default=None,
                     help="the ZInD data set ({DIR}/{building}/zind_data.json): also write floor_report_{building}_{floor}.json per floor -- rotation and "
                          "translation error against the ground truth, percent localized, floor-plan IoU -- and print the summary")
+    ap.add_argument("--axis-alignment", action="store_true",
+                    help="methods spanning_tree and pgo: align every relative pose by the two panoramas' vanishing angles first (the reference's "
+                         "--use_axis_alignment, which is ON by default there; here the default is off).  Needs --mhnet-predictions-data-root and --zind-root")
+    ap.add_argument("--mhnet-predictions-data-root", metavar="DIR", default=None,
+                    help="MHNet's predictions (horizon_net/{building}/*.json, vanishing_angle/{building}.json): the rooms, W/D/Os and angles of --axis-alignment")
     ap.add_argument("--report-seed", type=int, default=0, help="seed of the report's alignment RANSAC (default %(default)s)")
     ap.add_argument("--report-iters", type=int, default=1000, help="alignment subsets per floor (default %(default)s)")
     args = ap.parse_args(argv)
+    if args.axis_alignment:
+        if args.mhnet_predictions_data_root is None or args.zind_root is None:
+            ap.error("--axis-alignment needs --mhnet-predictions-data-root and --zind-root")
+        if args.method == "random_spanning_trees":
+            ap.error("--axis-alignment belongs to --method spanning_tree or pgo")
+    elif args.mhnet_predictions_data_root is not None:
+        ap.error("--mhnet-predictions-data-root belongs to --axis-alignment")
     meas = EdgeMeasurements.from_prediction_files(args.pred_dir, args.hypotheses)
+    if args.axis_alignment:
+        from salve_amd import hypotheses
+
+        options_axis = {"axis": AxisInputs.from_floors(hypotheses.load_floors(args.zind_root, args.mhnet_predictions_data_root,
+                                                                               sorted(set(meas.building_id))))}
+    else:
+        options_axis = {}
     if args.method == "random_spanning_trees":
         if args.filter_by_random_spanning_trees:
             ap.error("--filter-by-random-spanning-trees belongs to --method spanning_tree or pgo")
@@ -796,7 +1042,7 @@ def main(argv=None) -> int:
     elif args.pgo_max_iterations is not None or args.pgo_no_robust:
         ap.error("--pgo-max-iterations and --pgo-no-robust belong to --method pgo")
     solutions = run(meas, args.confidence_threshold, method=args.method, filter_by_random_spanning_trees=args.filter_by_random_spanning_trees,
-                    num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options)
+                    num_hypotheses=args.num_hypotheses, sampling_fraction=args.sampling_fraction, seed=args.seed, device=args.device, **options_axis, **options)
     for sol in solutions:
         write_json(sol, args.out or args.pred_dir)
         print(sol.summary())
